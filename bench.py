@@ -24,25 +24,35 @@ BEFORE this process makes any GPU call; under `python -m torch.distributed.run` 
 launcher's.  Either way: world size must equal --gpus, the node must have that many devices, and
 the JSON carries the communicator's own rank count (`rccl_ranks`).
 
-Every default line (`--config c2`, two-pass flow; N = 1 included) also carries a `config3` block: BASELINE configs[2] ITSELF
+With `--full`, every `--config c2` two-pass line (N = 1 included) also carries a `config3` block: BASELINE configs[2] ITSELF
 -- 64M paths x 252 steps in total, sharded over the job's N ranks (8M per GPU at N = 8), strong scaling -- timed through the
 job's communicator, with every rank's communicator-free time on its own shard and rank 0's time for the whole problem on
 one card beside it: `scaling_efficiency`, `speedup_vs_one_gpu`, and the sharded price checked against the one-GPU price
 (config3_block below; `--no-config3` / `--config3-paths` / `--config3-steps`).  The headline stays configs[1] per GPU.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+A plain run (no `--full`) does only what the headline needs: set up, warm up, time `--steps` pricings, write the last
+pricing's results if `--dump-outputs DIR` is given, print the line.  `ms_per_step` is the time of one timed pricing.
+
+Prints ONE JSON line (rank 0).  Extra objects of every line, from the timed pricings themselves:
   roofline          the dominant kernel (largest time share): algorithmic bytes per launch / mean
                     HIP-event duration of that launch inside the timed region, vs 8 TB/s HBM peak
   roofline_pathgen  the path-generation kernel named by north_star: (n_steps+1)*n_paths*4 bytes
   roofline_kernels  every big kernel of the pricing, same accounting (+ PMC traffic, source labelled)
-  roofline_per_step the per-timestep kernel north_star specifies (reference per-step flow), always
+and of `--full` lines only (runs of their own after the timed region; `--no-*` switches leave single ones out):
+  roofline_per_step the per-timestep kernel north_star specifies (reference per-step flow)
   price_check       GPU vs CPU oracle on the SAME Philox (seed, stream), bounded slice
   sustained         >= 3 s of back-to-back pricings (steady clocks), same kernels
+  variants          the other flows, config 5's NN regressor, the per-step ContNet flow
   cpu_baseline      the C oracle (oracle/, a port: the reference is Python) on this host
   config3           BASELINE configs[2] on this job's ranks (see above)
+
+`--dump-outputs DIR` writes what the timed path returned for its LAST timed pricing, one float64 array per numeric
+result field (DIR/price.npy, DIR/sum.npy, DIR/n_exercised.npy, ...; timings left out).  The inputs are fixed by the
+arguments (seed 42, Philox stream = step index), so two builds run with the same arguments can be compared file by file.
 """
 import argparse
 import json
+import numbers
 import os
 import sys
 import time
@@ -61,6 +71,9 @@ CONFIGS = {  # BASELINE.json configs[1..3]
     "c5": dict(model="gbm", paths_per_gpu=1_000_000),  # configs[4]: the NN regressor (2 x 64): its own flow, bench_c5()
     "c1nn": dict(model="gbm", paths_per_gpu=10_000),   # configs[0] as the reference itself runs it: its default call, bench_c1nn()
 }
+# (--steps, --warmup) when they are not given: a pricing of the NN lines takes ~1 s, the others under 50 ms
+DEFAULT_STEPS = {"c5": (5, 2), "c1nn": (10, 3)}
+DEFAULT_STEPS_OTHER = (50, 20)
 MARKET = dict(S0=100.0, K=100.0, r=0.05, sigma=0.2, T=1.0)
 HESTON = dict(v0=0.04, kappa=2.0, theta=0.04, xi=0.3, rho=-0.7)
 
@@ -135,6 +148,20 @@ def cpu_baseline(model, M, N, semantics, is_put, seed, stream, budget_s=25.0):
     }
 
 
+def dump_outputs(dirname, result) -> list:
+    """--dump-outputs: the result of the timed path's last pricing, one float64 array per numeric field
+    (DIR/<field>.npy).  Timings and event flags are measurements, not results, and are left out."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    names = []
+    for k, v in result.items():
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or k.startswith(("ms_", "seconds_")) or k == "timed":
+            continue
+        np.save(os.path.join(dirname, f"{k}.npy"), np.asarray(v, dtype=np.float64))
+        names.append(k)
+    return names
+
+
 # ---------------------------------------------------------------------------------------------
 def launch_ranks(n: int, deadline_s: float, argv=None) -> int:
     """Parent of a `--gpus N` run without a launcher: start N rank processes (this script again, with
@@ -155,7 +182,7 @@ def bench_c5(a) -> int:
     import torch
     from options_model_amd import nn_regressor as nnr
     M, N = a.paths_per_gpu or CONFIGS["c5"]["paths_per_gpu"], a.n_steps
-    steps, warm = max(1, min(a.steps, 5)), max(1, min(a.warmup, 2))
+    steps, warm = a.steps, a.warmup
     nnr.price_american_option_nn(100.0, 100.0, 0.05, 0.2, 1.0, 20_000, 25, seed=1, nn_epochs=2)
     for i in range(warm):
         nnr.price_american_option_nn(MARKET["S0"], MARKET["K"], MARKET["r"], MARKET["sigma"], MARKET["T"], M, N, seed=7 + i)
@@ -165,6 +192,8 @@ def bench_c5(a) -> int:
                                          seed=42 + i) for i in range(steps)]
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / steps
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, vars(outs[-1]))
     o = outs[0]
     flop = 2 * (8 * 64 + 64 * 64 + 64) + 2 * 2 * 64 * 64 + 2 * 8 * 64  # per row: forward, dH1, gW2, gW1
     tk = sum(x.timings_ms.get("train_kernels", 0.0) for x in outs) * 1e-3
@@ -203,7 +232,7 @@ def bench_c1nn(a) -> int:
     import torch
     from options_model_amd import AdvancedOptionPricer, RNGManager
     M, N = a.paths_per_gpu or CONFIGS["c1nn"]["paths_per_gpu"], (50 if a.n_steps == 252 else a.n_steps)
-    steps, warm = max(1, min(a.steps, 10)), max(1, min(a.warmup, 3))
+    steps, warm = a.steps, a.warmup
 
     def one(seed):
         q = AdvancedOptionPricer(MARKET["K"], MARKET["r"], MARKET["sigma"], "put", RNGManager(seed))
@@ -217,6 +246,8 @@ def bench_c1nn(a) -> int:
     outs = [one(42 + i) for i in range(steps)]
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / steps
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, dict(outs[-1][1], price=outs[-1][0]))
     price, o = outs[0]
     H = 128
     flop = 2 * (8 * H + 2 * H * H + H) + 2 * 2 * H * H + 2 * 2 * H * H + 2 * 8 * H  # per row: forward, dH x 2, gW x 2, gW1
@@ -364,10 +395,18 @@ def config3_block(a, _ffi, ctx, pricer, rank, world, local_rank, N, kw, barrier,
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=20,
-                    help="untimed pricings first (the GPU's clocks take ~10-20 ms of work to come up: "
-                         "profiles/r02f shows the same kernel 1.46 -> 0.93 ms over its first 13 launches)")
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed pricings (default 50; 5 with --config c5, 10 with --config c1nn)")
+    ap.add_argument("--warmup", type=int, default=None,
+                    help="untimed pricings first (default 20; 2 with --config c5, 3 with --config c1nn).  The GPU's clocks "
+                         "take ~10-20 ms of work to come up: profiles/r02f shows the same kernel 1.46 -> 0.93 ms over its "
+                         "first 13 launches")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline as well, each a run of its own after the timed region: the "
+                         "per-step roofline, the price check against the CPU oracle, the sustained loop, the other flows, "
+                         "the CPU baseline and the config3 block (the --no-* switches still leave single ones out)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed pricings, write the last one's results as DIR/<field>.npy (float64)")
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS),
                     help="c2: GBM put 1M paths/GPU (default); c3: 8M paths/GPU (64M over 8); c4: Heston call 4M")
     ap.add_argument("--paths-per-gpu", type=int, default=None, help="override the config's paths per GPU")
@@ -385,7 +424,8 @@ def main():
     ap.add_argument("--no-sustained", action="store_true")
     ap.add_argument("--only-timed", action="store_true",
                     help="warm-up + timed region only (for rocprofv3 --pmc passes: every dispatch of a kernel is then "
-                         "the same workload): no per-step extra, sustained loop, price check, variants, CPU baseline")
+                         "the same workload): no per-step extra, sustained loop, price check, variants, CPU baseline.  "
+                         "A plain run does this already; given together with --full, it overrides --full")
     ap.add_argument("--group", type=int, default=None,
                     help="pricings enqueued per omc_price_american_seq call (one host wait -- and, across GPUs, one result "
                          "collective -- per group); default: all --steps in one group, at most 50")
@@ -417,9 +457,15 @@ def main():
     ap.add_argument("--kernel-samples", type=int, default=4,
                     help="at least this many pricings of the timed region carry their own HIP events")
     a = ap.parse_args()
+    steps, warmup = DEFAULT_STEPS.get(a.config, DEFAULT_STEPS_OTHER)
+    a.steps = steps if a.steps is None else a.steps
+    a.warmup = warmup if a.warmup is None else a.warmup
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if a.group is None:
         a.group = max(1, min(a.steps, 50))
-    if a.only_timed:
+    if a.only_timed or not a.full:
+        a.only_timed = True
         a.no_cpu_baseline = a.no_variants = a.no_sustained = a.no_config3 = True
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -525,19 +571,20 @@ def main():
               heston_scheme="full_truncation" if model == "heston" else "reference")
 
     def price_group(ids, sem=a.semantics):
-        """Enqueue the pricings `ids` (Philox stream ids) back to back -> (price of the last, local results)."""
+        """Enqueue the pricings `ids` (Philox stream ids) back to back -> (price of the last, local results,
+        the last pricing's result as the caller of the pricing path receives it: the job's, across ranks)."""
         if pricer is not None:
             louts = pricer.price_american_seq(M * world, ids, **dict(kw, semantics=sem))
-            return louts[-1]["price"], [o["local"] for o in louts]
+            return louts[-1]["price"], [o["local"] for o in louts], louts[-1]
         outs = ctx.price_american_seq([params(sem, i) for i in ids])
-        return outs[-1]["price"], outs
+        return outs[-1]["price"], outs, outs[-1]
 
     def one_step(i):
         if pricer is not None:
             out = pricer.price_american(M * world, stream=i, **kw)
-            return out["price"], out["local"]
+            return out["price"], out["local"], out
         out = ctx.price_american(params(a.semantics, i))
-        return out["price"], out
+        return out["price"], out, out
 
     # Across GPUs a sequence overlaps each pricing's moment all-reduce with the next pricing's paths + pass 1
     # (library option "seq_overlap", default on for more than one rank).  Before anything is timed, every rank
@@ -613,7 +660,7 @@ def main():
         tot_lsm = 0.0
         for lo in range(0, a.steps, a.group):
             ids = list(range(lo, min(lo + a.group, a.steps)))
-            price, outs = price_group(ids)
+            price, outs, last_result = price_group(ids)
             last_out = outs[-1]
             for o in outs:
                 if o.get("timed"):
@@ -626,7 +673,7 @@ def main():
         ms_lsm = tot_lsm / a.steps - ms_paths
     else:
         for i in range(a.steps):
-            price, loc = one_step(i)
+            price, loc, last_result = one_step(i)
             last_out = loc
             ms_paths += loc["ms_paths"]
             ms_lsm += loc["ms_lsm"]
@@ -651,6 +698,8 @@ def main():
             raise SystemExit(f"bench.py rank {rank}: {e}")
         elapsed = pricer.allreduce_max(elapsed)
     ctx.set_option("seq_event_stride", 0)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last_result)
 
     # folded storage (omc_result.folded): half the matrix is written and read -- the algorithmic bytes of every kernel halve
     folded = bool(last_out.get("folded"))
@@ -814,7 +863,7 @@ def main():
             price_group(list(range(900, 900 + max(k, 2))), "reference")  # warm (workspaces)
             barrier(); ctx.sync()
             t1 = time.perf_counter()
-            pr, outs = price_group(list(range(reps)), "reference")
+            pr, outs, _ = price_group(list(range(reps)), "reference")
             barrier(); ctx.sync()
             dt = time.perf_counter() - t1
             if dist_mode:

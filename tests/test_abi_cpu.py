@@ -90,6 +90,11 @@ def test_facade_n_gpus_never_prices_on_fewer_gpus(monkeypatch):
     from options_model_amd import launcher, price_american_option
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         monkeypatch.delenv(k, raising=False)
+    # also on a GPU box: the ranks see no device (they inherit this environment), and a pool that earlier tests of
+    # this process left running is not reused
+    monkeypatch.setenv("HIP_VISIBLE_DEVICES", "")
+    monkeypatch.setenv("ROCR_VISIBLE_DEVICES", "")
+    launcher.close_pools()
     t0 = time.monotonic()
     with pytest.raises(launcher.RankError, match=r"rank \d"):  # whichever rank reports first
         price_american_option(100.0, 100.0, 0.05, 0.2, 1.0, 10_000, 50, n_gpus=2)

@@ -161,6 +161,29 @@ def test_bench_launcher_starts_n_ranks_and_fails_loudly_without_gpus():
     assert out.stderr.count("needs a GPU") >= 1
 
 
+def test_bench_steps_must_be_positive():
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                         timeout=120, cwd=root)
+    assert out.returncode != 0 and "--steps must be >= 1" in out.stderr and out.stdout.strip() == ""
+
+
+def test_bench_dump_outputs_writes_the_numeric_result_fields_as_float64(tmp_path):
+    """--dump-outputs: one float64 array per numeric field of a pricing's result; timings and flags of the
+    measurement itself stay out, so that two builds on the same arguments compare file by file."""
+    bench = _bench_module()
+    res = dict(price=7.25, sum=7.25e6, sumsq=9.5e7, std=3.1, zero_prob=0.4, n_paths=1_000_000, n_exercised=410_000,
+               n_zero=400_000, sum_nitm=2**40 + 1, ms_paths=0.1, ms_lsm=0.2, ms_total=0.3, ms_pass1=0.1, ms_pass2=0.1,
+               timed=1, seconds_train=2.0, trainer="hip", info={"batch": 256}, settled=True)
+    names = bench.dump_outputs(str(tmp_path / "out"), res)
+    assert sorted(f"{k}.npy" for k in names) == sorted(os.listdir(tmp_path / "out")) == sorted(
+        f"{k}.npy" for k in ("price", "sum", "sumsq", "std", "zero_prob", "n_paths", "n_exercised", "n_zero", "sum_nitm"))
+    for k in names:
+        a = np.load(tmp_path / "out" / f"{k}.npy")
+        assert a.dtype == np.float64 and float(a) == res[k]
+
+
 def test_bench_world_size_must_match_gpus():
     import subprocess
     import sys

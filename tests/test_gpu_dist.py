@@ -212,7 +212,7 @@ def test_bench_gpus_2_starts_its_own_ranks(ctx):
     from options_model_amd import _ffi
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     d = _bench_json([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                     "--paths-per-gpu", "100000", "--n-steps", "50", "--backend", "gloo", "--single-device",
+                     "--paths-per-gpu", "100000", "--n-steps", "50", "--backend", "gloo", "--single-device", "--full",
                      "--no-variants", "--no-cpu-baseline", "--no-sustained"], root)
     assert d["n_gpus"] == 2 and d["rccl_ranks"] == 2 and d["config"]["parallelism"] == "path-sharded x2"
     ref = ctx.price_american(_ffi.make_params(semantics="two_pass", n_paths=200000, n_steps=50, seed=42, stream=1))
@@ -290,7 +290,7 @@ def test_bench_single_gpu_line_carries_config3(ctx):
     from options_model_amd import _ffi
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     d = _bench_json([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                     "--paths-per-gpu", "50000", "--n-steps", "40", "--no-variants", "--no-cpu-baseline", "--no-sustained",
+                     "--paths-per-gpu", "50000", "--n-steps", "40", "--full", "--no-variants", "--no-cpu-baseline", "--no-sustained",
                      "--config3-steps", "2"], root)
     c3 = d["config3"]
     assert (c3["total_paths"], c3["n_gpus"], c3["paths_per_gpu"], c3["scaling"]) == (3_200_000, 1, 3_200_000, "strong")
@@ -299,9 +299,33 @@ def test_bench_single_gpu_line_carries_config3(ctx):
     assert c3["value"] == pytest.approx(3_200_000 * 40 / (c3["ms_per_step"] * 1e-3))
     assert d["config"]["paths_per_gpu"] == 50000 and d["scaling"] == "weak"  # the headline is untouched
     d = _bench_json([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                     "--paths-per-gpu", "50000", "--n-steps", "40", "--no-variants", "--no-cpu-baseline", "--no-sustained",
+                     "--paths-per-gpu", "50000", "--n-steps", "40", "--full", "--no-variants", "--no-cpu-baseline", "--no-sustained",
                      "--no-config3"], root)
     assert "config3" not in d
+
+
+def test_bench_plain_line_is_the_headline_and_dumps_the_last_pricing(ctx, tmp_path):
+    """A run without --full times exactly --steps pricings and carries none of the extras that take runs of their own;
+    --dump-outputs writes the last timed pricing's result (Philox stream steps - 1) as float64 arrays."""
+    import os
+    import sys
+    import numpy as np
+    from options_model_amd import _ffi
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "outputs"
+    d = _bench_json([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                     "--paths-per-gpu", "50000", "--n-steps", "40", "--dump-outputs", str(out)], root)
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "path-steps/s" and d["higher_is_better"] is True
+    assert d["value"] == pytest.approx(50000 * 40 / (d["ms_per_step"] * 1e-3))
+    for k in ("config3", "price_check", "sustained", "variants"):
+        assert k not in d, k
+    assert d["cpu_baseline"] is None and d["roofline_per_step"] is None
+    ref = ctx.price_american(_ffi.make_params(semantics="two_pass", n_paths=50000, n_steps=40, seed=42, stream=2))
+    assert d["price"] == ref["price"] and d["price_stream"] == 2
+    for k in ("price", "sum", "sumsq", "n_paths", "n_exercised", "n_zero", "sum_nitm"):
+        got = np.load(out / f"{k}.npy")
+        assert got.dtype == np.float64 and float(got) == float(ref[k]), k
+    assert not any(f.startswith("ms_") for f in os.listdir(out))
 
 
 def test_bench_force_dist_uses_native_rccl():
@@ -309,7 +333,7 @@ def test_bench_force_dist_uses_native_rccl():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     d = _bench_json([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                     "--paths-per-gpu", "100000", "--n-steps", "50", "--force-dist", "--no-variants",
+                     "--paths-per-gpu", "100000", "--n-steps", "50", "--force-dist", "--full", "--no-variants",
                      "--no-cpu-baseline", "--no-sustained"], root)
     assert d["n_gpus"] == 1 and d["rccl_ranks"] == 1 and d["comm"].startswith("rccl-native")
     assert d["price_check"]["rel_err"] < 1e-3 and d["seq_overlap"] == "off (one rank)"
@@ -317,7 +341,7 @@ def test_bench_force_dist_uses_native_rccl():
     os.environ["OMC_BENCH_SELFCHECK"] = "1"
     try:
         d2 = _bench_json([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
-                          "--paths-per-gpu", "100000", "--n-steps", "50", "--force-dist", "--no-variants",
+                          "--paths-per-gpu", "100000", "--n-steps", "50", "--force-dist", "--full", "--no-variants",
                           "--no-cpu-baseline", "--no-sustained"], root)
     finally:
         del os.environ["OMC_BENCH_SELFCHECK"]

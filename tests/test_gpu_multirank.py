@@ -50,7 +50,7 @@ def test_ranks_sharing_one_gpu_equal_the_unsharded_pricing(ctx, standin, world, 
     from options_model_amd import _ffi
     out, _ = _bench(["--gpus", str(world), "--single-device", "--backend", "rccl", "--steps", "4", "--warmup", "2",
                      "--paths-per-gpu", str(M_PER_GPU), "--n-steps", str(N), "--semantics", sem, "--group", "4",
-                     "--min-warmup-seconds", "0.05", "--no-variants", "--no-cpu-baseline", "--no-sustained",
+                     "--min-warmup-seconds", "0.05", "--full", "--no-variants", "--no-cpu-baseline", "--no-sustained",
                      "--config3-steps", "3"], standin)
     d = _line(out)
     assert d["n_gpus"] == world and d["rccl_ranks"] == world and d["comm"].startswith("rccl-native")
@@ -178,7 +178,7 @@ def test_direct_peer_exchange_equals_the_collective_path(ctx, standin, world):
     from options_model_amd import _ffi
     out, _ = _bench(["--gpus", str(world), "--single-device", "--backend", "rccl", "--steps", "4", "--warmup", "2",
                      "--paths-per-gpu", str(M_PER_GPU), "--n-steps", str(N), "--group", "4", "--p2p-exchange",
-                     "--min-warmup-seconds", "0.05", "--no-variants", "--no-cpu-baseline", "--no-sustained"], standin)
+                     "--min-warmup-seconds", "0.05", "--full", "--no-variants", "--no-cpu-baseline", "--no-sustained"], standin)
     d = _line(out)
     ps = d["roofline_per_step"]
     assert ps["exchange_across_ranks"].startswith("direct writes"), ps["exchange_across_ranks"]
@@ -364,7 +364,7 @@ def test_the_drivers_launch_form_torchrun_native_communicator(ctx, standin):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(29650 + os.getpid() % 40), os.path.join(ROOT, "bench.py"), "--gpus", "2",
            "--steps", "4", "--warmup", "2", "--paths-per-gpu", str(M_PER_GPU), "--n-steps", str(N), "--single-device",
-           "--backend", "rccl", "--group", "4", "--min-warmup-seconds", "0.05", "--no-variants", "--no-cpu-baseline"]
+           "--backend", "rccl", "--group", "4", "--min-warmup-seconds", "0.05", "--full", "--no-variants", "--no-cpu-baseline"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
     d = _line(out)
     assert d["n_gpus"] == 2 and d["rccl_ranks"] == 2 and d["comm"].startswith("rccl-native") and d["seq_overlap"] == "on"
@@ -480,7 +480,7 @@ def test_config3_shard_size_through_the_native_communicator(ctx, standin):
     decision-independent moment all-reduce and the result collective at config 3's per-GPU size."""
     from options_model_amd import _ffi
     out, took = _bench(["--gpus", "4", "--single-device", "--backend", "rccl", "--config", "c3", "--steps", "2", "--warmup",
-                        "1", "--min-warmup-seconds", "0.05", "--no-variants", "--no-cpu-baseline", "--no-sustained"],
+                        "1", "--min-warmup-seconds", "0.05", "--full", "--no-variants", "--no-cpu-baseline", "--no-sustained"],
                        standin, timeout=600)
     d = _line(out)
     assert d["rccl_ranks"] == 4 and d["config"]["paths_per_gpu"] == 8_000_000 and d["seq_overlap"] == "on"
