@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define OMC_ABI_VERSION 9
+#define OMC_ABI_VERSION 10
 
 typedef struct omc_ctx omc_ctx;
 
@@ -262,6 +262,29 @@ int omc_comm_allreduce_f64(omc_ctx* ctx, double* host_inout, int count, int op);
  * caller-owned device matrix [n_steps+1][ld] to receive the paths (NULL: internal workspace) */
 int omc_price_american(omc_ctx* ctx, const omc_params* p, omc_result* res, float* S_keep,
                        int64_t ld);
+/* Pathwise Greeks of the two-pass (v3) polynomial-LSM estimator with the exercise policy FROZEN:
+ * one GPU, p->semantics == OMC_SEM_TWO_PASS, paths stored as omc_price_american stores them (option "fold_antithetic";
+ * base.folded says which).  The policy is the fits pass 1 makes at p's parameters, or `betas` (host [n_steps+1][4] =
+ * b0, b1, b2, n as omc_lsm_apply_frozen takes them; n <= 0: no exercise at that step; pass 1 is then skipped and
+ * base.sum_nitm = 0).  betas_out (NULL or host [n_steps+1][4]) receives the policy used.  One sweep prices three
+ * scenarios per path -- S0, S0 (1 + bump), S0 (1 - bump) -- on the stored paths scaled by the factor (every model's spot is
+ * proportional to S0) and forms, per path, with s the exercise spot, k the exercise step (N: never), D_k = exp(-r (k-1) dt):
+ *   delta D_k phi'(s) s / S0, gamma (delta+ - delta-) / (2 bump S0) from the bumped scenarios' own exercise steps, and for
+ *   GBM vega, rho and theta (-dV/dT at fixed n_steps) from the path's Brownian value read back from s.  Heston: vega, rho,
+ *   theta and their standard errors are NaN.  Standard errors: sqrt(max(E[x^2] - E[x]^2, 0) / n_paths), antithetic
+ *   partners counted as independent paths.  float64 sums in a fixed order: identical calls return identical bits.
+ * Errors: -4 semantics != 2 or bump outside (0, 0.5]; -10 context with a communicator or all-reduce hook; -7 null out. */
+typedef struct {
+    omc_result base;                         /* the pricing, as omc_price_american returns it (ms_pass2 = 0: the sweep
+                                                below replaces pass 2)                                               */
+    double delta, gamma, vega, rho, theta;   /* raw units: per unit S0 / S0^2 / sigma / r / year                     */
+    double se_delta, se_gamma, se_vega, se_rho, se_theta;
+    double bump, price_up, price_down;       /* price_up / _down: the frozen-policy prices at S0 (1 +- bump)         */
+    int64_t n_exercised_up, n_exercised_down;
+    double ms_greeks;                        /* HIP-event time of the Greeks sweep                                   */
+} omc_greeks;
+int omc_price_american_greeks(omc_ctx* ctx, const omc_params* p, double bump, const double* betas, double* betas_out,
+                              omc_greeks* out);
 /* European discounted payoff from terminal values only (no path matrix): replaces
  * price_european_streaming options_model_3.py:382-437; sums2 host {sum, sumsq} */
 int omc_price_european(omc_ctx* ctx, const omc_params* p, omc_result* res);

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _build
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 SEMANTICS = {"reference": 0, "textbook": 1, "two_pass": 2}
 MODELS = {"gbm": 0, "heston": 1}
@@ -45,6 +45,18 @@ class Result(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class Greeks(C.Structure):
+    """omc_greeks: the base pricing plus the frozen-policy pathwise Greeks (omc_price_american_greeks)."""
+    _fields_ = [("base", Result),
+                ("delta", C.c_double), ("gamma", C.c_double), ("vega", C.c_double), ("rho", C.c_double),
+                ("theta", C.c_double),
+                ("se_delta", C.c_double), ("se_gamma", C.c_double), ("se_vega", C.c_double), ("se_rho", C.c_double),
+                ("se_theta", C.c_double),
+                ("bump", C.c_double), ("price_up", C.c_double), ("price_down", C.c_double),
+                ("n_exercised_up", C.c_int64), ("n_exercised_down", C.c_int64),
+                ("ms_greeks", C.c_double)]
 
 
 class MlpJob(C.Structure):
@@ -94,6 +106,7 @@ SIGNATURES = {
     "omc_p2p_disconnect": (C.c_int, [_P]),
     "omc_p2p_status": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
     "omc_price_american": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Result), _P, _I64]),
+    "omc_price_american_greeks": (C.c_int, [_P, C.POINTER(Params), _D, _P, _P, C.POINTER(Greeks)]),
     "omc_price_european": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Result)]),
     "omc_heston_price_strikes": (C.c_int, [_P, _I64, _I] + [_D] * 8 + [_U64, _U64, _I, _P, _I, _I, _P, _P]),
     "omc_heston_price_surface": (C.c_int, [_P, _I64, _I] + [_D] * 7 + [_U64, _I, _P, _P, _I, _P, _P, _I, _I, _P, _P]),
@@ -522,6 +535,27 @@ class Context:
             self.handle, C.byref(params), C.byref(res), keep_paths.ptr if keep_paths else None,
             keep_paths.shape[1] if keep_paths else 0))
         return res.as_dict()
+
+    def price_american_greeks(self, params: Params, bump=0.01, betas=None, want_betas=False):
+        """Frozen-policy pathwise Greeks of the two-pass flow (omc_price_american_greeks) -> dict: the base pricing's keys
+        (as price_american returns them) plus delta, gamma, vega, rho, theta (raw units), se_*, bump, price_up, price_down,
+        n_exercised_up / _down, ms_greeks; `betas` [n_steps+1][4] freezes a given policy; want_betas adds the policy used."""
+        N = int(params.n_steps)
+        b = None
+        if betas is not None:
+            b = np.ascontiguousarray(betas, np.float64)
+            if b.shape != (N + 1, 4):
+                raise ValueError(f"betas must have shape ({N + 1}, 4), got {b.shape}.")
+        bo = np.zeros((N + 1, 4)) if want_betas else None
+        g = Greeks()
+        _check(self.lib, self.lib.omc_price_american_greeks(self.handle, C.byref(params), float(bump),
+                                                             b.ctypes.data if b is not None else None,
+                                                             bo.ctypes.data if bo is not None else None, C.byref(g)))
+        d = g.base.as_dict()
+        d.update({k: getattr(g, k) for k, _ in Greeks._fields_ if k != "base"})
+        if want_betas:
+            d["betas"] = bo
+        return d
 
     def price_american_ols7(self, params: Params):
         """Fused pricing with regressor "ols7" (paths + omc_lsm_ols7 in the context's own matrix) -> result dict + fit."""

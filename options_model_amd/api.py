@@ -201,6 +201,72 @@ def price_american_option(S0, K, r, sigma, T, n_paths, n_steps, model="GBM", opt
                        timings_ms=dict(paths=out["ms_paths"], lsm=out["ms_lsm"], total=out["ms_total"]))
 
 
+@dataclass
+class GreeksResult:
+    """price_american_greeks: the frozen-policy pathwise Greeks of the two-pass poly estimator, in raw units (per unit
+    S0, S0^2, sigma, r; theta = -dV/dT per year).  Heston: vega, rho, theta are NaN."""
+    price: float
+    stderr: float
+    delta: float
+    gamma: float
+    vega: float
+    rho: float
+    theta: float
+    se_delta: float
+    se_gamma: float
+    se_vega: float
+    se_rho: float
+    se_theta: float
+    price_up: float
+    price_down: float
+    bump: float
+    n_paths: int
+    n_exercised: int
+    folded: bool
+    model: str
+    option_type: str
+    timings_ms: dict = field(default_factory=dict)
+
+    def as_reference_dict(self) -> dict:
+        """The keys and units of the reference's BlackScholesGreeks.greeks: Vega and Rho per 1 %, Theta per day."""
+        return {"Delta": self.delta, "Gamma": self.gamma, "Vega": self.vega / 100, "Theta": self.theta / 365,
+                "Rho": self.rho / 100}
+
+
+def price_american_greeks(S0, K, r, sigma, T, n_paths, n_steps, model="GBM", option_type="put", heston_params=None,
+                          heston_scheme="reference", antithetic=True, seed=42, stream=0, device=None, ctx=None,
+                          n_gpus=1, bump=0.01) -> GreeksResult:
+    """Delta, gamma, vega, rho and theta of the American price of price_american_option(regressor="poly",
+    semantics="two_pass") with the exercise policy pass 1 fits held fixed (omc_price_american_greeks).  They are exact
+    derivatives of that frozen-policy estimator; they differ from the true American Greeks only through the policy's
+    suboptimality.  gamma is a central difference of pathwise deltas at S0 (1 +- bump) on the same paths.  One GPU."""
+    model_l = str(model).lower()
+    if int(n_gpus) != 1:
+        raise ValueError("price_american_greeks runs on one GPU (n_gpus=1).")
+    if model_l not in ("gbm", "heston"):
+        raise ValueError("model must be 'GBM' or 'Heston'.")
+    if not (0.0 < float(bump) <= 0.5):
+        raise ValueError("bump must lie in (0, 0.5].")
+    _validate(S0, K, T, r, sigma, n_paths, n_steps, option_type, need_sigma=(model_l == "gbm"))
+    M = int(n_paths) // 2 * 2 if antithetic else int(n_paths)
+    if M <= 0:
+        raise ValueError("num_simulations and num_time_steps must be positive integers.")
+    c = ctx or _ffi.default_context(device)
+    p = _ffi.make_params(model=model_l, is_put=(option_type == "put"), semantics="two_pass", antithetic=antithetic,
+                         heston_scheme=heston_scheme, n_paths=M, n_steps=int(n_steps), S0=S0, K=K, r=r,
+                         sigma=sigma or 0.0, T=T, seed=seed, stream=stream, **heston_defaults(sigma, heston_params))
+    out = c.price_american_greeks(p, bump=float(bump))
+    var = max(out["sumsq"] / M - out["price"] ** 2, 0.0)
+    return GreeksResult(price=out["price"], stderr=math.sqrt(var / M), delta=out["delta"], gamma=out["gamma"],
+                        vega=out["vega"], rho=out["rho"], theta=out["theta"], se_delta=out["se_delta"],
+                        se_gamma=out["se_gamma"], se_vega=out["se_vega"], se_rho=out["se_rho"], se_theta=out["se_theta"],
+                        price_up=out["price_up"], price_down=out["price_down"], bump=out["bump"], n_paths=M,
+                        n_exercised=out["n_exercised"], folded=bool(out["folded"]), model=model_l,
+                        option_type=option_type,
+                        timings_ms=dict(paths=out["ms_paths"], pass1=out["ms_pass1"], greeks=out["ms_greeks"],
+                                        total=out["ms_total"]))
+
+
 _job = {}
 
 

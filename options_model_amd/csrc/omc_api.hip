@@ -13,6 +13,7 @@
 #include <sched.h>
 
 #include "omc_batch.h"
+#include "omc_greeks.h"
 #include "omc_comm.h"
 #include "omc_p2p.h"
 #include "omc_kernels.h"
@@ -145,6 +146,7 @@ struct omc_ctx {
     // sequence has two pricings in flight), each remembered by what it was filled from
     int fold = 1;
     DevBuf foldC;
+    DevBuf gk_part, gk_res;  // omc_price_american_greeks: per-workgroup partials, reduced sums
     struct FoldKey { int N = -1; double c0 = 0, g = 0; } fold_key[2];
     int world = 1;  // ranks whose sums the hook / communicator adds up (equal shards)
     omc_allreduce_fn hook = nullptr;
@@ -1201,6 +1203,104 @@ int omc_price_american(omc_ctx* c, const omc_params* p, omc_result* res, float* 
                 c->distributed() ? c->world : 1);  // distributed: sums are global
     res->folded = (!S_keep && fold_applies(c, p)) ? 1 : 0;
     return read_kernel_times(c->ev, p, res);
+}
+
+// ------------------------------------------------------------------ pathwise Greeks of the two-pass flow
+// Paths as omc_price_american stores them (plan_storage), pass 1 and its fits -- or the caller's fits -- then ONE sweep
+// that prices the base, S0 (1 + h) and S0 (1 - h) scenarios with the frozen fits and forms every Greek term from the
+// chains' (exercise spot, exercise step) pairs (omc_greeks.hip).  It replaces pass 2: the base scenario takes pass 2's
+// decisions with pass 2's expressions, so counts are those of omc_price_american and the price differs only in the
+// order of its float64 sum.
+int omc_price_american_greeks(omc_ctx* c, const omc_params* p, double bump, const double* betas, double* betas_out,
+                              omc_greeks* out)
+{
+    int rc;
+    if ((rc = bind(c))) return rc;
+    if (!out) return fail(-7, "null result pointer.");
+    if ((rc = check_params(p))) return rc;
+    if (p->semantics != OMC_SEM_TWO_PASS) return fail(-4, "Greeks are those of the two-pass flow (semantics 2).");
+    if (!(bump > 0.0 && bump <= 0.5)) return fail(-4, "bump must lie in (0, 0.5].");
+    if (c->distributed()) return fail(-10, "the Greeks sweep runs on one GPU.");
+    const int64_t M = p->n_paths;
+    const int N = p->n_steps;
+    int64_t ld = 0;
+    const double* cK = nullptr;
+    if ((rc = plan_storage(c, p, 0, &ld, &cK))) return rc;
+    if ((rc = c->S.ensure(sizeof(float) * (size_t)ld * (size_t)(N + 1)))) return rc;
+    float* S = (float*)c->S.p;
+    omc::LsmWorkspace w;
+    if ((rc = prepare_lsm(c, M, N, p->r, p->T, betas == nullptr, betas_out != nullptr, &w))) return rc;
+    if (betas) {
+        HIP_TRY(hipMemcpyAsync(w.betas, betas, sizeof(double) * 4 * (size_t)(N + 1), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));  // `betas` is caller memory
+    }
+    omc::GreeksArgs g;
+    g.S = S; g.ld = ld; g.cols = cK ? M / 2 : M;
+    g.N = N; g.is_put = p->is_put ? 1 : 0; g.gbm = p->model == OMC_MODEL_GBM ? 1 : 0;
+    g.K = p->K; g.S0 = p->S0; g.r = p->r; g.sigma = p->sigma; g.T = p->T; g.h = bump;
+    g.D = w.D; g.betas = w.betas; g.cK = cK; g.gmom = betas ? nullptr : w.gmom;
+    const int64_t nblk = omc::greeks_blocks(g);
+    if ((rc = c->gk_part.ensure(sizeof(double) * omc::kGreeksQ * (size_t)nblk))) return rc;
+    if ((rc = c->gk_res.ensure(sizeof(double) * omc::kGreeksQ))) return rc;
+    g.part = (double*)c->gk_part.p;
+    g.result = (double*)c->gk_res.p;
+    omc::LsmProblem prob{S, ld, M, N, p->is_put ? 1 : 0, p->K, p->r, p->T};
+    prob.fold_cK = cK;
+    w.ev_p1_end = c->ev[4];
+    HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+    if ((rc = enqueue_paths(c, p, S, ld, cK != nullptr))) return rc;
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    const bool fit = betas == nullptr && N >= 2;
+    if (fit) {
+        HIP_TRY(omc::lsm_pass1_moments(c->stream, prob, w));
+        HIP_TRY(omc::lsm_solve_betas(c->stream, w.gmom, w.betas, N));
+    }
+    HIP_TRY(omc::lsm_greeks(c->stream, g, c->ev[5], c->ev[6]));
+    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+    double h[omc::kGreeksQ];
+    HIP_TRY(hipMemcpyAsync(h, g.result, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    if (betas_out) {
+        if (betas) memcpy(betas_out, betas, sizeof(double) * 4 * (size_t)(N + 1));
+        else HIP_TRY(hipMemcpyAsync(betas_out, w.betas, sizeof(double) * 4 * (size_t)(N + 1), hipMemcpyDeviceToHost, c->stream));
+    }
+    if ((rc = wait_stream(c))) return rc;
+    memset(out, 0, sizeof *out);
+    fill_result(&out->base, h, M);
+    out->base.folded = cK ? 1 : 0;
+    const double Md = (double)M;
+    auto mean_se = [&](int q, double* mean, double* se) {
+        *mean = h[q] / Md;
+        const double var = h[q + 1] / Md - *mean * *mean;
+        *se = std::sqrt((var > 0.0 ? var : 0.0) / Md);
+    };
+    mean_se(8, &out->delta, &out->se_delta);
+    mean_se(10, &out->gamma, &out->se_gamma);
+    if (g.gbm) {
+        mean_se(12, &out->vega, &out->se_vega);
+        mean_se(14, &out->rho, &out->se_rho);
+        mean_se(16, &out->theta, &out->se_theta);
+    } else {  // no map from the stored spot to the variance path's parameters
+        out->vega = out->rho = out->theta = NAN;
+        out->se_vega = out->se_rho = out->se_theta = NAN;
+    }
+    out->bump = bump;
+    out->price_up = h[5] / Md;
+    out->price_down = h[6] / Md;
+    out->n_exercised_up = (int64_t)llround(h[18]);
+    out->n_exercised_down = (int64_t)llround(h[19]);
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    out->base.ms_paths = ms;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[1], c->ev[2]));
+    out->base.ms_lsm = ms;
+    out->base.ms_total = out->base.ms_paths + out->base.ms_lsm;
+    if (fit) {
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev[1], c->ev[4]));
+        out->base.ms_pass1 = ms;
+    }
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[5], c->ev[6]));
+    out->ms_greeks = ms;
+    return 0;
 }
 
 // ------------------------------------------------------------------ per-step ContNet flow (v1 / v2 regressor)
