@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define OMC_ABI_VERSION 10
+#define OMC_ABI_VERSION 11
 
 typedef struct omc_ctx omc_ctx;
 
@@ -116,6 +116,11 @@ int omc_memcpy_d2h(omc_ctx* ctx, void* dst, const void* src, size_t bytes);
  * normals, same first partners bit for bit, partner spots equal to the stored float32 ones up to their rounding (prices
  * agree to ~1e-6 relative; omc_result.folded says which storage a pricing used; oracle: orc_lsm_two_pass_folded).
  * Full storage = both partners, the layout omc_gbm_paths + omc_lsm produce),
+ * "pass2_tables" (1 = default: pass 2 of the two-pass flow on folded storage decides from per-step float32 exercise tables,
+ * the spot bit patterns at which its float64 decision switches, built by one small kernel right before the sweep; 0 = the
+ * float64 decisions per spot; both give the same decisions, so the same results bit for bit),
+ * "pass2_tables_irregular_every" (tests: k > 0 marks every k-th step of the tables irregular, i.e. decided by the float64
+ * fallback inside the table sweep; 0 = default, none),
  * "gbm_vec" / "heston_vec" (pairs per thread: 1,2,4; 0 = auto), "world_size" (ranks behind
  * the all-reduce hook, see below), "step_graph" (1 / 0: replay the per-step sweep as one captured HIP
  * graph or launch its kernels one by one; -1 = default, off: same speed at 1M x 252, and a capture per new
@@ -285,6 +290,13 @@ typedef struct {
 } omc_greeks;
 int omc_price_american_greeks(omc_ctx* ctx, const omc_params* p, double bump, const double* betas, double* betas_out,
                               omc_greeks* out);
+/* Tests of pass 2's exercise tables (option "pass2_tables"): builds the tables of the fits `betas` [n_steps+1][4]
+ * (b0, b1, b2, regression-set size; as omc_price_american_greeks returns them) and cK [n_steps+1] (the folded partner's
+ * C_t / K) on the device, then compares the table decision with the sweep's float64 decision at every non-negative
+ * float32 spot, for the stored path and its partner: mismatches [n_steps+1][2] (host), irregular [n_steps+1] (host: 1 =
+ * the step keeps the float64 decisions and is not compared).  irregular_every > 0 forces every k-th step irregular. */
+int omc_pass2_tables_check(omc_ctx* ctx, int is_put, double K, int n_steps, const double* betas, const double* cK,
+                           int irregular_every, int64_t* mismatches, int* irregular);
 /* European discounted payoff from terminal values only (no path matrix): replaces
  * price_european_streaming options_model_3.py:382-437; sums2 host {sum, sumsq} */
 int omc_price_european(omc_ctx* ctx, const omc_params* p, omc_result* res);

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _build
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 SEMANTICS = {"reference": 0, "textbook": 1, "two_pass": 2}
 MODELS = {"gbm": 0, "heston": 1}
@@ -107,6 +107,7 @@ SIGNATURES = {
     "omc_p2p_status": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
     "omc_price_american": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Result), _P, _I64]),
     "omc_price_american_greeks": (C.c_int, [_P, C.POINTER(Params), _D, _P, _P, C.POINTER(Greeks)]),
+    "omc_pass2_tables_check": (C.c_int, [_P, _I, _D, _I, _P, _P, _I, _P, _P]),
     "omc_price_european": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Result)]),
     "omc_heston_price_strikes": (C.c_int, [_P, _I64, _I] + [_D] * 8 + [_U64, _U64, _I, _P, _I, _I, _P, _P]),
     "omc_heston_price_surface": (C.c_int, [_P, _I64, _I] + [_D] * 7 + [_U64, _I, _P, _P, _I, _P, _P, _I, _I, _P, _P]),
@@ -535,6 +536,21 @@ class Context:
             self.handle, C.byref(params), C.byref(res), keep_paths.ptr if keep_paths else None,
             keep_paths.shape[1] if keep_paths else 0))
         return res.as_dict()
+
+    def pass2_tables_check(self, is_put, K, betas, cK, irregular_every=0):
+        """omc_pass2_tables_check -> (mismatches [N+1][2] int64, irregular [N+1] bool): pass 2's exercise tables of the fits
+        `betas` [N+1][4] and cK [N+1] against the float64 decisions at every non-negative float32 spot."""
+        b = np.ascontiguousarray(betas, np.float64)
+        ck = np.ascontiguousarray(cK, np.float64)
+        N = b.shape[0] - 1
+        if b.shape != (N + 1, 4) or ck.shape != (N + 1,):
+            raise ValueError("betas must be [N+1][4] and cK [N+1].")
+        mism = np.zeros((N + 1, 2), np.int64)
+        irr = np.zeros(N + 1, np.int32)
+        _check(self.lib, self.lib.omc_pass2_tables_check(self.handle, int(bool(is_put)), float(K), N, b.ctypes.data,
+                                                         ck.ctypes.data, int(irregular_every), mism.ctypes.data,
+                                                         irr.ctypes.data))
+        return mism, irr.astype(bool)
 
     def price_american_greeks(self, params: Params, bump=0.01, betas=None, want_betas=False):
         """Frozen-policy pathwise Greeks of the two-pass flow (omc_price_american_greeks) -> dict: the base pricing's keys

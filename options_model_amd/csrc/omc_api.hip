@@ -107,7 +107,7 @@ struct omc_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
-    DevBuf S, sx, tex, ex, D, part, gmom, betas, part1, result, scratch, sweep_args;
+    DevBuf S, sx, tex, ex, D, part, gmom, betas, part1, result, scratch, sweep_args, crit;
     DevBuf bslab, btable, bres, bdisc;  // batched path: problem slab, table, results, discounts
     DevBuf mlp_part, mlp_loss, mlp_wt;  // NN training: gradient partials, epoch loss, transposed connections
     DevBuf mlp_gred, shard;             // sharded NN training: reduced gradient of a step; epoch selection tables
@@ -145,6 +145,10 @@ struct omc_ctx {
     // 1 = default: pricings of at least kFoldMinPaths paths over all ranks, 2 always): two cK tables (the overlapped
     // sequence has two pricings in flight), each remembered by what it was filled from
     int fold = 1;
+    // pass 2 of the two-pass flow decides from per-step float32 exercise tables (option "pass2_tables": 1 = default,
+    // 0 = the float64 decisions; the same decisions either way)
+    int pass2_tables = 1;
+    int pass2_irr_every = 0;  // tests (option "pass2_tables_irregular_every"): every k-th step decided by the float64 fallback
     DevBuf foldC;
     DevBuf gk_part, gk_res;  // omc_price_american_greeks: per-workgroup partials, reduced sums
     struct FoldKey { int N = -1; double c0 = 0, g = 0; } fold_key[2];
@@ -269,6 +273,12 @@ int prepare_lsm(omc_ctx* c, int64_t M, int N, double r, double T, bool two_pass,
     if ((rc = c->result.ensure(sizeof(double) * 8))) return rc;
     w->part1 = nullptr;
     w->part1_tiles = 0;
+    w->crit = nullptr;
+    if (two_pass && c->pass2_tables) {
+        if ((rc = c->crit.ensure(sizeof(uint32_t) * 8 * (size_t)(N + 1)))) return rc;
+        w->crit = (uint32_t*)c->crit.p;
+    }
+    w->crit_irr_every = c->pass2_irr_every;
     if (two_pass) {
         const size_t tiles = omc::lsm_part1_tiles(M);
         if ((rc = c->part1.ensure(sizeof(double) * 8 * (size_t)(N + 1) * tiles))) return rc;
@@ -587,7 +597,7 @@ int omc_ctx_destroy(omc_ctx* c)
     for (DevBuf* b : {&c->S, &c->sx, &c->tex, &c->ex, &c->D, &c->part, &c->gmom, &c->betas, &c->part1,
                       &c->result, &c->scratch, &c->sweep_args, &c->bslab, &c->btable, &c->bres, &c->bdisc,
                       &c->mlp_part, &c->mlp_loss, &c->mlp_wt, &c->mlp_gred, &c->shard, &c->S2, &c->seq_local, &c->part1b, &c->gmomb, &c->seq_vote, &c->cn_scratch, &c->cn_data, &c->cn_net, &c->cn_cont,
-                      &c->mS, &c->mstate, &c->mtable, &c->mb_slab, &c->mb_table, &c->mb_bc})
+                      &c->mS, &c->mstate, &c->mtable, &c->mb_slab, &c->mb_table, &c->mb_bc, &c->crit})
         b->release();
     if (c->sweep_pin) (void)hipHostFree(c->sweep_pin);
     if (c->mtab_pin) (void)hipHostFree(c->mtab_pin);
@@ -680,6 +690,8 @@ int omc_set_option(omc_ctx* c, const char* key, int64_t value)
     if (!strcmp(key, "gbm_vec")) c->gbm_vec = (int)value;
     else if (!strcmp(key, "alloc_limit")) g_alloc_limit = value > 0 ? (size_t)value : 0;
     else if (!strcmp(key, "fold_antithetic")) c->fold = value <= 0 ? 0 : (value >= 2 ? 2 : 1);
+    else if (!strcmp(key, "pass2_tables")) c->pass2_tables = value ? 1 : 0;
+    else if (!strcmp(key, "pass2_tables_irregular_every")) c->pass2_irr_every = value > 0 ? (int)value : 0;
     else if (!strcmp(key, "heston_vec")) c->heston_vec = (int)value;
     else if (!strcmp(key, "world_size")) c->world = value > 0 ? (int)value : 1;
     else if (!strcmp(key, "step_graph")) c->step_graph = value < 0 ? -1 : (value ? 1 : 0);
@@ -1211,6 +1223,31 @@ int omc_price_american(omc_ctx* c, const omc_params* p, omc_result* res, float* 
 // chains' (exercise spot, exercise step) pairs (omc_greeks.hip).  It replaces pass 2: the base scenario takes pass 2's
 // decisions with pass 2's expressions, so counts are those of omc_price_american and the price differs only in the
 // order of its float64 sum.
+int omc_pass2_tables_check(omc_ctx* c, int is_put, double K, int n_steps, const double* betas, const double* cK,
+                           int irregular_every, int64_t* mismatches, int* irregular)
+{
+    if (!c || !betas || !cK || !mismatches || !irregular) return fail(-7, "null pointer.");
+    if (n_steps < 1 || n_steps > omc::kMaxSteps || !(K > 0.0)) return fail(-4, "invalid n_steps or strike.");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n1 = (size_t)n_steps + 1;
+    const size_t o_cK = sizeof(double) * 4 * n1, o_tab = o_cK + sizeof(double) * n1, o_mism = o_tab + sizeof(uint32_t) * 8 * n1,
+                 bytes = o_mism + sizeof(unsigned long long) * 2 * n1;
+    int rc;
+    if ((rc = c->scratch.ensure(bytes))) return rc;
+    char* b = (char*)c->scratch.p;
+    HIP_TRY(hipMemcpyAsync(b, betas, sizeof(double) * 4 * n1, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(b + o_cK, cK, sizeof(double) * n1, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(b + o_mism, 0, sizeof(unsigned long long) * 2 * n1, c->stream));
+    HIP_TRY(omc::lsm_crit_check(c->stream, (const double*)b, (const double*)(b + o_cK), (uint32_t*)(b + o_tab), n_steps,
+                                is_put ? 1 : 0, K, irregular_every, (unsigned long long*)(b + o_mism)));
+    std::vector<uint32_t> tab(8 * n1);
+    HIP_TRY(hipMemcpyAsync(tab.data(), b + o_tab, sizeof(uint32_t) * 8 * n1, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(mismatches, b + o_mism, sizeof(int64_t) * 2 * n1, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (size_t t = 0; t < n1; ++t) irregular[t] = tab[8 * t] == 0xffffffffu || tab[8 * t + 4] == 0xffffffffu;
+    return 0;
+}
+
 int omc_price_american_greeks(omc_ctx* c, const omc_params* p, double bump, const double* betas, double* betas_out,
                               omc_greeks* out)
 {

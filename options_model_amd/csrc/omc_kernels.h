@@ -100,6 +100,10 @@ struct LsmWorkspace {
     double* result;   // [8] sum, sumsq, n_exercised, n_zero, sum_nitm, -, -, -
     const float* cont = nullptr;  // per-step sweeps, "values" mode: continuation values [N+1][ldc]
     int64_t ldc = 0;
+    // two-pass flow, option "pass2_tables": pass 2's per-step exercise tables [N+1][8] (omc_crit.h); null = the sweep
+    // decides with its float64 arithmetic
+    uint32_t* crit = nullptr;
+    int crit_irr_every = 0;  // tests: every k-th step of the tables marked irregular (option "pass2_tables_irregular_every")
     // optional: events recorded right around the two big kernels of the two-pass flow
     hipEvent_t ev_p1_begin = nullptr, ev_p1_end = nullptr, ev_p2_begin = nullptr, ev_p2_end = nullptr;
 };
@@ -152,6 +156,11 @@ hipError_t lsm_pass1_moments(hipStream_t st, const LsmProblem& p, const LsmWorks
 // when write_state, leaves sums in w.result
 hipError_t lsm_pass2_apply(hipStream_t st, const LsmProblem& p, const LsmWorkspace& w,
                            bool write_state, bool solve_from_moments = false);
+// tests: pass 2's exercise tables from the fits `betas` [N+1][4] and cK [N+1] (device) into tab [N+1][8], then the
+// table decisions against the float64 ones at every non-negative float32 spot: mismatches per step and kind into
+// mism [N+1][2] (device, zeroed by the caller); irregular steps are not checked
+hipError_t lsm_crit_check(hipStream_t st, const double* betas, const double* cK, uint32_t* tab, int N, int is_put,
+                          double K, int irr_every, unsigned long long* mism);
 
 // valuation of (sx,tex): sums into w.result ; tval = 1 (reference flows) or 0 (textbook);
 // use_flags: state of the per-step reference sweep (w.live: unexercised paths take (S_N, N)),

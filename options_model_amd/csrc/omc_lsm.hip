@@ -61,8 +61,17 @@ __global__ __launch_bounds__(kBlock) void lsm_pass2_kernel(Pass2Args a) { lsm_pa
 // the two sweeps on the antithetic-folded matrix (omc_lsm_dev.h)
 template <int VEC, int TPW, int PUT>
 __global__ __launch_bounds__(kBlock) void lsm_pass1_fold_kernel(Pass1Args a) { lsm_pass1_fold_body<VEC, TPW, PUT>(a); }
-template <int VEC, int PUT>
-__global__ __launch_bounds__(kBlock) void lsm_pass2_fold_kernel(Pass2Args a) { lsm_pass2_fold_body<VEC, PUT>(a); }
+template <int VEC, int PUT, bool TAB>
+__global__ __launch_bounds__(kBlock) void lsm_pass2_fold_kernel(Pass2Args a) { lsm_pass2_fold_body<VEC, PUT, TAB>(a); }
+
+// pass 2's per-step exercise tables: one workgroup per step t = 0 .. N, a wave per path kind (omc_crit.h)
+__global__ __launch_bounds__(128) void lsm_crit_build_kernel(CritArgs a) { lsm_crit_build_body(a); }
+__global__ __launch_bounds__(kBlock) void lsm_crit_check_kernel(const uint32_t* tab, const double* betas, const double* cK,
+                                                                int N, int is_put, double K, double invK,
+                                                                unsigned long long* mism)
+{
+    lsm_crit_check_body(tab, betas, cK, N, is_put, K, invK, mism);
+}
 
 // cK[t] = c0 g^t, t = 0 .. N, by N sequential float64 multiplications (IEEE: the host oracle repeats them exactly)
 __global__ void lsm_fold_table_kernel(double* __restrict__ cK, int N, double c0, double g)
@@ -444,6 +453,18 @@ hipError_t lsm_pass2_apply(hipStream_t st, const LsmProblem& p, const LsmWorkspa
     const size_t dyn = sizeof(double) * 4 * (size_t)(p.N + 1);
     const bool v4 = vec4_ok(p);
     if (w.ev_p2_begin) (void)hipEventRecord(w.ev_p2_begin, st);
+    // exercise tables (option "pass2_tables"): built from the fits right before the sweep, which then reads the fits
+    // the table kernel solved (or was given) from w.betas instead of solving all N in every workgroup
+    const bool tab = w.crit != nullptr && p.fold_cK != nullptr && !write_state;
+    if (tab) {
+        CritArgs c;
+        c.gmom = a.gmom; c.betas = w.betas; c.betas_out = a.betas_out; c.cK = p.fold_cK; c.tab = w.crit;
+        c.N = p.N; c.is_put = p.is_put; c.K = a.K; c.invK = a.invK; c.irr_every = w.crit_irr_every;
+        hipLaunchKernelGGL(lsm_crit_build_kernel, dim3(p.N + 1), dim3(128), 0, st, c);
+        a.gmom = nullptr;
+        a.betas_out = nullptr;
+        a.crit = w.crit;
+    }
     if (p.fold_cK) {  // the folded matrix: M / 2 stored columns, both partners decided from every spot; no state arrays
         if (write_state) return hipErrorInvalidValue;
         a.M = p.M / 2;
@@ -451,8 +472,13 @@ hipError_t lsm_pass2_apply(hipStream_t st, const LsmProblem& p, const LsmWorkspa
         const bool f4 = (a.M % 4) == 0 && (p.ld % 4) == 0 && ((uintptr_t)p.S % 16) == 0;
         auto launch = [&](auto vec) {
             constexpr int V = decltype(vec)::value;
-            if (p.is_put) hipLaunchKernelGGL((lsm_pass2_fold_kernel<V, 1>), dim3(nblk), dim3(kBlock), dyn, st, a);
-            else hipLaunchKernelGGL((lsm_pass2_fold_kernel<V, 0>), dim3(nblk), dim3(kBlock), dyn, st, a);
+            if (tab) {
+                if (p.is_put) hipLaunchKernelGGL((lsm_pass2_fold_kernel<V, 1, true>), dim3(nblk), dim3(kBlock), dyn, st, a);
+                else hipLaunchKernelGGL((lsm_pass2_fold_kernel<V, 0, true>), dim3(nblk), dim3(kBlock), dyn, st, a);
+            } else {
+                if (p.is_put) hipLaunchKernelGGL((lsm_pass2_fold_kernel<V, 1, false>), dim3(nblk), dim3(kBlock), dyn, st, a);
+                else hipLaunchKernelGGL((lsm_pass2_fold_kernel<V, 0, false>), dim3(nblk), dim3(kBlock), dyn, st, a);
+            }
         };
         if (f4 && fvec == 4) launch(std::integral_constant<int, 4>{});
         else if (f4 && fvec == 2) launch(std::integral_constant<int, 2>{});
@@ -467,6 +493,19 @@ hipError_t lsm_pass2_apply(hipStream_t st, const LsmProblem& p, const LsmWorkspa
     if (w.ev_p2_end) (void)hipEventRecord(w.ev_p2_end, st);
     hipLaunchKernelGGL(lsm_finalize_kernel, dim3(1), dim3(kBlock), 0, st, w.part, w.gmom, w.result,
                        nblk, p.N, kPStride);
+    return hipGetLastError();
+}
+
+hipError_t lsm_crit_check(hipStream_t st, const double* betas, const double* cK, uint32_t* tab, int N, int is_put,
+                          double K, int irr_every, unsigned long long* mism)
+{
+    CritArgs c;
+    c.gmom = nullptr; c.betas = betas; c.betas_out = nullptr; c.cK = cK; c.tab = tab;
+    c.N = N; c.is_put = is_put; c.K = K; c.invK = 1.0 / K; c.irr_every = irr_every;
+    hipLaunchKernelGGL(lsm_crit_build_kernel, dim3(N + 1), dim3(128), 0, st, c);
+    if (N >= 2)
+        hipLaunchKernelGGL(lsm_crit_check_kernel, dim3(2048, N - 1), dim3(kBlock), 0, st, tab, betas, cK, N, is_put, K,
+                           c.invK, mism);
     return hipGetLastError();
 }
 

@@ -6,6 +6,7 @@
 #pragma once
 #include "omc_device.h"
 #include "omc_kernels.h"
+#include "omc_crit.h"
 #include <type_traits>
 
 namespace omc {
@@ -817,7 +818,157 @@ struct Pass2Args {
     const double* gmom = nullptr;
     double* betas_out = nullptr;
     const double* cK = nullptr;  // antithetic-folded storage (lsm_pass2_fold_body): see Pass1Args::cK; M = stored columns
+    // exercise tables of lsm_crit_build_body ([N+1][8]: the stored path's CritIv, then the partner's): the sweeps built
+    // with TAB decide from them; the fits are then read from `betas`, which the table kernel has filled
+    const uint32_t* crit = nullptr;
 };
+
+// ------------------------------------------------------------------ pass-2 exercise tables (omc_crit.h)
+// The decisions of the two sweeps below, as functions of the loaded spot: the expressions of `decide`, verbatim.
+struct CritStored {
+    double K, invK, b0, b1, b2;
+    int is_put;
+    __device__ bool operator()(float s) const
+    {
+        const double sd = (double)s;
+        const double imm = is_put ? K - sd : sd - K;
+        const double u = fma(sd, invK, -1.0);
+        const double cont = fma(u, fma(u, b2, b1), b0);
+        return (imm > 0.0) & (imm > cont);
+    }
+};
+struct CritPartner {
+    double K, ck, b0, b1, b2;
+    int is_put;
+    __device__ bool operator()(float s) const
+    {
+        const double ub = fold_u(ck, s);
+        const double immb = fold_pay(ub, K, is_put);
+        const double contb = fma(ub, fma(ub, b2, b1), b0);
+        return (immb > 0.0) & (immb > contb);
+    }
+};
+struct CritEither {
+    CritStored a;
+    CritPartner b;
+    int kind;
+    __device__ bool operator()(float s) const { return kind ? b(s) : a(s); }
+};
+constexpr uint32_t kCritIrregular = 0xffffffffu;  // lo[0] of an irregular step (a real lo is <= kCritTop)
+
+struct CritArgs {
+    const double* gmom;  // non-null: solve the fits from the reduced moments (and write them to betas_out) ...
+    const double* betas;  // ... else take them from here
+    double* betas_out;
+    const double* cK;  // null: no partner (full storage)
+    uint32_t* tab;     // [N+1][8]
+    int N, is_put;
+    double K, invK;
+    int irr_every = 0;  // tests: > 0 marks every step t with t % irr_every == 0 irregular (option "pass2_tables_irregular_every")
+};
+
+// One workgroup of 128 threads per step t = 0 .. N: wave 0 builds the stored path's intervals, wave 1 the partner's.
+// The fits are those pass 2 used to solve in its prologue: solve_poly2 of gmom[t], no fit where m[0] <= 0.5.
+__device__ __forceinline__ void lsm_crit_build_body(CritArgs a)
+{
+    const int t = (int)blockIdx.x, kind = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+    const int N = a.N;
+    const bool inner = t >= 1 && t < N;
+    double beta[3] = {0.0, 0.0, 0.0};
+    bool fit = false;
+    if (a.gmom) {
+        double m[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) m[q] = inner ? a.gmom[(size_t)t * 8 + q] : 0.0;
+        if (inner) solve_poly2(m, beta);
+        fit = inner && m[0] > 0.5;
+        if (inner && kind == 0 && lane == 0 && a.betas_out) {
+            double* bo = a.betas_out + (size_t)t * 4;
+            bo[0] = beta[0]; bo[1] = beta[1]; bo[2] = beta[2]; bo[3] = m[0];
+        }
+    } else if (inner) {
+        fit = a.betas[(size_t)t * 4 + 3] > 0.5;
+        if (fit) {
+            beta[0] = a.betas[(size_t)t * 4];
+            beta[1] = a.betas[(size_t)t * 4 + 1];
+            beta[2] = a.betas[(size_t)t * 4 + 2];
+        }
+    }
+    const double b0 = fit ? beta[0] : __builtin_huge_val(), b1 = fit ? beta[1] : 0.0, b2 = fit ? beta[2] : 0.0;
+    CritIv iv;
+    iv.lo[0] = iv.lo[1] = iv.len[0] = iv.len[1] = 0;
+    if (inner && (kind == 0 || a.cK)) {
+        const double ck = kind ? a.cK[t] : 0.0;
+        double cand[kCritMaxCand];
+        const int n = crit_candidates(kind, a.is_put, a.K, ck, b0, b1, b2, cand);
+        bool ok = n >= 0 && !(a.irr_every > 0 && t % a.irr_every == 0);
+        // one instantiation of the builder for both kinds: its code is fetched cold by every CU the launch reaches
+        if (ok) ok = crit_build(CritEither{CritStored{a.K, a.invK, b0, b1, b2, a.is_put},
+                                           CritPartner{a.K, ck, b0, b1, b2, a.is_put}, kind}, cand, n, iv);
+        if (!ok) {
+            iv.lo[0] = kCritIrregular;
+            iv.lo[1] = iv.len[0] = iv.len[1] = 0;
+        }
+    }
+    if (lane == 0) {
+        uint32_t* o = a.tab + (size_t)t * 8 + 4 * kind;
+        o[0] = iv.lo[0]; o[1] = iv.lo[1]; o[2] = iv.len[0]; o[3] = iv.len[1];
+    }
+}
+
+// The sweeps' table prologue: tab -> LDS ([N+1][8]), an irregular partner marking its step's stored half; returns
+// whether any step is irregular (the sweep then takes the loop that checks every step).  Block-wide, every thread.
+__device__ __forceinline__ bool crit_load_tables(const uint32_t* __restrict__ tab, uint32_t* sh_t, int N)
+{
+    int irr = 0;
+    for (int t = threadIdx.x; t <= N; t += kBlock) {
+        const uint4 x = *reinterpret_cast<const uint4*>(tab + (size_t)t * 8);
+        const uint4 y = *reinterpret_cast<const uint4*>(tab + (size_t)t * 8 + 4);
+        const bool bad = x.x == kCritIrregular || y.x == kCritIrregular;
+        irr |= bad;
+        *reinterpret_cast<uint4*>(sh_t + 8 * t) = make_uint4(bad ? kCritIrregular : x.x, x.y, x.z, x.w);
+        *reinterpret_cast<uint4*>(sh_t + 8 * t + 4) = y;
+    }
+    return __syncthreads_or(irr) != 0;
+}
+
+// the fits of step t as the float64 decisions use them (an irregular step of a table sweep reads them here)
+__device__ __forceinline__ void crit_fits(const double* __restrict__ betas, int t, int N, double& b0, double& b1,
+                                          double& b2)
+{
+    const bool fit = t >= 1 && t < N && betas[(size_t)t * 4 + 3] > 0.5;
+    b0 = fit ? betas[(size_t)t * 4] : __builtin_huge_val();
+    b1 = fit ? betas[(size_t)t * 4 + 1] : 0.0;
+    b2 = fit ? betas[(size_t)t * 4 + 2] : 0.0;
+}
+
+// Tests: for step t = 1 + blockIdx.y, the table decision against the float64 decision at EVERY non-negative float32
+// (bit patterns 0 .. kCritTop), both kinds; mismatches are added to mism[2 t + kind].  Irregular steps are skipped: the
+// sweeps decide them with the float64 code.
+__device__ __forceinline__ void lsm_crit_check_body(const uint32_t* __restrict__ tab, const double* __restrict__ betas,
+                                                    const double* __restrict__ cK, int N, int is_put, double K,
+                                                    double invK, unsigned long long* mism)
+{
+    const int t = 1 + (int)blockIdx.y;
+    CritIv ia, ib;
+    ia.lo[0] = tab[(size_t)t * 8]; ia.lo[1] = tab[(size_t)t * 8 + 1]; ia.len[0] = tab[(size_t)t * 8 + 2]; ia.len[1] = tab[(size_t)t * 8 + 3];
+    ib.lo[0] = tab[(size_t)t * 8 + 4]; ib.lo[1] = tab[(size_t)t * 8 + 5]; ib.len[0] = tab[(size_t)t * 8 + 6]; ib.len[1] = tab[(size_t)t * 8 + 7];
+    if (ia.lo[0] == kCritIrregular || ib.lo[0] == kCritIrregular) return;
+    double b0, b1, b2;
+    crit_fits(betas, t, N, b0, b1, b2);
+    const CritStored pa{K, invK, b0, b1, b2, is_put};
+    const CritPartner pb{K, cK[t], b0, b1, b2, is_put};
+    unsigned ma = 0, mb = 0;
+    const uint64_t n = (uint64_t)kCritTop + 1, stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t o = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; o < n; o += stride) {
+        const uint32_t bits = (uint32_t)o;
+        const float s = __uint_as_float(bits);
+        ma += pa(s) != crit_in(ia, bits);
+        mb += pb(s) != crit_in(ib, bits);
+    }
+    if (ma) atomicAdd(mism + 2 * t, (unsigned long long)ma);
+    if (mb) atomicAdd(mism + 2 * t + 1, (unsigned long long)mb);
+}
 
 // Pass 2 (options_model_3.py:615-651) with frozen per-step fits: every path is
 // independent, so one thread walks its VEC paths backward through all steps and stops as
@@ -932,45 +1083,56 @@ __device__ __forceinline__ void lsm_pass2_body(Pass2Args a)
 // every spot it loads; it stops when all 2 VEC paths have exercised.  A partner that exercises remembers the STORED
 // path's spot at that step (its own value is fold_pay(fold_u(cK[t], spot))): the valuation below recomputes it with the
 // very expressions of the decision.  The fits' table keeps cK[t] in its fourth slot.
-template <int VEC, int PUT = -1>
+// TAB: decide from the exercise tables of lsm_crit_build_body (a.crit; the fits in a.betas) -- per spot and partner two
+// unsigned interval tests on its bit pattern instead of the float64 arithmetic; irregular steps keep the float64 code.
+template <int VEC, int PUT = -1, bool TAB = false>
 __device__ __forceinline__ void lsm_pass2_fold_body(Pass2Args a)
 {
     if ((int)blockIdx.x >= a.nblk) return;
     __shared__ double red[kNQ * kRedStride];
-    extern __shared__ double sh_b[];  // [N+1][4]: b0, b1, b2, cK
+    extern __shared__ double sh_b[];  // [N+1][4]: b0, b1, b2, cK -- or, TAB, the tables [N+1][8] (uint32)
+    uint32_t* sh_t = reinterpret_cast<uint32_t*>(sh_b);
     const int tid = threadIdx.x;
     const int N = a.N;
-    if (a.gmom) {
-        for (int t = tid; t <= N; t += kBlock) {
-            double m[8], beta[3] = {0.0, 0.0, 0.0};
-            const bool inner = t >= 1 && t < N;
+    bool irr_any = false;
+    if (TAB) {
+        irr_any = crit_load_tables(a.crit, sh_t, N);
+    } else {
+        if (a.gmom) {
+            for (int t = tid; t <= N; t += kBlock) {
+                double m[8], beta[3] = {0.0, 0.0, 0.0};
+                const bool inner = t >= 1 && t < N;
 #pragma unroll
-            for (int q = 0; q < 8; ++q) m[q] = inner ? a.gmom[(size_t)t * 8 + q] : 0.0;
-            if (inner) solve_poly2(m, beta);
-            const bool fit = inner && m[0] > 0.5;
-            sh_b[4 * t] = fit ? beta[0] : __builtin_huge_val();
-            sh_b[4 * t + 1] = fit ? beta[1] : 0.0;
-            sh_b[4 * t + 2] = fit ? beta[2] : 0.0;
-            sh_b[4 * t + 3] = a.cK[t];
-            if (blockIdx.x == 0 && inner && a.betas_out) {
-                double* bo = a.betas_out + (size_t)t * 4;
-                bo[0] = beta[0]; bo[1] = beta[1]; bo[2] = beta[2]; bo[3] = m[0];
+                for (int q = 0; q < 8; ++q) m[q] = inner ? a.gmom[(size_t)t * 8 + q] : 0.0;
+                if (inner) solve_poly2(m, beta);
+                const bool fit = inner && m[0] > 0.5;
+                sh_b[4 * t] = fit ? beta[0] : __builtin_huge_val();
+                sh_b[4 * t + 1] = fit ? beta[1] : 0.0;
+                sh_b[4 * t + 2] = fit ? beta[2] : 0.0;
+                sh_b[4 * t + 3] = a.cK[t];
+                if (blockIdx.x == 0 && inner && a.betas_out) {
+                    double* bo = a.betas_out + (size_t)t * 4;
+                    bo[0] = beta[0]; bo[1] = beta[1]; bo[2] = beta[2]; bo[3] = m[0];
+                }
+            }
+        } else {
+            for (int k = tid; k < (N + 1) * 4; k += kBlock) {
+                const int t = k >> 2;
+                const bool fit = t >= 1 && t < N && a.betas[(size_t)t * 4 + 3] > 0.5;
+                sh_b[k] = (k & 3) == 3 ? a.cK[t] : (fit ? a.betas[k] : ((k & 3) == 0 ? __builtin_huge_val() : 0.0));
             }
         }
-    } else {
-        for (int k = tid; k < (N + 1) * 4; k += kBlock) {
-            const int t = k >> 2;
-            const bool fit = t >= 1 && t < N && a.betas[(size_t)t * 4 + 3] > 0.5;
-            sh_b[k] = (k & 3) == 3 ? a.cK[t] : (fit ? a.betas[k] : ((k & 3) == 0 ? __builtin_huge_val() : 0.0));
-        }
+        __syncthreads();
     }
-    __syncthreads();
     const double K = a.K, invK = a.invK;
     const int is_put = PUT < 0 ? a.is_put : PUT;  // (a compile-time side: the payoff is one subtraction, not two and a select)
     double acc[8];
 #pragma unroll
     for (int q = 0; q < 8; ++q) acc[q] = 0.0;
     const int64_t stride = (int64_t)a.nblk * kBlock * VEC;
+    // CHK (TAB only): some step is irregular -- every step looks at its flag (wave-uniform) before it decides
+    auto sweep = [&](auto chk) {
+    constexpr bool CHK = decltype(chk)::value;
     for (int64_t j = ((int64_t)blockIdx.x * kBlock + tid) * VEC; j < a.M; j += stride) {
         float sxa[VEC], sxb[VEC];
         int32_t texa[VEC], texb[VEC];
@@ -980,8 +1142,7 @@ __device__ __forceinline__ void lsm_pass2_fold_body(Pass2Args a)
             sxb[v] = sxa[v];
             texa[v] = texb[v] = N;
         }
-        auto decide = [&](const float (&row)[VEC], int t) {
-            const double b0 = sh_b[4 * t], b1 = sh_b[4 * t + 1], b2 = sh_b[4 * t + 2], ck = sh_b[4 * t + 3];
+        auto decide_f64 = [&](const float (&row)[VEC], int t, double b0, double b1, double b2, double ck) {
 #pragma unroll
             for (int v = 0; v < VEC; ++v) {
                 const double sd = (double)row[v];
@@ -999,13 +1160,41 @@ __device__ __forceinline__ void lsm_pass2_fold_body(Pass2Args a)
                 texb[v] = exb ? t : texb[v];
             }
         };
+        auto decide = [&](const float (&row)[VEC], int t) {
+            if constexpr (!TAB) {
+                decide_f64(row, t, sh_b[4 * t], sh_b[4 * t + 1], sh_b[4 * t + 2], sh_b[4 * t + 3]);
+            } else {
+                const uint4 ta = *reinterpret_cast<const uint4*>(sh_t + 8 * t);
+                if (CHK && __builtin_amdgcn_readfirstlane(ta.x) == kCritIrregular) {
+                    double b0, b1, b2;
+                    crit_fits(a.betas, t, N, b0, b1, b2);
+                    decide_f64(row, t, b0, b1, b2, a.cK[t]);
+                    return;
+                }
+                const uint4 tb = *reinterpret_cast<const uint4*>(sh_t + 8 * t + 4);
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) {
+                    const uint32_t bits = __float_as_uint(row[v]);
+                    const bool ex = (texa[v] == N) & (((bits - ta.x) < ta.z) | ((bits - ta.y) < ta.w));
+                    sxa[v] = ex ? row[v] : sxa[v];
+                    texa[v] = ex ? t : texa[v];
+                    const bool exb = (texb[v] == N) & (((bits - tb.x) < tb.z) | ((bits - tb.y) < tb.w));
+                    sxb[v] = exb ? row[v] : sxb[v];
+                    texb[v] = exb ? t : texb[v];
+                }
+            }
+        };
         auto live = [&]() {
             bool l = false;
 #pragma unroll
             for (int v = 0; v < VEC; ++v) l |= (texa[v] == N) | (texb[v] == N);
             return l;
         };
+#ifdef OMC_P2_U
+        constexpr int U = OMC_P2_U;
+#else
         constexpr int U = 8;
+#endif
         int t = N - 1;
         const float* col = a.S + j;
         // U rows per batch, the NEXT batch requested before the current one is worked on (the decisions of a batch are a
@@ -1017,8 +1206,11 @@ __device__ __forceinline__ void lsm_pass2_fold_body(Pass2Args a)
         };
         auto work = [&](const float (&b)[U][VEC], int tt) {
 #pragma unroll
-            for (int k = 0; k < U; ++k)
+            for (int k = 0; k < U; ++k) {
                 if (tt - k >= 1) decide(b[k], tt - k);
+                // TAB: one step's table words at a time (hoisted, a batch's would take 8 U registers)
+                if (TAB) __builtin_amdgcn_sched_barrier(0);
+            }
         };
         float bA[U][VEC], bB[U][VEC];
         if (t >= 1) fetch(bA, t);
@@ -1038,7 +1230,7 @@ __device__ __forceinline__ void lsm_pass2_fold_body(Pass2Args a)
             double p = payoff_d(sxa[v], K, is_put);
             p = p > 0.0 ? p : 0.0;
             const double cf = p * a.D[texa[v] - 1];
-            double pb = fold_pay(fold_u(sh_b[4 * texb[v] + 3], sxb[v]), K, is_put);
+            double pb = fold_pay(fold_u(TAB ? a.cK[texb[v]] : sh_b[4 * texb[v] + 3], sxb[v]), K, is_put);
             pb = pb > 0.0 ? pb : 0.0;
             const double cfb = pb * a.D[texb[v] - 1];
             acc[0] += cf;
@@ -1051,6 +1243,9 @@ __device__ __forceinline__ void lsm_pass2_fold_body(Pass2Args a)
             acc[3] += (cfb == 0.0) ? 1.0 : 0.0;
         }
     }
+    };
+    if (TAB && irr_any) sweep(std::true_type{});
+    else sweep(std::false_type{});
     const double s = block_reduce8(acc, red);
     if (tid < 64 && (tid & 7) == 0) a.part[(size_t)(tid >> 3) * a.pstride + blockIdx.x] = s;
 }
