@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define OMC_ABI_VERSION 11
+#define OMC_ABI_VERSION 12
 
 typedef struct omc_ctx omc_ctx;
 
@@ -300,6 +300,56 @@ int omc_pass2_tables_check(omc_ctx* ctx, int is_put, double K, int n_steps, cons
 /* European discounted payoff from terminal values only (no path matrix): replaces
  * price_european_streaming options_model_3.py:382-437; sums2 host {sum, sumsq} */
 int omc_price_european(omc_ctx* ctx, const omc_params* p, omc_result* res);
+
+/* ---- barrier options: knock-in / knock-out, European and American -------------------------- */
+/* The reference declares ExoticOptionPricer.price_barrier_option (options_model_2.py:61-67) as a stub; this is it.
+ * Paths: p's model, seed, stream and pair_offset, antithetic pairs only (p->antithetic = 1), spots bit-identical to
+ * omc_gbm_paths_f32 / omc_heston_paths_f32 wherever the option is live.
+ * Monitoring
+ *   OMC_MONITOR_DISCRETE    at grid steps t = 1..N: down barriers hit when (double)S_t <= H, up barriers when
+ *                           (double)S_t >= H (tested in float32 against the exact float32 threshold).
+ *   OMC_MONITOR_CONTINUOUS  GBM only: a partner not yet hit is also hit at step t when u_t < p_t, the Brownian-bridge
+ *                           crossing probability p_t = exp2((c x_{t-1}) x_t), c = -2 ln 2 / (sigma^2 dt) in float32,
+ *                           x_0 = float32(log2(float32(S0) / H)), x_t = x_{t-1} + (a + b z_t) in float32 -- the spot's own
+ *                           log2 increment (a - b z_t for the antithetic partner).  u_t: Philox4x32-10 with key = seed,
+ *                           counter = (pair lo, pair hi, 0x80000000 | ((t-1) >> 2), stream), word (t-1) & 3 (x, y, z, w),
+ *                           u = (word >> 8) * 2^-24 (box_muller's u2 rule: exact in float32, in [0, 1)); the normals use
+ *                           counter word 2 < 2^31, so no uniform shares a counter with a normal.  Both partners of a pair
+ *                           share u_t.
+ * Conventions: a knock-out is dead AT its hit step (and after), a knock-in is live FROM its hit step on (row 0 of a
+ * knock-in is dead).  S0 on or beyond the barrier is an argument error.  No rebate.
+ * Encoding (american = 1): the path matrix the two-pass LSM prices holds the real spot where the option is live and the
+ * DEAD SPOT elsewhere: the float32 nearest to K on its out-of-the-money side (put: the smallest float32 >= K, call: the
+ * largest float32 <= K -- the in-the-money threshold of the sweeps).  Its payoff is <= 0 and it is never in the money, so
+ * the unchanged full-storage sweeps exercise a knock-out only before its hit and a knock-in only from its hit on.  The
+ * matrix is the library's own or S_keep ([n_steps+1][ld], ld >= n_paths), always full storage (option "fold_antithetic"
+ * does not apply: knock state depends on the path).  base = omc_price_american's result on that matrix (folded = 0).
+ * american = 0: only the European sums are formed, no matrix is allocated (S_keep, if given, still receives the encoded
+ * matrix); base then holds the European option of `kind` (price, sum, sumsq, std, zero_prob; no LSM counts).
+ * European sums, on both paths of every pair: payoff of the REAL terminal spot discounted by exp(-r T) (as
+ * omc_price_european), knock-out where the partner never hit, knock-in where it hit: euro_in + euro_out is the vanilla
+ * European of the same stream, path by path.  Standard errors sqrt(max(E[x^2] - E[x]^2, 0) / n_paths).
+ * Errors (nothing is launched): omc_params checks as omc_price_american; -15 unknown kind / monitoring, american not 0/1,
+ * or p->antithetic = 0; -11 american with p->semantics != OMC_SEM_TWO_PASS; -12 continuous monitoring under Heston;
+ * -13 H not finite and positive; -14 S0 on the knocked side of H; -10 a distributed context (one GPU); -7 null b / out. */
+enum { OMC_BARRIER_DOWN_OUT = 0, OMC_BARRIER_UP_OUT = 1, OMC_BARRIER_DOWN_IN = 2, OMC_BARRIER_UP_IN = 3 };
+enum { OMC_MONITOR_DISCRETE = 0, OMC_MONITOR_CONTINUOUS = 1 };
+typedef struct {
+    int32_t kind;        /* OMC_BARRIER_*                                                        */
+    int32_t monitoring;  /* OMC_MONITOR_DISCRETE (grid steps 1..N), OMC_MONITOR_CONTINUOUS (GBM) */
+    int32_t american;    /* 1: LSM two-pass poly on the encoded matrix; 0: European only          */
+    int32_t reserved;
+    double H;
+} omc_barrier;
+typedef struct {
+    omc_result base;               /* American: as omc_price_american returns it (folded = 0)             */
+    double euro_out, euro_out_se;  /* European knock-out on the same paths                                */
+    double euro_in, euro_in_se;    /* European knock-in (euro_in + euro_out = the vanilla, per path)      */
+    double hit_prob;               /* fraction of paths that hit the barrier                              */
+    double ms_barrier_paths;       /* HIP-event time of the barrier generator (+ its finalize)            */
+} omc_barrier_result;
+int omc_price_barrier(omc_ctx* ctx, const omc_params* p, const omc_barrier* b, omc_barrier_result* out, float* S_keep,
+                      int64_t ld);
 
 /* ---- calibrator inner loop -------------------------------------- */
 /* replaces HestonPricer.price_options_batch / price_european_option

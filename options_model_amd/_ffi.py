@@ -12,11 +12,13 @@ import numpy as np
 
 from . import _build
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 SEMANTICS = {"reference": 0, "textbook": 1, "two_pass": 2}
 MODELS = {"gbm": 0, "heston": 1}
 HESTON_SCHEMES = {"reference": 0, "clamp": 0, "full_truncation": 1, "calibrator": 2}
+BARRIER_KINDS = {"down-and-out": 0, "up-and-out": 1, "down-and-in": 2, "up-and-in": 3}
+MONITORING = {"discrete": 0, "continuous": 1}
 
 
 class OmcError(RuntimeError):
@@ -57,6 +59,19 @@ class Greeks(C.Structure):
                 ("bump", C.c_double), ("price_up", C.c_double), ("price_down", C.c_double),
                 ("n_exercised_up", C.c_int64), ("n_exercised_down", C.c_int64),
                 ("ms_greeks", C.c_double)]
+
+
+class Barrier(C.Structure):
+    """omc_barrier: kind (BARRIER_KINDS), monitoring (MONITORING), american (1 / 0), H."""
+    _fields_ = [("kind", C.c_int32), ("monitoring", C.c_int32), ("american", C.c_int32), ("reserved", C.c_int32),
+                ("H", C.c_double)]
+
+
+class BarrierResult(C.Structure):
+    """omc_barrier_result: the American pricing of the encoded matrix plus the European knock-out / knock-in sums."""
+    _fields_ = [("base", Result),
+                ("euro_out", C.c_double), ("euro_out_se", C.c_double), ("euro_in", C.c_double),
+                ("euro_in_se", C.c_double), ("hit_prob", C.c_double), ("ms_barrier_paths", C.c_double)]
 
 
 class MlpJob(C.Structure):
@@ -109,6 +124,7 @@ SIGNATURES = {
     "omc_price_american_greeks": (C.c_int, [_P, C.POINTER(Params), _D, _P, _P, C.POINTER(Greeks)]),
     "omc_pass2_tables_check": (C.c_int, [_P, _I, _D, _I, _P, _P, _I, _P, _P]),
     "omc_price_european": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Result)]),
+    "omc_price_barrier": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Barrier), C.POINTER(BarrierResult), _P, _I64]),
     "omc_heston_price_strikes": (C.c_int, [_P, _I64, _I] + [_D] * 8 + [_U64, _U64, _I, _P, _I, _I, _P, _P]),
     "omc_heston_price_surface": (C.c_int, [_P, _I64, _I] + [_D] * 7 + [_U64, _I, _P, _P, _I, _P, _P, _I, _I, _P, _P]),
     "omc_price_american_seq": (C.c_int, [_P, C.POINTER(Params), _I, C.POINTER(Result)]),
@@ -571,6 +587,25 @@ class Context:
         d.update({k: getattr(g, k) for k, _ in Greeks._fields_ if k != "base"})
         if want_betas:
             d["betas"] = bo
+        return d
+
+    def price_barrier(self, params: Params, kind, H, monitoring="discrete", american=True,
+                      keep_paths: DeviceArray | None = None):
+        """Barrier option (omc_price_barrier) -> dict: the base pricing's keys (American: as price_american returns them on
+        the encoded matrix; European: the option of `kind`) plus euro_out, euro_out_se, euro_in, euro_in_se, hit_prob,
+        ms_barrier_paths.  kind: a key of BARRIER_KINDS or its code; monitoring: "discrete" / "continuous" (GBM);
+        keep_paths: device [n_steps+1][ld] receiving the encoded matrix."""
+        b = Barrier()
+        b.kind = BARRIER_KINDS.get(kind, -1) if isinstance(kind, str) else int(kind)
+        b.monitoring = MONITORING.get(monitoring, -1) if isinstance(monitoring, str) else int(monitoring)
+        b.american = int(bool(american))
+        b.H = float(H)
+        out = BarrierResult()
+        _check(self.lib, self.lib.omc_price_barrier(self.handle, C.byref(params), C.byref(b), C.byref(out),
+                                                     keep_paths.ptr if keep_paths else None,
+                                                     keep_paths.shape[1] if keep_paths else 0))
+        d = out.base.as_dict()
+        d.update({k: getattr(out, k) for k, _ in BarrierResult._fields_ if k != "base"})
         return d
 
     def price_american_ols7(self, params: Params):

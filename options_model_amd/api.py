@@ -267,6 +267,71 @@ def price_american_greeks(S0, K, r, sigma, T, n_paths, n_steps, model="GBM", opt
                                         total=out["ms_total"]))
 
 
+@dataclass
+class BarrierResult:
+    """price_barrier_option: price / stderr of the option of `barrier_type` in the asked style, the European knock-out
+    and knock-in on the same paths (euro_in + euro_out = the vanilla European, path by path) and the hit probability."""
+    price: float
+    stderr: float
+    n_exercised: int
+    hit_prob: float
+    euro_out: float
+    euro_out_se: float
+    euro_in: float
+    euro_in_se: float
+    n_paths: int
+    barrier: float
+    barrier_type: str
+    option_type: str
+    style: str
+    monitoring: str
+    model: str
+    timings_ms: dict = field(default_factory=dict)
+
+    def __float__(self):
+        return float(self.price)
+
+
+def price_barrier_option(S0, K, r, sigma, T, n_paths, n_steps, barrier, barrier_type="down-and-out", option_type="put",
+                         style="american", monitoring="discrete", model="GBM", heston_params=None,
+                         heston_scheme="reference", seed=42, stream=0, device=None, ctx=None) -> BarrierResult:
+    """Knock-in / knock-out barrier option (omc_price_barrier).  style "american": the two-pass poly
+    LSM (price_american_option(semantics="two_pass")) on the path matrix with the spots where the option is not live
+    replaced by a dead spot; "european": the discounted terminal payoff, no matrix.  monitoring "discrete" (grid steps
+    1..n_steps) or "continuous" (GBM: Brownian-bridge crossing test between grid points).  Antithetic paths, one GPU."""
+    model_l = str(model).lower()
+    if model_l not in ("gbm", "heston"):
+        raise ValueError("model must be 'GBM' or 'Heston'.")
+    if barrier_type not in _ffi.BARRIER_KINDS:
+        raise ValueError(f"barrier_type must be one of {sorted(_ffi.BARRIER_KINDS)}.")
+    if style not in ("american", "european"):
+        raise ValueError("style must be 'american' or 'european'.")
+    if monitoring not in _ffi.MONITORING:
+        raise ValueError("monitoring must be 'discrete' or 'continuous'.")
+    if monitoring == "continuous" and model_l != "gbm":
+        raise ValueError("continuous barrier monitoring is available for GBM only.")
+    if not (math.isfinite(float(barrier)) and float(barrier) > 0):
+        raise ValueError("barrier H must be finite and positive.")
+    _validate(S0, K, T, r, sigma, n_paths, n_steps, option_type, need_sigma=(model_l == "gbm"))
+    M = int(n_paths) // 2 * 2
+    if M <= 0:
+        raise ValueError("num_simulations and num_time_steps must be positive integers.")
+    c = ctx or _ffi.default_context(device)
+    p = _ffi.make_params(model=model_l, is_put=(option_type == "put"), semantics="two_pass", antithetic=True,
+                         heston_scheme=heston_scheme, n_paths=M, n_steps=int(n_steps), S0=S0, K=K, r=r,
+                         sigma=sigma or 0.0, T=T, seed=seed, stream=stream, **heston_defaults(sigma, heston_params))
+    out = c.price_barrier(p, barrier_type, float(barrier), monitoring=monitoring, american=(style == "american"))
+    var = max(out["sumsq"] / M - out["price"] ** 2, 0.0)
+    timings = dict(barrier_paths=out["ms_barrier_paths"], total=out["ms_total"])
+    if style == "american":
+        timings.update(pass1=out["ms_pass1"], pass2=out["ms_pass2"], lsm=out["ms_lsm"])
+    return BarrierResult(price=out["price"], stderr=math.sqrt(var / M), n_exercised=out["n_exercised"],
+                         hit_prob=out["hit_prob"], euro_out=out["euro_out"], euro_out_se=out["euro_out_se"],
+                         euro_in=out["euro_in"], euro_in_se=out["euro_in_se"], n_paths=M, barrier=float(barrier),
+                         barrier_type=barrier_type, option_type=option_type, style=style, monitoring=monitoring,
+                         model=model_l, timings_ms=timings)
+
+
 _job = {}
 
 

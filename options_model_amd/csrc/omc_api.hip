@@ -14,6 +14,7 @@
 
 #include "omc_batch.h"
 #include "omc_greeks.h"
+#include "omc_barrier.h"
 #include "omc_comm.h"
 #include "omc_p2p.h"
 #include "omc_kernels.h"
@@ -151,6 +152,7 @@ struct omc_ctx {
     int pass2_irr_every = 0;  // tests (option "pass2_tables_irregular_every"): every k-th step decided by the float64 fallback
     DevBuf foldC;
     DevBuf gk_part, gk_res;  // omc_price_american_greeks: per-workgroup partials, reduced sums
+    DevBuf bar_part, bar_res;  // omc_price_barrier: the generator's per-workgroup partials, reduced sums
     struct FoldKey { int N = -1; double c0 = 0, g = 0; } fold_key[2];
     int world = 1;  // ranks whose sums the hook / communicator adds up (equal shards)
     omc_allreduce_fn hook = nullptr;
@@ -597,7 +599,8 @@ int omc_ctx_destroy(omc_ctx* c)
     for (DevBuf* b : {&c->S, &c->sx, &c->tex, &c->ex, &c->D, &c->part, &c->gmom, &c->betas, &c->part1,
                       &c->result, &c->scratch, &c->sweep_args, &c->bslab, &c->btable, &c->bres, &c->bdisc,
                       &c->mlp_part, &c->mlp_loss, &c->mlp_wt, &c->mlp_gred, &c->shard, &c->S2, &c->seq_local, &c->part1b, &c->gmomb, &c->seq_vote, &c->cn_scratch, &c->cn_data, &c->cn_net, &c->cn_cont,
-                      &c->mS, &c->mstate, &c->mtable, &c->mb_slab, &c->mb_table, &c->mb_bc, &c->crit})
+                      &c->mS, &c->mstate, &c->mtable, &c->mb_slab, &c->mb_table, &c->mb_bc, &c->crit,
+                      &c->bar_part, &c->bar_res})
         b->release();
     if (c->sweep_pin) (void)hipHostFree(c->sweep_pin);
     if (c->mtab_pin) (void)hipHostFree(c->mtab_pin);
@@ -1948,6 +1951,101 @@ int omc_price_european(omc_ctx* c, const omc_params* p, omc_result* res)
     HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
     res->ms_paths = ms;
     res->ms_total = ms;
+    return 0;
+}
+
+// ------------------------------------------------------------------ barrier options
+// The barrier generator (omc_barrier.hip) writes the ENCODED matrix -- the real spot where the option is live, the dead
+// spot elsewhere -- and reduces the European knock-out / knock-in sums; the American price is then the unchanged two-pass
+// flow (enqueue_lsm) on that full-storage matrix.  European only: the generator without a matrix.
+int omc_price_barrier(omc_ctx* c, const omc_params* p, const omc_barrier* b, omc_barrier_result* out, float* S_keep,
+                      int64_t ld)
+{
+    int rc;
+    if ((rc = S_keep ? bind_in(c) : bind(c))) return rc;
+    if ((rc = check_params(p))) return rc;
+    if (!b || !out) return fail(-7, "null barrier or result pointer.");
+    if (b->kind < OMC_BARRIER_DOWN_OUT || b->kind > OMC_BARRIER_UP_IN || b->monitoring < OMC_MONITOR_DISCRETE ||
+        b->monitoring > OMC_MONITOR_CONTINUOUS || (b->american != 0 && b->american != 1))
+        return fail(-15, "unknown barrier kind, monitoring or style.");
+    if (!p->antithetic) return fail(-15, "barrier paths are antithetic pairs (antithetic = 1).");
+    if (b->american && p->semantics != OMC_SEM_TWO_PASS)
+        return fail(-11, "American barrier options are priced by the two-pass flow (semantics 2).");
+    if (b->monitoring == OMC_MONITOR_CONTINUOUS && p->model != OMC_MODEL_GBM)
+        return fail(-12, "continuous barrier monitoring is available for GBM only.");
+    if (!(std::isfinite(b->H) && b->H > 0.0)) return fail(-13, "barrier H must be finite and positive.");
+    const int up = (b->kind == OMC_BARRIER_UP_OUT || b->kind == OMC_BARRIER_UP_IN) ? 1 : 0;
+    const float thr = omc::barrier_threshold(b->H, up);
+    const float s0f = (float)p->S0;
+    if (up ? (p->S0 >= b->H || s0f >= thr) : (p->S0 <= b->H || s0f <= thr))
+        return fail(-14, "S0 lies on or beyond the barrier (the option is already knocked).");
+    if (c->distributed()) return fail(-10, "barrier pricing runs on one GPU.");
+    if (S_keep && ld < p->n_paths) return fail(-6, "leading dimension smaller than n_paths.");
+    const int64_t M = p->n_paths;
+    const int N = p->n_steps;
+    float* S = S_keep;
+    if (b->american && !S) {
+        ld = (M + 63) / 64 * 64;
+        if ((rc = c->S.ensure(sizeof(float) * (size_t)ld * (size_t)(N + 1)))) return rc;
+        S = (float*)c->S.p;
+    }
+    omc::BarrierGen g{};
+    g.model = p->model == OMC_MODEL_GBM ? 0 : 1; g.scheme = p->heston_scheme;
+    g.n_paths = M; g.n_steps = N;
+    g.S0 = p->S0; g.r = p->r; g.sigma = p->sigma; g.T = p->T;
+    g.v0 = p->v0; g.kappa = p->kappa; g.theta = p->theta; g.xi = p->xi; g.rho = p->rho;
+    g.seed = p->seed; g.pair_offset = p->pair_offset; g.stream = (uint32_t)p->stream;
+    g.is_put = p->is_put ? 1 : 0; g.up = up;
+    g.knock_in = (b->kind == OMC_BARRIER_DOWN_IN || b->kind == OMC_BARRIER_UP_IN) ? 1 : 0;
+    g.continuous = b->monitoring == OMC_MONITOR_CONTINUOUS ? 1 : 0;
+    g.K = p->K; g.H = b->H;
+    g.S = S; g.ld = S ? ld : 0;
+    const int64_t nblk = omc::barrier_blocks(g);
+    if ((rc = c->bar_part.ensure(sizeof(double) * omc::kBarrierQ * (size_t)nblk))) return rc;
+    if ((rc = c->bar_res.ensure(sizeof(double) * omc::kBarrierQ))) return rc;
+    g.part = (double*)c->bar_part.p;
+    g.result = (double*)c->bar_res.p;
+    omc::LsmWorkspace w;
+    if (b->american && (rc = prepare_lsm(c, M, N, p->r, p->T, true, false, &w))) return rc;
+    HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+    HIP_TRY(omc::launch_barrier_paths(c->stream, g));
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    if (b->american) {
+        omc::LsmProblem prob{S, ld, M, N, p->is_put ? 1 : 0, p->K, p->r, p->T};
+        w.ev_p1_end = c->ev[4]; w.ev_p2_begin = c->ev[5]; w.ev_p2_end = c->ev[6];
+        if ((rc = enqueue_lsm(c, prob, w, OMC_SEM_TWO_PASS, false))) return rc;
+        HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+        HIP_TRY(hipMemcpyAsync(c->hres, w.result, sizeof(double) * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    double h[omc::kBarrierQ];
+    HIP_TRY(hipMemcpyAsync(h, g.result, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = wait_stream(c))) return rc;
+    memset(out, 0, sizeof *out);
+    const double Md = (double)M;
+    auto mean_se = [&](int q, double* mean, double* se) {
+        *mean = h[q] / Md;
+        const double var = h[q + 1] / Md - *mean * *mean;
+        *se = std::sqrt((var > 0.0 ? var : 0.0) / Md);
+    };
+    mean_se(0, &out->euro_out, &out->euro_out_se);
+    mean_se(2, &out->euro_in, &out->euro_in_se);
+    out->hit_prob = h[4] / Md;
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    out->ms_barrier_paths = ms;
+    if (b->american) {
+        fill_result(&out->base, c->hres, M);
+        out->base.folded = 0;
+        if ((rc = read_kernel_times(c->ev, p, &out->base))) return rc;
+    } else {  // the European option of `kind`
+        const int q = g.knock_in ? 2 : 0;
+        const double e[8] = {h[q], h[q + 1], 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        fill_result(&out->base, e, M);
+        out->base.n_zero = 0;
+        out->base.zero_prob = 0.0;
+        out->base.ms_paths = ms;
+        out->base.ms_total = ms;
+    }
     return 0;
 }
 
