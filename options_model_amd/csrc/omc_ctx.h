@@ -1,0 +1,223 @@
+// omc_ctx.h -- private to libomc.so (not installed, not part of include/omc.h): the context, its device buffers and
+// the helpers the omc_api*.hip files share.  Definitions in omc_api.hip.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/omc.h"
+#include "omc_comm.h"
+#include "omc_kernels.h"
+#include "omc_p2p.h"
+
+namespace omc::abi {
+
+extern thread_local std::string g_err;  // omc_last_error()
+
+inline int fail(int code, const char* msg)
+{
+    g_err = msg;
+    return code;
+}
+
+#define HIP_TRY(expr)                                                                      \
+    do {                                                                                   \
+        hipError_t e_ = (expr);                                                            \
+        if (e_ != hipSuccess) {                                                            \
+            char buf_[256];                                                                \
+            snprintf(buf_, sizeof buf_, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
+                     __FILE__, __LINE__);                                                  \
+            g_err = buf_;                                                                  \
+            return (int)e_ > 0 ? (int)e_ : 999;                                            \
+        }                                                                                  \
+    } while (0)
+
+// Option "alloc_limit" (omc_set_option; per process, 0 = none): a single buffer of the library may not grow beyond this many
+// bytes -- a request above it fails like a hipMalloc that found no room (hipErrorOutOfMemory).  A memory budget for a
+// card shared with other tenants, and the way the tests make ONE rank of a job run out of memory.
+extern size_t g_alloc_limit;
+
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    int ensure(size_t bytes)
+    {
+        if (bytes <= cap) return 0;
+        if (g_alloc_limit && bytes > g_alloc_limit) {
+            g_err = "hipMalloc refused: " + std::to_string(bytes) + " bytes asked for, option alloc_limit is " +
+                    std::to_string(g_alloc_limit) + " (out of memory)";
+            return (int)hipErrorOutOfMemory;
+        }
+        if (p) {
+            hipError_t e = hipFree(p);
+            p = nullptr;
+            cap = 0;
+            if (e != hipSuccess) return (int)e;
+        }
+        size_t want = bytes + bytes / 8 + 256;
+        hipError_t e = hipMalloc(&p, want);
+        if (e != hipSuccess) {  // no room for the 12.5 % growth slack: ask for exactly what is needed
+            (void)hipGetLastError();
+            want = bytes;
+            e = hipMalloc(&p, want);
+        }
+        if (e != hipSuccess) {
+            (void)hipGetLastError();  // a failed hipMalloc must not surface at the next launch's hipGetLastError()
+            g_err = std::string("hipMalloc failed: ") + hipGetErrorString(e);
+            p = nullptr;
+            return (int)e;
+        }
+        cap = want;
+        return 0;
+    }
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;  // owns its allocation
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+};
+
+// argument checks: 0, or the error code with omc_last_error() set
+int check_market(double S0, double K, double T, double r);
+int check_sizes(int64_t n_paths, int n_steps);
+int check_matrix(const void* S, int64_t ld, int64_t n_paths);
+int check_lsm_args(const void* S, int64_t ld, int64_t n_paths, int n_steps, double K, double r, double T);
+int check_params(const omc_params* p);
+int check_contnet(omc_ctx* c, int hidden, int epochs, double lr);
+
+// streams, workspace, collectives
+int bind(omc_ctx* c);
+int bind_in(omc_ctx* c);
+int wait_stream(omc_ctx* c);
+int prepare_lsm(omc_ctx* c, int64_t M, int N, double r, double T, bool two_pass, bool clear_tables, omc::LsmWorkspace* w);
+int allreduce(omc_ctx* c, double* dptr, int count);
+int allreduce_host(omc_ctx* c, double* dev, double* host, int n);
+bool p2p_active(const omc_ctx* c);
+bool step_graph_enabled(const omc_ctx* c);
+int adam_bias_tables(omc_ctx* c, double beta1, double beta2, size_t need, size_t cap);
+int enqueue_lsm(omc_ctx* c, const omc::LsmProblem& p, const omc::LsmWorkspace& w, int semantics, bool write_state);
+int check_p2p(omc_ctx* c, const double* h = nullptr, int n = 0);
+
+// results, device scratch layouts
+void fill_result(omc_result* res, const double* h, int64_t M, int world = 1);  // clears *res first
+int copy_outputs(omc_ctx* c, const omc::LsmWorkspace& w, int64_t M, int N, double* betas_out, float* sx_out,
+                 int32_t* tex_out);
+inline size_t up256(size_t bytes) { return (bytes + 255) / 256 * 256; }  // the next block of a scratch layout
+
+// the library's own path matrix and the fused pricing
+inline int64_t padded_ld(int64_t cols) { return (cols + 63) / 64 * 64; }  // leading dimension of a matrix it owns
+enum class Storage { planned, full_only };  // plan_storage's choice, or the full matrix whatever the pricing
+int enqueue_paths(omc_ctx* c, const omc_params* p, float* S, int64_t ld, bool fold = false);
+bool fold_applies(const omc_ctx* c, const omc_params* p);
+int plan_storage(omc_ctx* c, const omc_params* p, int slot, int64_t* ld, const double** cK);
+int ensure_paths(omc_ctx* c, const omc_params* p, Storage how, float** S, int64_t* ld, const double** cK = nullptr);
+int enqueue_pricing(omc_ctx* c, const omc_params* p, float* S_keep, int64_t ld, double* result_dev, hipEvent_t* evs,
+                    double** result_out);
+int read_kernel_times(const hipEvent_t* evs, const omc_params* p, omc_result* res, bool has_end = true);
+
+}  // namespace omc::abi
+
+using omc::abi::DevBuf;
+
+// What the count call of omc_nn_build_rows (data == NULL) leaves for the call with `data` that follows it: the sweep's
+// results on the host, the counts / offsets in the context's scratch.  Valid only for the NEXT library call on the context
+// (every entry point clears it in bind()), and only for the same arguments.
+struct RowsCache {
+    bool valid = false;
+    const float* S = nullptr;
+    int64_t ld = 0, M = 0;
+    int N = 0, is_put = 0;
+    double K = 0, r = 0, T = 0;
+    int64_t R = 0;
+    double st[16] = {0};
+};
+
+constexpr size_t kVoteBytes = 1024;  // omc_ctx::seq_vote once a communicator / hook is installed (largest use: 40 doubles)
+
+struct omc_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    DevBuf S, sx, tex, ex, D, part, gmom, betas, part1, result, scratch, sweep_args, crit;
+    DevBuf bslab, btable, bres, bdisc;  // batched path: problem slab, table, results, discounts
+    DevBuf mlp_part, mlp_loss, mlp_wt;  // NN training: gradient partials, epoch loss, transposed connections
+    DevBuf mlp_gred, shard;             // sharded NN training: reduced gradient of a step; epoch selection tables
+    DevBuf cn_scratch, cn_data, cn_net, cn_cont;  // per-step ContNet flow: set bookkeeping, rows, net + Adam state, values
+    std::vector<char> h_table;
+    std::vector<double> h_disc, h_bres;
+    std::vector<double> hD;
+    int D_N = -1;
+    double D_r = 0, D_T = 0;
+    const double* D_ptr = nullptr;
+    double hres[8];
+    double* hres_pin = nullptr;  // pinned + mapped: the fused pricing call's last kernel writes its 8 sums here
+    double* hres_dev = nullptr;  // device-side address of hres_pin
+    double *seq_pin = nullptr, *seq_dev = nullptr;  // omc_price_american_seq: one 8-double slot per pricing
+    int seq_cap = 0;
+    hipEvent_t ev_seq = nullptr;
+    hipEvent_t ev_entry = nullptr;  // bind_in(): orders a context-owned stream after the device's default stream
+    hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // omc_price_american_seq: further event sets (7 each) for the pricings of a sequence that carry their own
+    // kernel timings ("seq_event_stride": every k-th pricing; 0 = the first one only)
+    std::vector<hipEvent_t> ev_pool;
+    int seq_event_stride = 0;
+    // omc_price_american_seq, per-step flows: K pricings advanced by one launch per time step
+    DevBuf mS, mstate, mtable;
+    DevBuf mb_slab, mb_table, mb_bc;      // omc_mlp_train_epoch_batch: per-problem scratch, table, 1 - beta^step tables
+    std::vector<double> mb_bc_host;       // [2][cap]: bc1 then bc2
+    double mb_beta1 = -1.0, mb_beta2 = -1.0;
+    size_t mb_bc_cap = 0;
+    char* mtab_pin = nullptr;  // pinned upload ring for the argument tables (one image per batch of K)
+    int mtab_slot = 0;
+    int seq_step_k = -1;       // -1: default (what fits the Infinity Cache, <= 16), 1: off, k: at most k pricings per launch
+    int seq_step_wgs = 0;      // workgroups one launch of the multi-pricing sweep may use (0: one per CU)
+    int gbm_vec = 0, heston_vec = 0;
+    // antithetic-folded storage of the fused GBM two-pass pricing (omc_lsm_dev.h; option "fold_antithetic": 0 never,
+    // 1 = default: pricings of at least kFoldMinPaths paths over all ranks, 2 always): two cK tables (the overlapped
+    // sequence has two pricings in flight), each remembered by what it was filled from
+    int fold = 1;
+    // pass 2 of the two-pass flow decides from per-step float32 exercise tables (option "pass2_tables": 1 = default,
+    // 0 = the float64 decisions; the same decisions either way)
+    int pass2_tables = 1;
+    int pass2_irr_every = 0;  // tests (option "pass2_tables_irregular_every"): every k-th step decided by the float64 fallback
+    DevBuf foldC;
+    DevBuf gk_part, gk_res;  // omc_price_american_greeks: per-workgroup partials, reduced sums
+    DevBuf bar_part, bar_res;  // omc_price_barrier: the generator's per-workgroup partials, reduced sums
+    struct FoldKey { int N = -1; double c0 = 0, g = 0; } fold_key[2];
+    int world = 1;  // ranks whose sums the hook / communicator adds up (equal shards)
+    omc_allreduce_fn hook = nullptr;
+    void* hook_user = nullptr;
+    omc::Comm* comm = nullptr;  // native RCCL communicator (omc_comm_init); takes precedence over the hook
+    // direct write-to-all-peers exchange of the per-step moments (omc_p2p_connect): replaces the per-step all-reduce
+    omc::P2P* p2p = nullptr;
+    int p2p_use = 1;            // option "p2p_exchange": 0 = keep the collective even when connected
+    bool p2p_used = false;      // an exchange was enqueued since the last wait
+    double p2p_deadline_s = 2.0;  // option "p2p_deadline_ms": how long an exchange waits for a peer's contribution
+    double p2p_first_deadline_s = 30.0;  // "p2p_first_deadline_ms": the same for the FIRST exchange of a call
+    // omc_price_american_seq across GPUs: the moment all-reduce of pricing k runs on its own stream while the
+    // main stream generates the paths of pricing k+1 into the second path buffer
+    hipStream_t comm_stream = nullptr;
+    hipEvent_t ev_moments[2] = {nullptr, nullptr}, ev_reduced[2] = {nullptr, nullptr};
+    RowsCache rows_cache;
+    DevBuf S2, seq_local, part1b, gmomb, seq_vote;
+    int seq_overlap = -1;  // -1: default (on when the communicator has more than one rank), 0 off, 1 on
+    bool defer_result_allreduce = false;  // inside omc_price_american_seq: one collective for all result sums
+    // captured per-step sweep (N launches + valuation + finalize), replayed for every pricing of the
+    // same geometry; its kernels read their arguments from `sweep_args`
+    hipGraph_t sweep_graph = nullptr;
+    hipGraphExec_t sweep_exec = nullptr;
+    int64_t sg_M = -1, sg_ld = -1;
+    int sg_N = -1, sg_sem = -1, sg_vec4 = -1, sg_failed = 0;
+    const void* sg_args = nullptr;
+    std::vector<char> sweep_img;   // last argument image uploaded to sweep_args
+    char* sweep_pin = nullptr;     // pinned upload ring
+    int sweep_pin_slot = 0;
+    int step_graph = -1;           // -1: environment default (off), 0 off, 1 on
+    int device_cus = 0;
+    bool distributed() const { return comm != nullptr || hook != nullptr; }
+    ~omc_ctx();  // releases everything it holds (omc_api.hip)
+};
+
