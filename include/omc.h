@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define OMC_ABI_VERSION 12
+#define OMC_ABI_VERSION 13
 
 typedef struct omc_ctx omc_ctx;
 
@@ -350,6 +350,62 @@ typedef struct {
 } omc_barrier_result;
 int omc_price_barrier(omc_ctx* ctx, const omc_params* p, const omc_barrier* b, omc_barrier_result* out, float* S_keep,
                       int64_t ld);
+
+/* ---- Andersen-Broadie price bounds for American options ----------------------------------- */
+/* A lower and an upper bound on the value of the Bermudan put / call on the pricing grid, both from ONE frozen exercise
+ * policy: the lower bound applies the policy as a stopping rule on fresh paths, the upper bound is the Andersen-Broadie
+ * (2004) dual estimator whose martingale comes from nested inner simulations.  GBM only, one GPU.
+ * The game: exercise dates t = 1..N on the grid dt = T / N; every value is discounted to t = 0,
+ *     Z_t = exp(-r t dt) max(phi(S_t), 0)
+ * -- the textbook convention, NOT the reference flows' valuation at t = dt (omc_result.price of semantics 0 / 2).
+ * The policy: a table betas [N+1][4] = (b0, b1, b2, n) as omc_lsm_poly returns it.  At t in 1..N-1 a path at spot s
+ * exercises iff n_t > 0.5 (a regression-set size), imm = phi(s) > 0 and imm > fma(u, fma(u, b2, b1), b0) with
+ * u = fma((double)s, 1/K, -1) -- omc_lsm_apply_frozen's float64 rule; at t = N it takes its payoff.  tau_t = the FIRST
+ * date >= t at which the rule fires (a stopping time).  The kernels decide from pass 2's float32 exercise tables
+ * (omc_crit.h, stored-path kind) on the steps the builder certifies and with the float64 rule on the others: the same
+ * decisions.
+ * policy (omc_bounds_config.policy): OMC_SEM_REFERENCE / OMC_SEM_TEXTBOOK / OMC_SEM_TWO_PASS = the fits omc_lsm_poly
+ * makes with that semantics on p->n_paths paths generated at (p->seed, p->stream, p->pair_offset, p->antithetic) --
+ * textbook is the best policy of the three; OMC_POLICY_GIVEN = the caller's table `betas`.  p->semantics is not used.
+ * Lower bound: n_lower paths of omc_gbm_paths_f32(n_lower, N, S0, r, sigma, T, seed, stream_lower, pair_offset 0,
+ * antithetic): the mean of Z at tau_1; its standard error from PAIR means (the two partners of a pair averaged first).
+ * Upper bound: n_outer outer paths of omc_gbm_paths_f32(.., stream_outer, ..) likewise.  For outer path i and t = 0..N-1,
+ *     Q^_t[i] = mean of Z at tau_{t+1} over n_inner inner paths started at S_t[i]
+ * Inner pair j of (i, t) is generator pair g = (i (N+1) + t) (n_inner/2) + j of Philox stream stream_inner; inner step
+ * k = 1..N-t consumes that pair's generator row k-1 (omc_gbm_normals_f32), the partner -z, and the spot recurrence is
+ * the generator's own (s = s * exp2(fma(+-b, z, a)) from the float32 S_t[i]): the inner spots are bit for bit
+ * omc_gbm_paths_from_normals_f32(z, S0 = S_t[i], r, sigma, T) with z = omc_gbm_normals_f32(n_inner/2, N, seed,
+ * stream_inner, pair_offset = (i (N+1) + t) n_inner/2) (rows after N-t unused).  Then per outer path
+ *     L^_t = Z_t if the policy exercises at t or t = N, else Q^_t  (t >= 1);   M^_0 = 0, M^_t = M^_{t-1} + L^_t - Q^_{t-1}
+ *     sample_i = max_{t=1..N} (Z_t - M^_t)
+ * upper = mean of the samples, se_upper from pair means (i and i + n_outer/2).  ci = [lower - 1.96 se_lower,
+ * upper + 1.96 se_upper].  The inner noise has conditional mean 0, so the upper estimate is biased upward only.
+ * Outputs: betas_out (NULL or host [N+1][4]) the policy used; q_out (NULL or host [n_outer][N]) the Q^_t; samples_out
+ * (NULL or host [n_outer]) the samples.  n_exercised_lower: lower paths stopped before N.  inner_path_steps: the steps
+ * the inner paths took, sum over all inner paths of (tau - t).  ms_*: HIP-event times of the policy fit, the lower
+ * sweep, the upper bound (outer paths, exercise tables, inner simulations, outer walk) and the whole call.  float64
+ * sums in a fixed order: identical calls return identical bits.  The inner simulations run as launches over blocks of
+ * outer paths, each bounded in work.
+ * Errors (nothing is launched): omc_params checks as omc_price_american; -12 a model other than GBM; -10 a context with
+ * a communicator or all-reduce hook; -4 policy not one of the four; -3 n_lower, n_outer or n_inner odd or < 2;
+ * -16 n_outer (N+1) n_inner above 2^32 or n_outer n_inner N (N+1) / 2 (the inner steps of a policy that never
+ * exercises) above 2^39; -7 null cfg / out, or betas NULL with OMC_POLICY_GIVEN. */
+enum { OMC_POLICY_GIVEN = 3 };
+typedef struct {
+    int32_t policy;    /* OMC_SEM_REFERENCE, OMC_SEM_TEXTBOOK, OMC_SEM_TWO_PASS: fitted here; OMC_POLICY_GIVEN: `betas` */
+    int32_t reserved;
+    int64_t n_lower, n_outer, n_inner;
+    uint64_t stream_lower, stream_outer, stream_inner;
+} omc_bounds_config;
+typedef struct {
+    double lower, se_lower, upper, se_upper, ci_lo, ci_hi; /* ci: lower - 1.96 se_lower, upper + 1.96 se_upper */
+    int64_t n_lower, n_outer, n_inner, n_exercised_lower, inner_path_steps;
+    double ms_fit, ms_lower, ms_upper, ms_total;
+} omc_bounds;
+int omc_price_american_bounds(omc_ctx* ctx, const omc_params* p, const omc_bounds_config* cfg,
+                              const double* betas /* policy == OMC_POLICY_GIVEN: host [N+1][4] */, double* betas_out,
+                              double* q_out /* NULL or host [n_outer][N]: Q^_t, for tests */,
+                              double* samples_out /* NULL or host [n_outer] */, omc_bounds* out);
 
 /* ---- calibrator inner loop -------------------------------------- */
 /* replaces HestonPricer.price_options_batch / price_european_option

@@ -12,13 +12,14 @@ import numpy as np
 
 from . import _build
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 SEMANTICS = {"reference": 0, "textbook": 1, "two_pass": 2}
 MODELS = {"gbm": 0, "heston": 1}
 HESTON_SCHEMES = {"reference": 0, "clamp": 0, "full_truncation": 1, "calibrator": 2}
 BARRIER_KINDS = {"down-and-out": 0, "up-and-out": 1, "down-and-in": 2, "up-and-in": 3}
 MONITORING = {"discrete": 0, "continuous": 1}
+BOUND_POLICIES = {"reference": 0, "textbook": 1, "two_pass": 2, "given": 3}
 
 
 class OmcError(RuntimeError):
@@ -74,6 +75,22 @@ class BarrierResult(C.Structure):
                 ("euro_in_se", C.c_double), ("hit_prob", C.c_double), ("ms_barrier_paths", C.c_double)]
 
 
+class BoundsConfig(C.Structure):
+    """omc_bounds_config: policy (BOUND_POLICIES), the three sizes and the three Philox streams."""
+    _fields_ = [("policy", C.c_int32), ("reserved", C.c_int32), ("n_lower", C.c_int64), ("n_outer", C.c_int64),
+                ("n_inner", C.c_int64), ("stream_lower", C.c_uint64), ("stream_outer", C.c_uint64),
+                ("stream_inner", C.c_uint64)]
+
+
+class Bounds(C.Structure):
+    """omc_bounds: the Andersen-Broadie lower / upper bounds of the Bermudan game on the grid (omc_price_american_bounds)."""
+    _fields_ = [("lower", C.c_double), ("se_lower", C.c_double), ("upper", C.c_double), ("se_upper", C.c_double),
+                ("ci_lo", C.c_double), ("ci_hi", C.c_double),
+                ("n_lower", C.c_int64), ("n_outer", C.c_int64), ("n_inner", C.c_int64), ("n_exercised_lower", C.c_int64),
+                ("inner_path_steps", C.c_int64),
+                ("ms_fit", C.c_double), ("ms_lower", C.c_double), ("ms_upper", C.c_double), ("ms_total", C.c_double)]
+
+
 class MlpJob(C.Structure):
     """omc_mlp_job: one network of a batch trained side by side (omc_mlp_train_epoch_batch)."""
     _fields_ = [("data", C.c_void_p), ("n_rows", C.c_int64), ("batch", C.c_int64),
@@ -125,6 +142,8 @@ SIGNATURES = {
     "omc_pass2_tables_check": (C.c_int, [_P, _I, _D, _I, _P, _P, _I, _P, _P]),
     "omc_price_european": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Result)]),
     "omc_price_barrier": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Barrier), C.POINTER(BarrierResult), _P, _I64]),
+    "omc_price_american_bounds": (C.c_int, [_P, C.POINTER(Params), C.POINTER(BoundsConfig), _P, _P, _P, _P,
+                                            C.POINTER(Bounds)]),
     "omc_heston_price_strikes": (C.c_int, [_P, _I64, _I] + [_D] * 8 + [_U64, _U64, _I, _P, _I, _I, _P, _P]),
     "omc_heston_price_surface": (C.c_int, [_P, _I64, _I] + [_D] * 7 + [_U64, _I, _P, _P, _I, _P, _P, _I, _I, _P, _P]),
     "omc_price_american_seq": (C.c_int, [_P, C.POINTER(Params), _I, C.POINTER(Result)]),
@@ -606,6 +625,41 @@ class Context:
                                                      keep_paths.shape[1] if keep_paths else 0))
         d = out.base.as_dict()
         d.update({k: getattr(out, k) for k, _ in BarrierResult._fields_ if k != "base"})
+        return d
+
+    def price_american_bounds(self, params: Params, policy="textbook", n_lower=1_000_000, n_outer=8192, n_inner=1024,
+                              stream_lower=None, stream_outer=None, stream_inner=None, betas=None, want_q=False,
+                              want_samples=False):
+        """Andersen-Broadie bounds of the Bermudan game on the grid (omc_price_american_bounds) -> dict with the fields of
+        omc_bounds plus `betas` (the policy used, [n_steps+1][4]) and, when asked, `q` ([n_outer][n_steps]: Q^_t) and
+        `samples` ([n_outer]).  policy: a key of BOUND_POLICIES or its code; betas: the table of policy "given".  Streams
+        default to params.stream + 1 / 2 / 3."""
+        N = int(params.n_steps)
+        cfg = BoundsConfig()
+        cfg.policy = BOUND_POLICIES.get(policy, -1) if isinstance(policy, str) else int(policy)
+        cfg.n_lower, cfg.n_outer, cfg.n_inner = int(n_lower), int(n_outer), int(n_inner)
+        base = int(params.stream)
+        cfg.stream_lower = base + 1 if stream_lower is None else int(stream_lower)
+        cfg.stream_outer = base + 2 if stream_outer is None else int(stream_outer)
+        cfg.stream_inner = base + 3 if stream_inner is None else int(stream_inner)
+        b = None
+        if betas is not None:
+            b = np.ascontiguousarray(betas, np.float64)
+            if b.shape != (N + 1, 4):
+                raise ValueError(f"betas must have shape ({N + 1}, 4), got {b.shape}.")
+        bo = np.zeros((N + 1, 4))
+        q = np.zeros((max(int(n_outer), 0), N)) if want_q else None
+        smp = np.zeros(max(int(n_outer), 0)) if want_samples else None
+        out = Bounds()
+        _check(self.lib, self.lib.omc_price_american_bounds(
+            self.handle, C.byref(params), C.byref(cfg), b.ctypes.data if b is not None else None, bo.ctypes.data,
+            q.ctypes.data if q is not None else None, smp.ctypes.data if smp is not None else None, C.byref(out)))
+        d = {k: getattr(out, k) for k, _ in Bounds._fields_}
+        d["betas"] = bo
+        if want_q:
+            d["q"] = q
+        if want_samples:
+            d["samples"] = smp
         return d
 
     def price_american_ols7(self, params: Params):

@@ -332,6 +332,63 @@ def price_barrier_option(S0, K, r, sigma, T, n_paths, n_steps, barrier, barrier_
                          model=model_l, timings_ms=timings)
 
 
+@dataclass
+class BoundsResult:
+    """price_american_bounds: Andersen-Broadie bounds on the value of the BERMUDAN option with exercise dates t = 1..n_steps
+    of the grid dt = T / n_steps, all values discounted to t = 0 (Z_t = exp(-r t dt) max(phi(S_t), 0)) -- the textbook
+    convention, not the t = dt valuation of the library's reference and two_pass flows -- from one frozen exercise policy
+    `betas` ([n_steps+1][4] = b0, b1, b2, n).  `lower` applies the policy as a stopping rule on fresh paths; `upper` is the
+    dual estimator with nested inner simulations (biased upward only).  [ci_lo, ci_hi] = [lower - 1.96 se_lower,
+    upper + 1.96 se_upper].  They bound the game on the grid, not the continuously exercisable American option."""
+    lower: float
+    se_lower: float
+    upper: float
+    se_upper: float
+    ci_lo: float
+    ci_hi: float
+    n_lower: int
+    n_outer: int
+    n_inner: int
+    n_exercised_lower: int
+    inner_path_steps: int
+    policy: str
+    betas: object
+    option_type: str
+    timings_ms: dict = field(default_factory=dict)
+
+
+def price_american_bounds(S0, K, r, sigma, T, n_paths, n_steps, option_type="put", policy="textbook", n_lower=1_000_000,
+                          n_outer=8192, n_inner=1024, seed=42, stream=0, betas=None, device=None,
+                          ctx=None) -> BoundsResult:
+    """Lower and upper bounds on the Bermudan value of a GBM put / call (omc_price_american_bounds).
+    policy: "textbook" (classic Longstaff-Schwartz fits, the best of the library's policies), "two_pass" or "reference"
+    (the fits of the headline flows), each fitted on n_paths paths at (seed, stream); or "given" with `betas`
+    [n_steps+1][4].  The lower-bound, outer and inner paths use Philox streams stream + 1, + 2, + 3.  One GPU."""
+    if policy not in _ffi.BOUND_POLICIES:
+        raise ValueError(f"policy must be one of {sorted(_ffi.BOUND_POLICIES)}.")
+    if (policy == "given") != (betas is not None):
+        raise ValueError("betas must be given exactly when policy='given'.")
+    for name, v in (("n_lower", n_lower), ("n_outer", n_outer), ("n_inner", n_inner)):
+        if int(v) < 2 or int(v) % 2:
+            raise ValueError(f"{name} must be an even integer >= 2 (antithetic pairs).")
+    _validate(S0, K, T, r, sigma, n_paths, n_steps, option_type)
+    M = int(n_paths) // 2 * 2
+    if M <= 0:
+        raise ValueError("num_simulations and num_time_steps must be positive integers.")
+    c = ctx or _ffi.default_context(device)
+    p = _ffi.make_params(is_put=(option_type == "put"), semantics="two_pass", n_paths=M, n_steps=int(n_steps), S0=S0, K=K,
+                         r=r, sigma=sigma, T=T, seed=seed, stream=stream)
+    out = c.price_american_bounds(p, policy=policy, n_lower=int(n_lower), n_outer=int(n_outer), n_inner=int(n_inner),
+                                  betas=betas)
+    return BoundsResult(lower=out["lower"], se_lower=out["se_lower"], upper=out["upper"], se_upper=out["se_upper"],
+                        ci_lo=out["ci_lo"], ci_hi=out["ci_hi"], n_lower=out["n_lower"], n_outer=out["n_outer"],
+                        n_inner=out["n_inner"], n_exercised_lower=out["n_exercised_lower"],
+                        inner_path_steps=out["inner_path_steps"], policy=policy, betas=out["betas"],
+                        option_type=option_type,
+                        timings_ms=dict(fit=out["ms_fit"], lower=out["ms_lower"], upper=out["ms_upper"],
+                                        total=out["ms_total"]))
+
+
 _job = {}
 
 

@@ -1,0 +1,120 @@
+// omc_api_bounds.hip -- Andersen-Broadie price bounds of American options (include/omc.h): the policy
+// fit, the lower-bound sweep, the outer paths, the inner simulations in launches over blocks of outer paths, the walk.
+#include "omc_bounds.h"
+#include "omc_ctx.h"
+
+using namespace omc::abi;
+
+namespace {
+constexpr double kMaxItemPairs = 4294967296.0;   // n_outer (N+1) n_inner
+constexpr double kMaxInnerSteps = 549755813888.0;  // 2^39: n_outer n_inner N (N+1) / 2, a never-exercising policy's steps
+constexpr double kLaunchSteps = 1073741824.0;    // 2^30 worst-case inner steps per launch of the inner kernel
+}  // namespace
+
+extern "C" int omc_price_american_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg,
+                                         const double* betas, double* betas_out, double* q_out, double* samples_out,
+                                         omc_bounds* out)
+{
+    int rc;
+    if ((rc = bind(c))) return rc;
+    if (!cfg || !out) return fail(-7, "null bounds config or result pointer.");
+    if ((rc = check_params(p))) return rc;
+    if (p->model != OMC_MODEL_GBM) return fail(-12, "price bounds are available for GBM only.");
+    if (c->distributed()) return fail(-10, "price bounds run on one GPU.");
+    const int policy = cfg->policy;
+    if (policy != OMC_SEM_REFERENCE && policy != OMC_SEM_TEXTBOOK && policy != OMC_SEM_TWO_PASS && policy != OMC_POLICY_GIVEN)
+        return fail(-4, "unknown policy (reference, textbook, two_pass or given).");
+    if (policy == OMC_POLICY_GIVEN && !betas) return fail(-7, "policy 'given' needs a betas table.");
+    const int64_t nl = cfg->n_lower, no = cfg->n_outer, ni = cfg->n_inner;
+    if (nl < 2 || no < 2 || ni < 2 || (nl & 1) || (no & 1) || (ni & 1))
+        return fail(-3, "n_lower, n_outer and n_inner must be even and at least 2 (antithetic pairs).");
+    const int N = p->n_steps;
+    const double work1 = (double)ni * 0.5 * (double)N * (double)(N + 1);  // worst-case inner steps of one outer path
+    if ((double)no * (double)(N + 1) * (double)ni > kMaxItemPairs || (double)no * work1 > kMaxInnerSteps)
+        return fail(-16, "bounds request too large: n_outer (N+1) n_inner must be <= 2^32 and n_outer n_inner N (N+1) / 2 "
+                         "<= 2^39.");
+    hipStream_t st = c->stream;
+    const bool fitted = policy != OMC_POLICY_GIVEN;
+    const int64_t M = fitted ? p->n_paths : 2;
+    omc::LsmWorkspace w;
+    if ((rc = prepare_lsm(c, M, N, p->r, p->T, policy == OMC_SEM_TWO_PASS, true, &w))) return rc;
+    if (!fitted) {
+        HIP_TRY(hipMemcpyAsync(w.betas, betas, sizeof(double) * 4 * (size_t)(N + 1), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));  // `betas` is caller memory
+    }
+    // the workspace: outer paths [N+1][n_outer] f32 | Q^ [n_outer][N] | samples [n_outer] | tables [N+1][8] u32 |
+    // partials [8][kPStride] | sums [16] | inner step count
+    const size_t o_q = up256(sizeof(float) * (size_t)(N + 1) * (size_t)no);
+    const size_t o_smp = o_q + up256(sizeof(double) * (size_t)no * (size_t)N);
+    const size_t o_tab = o_smp + up256(sizeof(double) * (size_t)no);
+    const size_t o_part = o_tab + up256(sizeof(uint32_t) * 8 * (size_t)(N + 1));
+    const size_t o_res = o_part + up256(sizeof(double) * 8 * omc::kMaxLsmBlocks);
+    const size_t o_steps = o_res + up256(sizeof(double) * 16);
+    if ((rc = c->bnd.ensure(o_steps + 256))) return rc;
+    char* b = (char*)c->bnd.p;
+    double* res = (double*)(b + o_res);
+
+    omc::BoundsArgs a{};
+    const double dt = p->T / N, L2E = 1.4426950408889634074;
+    a.N = N; a.is_put = p->is_put ? 1 : 0; a.K = p->K; a.invK = 1.0 / p->K;
+    a.s0 = (float)p->S0;  // launch_gbm_paths' constants, so every spot is the generator's
+    a.a = (float)((p->r - 0.5 * p->sigma * p->sigma) * dt * L2E);
+    a.b = (float)(p->sigma * std::sqrt(dt) * L2E);
+    a.k0 = (uint32_t)p->seed; a.k1 = (uint32_t)(p->seed >> 32);
+    a.D = w.D; a.betas = w.betas; a.tab = (uint32_t*)(b + o_tab);
+    a.n_lower = nl; a.stream_lower = (uint32_t)cfg->stream_lower;
+    a.So = (float*)b; a.n_outer = no; a.half_inner = ni / 2; a.stream_inner = (uint32_t)cfg->stream_inner;
+    a.q = (double*)(b + o_q); a.samples = (double*)(b + o_smp);
+    a.steps = (unsigned long long*)(b + o_steps);
+    a.part = (double*)(b + o_part);
+
+    HIP_TRY(hipEventRecord(c->ev[0], st));
+    if (fitted) {  // omc_lsm_poly's fits on the paths of p
+        float* S = nullptr;
+        int64_t ld = 0;
+        if ((rc = ensure_paths(c, p, Storage::full_only, &S, &ld))) return rc;
+        if ((rc = enqueue_paths(c, p, S, ld, false))) return rc;
+        omc::LsmProblem prob{S, ld, M, N, a.is_put, p->K, p->r, p->T};
+        if ((rc = enqueue_lsm(c, prob, w, policy, false))) return rc;
+    }
+    HIP_TRY(hipEventRecord(c->ev[1], st));
+    HIP_TRY(omc::bounds_tables(st, w.betas, (uint32_t*)a.tab, N, a.is_put, p->K, c->pass2_irr_every));
+    HIP_TRY(omc::bounds_lower(st, a, res));
+    HIP_TRY(hipEventRecord(c->ev[2], st));
+    HIP_TRY(omc::launch_gbm_paths(st, (float*)a.So, no, no, N, p->S0, p->r, p->sigma, p->T, p->seed,
+                                  (uint32_t)cfg->stream_outer, 0, 1, c->gbm_vec));
+    HIP_TRY(hipMemsetAsync(a.steps, 0, sizeof(unsigned long long), st));
+    // launches over blocks of outer paths, each at most kLaunchSteps inner steps even if the policy never exercises
+    int64_t blk = (int64_t)(kLaunchSteps / work1);
+    blk = blk < 1 ? 1 : (blk > no ? no : blk);
+    for (int64_t i0 = 0; i0 < no; i0 += blk) HIP_TRY(omc::bounds_inner(st, a, i0, no - i0 < blk ? no - i0 : blk));
+    HIP_TRY(omc::bounds_walk(st, a, res + 8));
+    HIP_TRY(hipEventRecord(c->ev[3], st));
+    double h[16];
+    unsigned long long steps = 0;
+    HIP_TRY(hipMemcpyAsync(h, res, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&steps, a.steps, sizeof steps, hipMemcpyDeviceToHost, st));
+    if (betas_out)
+        HIP_TRY(hipMemcpyAsync(betas_out, w.betas, sizeof(double) * 4 * (size_t)(N + 1), hipMemcpyDeviceToHost, st));
+    if (q_out) HIP_TRY(hipMemcpyAsync(q_out, a.q, sizeof(double) * (size_t)no * (size_t)N, hipMemcpyDeviceToHost, st));
+    if (samples_out) HIP_TRY(hipMemcpyAsync(samples_out, a.samples, sizeof(double) * (size_t)no, hipMemcpyDeviceToHost, st));
+    if ((rc = wait_stream(c))) return rc;
+    memset(out, 0, sizeof *out);
+    mean_and_se(h[0], h[1], (double)(nl / 2), &out->lower, &out->se_lower);  // pair means are the samples
+    mean_and_se(h[8], h[9], (double)(no / 2), &out->upper, &out->se_upper);
+    out->ci_lo = out->lower - 1.96 * out->se_lower;
+    out->ci_hi = out->upper + 1.96 * out->se_upper;
+    out->n_lower = nl; out->n_outer = no; out->n_inner = ni;
+    out->n_exercised_lower = (int64_t)llround(h[2]);
+    out->inner_path_steps = (int64_t)steps;
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    out->ms_fit = ms;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[1], c->ev[2]));
+    out->ms_lower = ms;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
+    out->ms_upper = ms;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[3]));
+    out->ms_total = ms;
+    return 0;
+}

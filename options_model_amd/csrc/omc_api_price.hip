@@ -6,14 +6,6 @@
 
 using namespace omc::abi;
 
-// the mean of M samples from their sum and sum of squares, and its standard error
-static void mean_and_se(double s, double s2, double M, double* mean, double* se)
-{
-    *mean = s / M;
-    const double var = s2 / M - *mean * *mean;
-    *se = std::sqrt((var > 0.0 ? var : 0.0) / M);
-}
-
 extern "C" {
 
 // ------------------------------------------------------------------ path generation

@@ -1,0 +1,42 @@
+// omc_bounds.h -- host interface of the Andersen-Broadie bound kernels (omc_bounds.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace omc {
+
+// Sums the two sweeps leave in their result buffers (8 doubles each, float64, fixed order; lsm_finalize's slots 0..3):
+//   lower:  0 sum of pair means of Z at tau_1   1 their squares   2 paths stopped before N   3 -
+//   upper:  0 sum of pair means of the samples  1 their squares   2 -                        3 -
+struct BoundsArgs {
+    int N, is_put;
+    double K, invK;
+    float s0, a, b;           // the generator's float32 start value and step constants (launch_gbm_paths)
+    uint32_t k0, k1;          // Philox key = seed
+    const double* D;          // [N+1] exp(-r dt t): Z_t = D[t] max(phi(S_t), 0)
+    const double* betas;      // [N+1][4] the policy (float64 fallback on irregular steps)
+    const uint32_t* tab;      // [N+1][8] exercise tables of lsm_crit_build_body (stored-path kind in slots 0..3)
+    // lower bound
+    int64_t n_lower;
+    uint32_t stream_lower;
+    // upper bound
+    const float* So;          // [N+1][n_outer] outer paths (omc_gbm_paths_f32 at stream_outer)
+    int64_t n_outer, half_inner;
+    uint32_t stream_inner;
+    double* q;                // [n_outer][N] Q^_t
+    double* samples;          // [n_outer]
+    unsigned long long* steps;  // inner path steps (integer sum)
+    double* part;             // [8][kPStride] per-workgroup partials
+};
+
+int64_t bounds_lower_blocks(const BoundsArgs& a);
+hipError_t bounds_lower(hipStream_t st, const BoundsArgs& a, double* result);
+// Q^_t[i] for outer paths [i0, i0 + ni) and t = 0..N-1
+hipError_t bounds_inner(hipStream_t st, const BoundsArgs& a, int64_t i0, int64_t ni);
+int64_t bounds_walk_blocks(const BoundsArgs& a);
+hipError_t bounds_walk(hipStream_t st, const BoundsArgs& a, double* result);
+// the stored-path exercise tables of `betas` (device [N+1][4]) into tab [N+1][8]
+hipError_t bounds_tables(hipStream_t st, const double* betas, uint32_t* tab, int N, int is_put, double K, int irr_every);
+
+}  // namespace omc

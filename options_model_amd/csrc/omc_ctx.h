@@ -105,6 +105,13 @@ int check_p2p(omc_ctx* c, const double* h = nullptr, int n = 0);
 void fill_result(omc_result* res, const double* h, int64_t M, int world = 1);  // clears *res first
 int copy_outputs(omc_ctx* c, const omc::LsmWorkspace& w, int64_t M, int N, double* betas_out, float* sx_out,
                  int32_t* tex_out);
+// the mean of M samples from their sum and sum of squares, and its standard error
+inline void mean_and_se(double s, double s2, double M, double* mean, double* se)
+{
+    *mean = s / M;
+    const double var = s2 / M - *mean * *mean;
+    *se = std::sqrt((var > 0.0 ? var : 0.0) / M);
+}
 inline size_t up256(size_t bytes) { return (bytes + 255) / 256 * 256; }  // the next block of a scratch layout
 
 // the library's own path matrix and the fused pricing
@@ -186,6 +193,7 @@ struct omc_ctx {
     DevBuf foldC;
     DevBuf gk_part, gk_res;  // omc_price_american_greeks: per-workgroup partials, reduced sums
     DevBuf bar_part, bar_res;  // omc_price_barrier: the generator's per-workgroup partials, reduced sums
+    DevBuf bnd;                // omc_price_american_bounds: outer paths, Q^ table, samples, tables, partials, sums
     struct FoldKey { int N = -1; double c0 = 0, g = 0; } fold_key[2];
     int world = 1;  // ranks whose sums the hook / communicator adds up (equal shards)
     omc_allreduce_fn hook = nullptr;
