@@ -21,7 +21,7 @@ HEADERS = ["omc_ctx.h", "omc_device.h", "omc_crit.h", "omc_kernels.h", "omc_lsm_
            os.path.join("..", "..", "include", "omc.h")]
 ARCH = "gfx950"
 # The extra compiler flags the library was built with (OMC_HIPCC_FLAGS: experiment builds such as
-# -DOMC_DIAG_BUILD or -DOMC_P2_U=16) are recorded next to it: a library left behind by an experiment is
+# -DOMC_DIAG_BUILD) are recorded next to it: a library left behind by an experiment is
 # stale for every process that does not ask for the same flags, so tests / bench / profiles can never
 # silently run a non-default build.
 FLAGS_STAMP = os.path.join(LIBDIR, "libomc.flags")

@@ -370,6 +370,13 @@ int copy_outputs(omc_ctx* c, const omc::LsmWorkspace& w, int64_t M, int N, doubl
     return 0;
 }
 
+int upload_fits(omc_ctx* c, const omc::LsmWorkspace& w, const double* betas, int N)
+{
+    HIP_TRY(hipMemcpyAsync(w.betas, betas, sizeof(double) * 4 * (size_t)(N + 1), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 int check_params(const omc_params* p)
 {
     int rc;

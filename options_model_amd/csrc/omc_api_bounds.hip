@@ -38,10 +38,7 @@ extern "C" int omc_price_american_bounds(omc_ctx* c, const omc_params* p, const 
     const int64_t M = fitted ? p->n_paths : 2;
     omc::LsmWorkspace w;
     if ((rc = prepare_lsm(c, M, N, p->r, p->T, policy == OMC_SEM_TWO_PASS, true, &w))) return rc;
-    if (!fitted) {
-        HIP_TRY(hipMemcpyAsync(w.betas, betas, sizeof(double) * 4 * (size_t)(N + 1), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st));  // `betas` is caller memory
-    }
+    if (!fitted && (rc = upload_fits(c, w, betas, N))) return rc;
     // the workspace: outer paths [N+1][n_outer] f32 | Q^ [n_outer][N] | samples [n_outer] | tables [N+1][8] u32 |
     // partials [8][kPStride] | sums [16] | inner step count
     const size_t o_q = up256(sizeof(float) * (size_t)(N + 1) * (size_t)no);
@@ -78,7 +75,10 @@ extern "C" int omc_price_american_bounds(omc_ctx* c, const omc_params* p, const 
         if ((rc = enqueue_lsm(c, prob, w, policy, false))) return rc;
     }
     HIP_TRY(hipEventRecord(c->ev[1], st));
-    HIP_TRY(omc::bounds_tables(st, w.betas, (uint32_t*)a.tab, N, a.is_put, p->K, c->pass2_irr_every));
+    omc::CritArgs ct;  // the stored-path tables of the policy
+    ct.betas = w.betas; ct.tab = (uint32_t*)a.tab;
+    ct.N = N; ct.is_put = a.is_put; ct.K = p->K; ct.irr_every = c->pass2_irr_every;
+    HIP_TRY(omc::lsm_crit_build(st, ct));
     HIP_TRY(omc::bounds_lower(st, a, res));
     HIP_TRY(hipEventRecord(c->ev[2], st));
     HIP_TRY(omc::launch_gbm_paths(st, (float*)a.So, no, no, N, p->S0, p->r, p->sigma, p->T, p->seed,

@@ -2,6 +2,7 @@
 // the fused pricing, European, the pass-2 tables check, pathwise Greeks, barrier options, the calibrator's inner loop.
 #include "omc_ctx.h"
 #include "omc_barrier.h"
+#include "omc_crit.h"
 #include "omc_greeks.h"
 
 using namespace omc::abi;
@@ -147,9 +148,7 @@ int omc_lsm_apply_frozen(omc_ctx* c, const float* S, int64_t ld, int64_t n_paths
     if (!betas || !res) return fail(-7, "null pointer.");
     omc::LsmWorkspace w;
     if ((rc = prepare_lsm(c, n_paths, n_steps, r, T, false, true, &w))) return rc;
-    HIP_TRY(hipMemcpyAsync(w.betas, betas, sizeof(double) * 4 * (size_t)(n_steps + 1),
-                           hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));  // `betas` is caller memory
+    if ((rc = upload_fits(c, w, betas, n_steps))) return rc;
     omc::LsmProblem p{S, ld, n_paths, n_steps, is_put ? 1 : 0, K, r, T};
     HIP_TRY(omc::lsm_pass2_apply(c->stream, p, w, sx_out || tex_out));
     if ((rc = copy_outputs(c, w, n_paths, n_steps, nullptr, sx_out, tex_out))) return rc;
@@ -232,7 +231,8 @@ int omc_pass2_tables_check(omc_ctx* c, int is_put, double K, int n_steps, const 
     HIP_TRY(hipMemcpyAsync(tab.data(), b + o_tab, sizeof(uint32_t) * 8 * n1, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(mismatches, b + o_mism, sizeof(int64_t) * 2 * n1, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    for (size_t t = 0; t < n1; ++t) irregular[t] = tab[8 * t] == 0xffffffffu || tab[8 * t + 4] == 0xffffffffu;
+    for (size_t t = 0; t < n1; ++t)
+        irregular[t] = tab[8 * t] == omc::kCritIrregular || tab[8 * t + 4] == omc::kCritIrregular;
     return 0;
 }
 
@@ -259,10 +259,7 @@ int omc_price_american_greeks(omc_ctx* c, const omc_params* p, double bump, cons
     if ((rc = ensure_paths(c, p, Storage::planned, &S, &ld, &cK))) return rc;
     omc::LsmWorkspace w;
     if ((rc = prepare_lsm(c, M, N, p->r, p->T, betas == nullptr, betas_out != nullptr, &w))) return rc;
-    if (betas) {
-        HIP_TRY(hipMemcpyAsync(w.betas, betas, sizeof(double) * 4 * (size_t)(N + 1), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));  // `betas` is caller memory
-    }
+    if (betas && (rc = upload_fits(c, w, betas, N))) return rc;
     omc::GreeksArgs g;
     g.S = S; g.ld = ld; g.cols = cK ? M / 2 : M;
     g.N = N; g.is_put = p->is_put ? 1 : 0; g.gbm = p->model == OMC_MODEL_GBM ? 1 : 0;

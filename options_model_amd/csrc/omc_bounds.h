@@ -36,7 +36,5 @@ hipError_t bounds_lower(hipStream_t st, const BoundsArgs& a, double* result);
 hipError_t bounds_inner(hipStream_t st, const BoundsArgs& a, int64_t i0, int64_t ni);
 int64_t bounds_walk_blocks(const BoundsArgs& a);
 hipError_t bounds_walk(hipStream_t st, const BoundsArgs& a, double* result);
-// the stored-path exercise tables of `betas` (device [N+1][4]) into tab [N+1][8]
-hipError_t bounds_tables(hipStream_t st, const double* betas, uint32_t* tab, int N, int is_put, double K, int irr_every);
 
 }  // namespace omc

@@ -19,25 +19,13 @@
 
 namespace omc {
 
-// the float64 rule of omc_lsm_apply_frozen at date d (1 <= d < N): n_d > 0.5, imm > 0, imm > the fitted continuation
-__device__ __forceinline__ bool bd_rule(float s, int d, const BoundsArgs& a)
-{
-    double b0, b1, b2;
-    crit_fits(a.betas, d, a.N, b0, b1, b2);
-    const double sd = (double)s;
-    const double imm = a.is_put ? a.K - sd : sd - a.K;
-    const double u = fma(sd, a.invK, -1.0);
-    const double cont = fma(u, fma(u, b2, b1), b0);
-    return (imm > 0.0) & (imm > cont);
-}
-
-// does a path at spot s stop at date d?  iv = the date's table (lo0, lo1, len0, len1)
+// does a path at spot s stop at date d?  iv = the date's table (lo0, lo1, len0, len1); an irregular date decides with
+// the float64 rule of omc_lsm_apply_frozen
 __device__ __forceinline__ bool bd_stop(float s, int d, uint4 iv, const BoundsArgs& a)
 {
     if (d >= a.N) return true;
-    if (iv.x == kCritIrregular) return bd_rule(s, d, a);
-    const uint32_t bits = __float_as_uint(s);
-    return ((bits - iv.x) < iv.z) | ((bits - iv.y) < iv.w);
+    if (iv.x == kCritIrregular) return exercises(pay_stored(s, a.K, a.invK, a.is_put), fit_given(a.betas, d, a.N));
+    return crit_in(iv, __float_as_uint(s));
 }
 
 __device__ __forceinline__ double bd_value(float s, int d, const BoundsArgs& a)
@@ -51,18 +39,6 @@ __device__ __forceinline__ void bd_load_tables(const BoundsArgs& a, uint4* sh)
 {
     for (int t = threadIdx.x; t <= a.N; t += blockDim.x) sh[t] = *reinterpret_cast<const uint4*>(a.tab + (size_t)t * 8);
     __syncthreads();
-}
-
-// ------------------------------------------------------------------ exercise tables (the builder of pass 2)
-__global__ __launch_bounds__(128) void bounds_crit_build_kernel(CritArgs c) { lsm_crit_build_body(c); }
-
-hipError_t bounds_tables(hipStream_t st, const double* betas, uint32_t* tab, int N, int is_put, double K, int irr_every)
-{
-    CritArgs c;
-    c.gmom = nullptr; c.betas = betas; c.betas_out = nullptr; c.cK = nullptr; c.tab = tab;
-    c.N = N; c.is_put = is_put; c.K = K; c.invK = 1.0 / K; c.irr_every = irr_every;
-    hipLaunchKernelGGL(bounds_crit_build_kernel, dim3(N + 1), dim3(128), 0, st, c);
-    return hipGetLastError();
 }
 
 // ------------------------------------------------------------------ lower bound

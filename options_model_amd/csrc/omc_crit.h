@@ -33,11 +33,18 @@ namespace omc {
 constexpr uint32_t kCritTop = 0x7f800000u;  // +inf: the last ordinal of the domain
 constexpr int kCritHalf = 32;               // a candidate's window: ordinals [o - 32, o + 32)
 constexpr int kCritMaxCand = 6;
+constexpr uint32_t kCritIrregular = 0xffffffffu;  // lo[0] of an irregular step (a real lo is <= kCritTop)
 
-// decisions of one path kind at one step: spot bits b exercise iff (b - lo[i]) < len[i] (unsigned) for i = 0 or 1
+// decisions of one path kind at one step: spot bits b exercise iff crit_in(lo[0], lo[1], len[0], len[1], b)
 struct CritIv {
     uint32_t lo[2], len[2];
 };
+
+// the table test: (b - lo) < len (unsigned) holds exactly for b in [lo, lo + len); `|`, not `||`, keeps it branch-free
+OMC_HD inline bool crit_in(uint32_t lo0, uint32_t lo1, uint32_t len0, uint32_t len1, uint32_t b)
+{
+    return ((b - lo0) < len0) | ((b - lo1) < len1);
+}
 
 OMC_HD inline float crit_float(uint32_t o) { return __builtin_bit_cast(float, o); }
 OMC_HD inline uint32_t crit_bits(float f) { return __builtin_bit_cast(uint32_t, f); }
@@ -186,9 +193,6 @@ OMC_HD inline bool crit_build(const P& pred, const double* cand, int ncand, Crit
     return true;
 }
 
-OMC_HD inline bool crit_in(const CritIv& t, uint32_t b)
-{
-    return (b - t.lo[0]) < t.len[0] || (b - t.lo[1]) < t.len[1];
-}
+OMC_HD inline bool crit_in(const CritIv& t, uint32_t b) { return crit_in(t.lo[0], t.lo[1], t.len[0], t.len[1], b); }
 
 }  // namespace omc

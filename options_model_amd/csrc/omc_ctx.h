@@ -105,6 +105,8 @@ int check_p2p(omc_ctx* c, const double* h = nullptr, int n = 0);
 void fill_result(omc_result* res, const double* h, int64_t M, int world = 1);  // clears *res first
 int copy_outputs(omc_ctx* c, const omc::LsmWorkspace& w, int64_t M, int N, double* betas_out, float* sx_out,
                  int32_t* tex_out);
+// the caller's fits [N+1][4] into w.betas; returns once they are copied (`betas` is caller memory)
+int upload_fits(omc_ctx* c, const omc::LsmWorkspace& w, const double* betas, int N);
 // the mean of M samples from their sum and sum of squares, and its standard error
 inline void mean_and_se(double s, double s2, double M, double* mean, double* se)
 {

@@ -28,8 +28,6 @@ struct GreeksArgs {
 // workgroups of the sweep (one thread per `greeks_vec(..)` columns, no grid-stride loop) and its column width
 int greeks_vec(const GreeksArgs& a);
 int64_t greeks_blocks(const GreeksArgs& a);
-// betas[t] = solve_poly2(gmom[t]), n = gmom[t][0] for t = 1 .. N-1: the fits pass 2 solves for itself
-hipError_t lsm_solve_betas(hipStream_t st, const double* gmom, double* betas, int N);
 // the sweep (events around it when given) + its finalize: sums -> a.result
 hipError_t lsm_greeks(hipStream_t st, const GreeksArgs& a, hipEvent_t ev_begin, hipEvent_t ev_end);
 

@@ -11,8 +11,8 @@
 //   gamma  (delta+ - delta-) / (2 h S0), delta+- = D_k+- phi'(lambda+- s_k+-) s_k+- / S0
 // with D_k = D[k-1] (valued at t = dt, as the pricing) and phi' = -1{imm > 0} (put) / +1{imm > 0} (call).
 //
-// One thread owns VEC columns and walks them backward until every chain has exercised; rows arrive U at a time with
-// the next batch requested before the current one is decided (pass 2's look-ahead).  Grid = one thread per VEC columns
+// One thread owns VEC columns and walks them backward until every chain has exercised; rows arrive in batches with
+// the next batch requested before the current one is decided (walk_rows, as the folded pass 2).  Grid = one thread per VEC columns
 // (no grid-stride loop: the 20 sums are live only after the sweep), per-workgroup partials in a fixed order, then one
 // finalize launch: two identical calls return identical bits.
 #include "omc_greeks.h"
@@ -27,12 +27,7 @@ __device__ __forceinline__ void greeks_body(const GreeksArgs& a)
     __shared__ double red[kNQ * kRedStride];
     const int tid = threadIdx.x;
     const int N = a.N;
-    for (int k = tid; k < (N + 1) * 4; k += kBlock) {
-        const int t = k >> 2;
-        const bool fit = t >= 1 && t < N && a.betas[(size_t)t * 4 + 3] > 0.5;
-        sh_b[k] = (FOLD && (k & 3) == 3) ? a.cK[t] : (fit ? a.betas[k] : ((k & 3) == 0 ? __builtin_huge_val() : 0.0));
-    }
-    __syncthreads();
+    fits_to_lds<FOLD>(sh_b, nullptr, nullptr, a.betas, a.cK, N);
     const double K = a.K, invK = 1.0 / a.K;
     const double lup = 1.0 + a.h, ldn = 1.0 - a.h;
     const int64_t j = ((int64_t)blockIdx.x * kBlock + tid) * VEC;
@@ -56,28 +51,25 @@ __device__ __forceinline__ void greeks_body(const GreeksArgs& a)
         }
     }
     auto decide = [&](const float (&row)[VEC], int t) {
-        const double b0 = sh_b[4 * t], b1 = sh_b[4 * t + 1], b2 = sh_b[4 * t + 2];
-        auto chain = [&](int c, int v, double imm, double u) {
-            const double cont = fma(u, fma(u, b2, b1), b0);
-            const bool ex = (tx[c][v] == N) & (imm > 0.0) & (imm > cont);
+        const Fit f = fit_lds(sh_b, t);
+        auto chain = [&](int c, int v, const PayU& p) {
+            const bool ex = (tx[c][v] == N) & exercises(p, f);
             sx[c][v] = ex ? row[v] : sx[c][v];
             tx[c][v] = ex ? t : tx[c][v];
         };
-        auto scen = [&](int c, int v, double s) {  // a bumped chain decides on spot s = lambda * spot, in double
-            chain(c, v, PUT ? K - s : s - K, fma(s, invK, -1.0));
-        };
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
+            // the bumped chains decide on spot lambda * spot, in double
             const double sd = (double)row[v];
-            chain(0, v, PUT ? K - sd : sd - K, fma(sd, invK, -1.0));  // pass 2's expressions
-            scen(1, v, lup * sd);
-            scen(2, v, ldn * sd);
+            chain(0, v, pay_stored(sd, K, invK, PUT));
+            chain(1, v, pay_stored(lup * sd, K, invK, PUT));
+            chain(2, v, pay_stored(ldn * sd, K, invK, PUT));
             if constexpr (FOLD) {
-                const double ub = fold_u(sh_b[4 * t + 3], row[v]);
-                chain(3, v, fold_pay(ub, K, PUT), ub);  // pass 2's expressions for the partner
-                const double sb = K * (1.0 + ub);
-                scen(4, v, lup * sb);
-                scen(5, v, ldn * sb);
+                const PayU pb = pay_partner(sh_b[4 * t + 3], row[v], K, PUT);
+                chain(3, v, pb);
+                const double sb = K * (1.0 + pb.u);
+                chain(4, v, pay_stored(lup * sb, K, invK, PUT));
+                chain(5, v, pay_stored(ldn * sb, K, invK, PUT));
             }
         }
     };
@@ -90,30 +82,7 @@ __device__ __forceinline__ void greeks_body(const GreeksArgs& a)
         }
         return l;
     };
-    constexpr int U = 8;
-    int t = N - 1;
-    auto fetch = [&](float (&b)[U][VEC], int tt) {
-#pragma unroll
-        for (int k = 0; k < U; ++k) loadf_stream<VEC>(col + (int64_t)max(tt - k, 1) * a.ld, b[k]);
-    };
-    auto work = [&](const float (&b)[U][VEC], int tt) {
-#pragma unroll
-        for (int k = 0; k < U; ++k)
-            if (tt - k >= 1) decide(b[k], tt - k);
-    };
-    float bA[U][VEC], bB[U][VEC];
-    if (t >= 1 && live()) fetch(bA, t);
-    while (t >= 1 && live()) {
-        if (t - U >= 1) fetch(bB, t - U);
-        __builtin_amdgcn_sched_barrier(0);
-        work(bA, t);
-        t -= U;
-        if (!(t >= 1 && live())) break;
-        if (t - U >= 1) fetch(bA, t - U);
-        __builtin_amdgcn_sched_barrier(0);
-        work(bB, t);
-        t -= U;
-    }
+    walk_rows<VEC, false>(col, a.ld, N, decide, live);
 
     // ---- the per-path terms, from the (spot, step) pairs alone
     double g0[kNQ], g1[kNQ], g2[kNQ];
@@ -139,16 +108,12 @@ __device__ __forceinline__ void greeks_body(const GreeksArgs& a)
                     s = (double)sx[c][v];
                     imm = payoff_d(sx[c][v], K, PUT);
                 } else {
-                    const double ub = fold_u(sh_b[4 * k + 3], sx[c][v]);
-                    imm = fold_pay(ub, K, PUT);
-                    s = K * (1.0 + ub);
+                    const PayU pb = pay_partner(sh_b[4 * k + 3], sx[c][v], K, PUT);
+                    imm = pb.imm;
+                    s = K * (1.0 + pb.u);
                 }
                 const double Dk = a.D[k - 1];
-                const double cf = (imm > 0.0 ? imm : 0.0) * Dk;  // the pricing's cash-flow, bit for bit
-                g0[0] += cf;
-                g0[1] += cf * cf;
-                g0[2] += k < N ? 1.0 : 0.0;
-                g0[3] += cf == 0.0 ? 1.0 : 0.0;
+                const double cf = add_cash_flow(g0, imm, Dk, k < N);  // the pricing's cash-flow, bit for bit
                 const double Ds = (imm > 0.0 ? sign : 0.0) * Dk * s;  // D_k phi'(s) s
                 const double delta = Ds * invS0;
                 g1[0] += delta;
@@ -222,11 +187,6 @@ __global__ __launch_bounds__(kBlock) void lsm_greeks_finalize_kernel(const doubl
     if (tid < 64 && (tid & 7) == 0) result[8 * g + (tid >> 3)] = s;
 }
 
-__global__ void lsm_solve_betas_kernel(const double* __restrict__ gmom, double* __restrict__ betas, int N)
-{
-    lsm_solve_all_body(gmom, betas, N);
-}
-
 int greeks_vec(const GreeksArgs& a)
 {
     return ((a.cols % 2) == 0 && (a.ld % 2) == 0 && ((uintptr_t)a.S % 8) == 0) ? 2 : 1;
@@ -236,13 +196,6 @@ int64_t greeks_blocks(const GreeksArgs& a)
 {
     const int64_t per = (int64_t)kBlock * greeks_vec(a);
     return (a.cols + per - 1) / per;
-}
-
-hipError_t lsm_solve_betas(hipStream_t st, const double* gmom, double* betas, int N)
-{
-    if (N < 2) return hipSuccess;
-    hipLaunchKernelGGL(lsm_solve_betas_kernel, dim3((N + kBlock - 1) / kBlock), dim3(kBlock), 0, st, gmom, betas, N);
-    return hipGetLastError();
 }
 
 hipError_t lsm_greeks(hipStream_t st, const GreeksArgs& a, hipEvent_t ev_begin, hipEvent_t ev_end)

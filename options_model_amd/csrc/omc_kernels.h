@@ -156,6 +156,20 @@ hipError_t lsm_pass1_moments(hipStream_t st, const LsmProblem& p, const LsmWorks
 // when write_state, leaves sums in w.result
 hipError_t lsm_pass2_apply(hipStream_t st, const LsmProblem& p, const LsmWorkspace& w,
                            bool write_state, bool solve_from_moments = false);
+// betas[t] = solve_poly2(gmom[t]), n = gmom[t][0] for t = 1 .. N-1: the fits pass 2 solves for itself
+hipError_t lsm_solve_betas(hipStream_t st, const double* gmom, double* betas, int N);
+// pass 2's exercise tables [N+1][8] (omc_crit.h; the stored path's words, then the partner's) of one set of fits
+struct CritArgs {
+    const double* gmom = nullptr;  // non-null: solve the fits from the reduced moments (and write them to betas_out) ...
+    const double* betas = nullptr;  // ... else take them from here ([N+1][4])
+    double* betas_out = nullptr;
+    const double* cK = nullptr;  // null: no partner (full storage)
+    uint32_t* tab = nullptr;     // [N+1][8]
+    int N = 0, is_put = 0;
+    double K = 0.0, invK = 0.0;  // invK: filled by lsm_crit_build
+    int irr_every = 0;  // tests: > 0 marks every step t with t % irr_every == 0 irregular (option "pass2_tables_irregular_every")
+};
+hipError_t lsm_crit_build(hipStream_t st, CritArgs c);
 // tests: pass 2's exercise tables from the fits `betas` [N+1][4] and cK [N+1] (device) into tab [N+1][8], then the
 // table decisions against the float64 ones at every non-negative float32 spot: mismatches per step and kind into
 // mism [N+1][2] (device, zeroed by the caller); irregular steps are not checked

@@ -55,6 +55,11 @@ __global__ __launch_bounds__(kBlock) void lsm_reduce_pass1_kernel(const double* 
     lsm_reduce_pass1_body(part1, gmom, ntiles, N);
 }
 
+__global__ void lsm_solve_betas_kernel(const double* __restrict__ gmom, double* __restrict__ betas, int N)
+{
+    lsm_solve_all_body(gmom, betas, N);
+}
+
 template <int VEC, bool WRITE_STATE>
 __global__ __launch_bounds__(kBlock) void lsm_pass2_kernel(Pass2Args a) { lsm_pass2_body<VEC, WRITE_STATE>(a); }
 
@@ -459,8 +464,9 @@ hipError_t lsm_pass2_apply(hipStream_t st, const LsmProblem& p, const LsmWorkspa
     if (tab) {
         CritArgs c;
         c.gmom = a.gmom; c.betas = w.betas; c.betas_out = a.betas_out; c.cK = p.fold_cK; c.tab = w.crit;
-        c.N = p.N; c.is_put = p.is_put; c.K = a.K; c.invK = a.invK; c.irr_every = w.crit_irr_every;
-        hipLaunchKernelGGL(lsm_crit_build_kernel, dim3(p.N + 1), dim3(128), 0, st, c);
+        c.N = p.N; c.is_put = p.is_put; c.K = p.K; c.irr_every = w.crit_irr_every;
+        const hipError_t e = lsm_crit_build(st, c);
+        if (e != hipSuccess) return e;
         a.gmom = nullptr;
         a.betas_out = nullptr;
         a.crit = w.crit;
@@ -496,16 +502,29 @@ hipError_t lsm_pass2_apply(hipStream_t st, const LsmProblem& p, const LsmWorkspa
     return hipGetLastError();
 }
 
+hipError_t lsm_crit_build(hipStream_t st, CritArgs c)
+{
+    c.invK = 1.0 / c.K;
+    hipLaunchKernelGGL(lsm_crit_build_kernel, dim3(c.N + 1), dim3(128), 0, st, c);
+    return hipGetLastError();
+}
+
 hipError_t lsm_crit_check(hipStream_t st, const double* betas, const double* cK, uint32_t* tab, int N, int is_put,
                           double K, int irr_every, unsigned long long* mism)
 {
     CritArgs c;
-    c.gmom = nullptr; c.betas = betas; c.betas_out = nullptr; c.cK = cK; c.tab = tab;
-    c.N = N; c.is_put = is_put; c.K = K; c.invK = 1.0 / K; c.irr_every = irr_every;
-    hipLaunchKernelGGL(lsm_crit_build_kernel, dim3(N + 1), dim3(128), 0, st, c);
-    if (N >= 2)
-        hipLaunchKernelGGL(lsm_crit_check_kernel, dim3(2048, N - 1), dim3(kBlock), 0, st, tab, betas, cK, N, is_put, K,
-                           c.invK, mism);
+    c.betas = betas; c.cK = cK; c.tab = tab; c.N = N; c.is_put = is_put; c.K = K; c.irr_every = irr_every;
+    const hipError_t e = lsm_crit_build(st, c);
+    if (e != hipSuccess || N < 2) return e;
+    hipLaunchKernelGGL(lsm_crit_check_kernel, dim3(2048, N - 1), dim3(kBlock), 0, st, tab, betas, cK, N, is_put, K,
+                       1.0 / K, mism);
+    return hipGetLastError();
+}
+
+hipError_t lsm_solve_betas(hipStream_t st, const double* gmom, double* betas, int N)
+{
+    if (N < 2) return hipSuccess;
+    hipLaunchKernelGGL(lsm_solve_betas_kernel, dim3((N + kBlock - 1) / kBlock), dim3(kBlock), 0, st, gmom, betas, N);
     return hipGetLastError();
 }
 

@@ -801,6 +801,140 @@ __device__ __forceinline__ void lsm_solve_all_body(const double* __restrict__ gm
     bo[0] = beta[0]; bo[1] = beta[1]; bo[2] = beta[2]; bo[3] = m[0];
 }
 
+// ------------------------------------------------------------------ the frozen exercise policy of the two-pass flow
+// Pass 2 (full and folded storage, float64 or table decisions), its exercise tables, the Greeks sweep and the price
+// bounds must agree on the rule bit for bit: which steps have a fit, how a spot becomes (payoff, moneyness), when a path
+// exercises and what its cash-flow is worth.  This section is its one statement; the CPU restatements the tests check
+// against (oracle, tests/helpers) stay independent of it.
+
+// the continuation value b0 + b1 u + b2 u^2 of one step at moneyness u
+struct Fit {
+    double b0, b1, b2;
+};
+// a step without a fit (t outside [1, N), or a regression set of at most half a path) gets an infinite continuation
+// value instead of a branch in the sweeps: it never exercises
+__device__ __forceinline__ Fit no_fit() { return {__builtin_huge_val(), 0.0, 0.0}; }
+
+// the fit of step t from a table betas [N+1][4] (b0, b1, b2, n)
+__device__ __forceinline__ Fit fit_given(const double* __restrict__ betas, int t, int N)
+{
+    if (t >= 1 && t < N && betas[(size_t)t * 4 + 3] > 0.5)
+        return {betas[(size_t)t * 4], betas[(size_t)t * 4 + 1], betas[(size_t)t * 4 + 2]};
+    return no_fit();
+}
+
+// the fit of step t solved from the reduced moments gmom [N+1][8] -- the very function lsm_solve_betas_kernel runs: same
+// bits -- and, when betas_out is given, written to it as (b0, b1, b2, n)
+__device__ __forceinline__ Fit fit_solved(const double* __restrict__ gmom, int t, int N, double* betas_out)
+{
+    const bool inner = t >= 1 && t < N;
+    double m[8], beta[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int q = 0; q < 8; ++q) m[q] = inner ? gmom[(size_t)t * 8 + q] : 0.0;
+    if (inner) solve_poly2(m, beta);
+    if (inner && betas_out) {
+        double* bo = betas_out + (size_t)t * 4;
+        bo[0] = beta[0]; bo[1] = beta[1]; bo[2] = beta[2]; bo[3] = m[0];
+    }
+    if (inner && m[0] > 0.5) return {beta[0], beta[1], beta[2]};
+    return no_fit();
+}
+
+// The sweeps' prologue, every thread of the workgroup: the fits of all steps into LDS sh_b [N+1][4] -- b0, b1, b2 and,
+// FOLD, cK[t] -- solved from gmom when it is given (workgroup 0 also writing them to betas_out), else read from betas.
+template <bool FOLD>
+__device__ __forceinline__ void fits_to_lds(double* sh_b, const double* __restrict__ gmom, double* betas_out,
+                                            const double* __restrict__ betas, const double* __restrict__ cK, int N)
+{
+    auto put = [&](int t, const Fit& f) {
+        sh_b[4 * t] = f.b0;
+        sh_b[4 * t + 1] = f.b1;
+        sh_b[4 * t + 2] = f.b2;
+        sh_b[4 * t + 3] = FOLD ? cK[t] : 0.0;
+    };
+    if (gmom) {
+        for (int t = threadIdx.x; t <= N; t += kBlock) put(t, fit_solved(gmom, t, N, blockIdx.x == 0 ? betas_out : nullptr));
+    } else {
+        for (int t = threadIdx.x; t <= N; t += kBlock) put(t, fit_given(betas, t, N));
+    }
+    __syncthreads();
+}
+__device__ __forceinline__ Fit fit_lds(const double* sh_b, int t) { return {sh_b[4 * t], sh_b[4 * t + 1], sh_b[4 * t + 2]}; }
+
+// a path at one step: its payoff imm and its moneyness u
+struct PayU {
+    double imm, u;
+};
+// the stored path at spot s (a double: the Greeks' bumped chains decide on lambda s)
+__device__ __forceinline__ PayU pay_stored(double s, double K, double invK, int is_put)
+{
+    return {is_put ? K - s : s - K, fma(s, invK, -1.0)};
+}
+// the folded partner of the stored path at spot s
+__device__ __forceinline__ PayU pay_partner(double ck, float s, double K, int is_put)
+{
+    const double u = fold_u(ck, s);
+    return {fold_pay(u, K, is_put), u};
+}
+// the decision: the payoff is positive and above the fitted continuation value
+__device__ __forceinline__ bool exercises(const PayU& p, const Fit& f)
+{
+    return (p.imm > 0.0) & (p.imm > fma(p.u, fma(p.u, f.b2, f.b1), f.b0));
+}
+
+// the table test on a step's words as the sweeps read them from LDS: (lo0, lo1, len0, len1)
+__device__ __forceinline__ bool crit_in(uint4 iv, uint32_t b) { return crit_in(iv.x, iv.y, iv.z, iv.w, b); }
+
+// a path's cash-flow cf = max(imm, 0) D, with D the discount factor of its exercise step, added to the four sums (cf,
+// cf^2, exercised before maturity, cf == 0); returns cf
+__device__ __forceinline__ double add_cash_flow(double* acc, double imm, double D, bool exercised)
+{
+    const double cf = (imm > 0.0 ? imm : 0.0) * D;
+    acc[0] += cf;
+    acc[1] += cf * cf;
+    acc[2] += exercised ? 1.0 : 0.0;
+    acc[3] += cf == 0.0 ? 1.0 : 0.0;
+    return cf;
+}
+
+// The look-ahead backward walk of the folded pass 2 and the Greeks sweep over rows N-1 .. 1 of a thread's columns (col,
+// row stride ld): kWalkRows rows per batch, the NEXT batch requested before the current one is decided (the decisions of
+// a batch are a dependent chain of ~450 vector instructions: without the look-ahead every batch waited out a whole
+// memory round trip with 4 waves per SIMD to cover it).  Rows below 1 are clamped to row 1 and not decided; the walk
+// ends once live() is false.  ROW_BARRIER: a scheduling barrier after every row (the table sweep: one step's table words
+// at a time -- hoisted, a batch's would take 8 kWalkRows registers).
+constexpr int kWalkRows = 8;
+template <int VEC, bool ROW_BARRIER, class Decide, class Live>
+__device__ __forceinline__ void walk_rows(const float* col, int64_t ld, int N, const Decide& decide, const Live& live)
+{
+    constexpr int U = kWalkRows;
+    auto fetch = [&](float (&b)[U][VEC], int t) {
+#pragma unroll
+        for (int k = 0; k < U; ++k) loadf_stream<VEC>(col + (int64_t)max(t - k, 1) * ld, b[k]);
+    };
+    auto work = [&](const float (&b)[U][VEC], int t) {
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            if (t - k >= 1) decide(b[k], t - k);
+            if (ROW_BARRIER) __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+    float bA[U][VEC], bB[U][VEC];
+    int t = N - 1;
+    if (t >= 1 && live()) fetch(bA, t);
+    while (t >= 1 && live()) {
+        if (t - U >= 1) fetch(bB, t - U);
+        __builtin_amdgcn_sched_barrier(0);
+        work(bA, t);
+        t -= U;
+        if (!(t >= 1 && live())) break;
+        if (t - U >= 1) fetch(bA, t - U);
+        __builtin_amdgcn_sched_barrier(0);
+        work(bB, t);
+        t -= U;
+    }
+}
+
 struct Pass2Args {
     const float* S;
     int64_t ld, M;
@@ -824,29 +958,18 @@ struct Pass2Args {
 };
 
 // ------------------------------------------------------------------ pass-2 exercise tables (omc_crit.h)
-// The decisions of the two sweeps below, as functions of the loaded spot: the expressions of `decide`, verbatim.
+// The policy's decisions at one step as functions of the loaded spot, one per path kind.
 struct CritStored {
-    double K, invK, b0, b1, b2;
+    double K, invK;
+    Fit f;
     int is_put;
-    __device__ bool operator()(float s) const
-    {
-        const double sd = (double)s;
-        const double imm = is_put ? K - sd : sd - K;
-        const double u = fma(sd, invK, -1.0);
-        const double cont = fma(u, fma(u, b2, b1), b0);
-        return (imm > 0.0) & (imm > cont);
-    }
+    __device__ bool operator()(float s) const { return exercises(pay_stored(s, K, invK, is_put), f); }
 };
 struct CritPartner {
-    double K, ck, b0, b1, b2;
+    double K, ck;
+    Fit f;
     int is_put;
-    __device__ bool operator()(float s) const
-    {
-        const double ub = fold_u(ck, s);
-        const double immb = fold_pay(ub, K, is_put);
-        const double contb = fma(ub, fma(ub, b2, b1), b0);
-        return (immb > 0.0) & (immb > contb);
-    }
+    __device__ bool operator()(float s) const { return exercises(pay_partner(ck, s, K, is_put), f); }
 };
 struct CritEither {
     CritStored a;
@@ -854,57 +977,24 @@ struct CritEither {
     int kind;
     __device__ bool operator()(float s) const { return kind ? b(s) : a(s); }
 };
-constexpr uint32_t kCritIrregular = 0xffffffffu;  // lo[0] of an irregular step (a real lo is <= kCritTop)
-
-struct CritArgs {
-    const double* gmom;  // non-null: solve the fits from the reduced moments (and write them to betas_out) ...
-    const double* betas;  // ... else take them from here
-    double* betas_out;
-    const double* cK;  // null: no partner (full storage)
-    uint32_t* tab;     // [N+1][8]
-    int N, is_put;
-    double K, invK;
-    int irr_every = 0;  // tests: > 0 marks every step t with t % irr_every == 0 irregular (option "pass2_tables_irregular_every")
-};
-
 // One workgroup of 128 threads per step t = 0 .. N: wave 0 builds the stored path's intervals, wave 1 the partner's.
-// The fits are those pass 2 used to solve in its prologue: solve_poly2 of gmom[t], no fit where m[0] <= 0.5.
+// The fits are those pass 2 would otherwise solve in its prologue (one lane writes them to betas_out).
 __device__ __forceinline__ void lsm_crit_build_body(CritArgs a)
 {
     const int t = (int)blockIdx.x, kind = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
     const int N = a.N;
-    const bool inner = t >= 1 && t < N;
-    double beta[3] = {0.0, 0.0, 0.0};
-    bool fit = false;
-    if (a.gmom) {
-        double m[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) m[q] = inner ? a.gmom[(size_t)t * 8 + q] : 0.0;
-        if (inner) solve_poly2(m, beta);
-        fit = inner && m[0] > 0.5;
-        if (inner && kind == 0 && lane == 0 && a.betas_out) {
-            double* bo = a.betas_out + (size_t)t * 4;
-            bo[0] = beta[0]; bo[1] = beta[1]; bo[2] = beta[2]; bo[3] = m[0];
-        }
-    } else if (inner) {
-        fit = a.betas[(size_t)t * 4 + 3] > 0.5;
-        if (fit) {
-            beta[0] = a.betas[(size_t)t * 4];
-            beta[1] = a.betas[(size_t)t * 4 + 1];
-            beta[2] = a.betas[(size_t)t * 4 + 2];
-        }
-    }
-    const double b0 = fit ? beta[0] : __builtin_huge_val(), b1 = fit ? beta[1] : 0.0, b2 = fit ? beta[2] : 0.0;
+    const Fit f = a.gmom ? fit_solved(a.gmom, t, N, kind == 0 && lane == 0 ? a.betas_out : nullptr)
+                         : fit_given(a.betas, t, N);
     CritIv iv;
     iv.lo[0] = iv.lo[1] = iv.len[0] = iv.len[1] = 0;
-    if (inner && (kind == 0 || a.cK)) {
+    if (t >= 1 && t < N && (kind == 0 || a.cK)) {
         const double ck = kind ? a.cK[t] : 0.0;
         double cand[kCritMaxCand];
-        const int n = crit_candidates(kind, a.is_put, a.K, ck, b0, b1, b2, cand);
+        const int n = crit_candidates(kind, a.is_put, a.K, ck, f.b0, f.b1, f.b2, cand);
         bool ok = n >= 0 && !(a.irr_every > 0 && t % a.irr_every == 0);
         // one instantiation of the builder for both kinds: its code is fetched cold by every CU the launch reaches
-        if (ok) ok = crit_build(CritEither{CritStored{a.K, a.invK, b0, b1, b2, a.is_put},
-                                           CritPartner{a.K, ck, b0, b1, b2, a.is_put}, kind}, cand, n, iv);
+        if (ok) ok = crit_build(CritEither{CritStored{a.K, a.invK, f, a.is_put}, CritPartner{a.K, ck, f, a.is_put}, kind},
+                                cand, n, iv);
         if (!ok) {
             iv.lo[0] = kCritIrregular;
             iv.lo[1] = iv.len[0] = iv.len[1] = 0;
@@ -932,16 +1022,6 @@ __device__ __forceinline__ bool crit_load_tables(const uint32_t* __restrict__ ta
     return __syncthreads_or(irr) != 0;
 }
 
-// the fits of step t as the float64 decisions use them (an irregular step of a table sweep reads them here)
-__device__ __forceinline__ void crit_fits(const double* __restrict__ betas, int t, int N, double& b0, double& b1,
-                                          double& b2)
-{
-    const bool fit = t >= 1 && t < N && betas[(size_t)t * 4 + 3] > 0.5;
-    b0 = fit ? betas[(size_t)t * 4] : __builtin_huge_val();
-    b1 = fit ? betas[(size_t)t * 4 + 1] : 0.0;
-    b2 = fit ? betas[(size_t)t * 4 + 2] : 0.0;
-}
-
 // Tests: for step t = 1 + blockIdx.y, the table decision against the float64 decision at EVERY non-negative float32
 // (bit patterns 0 .. kCritTop), both kinds; mismatches are added to mism[2 t + kind].  Irregular steps are skipped: the
 // sweeps decide them with the float64 code.
@@ -954,10 +1034,9 @@ __device__ __forceinline__ void lsm_crit_check_body(const uint32_t* __restrict__
     ia.lo[0] = tab[(size_t)t * 8]; ia.lo[1] = tab[(size_t)t * 8 + 1]; ia.len[0] = tab[(size_t)t * 8 + 2]; ia.len[1] = tab[(size_t)t * 8 + 3];
     ib.lo[0] = tab[(size_t)t * 8 + 4]; ib.lo[1] = tab[(size_t)t * 8 + 5]; ib.len[0] = tab[(size_t)t * 8 + 6]; ib.len[1] = tab[(size_t)t * 8 + 7];
     if (ia.lo[0] == kCritIrregular || ib.lo[0] == kCritIrregular) return;
-    double b0, b1, b2;
-    crit_fits(betas, t, N, b0, b1, b2);
-    const CritStored pa{K, invK, b0, b1, b2, is_put};
-    const CritPartner pb{K, cK[t], b0, b1, b2, is_put};
+    const Fit f = fit_given(betas, t, N);
+    const CritStored pa{K, invK, f, is_put};
+    const CritPartner pb{K, cK[t], f, is_put};
     unsigned ma = 0, mb = 0;
     const uint64_t n = (uint64_t)kCritTop + 1, stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t o = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; o < n; o += stride) {
@@ -982,15 +1061,15 @@ __device__ __forceinline__ void lsm_pass2_body(Pass2Args a)
     extern __shared__ double sh_b[];  // [N+1][4]
     const int tid = threadIdx.x;
     const int N = a.N;
-    // a step with an empty regression set never exercises: give it an infinite continuation
-    // value instead of a branch in the sweep
+    // the policy's fits (no_fit where the regression set is empty), written out here rather than through fits_to_lds:
+    // that prologue takes this kernel from 42 to 103 VGPRs (8 -> 4 waves per SIMD) at VEC = 1
     if (a.gmom) {
         for (int t = tid; t <= N; t += kBlock) {
             double m[8], beta[3] = {0.0, 0.0, 0.0};
             const bool inner = t >= 1 && t < N;
 #pragma unroll
             for (int q = 0; q < 8; ++q) m[q] = inner ? a.gmom[(size_t)t * 8 + q] : 0.0;
-            if (inner) solve_poly2(m, beta);  // the very function lsm_solve_all_kernel runs: same bits
+            if (inner) solve_poly2(m, beta);  // the very function lsm_solve_betas_kernel runs: same bits
             const bool fit = inner && m[0] > 0.5;
             sh_b[4 * t] = fit ? beta[0] : __builtin_huge_val();
             sh_b[4 * t + 1] = fit ? beta[1] : 0.0;
@@ -1024,14 +1103,10 @@ __device__ __forceinline__ void lsm_pass2_body(Pass2Args a)
         // One row of decisions, branch-free: a path that has already exercised (tex != N), is
         // out of the money, or sits below the fitted continuation value keeps its state.
         auto decide = [&](const float (&row)[VEC], int t) {
-            const double b0 = sh_b[4 * t], b1 = sh_b[4 * t + 1], b2 = sh_b[4 * t + 2];
+            const Fit f = fit_lds(sh_b, t);
 #pragma unroll
             for (int v = 0; v < VEC; ++v) {
-                const double sd = (double)row[v];
-                const double imm = is_put ? K - sd : sd - K;
-                const double u = fma(sd, invK, -1.0);
-                const double cont = fma(u, fma(u, b2, b1), b0);
-                const bool ex = (tex[v] == N) & (imm > 0.0) & (imm > cont);
+                const bool ex = (tex[v] == N) & exercises(pay_stored(row[v], K, invK, is_put), f);
                 sx[v] = ex ? row[v] : sx[v];
                 tex[v] = ex ? t : tex[v];
             }
@@ -1061,15 +1136,7 @@ __device__ __forceinline__ void lsm_pass2_body(Pass2Args a)
             decide(st, t);
         }
 #pragma unroll
-        for (int v = 0; v < VEC; ++v) {
-            double p = payoff_d(sx[v], K, is_put);
-            p = p > 0.0 ? p : 0.0;
-            const double cf = p * a.D[tex[v] - 1];
-            acc[0] += cf;
-            acc[1] += cf * cf;
-            acc[2] += (tex[v] < N) ? 1.0 : 0.0;
-            acc[3] += (cf == 0.0) ? 1.0 : 0.0;
-        }
+        for (int v = 0; v < VEC; ++v) add_cash_flow(acc, payoff_d(sx[v], K, is_put), a.D[tex[v] - 1], tex[v] < N);
         if (WRITE_STATE) {
             storef<VEC>(a.sx + j, sx);
             storei<VEC>(a.tex + j, tex);
@@ -1095,35 +1162,8 @@ __device__ __forceinline__ void lsm_pass2_fold_body(Pass2Args a)
     const int tid = threadIdx.x;
     const int N = a.N;
     bool irr_any = false;
-    if (TAB) {
-        irr_any = crit_load_tables(a.crit, sh_t, N);
-    } else {
-        if (a.gmom) {
-            for (int t = tid; t <= N; t += kBlock) {
-                double m[8], beta[3] = {0.0, 0.0, 0.0};
-                const bool inner = t >= 1 && t < N;
-#pragma unroll
-                for (int q = 0; q < 8; ++q) m[q] = inner ? a.gmom[(size_t)t * 8 + q] : 0.0;
-                if (inner) solve_poly2(m, beta);
-                const bool fit = inner && m[0] > 0.5;
-                sh_b[4 * t] = fit ? beta[0] : __builtin_huge_val();
-                sh_b[4 * t + 1] = fit ? beta[1] : 0.0;
-                sh_b[4 * t + 2] = fit ? beta[2] : 0.0;
-                sh_b[4 * t + 3] = a.cK[t];
-                if (blockIdx.x == 0 && inner && a.betas_out) {
-                    double* bo = a.betas_out + (size_t)t * 4;
-                    bo[0] = beta[0]; bo[1] = beta[1]; bo[2] = beta[2]; bo[3] = m[0];
-                }
-            }
-        } else {
-            for (int k = tid; k < (N + 1) * 4; k += kBlock) {
-                const int t = k >> 2;
-                const bool fit = t >= 1 && t < N && a.betas[(size_t)t * 4 + 3] > 0.5;
-                sh_b[k] = (k & 3) == 3 ? a.cK[t] : (fit ? a.betas[k] : ((k & 3) == 0 ? __builtin_huge_val() : 0.0));
-            }
-        }
-        __syncthreads();
-    }
+    if (TAB) irr_any = crit_load_tables(a.crit, sh_t, N);
+    else fits_to_lds<true>(sh_b, a.gmom, a.betas_out, a.betas, a.cK, N);
     const double K = a.K, invK = a.invK;
     const int is_put = PUT < 0 ? a.is_put : PUT;  // (a compile-time side: the payoff is one subtraction, not two and a select)
     double acc[8];
@@ -1142,43 +1182,34 @@ __device__ __forceinline__ void lsm_pass2_fold_body(Pass2Args a)
             sxb[v] = sxa[v];
             texa[v] = texb[v] = N;
         }
-        auto decide_f64 = [&](const float (&row)[VEC], int t, double b0, double b1, double b2, double ck) {
+        auto decide_f64 = [&](const float (&row)[VEC], int t, const Fit& f, double ck) {
 #pragma unroll
             for (int v = 0; v < VEC; ++v) {
-                const double sd = (double)row[v];
-                const double imm = is_put ? K - sd : sd - K;
-                const double u = fma(sd, invK, -1.0);
-                const double cont = fma(u, fma(u, b2, b1), b0);
-                const bool ex = (texa[v] == N) & (imm > 0.0) & (imm > cont);
+                const bool ex = (texa[v] == N) & exercises(pay_stored(row[v], K, invK, is_put), f);
                 sxa[v] = ex ? row[v] : sxa[v];
                 texa[v] = ex ? t : texa[v];
-                const double ub = fold_u(ck, row[v]);
-                const double immb = fold_pay(ub, K, is_put);
-                const double contb = fma(ub, fma(ub, b2, b1), b0);
-                const bool exb = (texb[v] == N) & (immb > 0.0) & (immb > contb);
+                const bool exb = (texb[v] == N) & exercises(pay_partner(ck, row[v], K, is_put), f);
                 sxb[v] = exb ? row[v] : sxb[v];
                 texb[v] = exb ? t : texb[v];
             }
         };
         auto decide = [&](const float (&row)[VEC], int t) {
             if constexpr (!TAB) {
-                decide_f64(row, t, sh_b[4 * t], sh_b[4 * t + 1], sh_b[4 * t + 2], sh_b[4 * t + 3]);
+                decide_f64(row, t, fit_lds(sh_b, t), sh_b[4 * t + 3]);
             } else {
                 const uint4 ta = *reinterpret_cast<const uint4*>(sh_t + 8 * t);
                 if (CHK && __builtin_amdgcn_readfirstlane(ta.x) == kCritIrregular) {
-                    double b0, b1, b2;
-                    crit_fits(a.betas, t, N, b0, b1, b2);
-                    decide_f64(row, t, b0, b1, b2, a.cK[t]);
+                    decide_f64(row, t, fit_given(a.betas, t, N), a.cK[t]);
                     return;
                 }
                 const uint4 tb = *reinterpret_cast<const uint4*>(sh_t + 8 * t + 4);
 #pragma unroll
                 for (int v = 0; v < VEC; ++v) {
                     const uint32_t bits = __float_as_uint(row[v]);
-                    const bool ex = (texa[v] == N) & (((bits - ta.x) < ta.z) | ((bits - ta.y) < ta.w));
+                    const bool ex = (texa[v] == N) & crit_in(ta, bits);
                     sxa[v] = ex ? row[v] : sxa[v];
                     texa[v] = ex ? t : texa[v];
-                    const bool exb = (texb[v] == N) & (((bits - tb.x) < tb.z) | ((bits - tb.y) < tb.w));
+                    const bool exb = (texb[v] == N) & crit_in(tb, bits);
                     sxb[v] = exb ? row[v] : sxb[v];
                     texb[v] = exb ? t : texb[v];
                 }
@@ -1190,57 +1221,12 @@ __device__ __forceinline__ void lsm_pass2_fold_body(Pass2Args a)
             for (int v = 0; v < VEC; ++v) l |= (texa[v] == N) | (texb[v] == N);
             return l;
         };
-#ifdef OMC_P2_U
-        constexpr int U = OMC_P2_U;
-#else
-        constexpr int U = 8;
-#endif
-        int t = N - 1;
-        const float* col = a.S + j;
-        // U rows per batch, the NEXT batch requested before the current one is worked on (the decisions of a batch are a
-        // dependent chain of ~450 vector instructions: without the look-ahead every batch waited out a whole memory round
-        // trip with 4 waves per SIMD to cover it).  Rows below 1 are clamped to row 1 and not decided.
-        auto fetch = [&](float (&b)[U][VEC], int tt) {
-#pragma unroll
-            for (int k = 0; k < U; ++k) loadf_stream<VEC>(col + (int64_t)max(tt - k, 1) * a.ld, b[k]);
-        };
-        auto work = [&](const float (&b)[U][VEC], int tt) {
-#pragma unroll
-            for (int k = 0; k < U; ++k) {
-                if (tt - k >= 1) decide(b[k], tt - k);
-                // TAB: one step's table words at a time (hoisted, a batch's would take 8 U registers)
-                if (TAB) __builtin_amdgcn_sched_barrier(0);
-            }
-        };
-        float bA[U][VEC], bB[U][VEC];
-        if (t >= 1) fetch(bA, t);
-        while (t >= 1 && live()) {
-            if (t - U >= 1) fetch(bB, t - U);
-            __builtin_amdgcn_sched_barrier(0);
-            work(bA, t);
-            t -= U;
-            if (!(t >= 1 && live())) break;
-            if (t - U >= 1) fetch(bA, t - U);
-            __builtin_amdgcn_sched_barrier(0);
-            work(bB, t);
-            t -= U;
-        }
+        walk_rows<VEC, TAB>(a.S + j, a.ld, N, decide, live);
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
-            double p = payoff_d(sxa[v], K, is_put);
-            p = p > 0.0 ? p : 0.0;
-            const double cf = p * a.D[texa[v] - 1];
-            double pb = fold_pay(fold_u(TAB ? a.cK[texb[v]] : sh_b[4 * texb[v] + 3], sxb[v]), K, is_put);
-            pb = pb > 0.0 ? pb : 0.0;
-            const double cfb = pb * a.D[texb[v] - 1];
-            acc[0] += cf;
-            acc[1] += cf * cf;
-            acc[2] += (texa[v] < N) ? 1.0 : 0.0;
-            acc[3] += (cf == 0.0) ? 1.0 : 0.0;
-            acc[0] += cfb;
-            acc[1] += cfb * cfb;
-            acc[2] += (texb[v] < N) ? 1.0 : 0.0;
-            acc[3] += (cfb == 0.0) ? 1.0 : 0.0;
+            add_cash_flow(acc, payoff_d(sxa[v], K, is_put), a.D[texa[v] - 1], texa[v] < N);
+            const double ck = TAB ? a.cK[texb[v]] : sh_b[4 * texb[v] + 3];
+            add_cash_flow(acc, pay_partner(ck, sxb[v], K, is_put).imm, a.D[texb[v] - 1], texb[v] < N);
         }
     }
     };
@@ -1292,15 +1278,8 @@ __device__ __forceinline__ void lsm_final_body(FinalArgs a)
             }
         }
 #pragma unroll
-        for (int v = 0; v < VEC; ++v) {
-            double p = payoff_d(sx[v], a.K, a.is_put);
-            p = p > 0.0 ? p : 0.0;
-            const double cf = p * a.D[tex[v] - a.tval];
-            acc[0] += cf;
-            acc[1] += cf * cf;
-            acc[2] += (tex[v] < a.N) ? 1.0 : 0.0;
-            acc[3] += (cf == 0.0) ? 1.0 : 0.0;
-        }
+        for (int v = 0; v < VEC; ++v)
+            add_cash_flow(acc, payoff_d(sx[v], a.K, a.is_put), a.D[tex[v] - a.tval], tex[v] < a.N);
     }
     const double s = block_reduce8(acc, red);
     if (tid < 64 && (tid & 7) == 0) a.part[(size_t)(tid >> 3) * a.pstride + blockIdx.x] = s;
