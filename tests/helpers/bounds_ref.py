@@ -106,49 +106,75 @@ def first_stop(S, t0, N, K, r, T, is_put, betas4):
 
 
 def _pair_mean_se(x):
+    """Pair means m of an antithetic layout -> (mean, standard error, E[m^2] / Var[m]).  Both sums are math.fsum: exactly
+    rounded, so against a device sum only the device's own rounding counts.  The ratio is what the subtraction
+    E[m^2] - mean^2 loses to cancellation (1.0 where the variance is zero)."""
     P = x.size // 2
     m = 0.5 * (x[:P] + x[P:])
-    mean = m.sum() / P
-    return mean, math.sqrt(max((m * m).sum() / P - mean * mean, 0.0) / P)
+    mean = math.fsum(m) / P
+    e2 = math.fsum(m * m) / P
+    var = max(e2 - mean * mean, 0.0)
+    return mean, math.sqrt(var / P), (e2 / var if var > 0.0 else 1.0)
 
 
 def lower_bound(S, K, r, T, is_put, betas4):
-    """S: the n_lower lower-bound paths [N+1][n_lower] (antithetic layout) -> dict lower, se_lower, n_exercised, ties."""
+    """S: the n_lower lower-bound paths [N+1][n_lower] (antithetic layout) -> dict lower, se_lower, se_cancel (E[m^2] /
+    Var[m] of the pair means), n_exercised, ties."""
     N = S.shape[0] - 1
     tau, Z, ties = first_stop(S, 0, N, K, r, T, is_put, betas4)
-    lo, se = _pair_mean_se(Z)
-    return dict(lower=lo, se_lower=se, n_exercised=int(np.count_nonzero(tau < N)), ties=ties)
+    lo, se, ratio = _pair_mean_se(Z)
+    return dict(lower=lo, se_lower=se, se_cancel=ratio, n_exercised=int(np.count_nonzero(tau < N)), ties=ties)
 
 
-def upper_bound(So, inner, K, r, T, is_put, betas4):
-    """So: outer paths [N+1][n_outer]; inner(i, t) -> the inner paths of item (i, t) as [N - t + 1][n_inner] float32 (row
-    0 = S_t[i]).  -> dict upper, se_upper, q [n_outer][N], samples [n_outer], inner_path_steps, ties."""
-    N, n_outer = So.shape[0] - 1, So.shape[1]
-    D = np.exp(-r * (T / N) * np.arange(N + 1))
-    q = np.zeros((n_outer, N))
+def q_rows(So, inner, rows, K, r, T, is_put, betas4):
+    """Q^_t[i] for the outer paths i in `rows`, all dates t = 0..N-1 -> dict q [len(rows)][N], inner_path_steps, ties."""
+    N = So.shape[0] - 1
+    q = np.zeros((len(rows), N))
     steps = 0
     ties = 0
-    for i in range(n_outer):
+    for k, i in enumerate(rows):
         for t in range(N):
             tau, Z, ti = first_stop(inner(i, t), t, N, K, r, T, is_put, betas4)
-            q[i, t] = Z.sum() / Z.size
+            q[k, t] = Z.sum() / Z.size
             steps += int((tau - t).sum())
             ties += ti
-    samples = np.zeros(n_outer)
-    for i in range(n_outer):
+    return dict(q=q, inner_path_steps=steps, ties=ties)
+
+
+def walk_rows(So, q, rows, K, r, T, is_put, betas4):
+    """The martingale walk of the outer paths i in `rows` with their Q^ q [len(rows)][N] -> dict samples [len(rows)]
+    (max_t Z_t - M^_t), ties, zmax (the largest Z_t met: the scale of the walk's rounding)."""
+    N = So.shape[0] - 1
+    D = np.exp(-r * (T / N) * np.arange(N + 1))
+    samples = np.zeros(len(rows))
+    ties = 0
+    zmax = 0.0
+    for k, i in enumerate(rows):
         M, best = 0.0, -math.inf
         for t in range(1, N + 1):
             s = So[t, i:i + 1]
             phi = (K - float(s[0])) if is_put else (float(s[0]) - K)
             Zt = D[t] * max(phi, 0.0)
+            zmax = max(zmax, Zt)
             st, ti = stop_rule(s, t, N, K, is_put, betas4)
             ties += ti
-            L = Zt if st[0] else q[i, t]
-            M = M + L - q[i, t - 1]
+            qt = q[k, t] if t < N else 0.0
+            L = Zt if st[0] else qt
+            M = M + L - q[k, t - 1]
             best = max(best, Zt - M)
-        samples[i] = best
-    up, se = _pair_mean_se(samples)
-    return dict(upper=up, se_upper=se, q=q, samples=samples, inner_path_steps=steps, ties=ties)
+        samples[k] = best
+    return dict(samples=samples, ties=ties, zmax=zmax)
+
+
+def upper_bound(So, inner, K, r, T, is_put, betas4):
+    """So: outer paths [N+1][n_outer]; inner(i, t) -> the inner paths of item (i, t) as [N - t + 1][n_inner] float32 (row
+    0 = S_t[i]).  -> dict upper, se_upper, se_cancel, q [n_outer][N], samples [n_outer], inner_path_steps, ties, zmax."""
+    rows = range(So.shape[1])
+    qr = q_rows(So, inner, rows, K, r, T, is_put, betas4)
+    wk = walk_rows(So, qr["q"], rows, K, r, T, is_put, betas4)
+    up, se, ratio = _pair_mean_se(wk["samples"])
+    return dict(upper=up, se_upper=se, se_cancel=ratio, q=qr["q"], samples=wk["samples"],
+                inner_path_steps=qr["inner_path_steps"], ties=qr["ties"] + wk["ties"], zmax=wk["zmax"])
 
 
 def inner_from_normals(Z, So, n_inner, S0_paths):
@@ -163,3 +189,23 @@ def inner_from_normals(Z, So, n_inner, S0_paths):
         return S0_paths(np.ascontiguousarray(Z[:, g0:g0 + H]), float(So[t, i]))[:N - t + 1]
 
     return inner
+
+
+def inner_by_item(normals, So, n_inner, S0_paths):
+    """inner(i, t) as inner_from_normals gives it, with every item's normals generated on their own: normals(pair_offset,
+    n_pairs) -> [N][n_pairs] of stream_inner (gbm_normals of the device or of the C oracle), asked for at pair offset
+    (i (N+1) + t) n_inner/2.  No array over the whole call: serves a few sampled outer paths of a large one."""
+    N = So.shape[0] - 1
+    H = n_inner // 2
+
+    def inner(i, t):
+        z = normals((i * (N + 1) + t) * H, H)
+        return S0_paths(np.ascontiguousarray(z), float(So[t, i]))[:N - t + 1]
+
+    return inner
+
+
+def samples_atol(N, q, zmax):
+    """Absolute tolerance of a sample max_t (Z_t - M^_t) between two float64 evaluations whose Q^ agree to 1e-12
+    relative: M^_t adds 2 t values of Q^ / Z, each within 1e-12 of the largest of them."""
+    return 2 * N * 1e-12 * max(float(np.max(q, initial=0.0)), zmax)

@@ -1,7 +1,9 @@
 """Andersen-Broadie price bounds (omc_price_american_bounds, options_model_amd/csrc/omc_bounds.hip).
 
 The device's Q^_t, samples, bounds and counts against the numpy restatement of tests/helpers/bounds_ref.py on the
-device's own spots (the generators at the documented streams and pair offsets), the bracket around the Bermudan lattice,
+device's own spots (the generators at the documented streams and pair offsets; sweep 14 of tests/test_gpu_fuzz.py runs
+the same comparison over random shapes), a call of three inner launches restated on sampled outer paths, the bracket around
+the Bermudan lattice,
 known answers at one exercise date and for a never-exercising policy, determinism, refusals, the facade and the C
 example."""
 import ctypes as C
@@ -103,6 +105,42 @@ def test_brackets_the_bermudan_value(ctx, S0, is_put):
     else:  # no dividends: the Bermudan call is the European
         bs = br.black_scholes(S0, K, R, SIG, T, False)
         assert d["lower"] - 3 * d["se_lower"] <= bs <= d["upper"] + 3 * d["se_upper"], (d, bs)
+
+
+def test_launch_blocks_restated_on_sampled_outer_paths(ctx):
+    """The inner kernel runs as launches over blocks of outer paths, each at most 2^30 worst-case inner steps
+    (n_inner N (N+1) / 2 per outer path): at the sizes of the bracket test above that is blocks of 1644
+    outer paths, three launches.  Q^ of the first, last and a middle outer path of every block, and of the antithetic
+    partner columns of two of them, all 50 dates each, against the restatement on the device's own spots: q at rtol 1e-12
+    (a mean of 512 summands >= 0 in either order), the samples at bounds_ref.samples_atol (the walk adds 2 t such values)."""
+    N, n_outer, n_inner = 50, BIG["n_outer"], BIG["n_inner"]
+    blk = (1 << 30) // (n_inner // 2 * N * (N + 1))
+    starts = list(range(0, n_outer, blk))
+    assert blk == 1644 and len(starts) >= 3  # a changed launch rule must not empty this test
+    rows = []
+    for i0 in starts:
+        i1 = min(i0 + blk, n_outer)
+        rows += [i0, (i0 + i1) // 2, i1 - 1]
+    rows += [rows[1] + n_outer // 2, rows[2] + n_outer // 2]  # partner columns: other blocks' interiors
+    assert len(set(rows)) == len(rows) and max(rows) < n_outer
+    p = _params(N=N, M=20_000)
+    d = ctx.price_american_bounds(p, policy="textbook", n_lower=4096, n_outer=n_outer, n_inner=n_inner, want_q=True,
+                                  want_samples=True)
+
+    def host(a):
+        h = a.to_host()
+        a.free()
+        return h
+
+    So = host(ctx.gbm_paths(n_outer, N, 100.0, R, SIG, T, 42, 2))
+    inner = br.inner_by_item(lambda off, n: host(ctx.gbm_normals(n, N, 42, 3, off)), So, n_inner,
+                             lambda z, s0: host(ctx.gbm_paths_from_normals(z, s0, R, SIG, T)))
+    qr = br.q_rows(So, inner, rows, K, R, T, True, d["betas"])
+    wk = br.walk_rows(So, qr["q"], rows, K, R, T, True, d["betas"])
+    print(f"blocks of {blk}: rows {rows}, ties {qr['ties']} + {wk['ties']}")
+    assert qr["ties"] == 0 and wk["ties"] == 0  # numpy's decisions are the device's
+    np.testing.assert_allclose(d["q"][rows], qr["q"], rtol=1e-12, atol=0)
+    np.testing.assert_allclose(d["samples"][rows], wk["samples"], rtol=0, atol=br.samples_atol(N, qr["q"], wk["zmax"]))
 
 
 @pytest.mark.parametrize("is_put", [True, False])

@@ -13,7 +13,14 @@
   9. curve batches (American and European) == single calls;
  10. the calibrator's inner Monte-Carlo (one expiry, many strikes) against the C oracle's terminal spots;
  11. the local-vol simulator with random IV networks against the per-step PyTorch evaluation;
- 12. a whole quote surface in one launch set == its per-expiry calls, bit for bit (round 6).
+ 12. a whole quote surface in one launch set == its per-expiry calls, bit for bit (round 6);
+ 13. the frozen-policy Greeks sweep against the numpy restatement (tests/helpers/greeks_ref.py) on the matrix the device
+     stores: all four kernel variants (VEC 1 / 2 x folded / full storage), 1 .. 70 steps, pair offsets, bumps, given policies
+     with holes;
+ 14. the Andersen-Broadie bounds against the numpy restatement (tests/helpers/bounds_ref.py) on the device's own spots: lane
+     refill, a wave's second item, the lower sweep's grid-stride loop, ragged outer matrices, all four policy kinds.
+(The folded-storage pricing has its own sweep between 1 and 2.)  The generators of 13 and 14 deal the kernel variants and code
+paths they are there for whatever the seed, asserted at import and, without a GPU, by tests/test_fuzz_cases_cpu.py.
 
 OMC_FUZZ_SCALE multiplies every sweep's case count and OMC_FUZZ_SEED shifts its seed: soak runs (profiles/r05_fuzz_soak.txt:
 what they found -- exact ties, ill-conditioned fits, units on their ReLU kink, an ill-conditioned recurrence -- and how
@@ -669,3 +676,297 @@ def test_local_vol_kernel_matches_the_torch_evaluation(ctx, case):
     err_hip = float((a[-1].double() / S - 1).abs().max())
     err_torch = float((b[-1].double() / S - 1).abs().max())
     assert err_hip <= max(2e-5, 3.0 * err_torch), (rel, err_hip, err_torch)
+
+
+# ---------------------------------------------------------------------------------------------- 13: the Greeks sweep
+# lsm_greeks_kernel<VEC, folded> takes VEC = 2 where the stored matrix has an even number of columns (the matrices the
+# library owns are padded to an even leading dimension and 8-byte aligned): folded storage stores n_paths / 2 columns.
+_GREEKS_M_FOLD = {1: [254, 1026, 4098, 33_334, 65_538], 2: [64, 1000, 131_072]}  # by VEC: n_paths / 2 odd / even
+_GREEKS_M_EVEN = _GREEKS_M_FOLD[1] + _GREEKS_M_FOLD[2]
+_GREEKS_HESTON = dict(v0=0.04, kappa=2.0, theta=0.04, xi=0.3, rho=-0.7)
+
+
+def _greeks_cols(c):
+    """columns of the matrix the Greeks sweep walks"""
+    return c["M"] // 2 if c["fold"] else c["M"]
+
+
+def _greeks_variant(c):
+    return (1 if _greeks_cols(c) % 2 else 2, bool(c["fold"]))
+
+
+def _greeks_cases(n, seed):
+    """The first eight cases are dealt two to each kernel variant (VEC 1 / 2 x folded / full storage), one with the fitted
+    and one with a given policy, and every twelve cases every step count once, whatever the seed; the rest is drawn freely.
+    Contract lists: those of the folded-pricing sweep above (the second in this file)."""
+    rng = np.random.default_rng(seed)
+    steps = [1, 2, 3, 7, 8, 9, 15, 16, 17, 33, 50, 70]  # no sweep at all, one row, walk_rows' batches of 8 short / full / over
+    out = []
+    for i in range(n):
+        if i % len(steps) == 0:  # every step count once in twelve cases
+            deal = rng.permutation(steps)
+        vec, fold = ((1, True), (2, True), (1, False), (2, False))[i % 4] if i < 8 else (0, False)
+        if vec == 0:  # free: storage, model and size all drawn
+            model = "heston" if rng.random() < 0.3 else "gbm"
+            anti = True if model == "heston" else bool(rng.integers(0, 2))
+            fold = model == "gbm" and anti and bool(rng.integers(0, 2))
+            M = int(rng.choice(_GREEKS_M_EVEN if anti else _GREEKS_M_EVEN + [10_001]))
+        elif fold:
+            model, anti, M = "gbm", True, int(rng.choice(_GREEKS_M_FOLD[vec]))
+        elif vec == 1:  # full storage with an odd column count: no antithetic pairs
+            model, anti, M = "gbm", False, 10_001
+        else:
+            model = "heston" if rng.random() < 0.5 else "gbm"
+            anti = True if model == "heston" else bool(rng.integers(0, 2))
+            M = int(rng.choice(_GREEKS_M_EVEN))
+        out.append(dict(model=model, antithetic=anti, fold=2 if fold else 0, M=M, scheme=int(rng.integers(0, 3)),
+                        N=int(deal[i % len(steps)]), is_put=bool(rng.integers(0, 2)),
+                        S0=float(rng.choice([60.0, 80.0, 100.0, 120.0, 150.0])), K=float(rng.choice([90.0, 100.0, 100.5, 110.0])),
+                        r=float(rng.choice([0.0, 0.03, 0.08])), sigma=float(rng.choice([0.05, 0.1, 0.2, 0.45, 0.9])),
+                        T=float(rng.choice([0.02, 0.1, 1.0, 2.5])), seed=int(rng.integers(1, 2 ** 31)),
+                        stream=int(rng.integers(0, 5)), off=int(rng.choice([0, 12345, 2 ** 33 + 7])),
+                        bump=float(rng.choice([0.001, 0.01, 0.1, 0.5])),
+                        given=bool(i // 4 % 2) if i < 8 else bool(rng.integers(0, 2)),  # each variant: one fitted, one given
+                        holes=int(rng.integers(0, 2 ** 31))))
+    return out
+
+
+def _greeks_id(c):
+    return (f"{c['model']}-{'fold' if c['fold'] else 'full'}-v{_greeks_variant(c)[0]}-{c['M']}x{c['N']}-"
+            f"{'put' if c['is_put'] else 'call'}-{'given' if c['given'] else 'fit'}-h{c['bump']}")
+
+
+def _holes(betas4, seed):
+    """a given policy: the fits with a random third of the exercise dates 1 .. N-1 set to n = 0 (no exercise there)"""
+    b = np.array(betas4, np.float64)
+    N = b.shape[0] - 1
+    if N >= 2:
+        dates = np.random.default_rng(seed).permutation(np.arange(1, N))[:(N - 1 + 2) // 3]
+        b[dates, 3] = 0.0
+    return b
+
+
+_GREEKS_CASES = _greeks_cases(16 * _SCALE, 131313 + _SHIFT)
+for _v in ((1, True), (2, True), (1, False), (2, False)):  # every kernel variant twice, from cols % 2 alone
+    assert sum(_greeks_variant(c) == _v for c in _GREEKS_CASES) >= 2, _v
+_GREEKS_EXCUSED = []  # ids of the cases whose values were not compared because a tie went the other way
+
+
+def _greeks_params(c, stream=None):
+    from options_model_amd import _ffi
+    kw = dict(model=c["model"], semantics="two_pass", is_put=c["is_put"], antithetic=c["antithetic"], n_paths=c["M"],
+              n_steps=c["N"], S0=c["S0"], K=c["K"], r=c["r"], sigma=c["sigma"], T=c["T"], seed=c["seed"],
+              stream=c["stream"] if stream is None else stream, pair_offset=c["off"], heston_scheme=c["scheme"])
+    if c["model"] == "heston":
+        kw.update(_GREEKS_HESTON)
+    return _ffi.make_params(**kw)
+
+
+@pytest.mark.parametrize("case", _GREEKS_CASES, ids=_greeks_id)
+def test_greeks_match_the_numpy_restatement(ctx, case):
+    """omc_price_american_greeks against tests/helpers/greeks_ref.py on the matrix the device stores and the device's own
+    fits, as tests/test_gpu_greeks.py compares them (counts exact unless the restatement shows ties, values rel 1e-9 / abs
+    1e-12), over what that file's fixed shapes leave out: all four kernel variants (VEC 1 needs an odd column count), 1 .. 70
+    steps (no sweep at all, one row, the 8-row batches of walk_rows full, one short and one over), pair offsets, bumps from
+    0.001 to 0.5, r = 0, T != 1, and given policies with n = 0 holes."""
+    from helpers import greeks_check as gc
+    from helpers import greeks_ref as gr
+    c = case
+    p = _greeks_params(c)
+    ctx.set_option("fold_antithetic", c["fold"])
+    try:
+        given = None
+        if c["given"]:  # the fits of another stream, a third of the dates without exercise
+            given = _holes(ctx.price_american_greeks(_greeks_params(c, c["stream"] + 7), bump=c["bump"], want_betas=True)["betas"],
+                           c["holes"])
+        d = ctx.price_american_greeks(p, bump=c["bump"], betas=given, want_betas=True)
+        Sd = gc.stored_half(ctx, p) if c["fold"] else gc.stored(ctx, p)
+    finally:
+        ctx.set_option("fold_antithetic", 1)
+    S = Sd.to_host()
+    Sd.free()
+    assert d["folded"] == (1 if c["fold"] else 0) and d["n_paths"] == c["M"] and S.shape[1] == _greeks_cols(c)
+    if given is not None:
+        np.testing.assert_array_equal(d["betas"], given)
+    cK = None
+    if c["fold"]:
+        c0, g = orc.fold_constants(p.S0, p.K, p.r, p.sigma, p.T, p.n_steps)
+        cK = orc.fold_table(p.n_steps, c0, g)
+    ref = gr.greeks(S, p.K, p.r, p.T, c["is_put"], d["betas"], p.S0, p.sigma, h=c["bump"], cK=cK, gbm=(c["model"] == "gbm"))
+    print(f"greeks {_greeks_id(c)}: ties {ref['ties']} counts {d['n_exercised']}/{d['n_exercised_up']}/{d['n_exercised_down']}")
+    if not gc.agrees(d, ref, p):
+        _GREEKS_EXCUSED.append(_greeks_id(c))
+
+
+def test_greeks_sweep_excused_few_cases():
+    """The tie rule must not hide failures: at most one case in eight may go without its value comparison."""
+    print(f"greeks sweep: {len(_GREEKS_EXCUSED)} of {len(_GREEKS_CASES)} cases excused by ties: {_GREEKS_EXCUSED}")
+    assert 8 * len(_GREEKS_EXCUSED) <= len(_GREEKS_CASES), _GREEKS_EXCUSED
+
+
+# ---------------------------------------------------------------------------------------------- 14: the bounds sweep
+_BOUNDS_R, _BOUNDS_T = 0.05, 1.0
+_BOUNDS_INNER = [2, 64, 130, 200, 320, 642, 1026, 2048]
+_BOUNDS_BUDGET = 3_000_000  # n_outer N n_inner of a case: keeps the numpy restatement of one case at a few seconds
+
+
+def _bounds_refills(c):
+    """a 64-lane wave has more pairs per item than lanes: finished lanes take the item's next pairs"""
+    return c["n_inner"] // 2 > 64
+
+
+def _bounds_second_item(c):
+    """more items than the grid has waves (at most 2048 workgroups of 4): a wave takes a second item"""
+    return c["n_outer"] * c["N"] > 8192
+
+
+def _bounds_lower_strides(c):
+    """more pairs than the lower sweep's grid has threads (at most 1024 workgroups of 256): its grid-stride loop turns"""
+    return c["n_lower"] // 2 > 262_144
+
+
+def _bounds_cases(n, seed):
+    """Of every twelve cases, the even ones are dealt a refilling n_inner, cases 1 and 7 a wave's second item (with
+    n_inner <= 130: the restatement runs every item), cases 3 and 9 the lower sweep's grid-stride loop, case 5 a given
+    policy (with n = 0 holes) and case 11 n_inner = 2; the others' numbers of dates are dealt so that each occurs; the
+    rest is drawn freely, n_inner within the restatement's budget.  S0, K and sigma: the lists of the Greeks sweep (for the dealt
+    odd cases redrawn until the strike is in reach of the spot)."""
+    rng = np.random.default_rng(seed)
+    dates = [1, 2, 3, 5, 7, 9, 13, 17]
+    out = []
+    for i in range(n):
+        k = i % 12
+        if k == 0:  # every number of dates once among the ten cases that draw it themselves
+            deal = iter([int(x) for x in rng.permutation(dates)] + [int(x) for x in rng.choice(dates, 2)])
+        N = next(deal) if k not in (1, 7) else 0
+        n_outer = int(rng.choice([2, 34, 66, 70, 130, 258, 1026]))
+        n_lower = int(rng.choice([2, 4098, 70_000, 600_002]))
+        if k in (1, 7):
+            N, n_outer = int(rng.choice([9, 13, 17])), 1026
+        if k in (3, 9):
+            n_lower = 600_002
+        fits = [x for x in _BOUNDS_INNER if n_outer * N * x <= _BOUNDS_BUDGET]
+        if k % 2 == 0:
+            fits = [x for x in fits if x // 2 > 64]
+        if k in (1, 7):
+            fits = [x for x in fits if x <= 130]
+        if k == 11:
+            fits = [2]  # one lane of the wave active
+        n_inner, is_put, M = int(rng.choice(fits)), bool(rng.integers(0, 2)), int(rng.choice([1024, 4096, 16_384]))
+        while True:
+            S0, K = float(rng.choice([60.0, 80.0, 100.0, 120.0, 150.0])), float(rng.choice([90.0, 100.0, 100.5, 110.0]))
+            sigma = float(rng.choice([0.05, 0.1, 0.2, 0.45, 0.9]))
+            # a case dealt for a mechanism needs payoffs to show it: the strike within two standard deviations of S0
+            if k % 2 == 0 or abs(np.log(S0 / K)) <= 2.0 * sigma * np.sqrt(_BOUNDS_T):
+                break
+        out.append(dict(N=N, n_outer=n_outer, n_inner=n_inner, n_lower=n_lower, is_put=is_put, M=M, S0=S0, K=K, sigma=sigma,
+                        seed=int(rng.integers(1, 2 ** 31)),
+                        stream=int(rng.integers(0, 5)),
+                        policy=str(rng.choice(["textbook", "two_pass", "reference", "given"])) if k != 5 else "given",
+                        irr=int(rng.choice([0, 1, 3])), holes=int(rng.integers(0, 2 ** 31))))
+    return out
+
+
+def _bounds_id(c):
+    return (f"{'put' if c['is_put'] else 'call'}-{c['policy']}-N{c['N']}-o{c['n_outer']}-i{c['n_inner']}-l{c['n_lower']}-"
+            f"S{c['S0']:.0f}K{c['K']:.0f}s{c['sigma']}-irr{c['irr']}")
+
+
+_BOUNDS_CASES = _bounds_cases(12 * _SCALE, 141414 + _SHIFT)
+assert 2 * sum(_bounds_refills(c) for c in _BOUNDS_CASES) >= len(_BOUNDS_CASES)
+assert sum(_bounds_second_item(c) and c["n_inner"] <= 130 for c in _BOUNDS_CASES) >= 2
+assert sum(_bounds_lower_strides(c) for c in _BOUNDS_CASES) >= 2
+_BOUNDS_EXCUSED = []
+
+
+def _bounds_agree(d, lo, up, c):
+    """The device's bounds d against the restatement (lo, up: helpers/bounds_ref.py lower_bound / upper_bound on the
+    device's spots and policy) -> True when the values were compared.  Tolerances, from the arithmetic (u = 2^-53):
+      q        a mean of n_inner summands >= 0: any summation order is within (n_inner - 1) u relative of the exact sum, so
+               device and numpy are within 2 * 2047 * 1.1e-16 = 4.5e-13 of each other for n_inner <= 2048: rtol 1e-12;
+      samples, upper   the martingale adds 2 t values of Q^ / Z: absolute 2 N 1e-12 max(Q^, Z) (bounds_ref.samples_atol);
+      lower    the restated mean is math.fsum (exactly rounded), so only the device's sum counts: a thread adds at most
+               ceil(300_001 / (1024 * 256)) = 2 pair means, block_reduce8 adds 32 values in sequence and 3 more in a tree,
+               and lsm_finalize adds at most 4 workgroup partials per thread before another block_reduce8: 2 + 35 + 4 + 35 =
+               76 additions of non-negative terms, 76 u = 8.4e-15 relative: rel 1e-12 holds;
+      se_*     sqrt((E[m^2] - mean^2) / P) loses E[m^2] / Var[m] to cancellation: rel 1e-12 times that ratio of the
+               restatement (se_upper: plus what the samples' own tolerance moves it by, at most that tolerance).
+    Decisions within 1e-10 K of the continuation value are ties: the counts may then differ by that many, and the values
+    are not compared (-> False)."""
+    from helpers import bounds_ref as br
+    K = c["K"]
+    assert abs(d["n_exercised_lower"] - lo["n_exercised"]) <= lo["ties"], (d["n_exercised_lower"], lo["n_exercised"], lo["ties"])
+    if up["ties"] == 0:
+        assert d["inner_path_steps"] == up["inner_path_steps"]
+    if d["n_exercised_lower"] != lo["n_exercised"] or d["inner_path_steps"] != up["inner_path_steps"]:
+        return False  # (only with ties: asserted above)
+    np.testing.assert_allclose(d["q"], up["q"], rtol=1e-12, atol=1e-12 * K)
+    atol = br.samples_atol(c["N"], up["q"], up["zmax"])
+    np.testing.assert_allclose(d["samples"], up["samples"], rtol=0, atol=atol)
+    assert abs(d["upper"] - up["upper"]) <= atol, (d["upper"], up["upper"], atol)
+    assert abs(d["lower"] - lo["lower"]) <= 1e-12 * abs(lo["lower"]), (d["lower"], lo["lower"])
+
+    def se_tol(se, ratio, mean, P):  # (zero variance: what 1e-12 of E[m^2] = mean^2 leaves under the root)
+        return 1e-12 * ratio * se if se > 0.0 else 1e-6 * abs(mean) / P ** 0.5
+
+    tol = se_tol(lo["se_lower"], lo["se_cancel"], lo["lower"], c["n_lower"] // 2)
+    assert abs(d["se_lower"] - lo["se_lower"]) <= tol, (d["se_lower"], lo["se_lower"], lo["se_cancel"])
+    tol = se_tol(up["se_upper"], up["se_cancel"], up["upper"], c["n_outer"] // 2) + atol
+    assert abs(d["se_upper"] - up["se_upper"]) <= tol, (d["se_upper"], up["se_upper"], up["se_cancel"])
+    assert d["ci_lo"] == d["lower"] - 1.96 * d["se_lower"] and d["ci_hi"] == d["upper"] + 1.96 * d["se_upper"]
+    assert (d["n_lower"], d["n_outer"], d["n_inner"]) == (c["n_lower"], c["n_outer"], c["n_inner"])
+    return True
+
+
+@pytest.mark.parametrize("case", _BOUNDS_CASES, ids=_bounds_id)
+def test_bounds_match_the_numpy_restatement(ctx, case):
+    """omc_price_american_bounds against tests/helpers/bounds_ref.py on the device's own spots (the generators at the
+    documented streams and pair offsets) and the device's policy -- everything tests/test_gpu_bounds.py compares at its one
+    tiny shape, over the shapes that shape leaves out: items with more pairs than a wave has lanes (the lane refill decides
+    which Philox pairs an item consumes), more items than waves, a lower sweep longer than its grid, one lane active
+    (n_inner = 2), outer matrices narrower than and ragged against the generator's 64-column stores, 1 .. 17 dates, given
+    policies with n = 0 holes, and every k-th date decided by the float64 rule instead of the tables."""
+    from helpers import bounds_ref as br
+    from options_model_amd import _ffi
+    c = case
+    N, K, r, T = c["N"], c["K"], _BOUNDS_R, _BOUNDS_T
+    p = _ffi.make_params(semantics="two_pass", is_put=c["is_put"], n_paths=c["M"], n_steps=N, S0=c["S0"], K=K, r=r,
+                         sigma=c["sigma"], T=T, seed=c["seed"], stream=c["stream"])
+
+    def host(a):
+        h = a.to_host()
+        a.free()
+        return h
+
+    def fits(policy, stream):  # omc_lsm_poly's fits on the paths of p (or of another stream)
+        S = ctx.gbm_paths(c["M"], N, c["S0"], r, c["sigma"], T, c["seed"], stream)
+        f = ctx.lsm_poly(S, K, r, T, c["is_put"], policy)
+        S.free()
+        b = np.zeros((N + 1, 4))
+        b[:, :3], b[:, 3] = f["betas"], f["nitm"]
+        return b
+
+    given = _holes(fits("textbook", c["stream"] + 9), c["holes"]) if c["policy"] == "given" else None
+    ctx.set_option("pass2_tables_irregular_every", c["irr"])
+    try:
+        d = ctx.price_american_bounds(p, policy=c["policy"], n_lower=c["n_lower"], n_outer=c["n_outer"], n_inner=c["n_inner"],
+                                      betas=given, want_q=True, want_samples=True)
+    finally:
+        ctx.set_option("pass2_tables_irregular_every", 0)
+    b4 = d["betas"]
+    np.testing.assert_array_equal(b4, given if given is not None else fits(c["policy"], c["stream"]))
+    Sl = host(ctx.gbm_paths(c["n_lower"], N, c["S0"], r, c["sigma"], T, c["seed"], c["stream"] + 1))
+    So = host(ctx.gbm_paths(c["n_outer"], N, c["S0"], r, c["sigma"], T, c["seed"], c["stream"] + 2))
+    inner = br.inner_by_item(lambda off, n: host(ctx.gbm_normals(n, N, c["seed"], c["stream"] + 3, off)), So, c["n_inner"],
+                             lambda z, s0: host(ctx.gbm_paths_from_normals(z, s0, r, c["sigma"], T)))
+    lo = br.lower_bound(Sl, K, r, T, c["is_put"], b4)
+    up = br.upper_bound(So, inner, K, r, T, c["is_put"], b4)
+    print(f"bounds {_bounds_id(c)}: ties {lo['ties']} + {up['ties']}  lower {d['lower']:.6f} upper {d['upper']:.6f}")
+    if not _bounds_agree(d, lo, up, c):
+        _BOUNDS_EXCUSED.append(_bounds_id(c))
+
+
+def test_bounds_sweep_excused_few_cases():
+    """The tie rule must not hide failures: at most one case in eight may go without its value comparison."""
+    print(f"bounds sweep: {len(_BOUNDS_EXCUSED)} of {len(_BOUNDS_CASES)} cases excused by ties: {_BOUNDS_EXCUSED}")
+    assert 8 * len(_BOUNDS_EXCUSED) <= len(_BOUNDS_CASES), _BOUNDS_EXCUSED

@@ -1,6 +1,8 @@
 """Frozen-policy pathwise Greeks of the two-pass flow (omc_price_american_greeks, options_model_amd/csrc/omc_greeks.hip)
 against the numpy restatement of their definitions (tests/helpers/greeks_ref.py) on the very matrix the device stores,
-against omc_price_american, against Black-Scholes for the all-n = 0 (European) policy, and for determinism.
+against omc_price_american, against Black-Scholes for the all-n = 0 (European) policy, and for determinism.  (Sweep 13 of
+tests/test_gpu_fuzz.py runs the same comparison over random shapes: all four kernel variants, short and ragged matrices,
+pair offsets, given policies with holes.)
 
 Agreement with the restatement: exercise counts of the three scenarios identical -- unless the restatement shows at
 least as many decisions taken within 1e-10 K of the continuation value (ties: either branch is worth the same, and the
@@ -12,6 +14,9 @@ import numpy as np
 import pytest
 
 from helpers import greeks_ref as gr
+from helpers.greeks_check import agrees as _agrees
+from helpers.greeks_check import close as _close
+from helpers.greeks_check import stored as _stored
 from oracle import cpu as orc
 from options_model_amd import _ffi
 from options_model_amd.pricer import BlackScholesGreeks as BSG
@@ -19,7 +24,6 @@ from options_model_amd.pricer import BlackScholesGreeks as BSG
 pytestmark = pytest.mark.gpu
 
 HESTON = dict(v0=0.04, kappa=2.0, theta=0.04, xi=0.3, rho=-0.7)
-VALS = ("price", "delta", "gamma", "vega", "rho", "theta", "price_up", "price_down")
 
 
 @pytest.fixture
@@ -28,41 +32,11 @@ def fold_opt(ctx):
     ctx.set_option("fold_antithetic", 1)
 
 
-def _stored(ctx, p):
-    """the full matrix the pricing stores (fold_antithetic 0, or Heston)"""
-    if p.model == 1:
-        return ctx.heston_paths(p.n_paths, p.n_steps, p.S0, p.r, p.T, p.v0, p.kappa, p.theta, p.xi, p.rho, p.seed,
-                                p.stream, p.pair_offset, scheme=p.heston_scheme)
-    return ctx.gbm_paths(p.n_paths, p.n_steps, p.S0, p.r, p.sigma, p.T, p.seed, p.stream, p.pair_offset,
-                         antithetic=bool(p.antithetic))
-
-
 def _restate(ctx, p, d, h):
     S = _stored(ctx, p)
     Sh = S.to_host()
     S.free()
     return gr.greeks(Sh, p.K, p.r, p.T, p.is_put, d["betas"], p.S0, p.sigma, h=h, gbm=(p.model == 0))
-
-
-def _close(a, b, rel=1e-9, abs_=1e-12):
-    return abs(a - b) <= max(rel * abs(b), abs_)
-
-
-def _agrees(d, ref, p):
-    counts = [(d["n_exercised"], ref["n_exercised"]), (d["n_exercised_up"], ref["n_exercised_up"]),
-              (d["n_exercised_down"], ref["n_exercised_down"])]
-    exact = all(a == b for a, b in counts)
-    for (a, b), ties in zip(counts, ref["ties"]):
-        assert abs(a - b) <= ties, (counts, ref["ties"])
-    if not exact:  # a tie went the other way: the values move by that path's share only
-        return
-    for k in VALS:
-        if p.model == 1 and k in ("vega", "rho", "theta"):
-            assert math.isnan(d[k]) and math.isnan(d["se_" + k])
-            continue
-        assert _close(d[k], ref[k]), (k, d[k], ref[k])
-        if k not in ("price", "price_up", "price_down"):
-            assert _close(d["se_" + k], ref["se_" + k], rel=1e-6), (k, d["se_" + k], ref["se_" + k])
 
 
 FULL = [
