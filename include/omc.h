@@ -539,7 +539,7 @@ int omc_mlp_shuffle_indices(omc_ctx* ctx, int64_t n_rows, uint64_t shuffle_key, 
 int omc_mlp_train_variant(int hidden, int layers, int64_t batch);
 /* Inspection: the dropout masks themselves.  nn.Dropout's random stream in the reference is torch's global generator
  * (options_model_3.py:455, 85-103); here a unit's 16 random bits come from Philox4x32-10 keyed by `seed` with counter
- * (row key, step, layer / half-tile tag, constant), stretched by a multiply-with-carry stream (csrc/omc_mlp.hip
+ * (row key, step, layer / half-tile tag, constant), stretched by a multiply-with-carry stream (csrc/omc_mlp_dev.h
  * relu_dropout).  out (host, [layers][n_rows][hidden] bytes): 1 = kept, 0 = dropped, as kernel `variant` draws them
  * (0 = pass 2, omc_lsm_apply_mlp: row key = path column, step = time step t; 1 .. 4 = omc_mlp_train_variant: row key
  * = position in the minibatch, step = optimizer step counted from 1).  keys (host, n_rows, may be NULL = 0, 1, 2, ...).

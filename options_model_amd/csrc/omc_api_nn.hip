@@ -46,7 +46,7 @@ int contnet_sweep(omc_ctx* c, const omc::LsmProblem& p, omc::LsmWorkspace& w, in
 {
     int rc;
     const int H = omc::cn_padded_width(hidden);
-    const int np = omc::mlp_train_param_count(H, 2);
+    const int np = omc::mlp_param_count(H, 2);
     const int64_t M = p.M;
     const int N = p.N;
     if ((rc = c->cn_scratch.ensure(omc::cn_scratch_bytes(M)))) return rc;
@@ -130,7 +130,7 @@ int omc_contnet_init_params(omc_ctx* c, int nn_hidden, int t, uint64_t nn_seed, 
     if ((rc = bind_in(c))) return rc;
     const int H = omc::cn_padded_width(nn_hidden);
     if (nn_hidden < 1 || H < 0) return fail(-4, "nn_hidden must be in 1 .. 128.");
-    const int np = omc::mlp_train_param_count(H, 2);
+    const int np = omc::mlp_param_count(H, 2);
     if (!params_out || n != np) return fail(-7, "params_out must hold the padded net's parameters.");
     if ((rc = c->cn_net.ensure(sizeof(float) * 3 * (size_t)np))) return rc;
     float* net = (float*)c->cn_net.p;
@@ -171,7 +171,7 @@ int omc_price_american_contnet(omc_ctx* c, const omc_params* p, int nn_hidden, i
     return read_kernel_times(c->ev, p, res);
 }
 
-int omc_mlp_param_count(int hidden, int layers) { return omc::mlp_apply_param_count(hidden, layers); }
+int omc_mlp_param_count(int hidden, int layers) { return omc::mlp_param_count(hidden, layers); }
 
 int omc_mlp_train_supported(int hidden, int layers, int64_t batch)
 {
@@ -730,7 +730,7 @@ int omc_mlp_train_epoch_sharded(omc_ctx* c, const float* data_epoch, int64_t n_r
     const int64_t kb = omc::mlp_plan_kernel_batch(t);
     if (omc::mlp_train_kernel_choice(hidden, layers, kb) == 0)
         return fail(-9, "the fused trainer supports hidden = 32, 64 or 128 with 2 or 3 hidden layers.");
-    const int np = omc::mlp_train_param_count(hidden, layers);
+    const int np = omc::mlp_param_count(hidden, layers);
     if ((rc = c->mlp_part.ensure(omc::mlp_partial_bytes(hidden, layers, kb)))) return rc;
     if ((rc = c->mlp_wt.ensure(omc::mlp_wt_bytes(hidden, layers)))) return rc;
     if ((rc = c->mlp_loss.ensure(sizeof(double)))) return rc;

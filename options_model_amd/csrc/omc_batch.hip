@@ -427,7 +427,7 @@ static size_t cn_plan(const BatchItem& it, int H, size_t base, size_t* off /*[11
     const size_t nb = (size_t)((M + kCnSpan - 1) / kCnSpan);
     const int np = H * 8 + H * H + H + H + 1;
     const size_t tiles = (size_t)((M + 31) / 32);
-    const size_t pstride = (size_t)((np + 1 + 63) / 64 * 64);  // the tile trainer's partial stride (omc_mlp.hip)
+    const size_t pstride = (size_t)((np + 1 + 63) / 64 * 64);  // the tile trainers' partial stride (tile_pstride, omc_mlp_dev.h)
     size_t o = align_up(base, 256);
     auto take = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes, 256); return r; };
     off[0] = take(4 * (nb + 2));            // cnt

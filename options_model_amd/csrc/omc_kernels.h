@@ -182,14 +182,16 @@ hipError_t lsm_crit_check(hipStream_t st, const double* betas, const double* cK,
 hipError_t lsm_final_reduce(hipStream_t st, const LsmProblem& p, const LsmWorkspace& w, int tval,
                             bool use_flags = false, bool fill_state = false);
 
-// ---- continuation-value network of the NN flow (omc_mlp.hip): 7 -> 64 -> 64 (-> 64) -> 1
+// ---- continuation-value network of the NN flow: 7 -> H -> H (-> H) -> 1, H = 32 | 64 | 128.  One network trained:
+// omc_mlp.hip; many side by side: omc_mlp_batch.hip; pass 2, local-vol paths, mask probe: omc_mlp_apply.hip; feature
+// statistics, epoch order, sharded epochs: omc_nn_epoch.hip
 constexpr int kMlpPartialStride2 = 4800;                   // gradient partial per workgroup, 2 / 3 hidden layers
 constexpr int kMlpPartialStride3 = 8960;                   // (>= parameters + 1 loss slot, multiple of 64)
 constexpr int kMlpMaxGroups = 256;                         // one workgroup per CU
 constexpr int kMlpQ16MaxRows = 4096;                       // minibatches up to here run in 16-row tiles (mlp_train_q16_kernel): one tile per CU
 struct MlpTrainPlan {
     const float* data;  // [nrows][8] float32: 7 inputs + target
-    float* params;      // [mlp_train_param_count(64, layers)], updated in place
+    float* params;      // [mlp_param_count(hidden, layers)], updated in place
     float* adam_m;
     float* adam_v;
     float* partial;     // mlp_partial_bytes()
@@ -247,15 +249,25 @@ hipError_t mlp_train_step_batch(hipStream_t st, const void* table_dev, int n, in
 hipError_t mlp_tile_prefix(hipStream_t st, const void* table_dev, int n, int* prefix_dev);
 size_t mlp_partial_bytes(int hidden, int layers, int64_t batch);
 size_t mlp_wt_bytes(int hidden, int layers);
-int mlp_train_param_count(int hidden, int layers);               // -1: shape not covered by a trainer
-int mlp_train_kernel_choice(int hidden, int layers, int64_t batch);  // 0: this batch size is not covered
-// keep (1) / drop (0) of every hidden activation as kernel `variant` draws it (0: pass 2, 1 / 2 / 3: the trainers, the
-// values of mlp_train_kernel_choice) -> out [layers][n_rows][hidden] (device); keys: per-row dropout key or null (= row)
+// floats of the flat parameter vector (trainers and pass 2 share the layout); -1: hidden not in {32, 64, 128} or
+// layers (hidden layers) not in {2, 3}
+int mlp_param_count(int hidden, int layers);
+// the forward / backward kernel of a training step (omc_mlp.hip); the numbers are ABI (omc_mlp_train_variant,
+// oracle/dropout.py)
+enum MlpKernel {
+    kNone = 0,   // shape or batch size not covered
+    kGroup = 1,  // mlp_train_kernel: weights in LDS, a workgroup walks many tiles
+    kTile = 2,   // mlp_train_tile_kernel: one wave per 32-row tile
+    kQuad = 3,   // mlp_train_quad_kernel: one workgroup per 32-row tile
+    kQ16 = 4     // mlp_train_q16_kernel: one workgroup per 16-row tile
+};
+MlpKernel mlp_train_kernel_choice(int hidden, int layers, int64_t batch);
+// keep (1) / drop (0) of every hidden activation as kernel `variant` draws it (0: pass 2, 1 .. 4: the trainers, the
+// values of MlpKernel) -> out [layers][n_rows][hidden] (device); keys: per-row dropout key or null (= row)
 hipError_t mlp_dropout_masks(hipStream_t st, int variant, int hidden, int layers, int64_t n_rows, const uint32_t* keys,
                              uint32_t step, uint64_t seed, double dropout, uint8_t* out);
 // pass 2 of the NN flow: sticky sweep with the network as continuation value -> (sx, tex)
-// hidden in {64, 128}, layers (hidden layers) in {2, 3}; mlp_apply_param_count: floats, -1 otherwise
-int mlp_apply_param_count(int hidden, int layers);
+// (every shape of mlp_param_count)
 hipError_t mlp_apply_pass2(hipStream_t st, const LsmProblem& p, int hidden, int layers, const float* params,
                            const double* feat_mean, const double* feat_std, double y_mean, double y_std,
                            double dropout, uint64_t seed, float* sx, int32_t* tex, int64_t col_base0, int64_t col_base1);

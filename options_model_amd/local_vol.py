@@ -5,7 +5,7 @@ drop-in for `IVModel` (options_model_3/options_model_3.py:263-298) and
 Per time step the reference calls the IV network on ALL paths (2 -> 64 -> 4 x [Linear 64x64,
 LayerNorm, GELU, residual] -> 1; NN_training_stock_iv.py:109-155) through numpy <-> torch-CPU
 round trips.  Here the whole simulation is ONE kernel of the library (`omc_localvol_paths_f32`,
-csrc/omc_mlp.hip): a wave carries 32 columns through all time steps and evaluates the network on
+csrc/omc_mlp_apply.hip): a wave carries 32 columns through all time steps and evaluates the network on
 the matrix cores in float32, weights in LDS, activations in registers; normals come from the
 library's Philox generator (`omc_gbm_normals_f32`, the GBM kernel's counter layout).  Networks of
 another width go through PyTorch-ROCm (batched GEMMs per step; backend="torch" forces that

@@ -53,7 +53,7 @@ def segment_tables(counts_all, rank: int):
 
 
 def locate(gstart, lstart, g):
-    """Host mirror of the kernel's lookup (csrc/omc_mlp.hip shard_locate): own row of global row g, or -1."""
+    """Host mirror of the kernel's lookup (csrc/omc_nn_epoch.hip shard_locate): own row of global row g, or -1."""
     s = int(np.searchsorted(gstart, g, side="right")) - 1  # the LAST segment starting at or before g: the non-empty one
     return -1 if lstart[s] < 0 else int(lstart[s] + (g - gstart[s]))
 

@@ -14,7 +14,7 @@ What differs, by construction (DESIGN.md "Parity"):
     numpy's PCG64 -- the master-seed draw sequence (two draws per LSM pricing, one per
     500-path European chunk) is kept so curves consume seeds exactly as the reference does;
   * the continuation-value regressor is the reference's: ONE SingleLSMNet trained on the pass-1 rows
-    (regressor="nn", the default; nn_regressor.py + the MFMA kernels of csrc/omc_mlp.hip);
+    (regressor="nn", the default; nn_regressor.py + the MFMA kernels of csrc/omc_mlp.hip, omc_mlp_apply.hip);
     regressor="poly" (OLS on [1,u,u^2] per time step, same control flow) is the explicit fast option;
   * iv_model: pass an `options_model_amd.local_vol.IVModel` (same constructor contract as the
     reference's); paths are then simulated on the GPU through the IV network (local_vol.py).

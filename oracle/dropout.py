@@ -22,7 +22,7 @@ Pinning: the Philox core against the Random123 known-answer vectors (tests/test_
 multiply-with-carry stretch and the unit order against the device (`omc_mlp_dropout_masks`, tests/test_gpu_dropout.py),
 the Bernoulli rate and independence statistically (tests/test_dropout_oracle_cpu.py).
 
-Definition (the build's; csrc/omc_mlp.hip `relu_dropout`, `relu_dropout_1`, and the call sites of the four kernels):
+Definition (the build's; csrc/omc_mlp_dev.h `relu_dropout`, `relu_dropout_1`, and the call sites of the four kernels):
 
 * keep16 = round((1 - p) * 65536); a unit is kept iff its 16 random bits are < keep16; a kept activation is
   multiplied by inv_keep = float32(65536 / keep16)  (p = 0.1: keep16 = 58982, keep probability 0.899994).

@@ -1,4 +1,4 @@
-"""Unit test of the sharded trainer's epoch selection (csrc/omc_mlp.hip shard_select / gather / step_off kernels behind
+"""Unit test of the sharded trainer's epoch selection (csrc/omc_nn_epoch.hip shard_select / gather / step_off kernels behind
 omc_mlp_shard_epoch) against a numpy mirror: the device's own keyed permutation (omc_mlp_shuffle_indices, proven a
 permutation in test_gpu_mlp.py) + nn_dist.locate on the same segment tables.  One process plays every rank in turn:
 the ranks' selections must partition the epoch's positions, each in ascending position order, rows gathered from the
