@@ -70,7 +70,9 @@ typedef struct {
     double zero_prob;      /* P(cash-flow == 0), Options_model.py:155                     */
     int64_t n_paths, n_exercised, n_zero, sum_nitm;
     double ms_paths, ms_lsm, ms_total; /* HIP-event times of this call on the context's stream */
-    double ms_pass1, ms_pass2;         /* omc_price_american, two-pass flow: the two big LSM kernels */
+    double ms_pass1, ms_pass2;         /* omc_price_american, two-pass flow: the two big LSM kernels (ms_pass2: with the
+                                          table build in front of the sweep; the sweep alone for a member of a group of
+                                          omc_price_american_seq, see omc_seq_group_width) */
     int64_t timed;         /* omc_price_american_seq: 1 = this pricing carried its own HIP events (the ms_* kernel
                               times above are its own), 0 = they repeat those of the latest timed pricing before it */
     int64_t folded;        /* omc_price_american (no S_keep) / _seq: 1 = the pricing ran on antithetic-FOLDED storage
@@ -131,6 +133,8 @@ int omc_memcpy_d2h(omc_ctx* ctx, void* dst, const void* src, size_t bytes);
  * communicator, that both forms return the same bits, as bench.py does),
  * "seq_event_stride" (omc_price_american_seq: k > 0 = every k-th pricing of a sequence carries its own HIP
  * events, so a sequence yields several samples of the per-kernel times; 0 = default: the first pricing only),
+ * "seq_step_k" / "seq_two_pass_k" (omc_price_american_seq: pricings per shared launch of the per-step flows / per group
+ * of the two-pass flow; see omc_seq_step_width and omc_seq_group_width),
  * "alloc_limit" (PER PROCESS, bytes; 0 = none: no single buffer of the library -- path matrix, workspace, row scratch --
  * may grow beyond it; a larger request fails like a hipMalloc that found no room, code 2 = hipErrorOutOfMemory.  A
  * budget for a card shared with other tenants; on a distributed context such a rank-local failure is reported on
@@ -645,6 +649,24 @@ int omc_price_american_seq(omc_ctx* ctx, const omc_params* p, int n, omc_result*
  * budget for the resident matrices (OMC_SEQ_STEP_BYTES, default 64e9).  This returns the K a sequence would use
  * (1 = one pricing at a time, 0 = invalid arguments). */
 int omc_seq_step_width(omc_ctx* ctx, const omc_params* p, int n);
+/* Two-pass flow (semantics 2) on one card: a run of consecutive pricings on folded storage with option "pass2_tables"
+ * on that share n_paths, n_steps, r, T and the fold constants (S0^2 / K and the drift: one fold table, one discount
+ * table; is_put, seed, stream and pair_offset may differ) is priced in GROUPS of K.  Every member keeps its own
+ * generator, pass-1 sweep and pass-2 sweep, each a launch of its own and the generator right in front of its pass 1,
+ * but the group's K pass-1 reductions, K table builds and K finalizes run as three launches instead of 3K: those are
+ * the latency-bound launches of a pricing (46 us of its 362 us of kernel time at 1M paths x 252 steps), during which
+ * the chip is nearly empty.  res[i] still carries the bits of omc_price_american(p[i]).  A timed member
+ * (res[i].timed) reports ms_pass2 of its pass-2 SWEEP alone; outside a group ms_pass2 includes the table build in
+ * front of the sweep.  ms_total and ms_lsm = ms_total - ms_paths are per pricing over the whole sequence as ever, the
+ * shared launches inside them.  Every member keeps its path matrix resident until its group ends.
+ * Option "seq_two_pass_k": -1 = default (groups of 8; pricings of more than 2^29 path-steps, 2.1M paths x 252 steps,
+ * one at a time: groups gain 2 % at 2M paths x 252 steps, nothing at 4M and lose 1 % at 8M), 1 = one pricing at a time (the launch order of omc_price_american), k <= 32; the
+ * environment variable OMC_SEQ_TWO_PASS_K sets the same where the option is -1.  K is further limited by the byte
+ * budget of the resident matrices (OMC_SEQ_STEP_BYTES, default 64e9, and 80 % of the card's free memory) and halves
+ * when an allocation fails.  A context with a communicator or an all-reduce hook, full storage, "pass2_tables" = 0 and
+ * every other flow: one pricing at a time, as before.  This returns the K of the run that starts at p[0] (1 = not
+ * grouped, 0 = invalid arguments). */
+int omc_seq_group_width(omc_ctx* ctx, const omc_params* p, int n);
 
 /* ---- many small pricings in one go ------------------------------------------------------- */
 /* replaces the curve loops compute_curve_for_S0 (options_model_3.py:697-713, Options_model.py:

@@ -148,6 +148,7 @@ SIGNATURES = {
     "omc_heston_price_surface": (C.c_int, [_P, _I64, _I] + [_D] * 7 + [_U64, _I, _P, _P, _I, _P, _P, _I, _I, _P, _P]),
     "omc_price_american_seq": (C.c_int, [_P, C.POINTER(Params), _I, C.POINTER(Result)]),
     "omc_seq_step_width": (C.c_int, [_P, C.POINTER(Params), _I]),
+    "omc_seq_group_width": (C.c_int, [_P, C.POINTER(Params), _I]),
     "omc_price_american_batch": (C.c_int, [_P, C.POINTER(Params), _I, C.POINTER(Result)]),
     "omc_price_european_batch": (C.c_int, [_P, C.POINTER(Params), _I, C.POINTER(Result)]),
     "omc_price_american_contnet_batch": (C.c_int, [_P, C.POINTER(Params), _I, _I, _I, _D, C.POINTER(C.c_uint64),
@@ -855,6 +856,12 @@ class Context:
         plist = list(params_list)
         arr = (Params * len(plist))(*plist)
         return int(self.lib.omc_seq_step_width(self.handle, arr, len(plist)))
+
+    def seq_group_width(self, params_list) -> int:
+        """How many pricings of the run that starts this sequence share their small launches (two-pass flow; 1 = none)."""
+        plist = list(params_list)
+        arr = (Params * len(plist))(*plist)
+        return int(self.lib.omc_seq_group_width(self.handle, arr, len(plist)))
 
     def price_american_batch(self, params_list):
         return self._batch(self.lib.omc_price_american_batch, list(params_list))

@@ -697,6 +697,7 @@ int omc_set_option(omc_ctx* c, const char* key, int64_t value)
     else if (!strcmp(key, "seq_overlap")) c->seq_overlap = value < 0 ? -1 : (value ? 1 : 0);
     else if (!strcmp(key, "seq_event_stride")) c->seq_event_stride = value > 0 ? (int)value : 0;
     else if (!strcmp(key, "seq_step_k")) c->seq_step_k = value < 0 ? -1 : (int)(value > 32 ? 32 : value);
+    else if (!strcmp(key, "seq_two_pass_k")) c->seq_two_pass_k = value < 0 ? -1 : (int)(value > 32 ? 32 : value);
     else if (!strcmp(key, "seq_step_wgs")) c->seq_step_wgs = value > 0 ? (int)value : 0;
     else if (!strcmp(key, "p2p_exchange")) c->p2p_use = value ? 1 : 0;
     else if (!strcmp(key, "p2p_deadline_ms") || !strcmp(key, "p2p_first_deadline_ms")) {

@@ -1,5 +1,6 @@
-// omc_api_seq.hip -- omc_price_american_seq and omc_seq_step_width (include/omc.h): sequences of pricings, overlapped
-// across GPUs or advanced K per launch by the per-step flows.
+// omc_api_seq.hip -- omc_price_american_seq, omc_seq_step_width and omc_seq_group_width (include/omc.h): sequences of
+// pricings, overlapped across GPUs, advanced K per launch by the per-step flows, or -- two-pass flow -- in groups of K
+// that share their small launches.
 #include <cstdlib>
 
 #include "omc_ctx.h"
@@ -176,21 +177,27 @@ static int seq_multi_ideal(const omc_ctx* c, const omc_params* p, int n)
 // of the 288 (OMC_SEQ_STEP_BYTES), and never more than 80 % of what is free on this card right now plus what the context
 // already holds for them (a card shared with torch or with other ranks has less; seq_multi_reserve also halves K when
 // the allocation fails all the same).
-static int seq_multi_fit(const omc_ctx* c, const omc_params* p, int k)
+// (`held`: bytes the context already holds for the matrices in question; shared by the two-pass groups below)
+static double seq_resident_budget(const omc_ctx* c, size_t held)
 {
     static const double cap = getenv("OMC_SEQ_STEP_BYTES") ? atof(getenv("OMC_SEQ_STEP_BYTES")) : 64e9;
     double budget = cap;
     size_t free_b = 0, total_b = 0;
     (void)hipSetDevice(c->device);
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-        const double avail = 0.8 * (double)free_b + (double)c->mS.cap;
+        const double avail = 0.8 * (double)free_b + (double)held;
         if (avail < budget) budget = avail;
     } else {
         (void)hipGetLastError();
     }
+    return budget;
+}
+
+static int seq_multi_fit(const omc_ctx* c, const omc_params* p, int k)
+{
     const int64_t ld = padded_ld(p[0].n_paths);
     const double sbytes = 4.0 * (double)ld * (double)(p[0].n_steps + 1);
-    const int fit = (int)(budget / sbytes);
+    const int fit = (int)(seq_resident_budget(c, c->mS.cap) / sbytes);
     if (k > fit) k = fit;
     return k < 2 ? 1 : k;
 }
@@ -349,6 +356,177 @@ int omc_seq_step_width(omc_ctx* c, const omc_params* p, int n)
     return seq_multi_width(c, p, n);
 }
 
+// ---- two-pass flow on folded storage: the small launches of K pricings of one geometry shared ----------------
+// Per pricing the stream carries six dependent launches, three of them latency-bound: the pass-1 reduction (N - 1
+// workgroups), the table build (N + 1 workgroups of two waves that wait on a dependency chain) and the finalize (ONE
+// workgroup) -- at 1M paths x 252 steps 36 + 5 + 5 = 46 us of the 362 us of kernel time of a pricing
+// (profiles/r08_seq_group_kernel_stats.txt), during which the chip is nearly empty; the kernel boundaries between them
+// cost next to nothing beside that.  A run of pricings that agree in geometry and fold constants is therefore priced in groups of K:
+//     for k: generator(k) -> S[k]; pass-1 sweep(k) -> part1[k]        (single launches; the generator stays in front
+//     ONE launch: the K reductions        part1[k] -> gmom[k]          of ITS pass 1, no pass 2 behind a generator)
+//     ONE launch: the K table builds      gmom[k] -> betas[k], crit[k]
+//     for k: pass-2 sweep(k) -> part[k]
+//     ONE launch: the K finalizes         part[k], gmom[k] -> result slot of the pricing
+// The three launches take the pricing from grid.y and run the bodies of the single launches (omc_lsm.hip), so res[i]
+// keeps the bits of omc_price_american(p[i]).  One stream, no host wait and no grid-wide barrier inside a group.
+// One card only: a distributed context all-reduces every pricing's moment table between its pass 1 and its fits.
+
+// pricing `q` can be a member of a group (the context is not distributed)
+static bool seq_group_eligible(const omc_ctx* c, const omc_params* q)
+{
+    return c->pass2_tables && q->semantics == OMC_SEM_TWO_PASS && q->n_steps >= 2 && fold_applies(c, q);
+}
+
+// how many pricings from p[0] on form one run: eligible, same geometry, ONE fold table and ONE discount table
+static int seq_group_run(const omc_ctx* c, const omc_params* p, int n)
+{
+    if (c->distributed() || !seq_group_eligible(c, &p[0])) return 1;
+    double c0, g;
+    omc::gbm_fold_constants(p[0].S0, p[0].K, p[0].r, p[0].sigma, p[0].T, p[0].n_steps, &c0, &g);
+    int run = 1;
+    for (; run < n; ++run) {
+        const omc_params& q = p[run];
+        if (!seq_group_eligible(c, &q) || q.n_paths != p[0].n_paths || q.n_steps != p[0].n_steps || q.r != p[0].r ||
+            q.T != p[0].T)
+            break;
+        double c0q, gq;
+        omc::gbm_fold_constants(q.S0, q.K, q.r, q.sigma, q.T, q.n_steps, &c0q, &gq);
+        if (c0q != c0 || gq != g) break;
+    }
+    return run;
+}
+
+// device bytes one member of a group owns: its path matrix, and [part1 | gmom | betas | crit | part]
+struct SeqGroupLayout {
+    int64_t ld;
+    size_t sbytes, o_gmom, o_betas, o_crit, o_part, per;
+    SeqGroupLayout(int64_t M, int N)
+    {
+        const size_t n1 = (size_t)N + 1;
+        ld = padded_ld(M / 2);
+        sbytes = sizeof(float) * (size_t)ld * n1;
+        o_gmom = up256(sizeof(double) * 8 * n1 * omc::lsm_part1_tiles(M));
+        o_betas = o_gmom + up256(sizeof(double) * 8 * n1);
+        o_crit = o_betas + up256(sizeof(double) * 4 * n1);
+        o_part = o_crit + up256(sizeof(uint32_t) * 8 * n1);
+        per = o_part + up256(sizeof(double) * 2 * 8 * omc::kMaxLsmBlocks);
+    }
+};
+
+// The width a run of `run` pricings like p[0] asks for.  Default (profiles/r08_seq_group_sweep.txt): sharing saves a
+// fixed ~35 us of small kernels per pricing, and the big kernels of a group run 2-3 % slower than back to back on one
+// matrix, a loss that grows with the pricing's own time, i.e. with paths x steps.  Measured at 252 steps, groups of 8
+// against single pricings: 1.26 x at 65,536 paths, 1.09 x at 1M, 1.02 x at 2M, 1.00 x at 4M, 0.99 x at 8M (16: under 2 %
+// more at any size, for twice the resident path matrices).  So pricings of more than 2^29 path-steps (2.1M paths x 252
+// steps) stay single.  (Fewer steps, more paths, all below the bound: 2M x 50 1.12 x, 4M x 126 1.015 x, 8M x 50 1.01 x.)
+static int seq_group_ideal(const omc_ctx* c, const omc_params* p, int run)
+{
+    if (run < 2) return 1;
+    static const int env_k = getenv("OMC_SEQ_TWO_PASS_K") ? atoi(getenv("OMC_SEQ_TWO_PASS_K")) : -1;
+    int k = c->seq_two_pass_k >= 0 ? c->seq_two_pass_k : env_k;
+    if (k < 0) k = (double)p[0].n_paths * (double)p[0].n_steps > 536870912.0 ? 1 : 8;
+    if (k > omc::kSeqGroupMax) k = omc::kSeqGroupMax;
+    if (k > run) k = run;
+    return k < 2 ? 1 : k;
+}
+
+// ... and what this card has room for: the byte budget of the per-step flows' resident matrices (seq_multi_fit)
+static int seq_group_fit(const omc_ctx* c, const omc_params* p, int k)
+{
+    const SeqGroupLayout L(p[0].n_paths, p[0].n_steps);
+    const int fit = (int)(seq_resident_budget(c, c->gS.cap + c->gstate.cap) / ((double)L.sbytes + (double)L.per));
+    if (k > fit) k = fit;
+    return k < 2 ? 1 : k;
+}
+
+// Reserve the group buffers; no room (a shared card, option "alloc_limit"): halve K down to one pricing at a time
+// instead of failing the sequence.
+static int seq_group_reserve(omc_ctx* c, const omc_params* p, int run, int* K_out)
+{
+    *K_out = 1;
+    int K = seq_group_ideal(c, p, run);
+    const SeqGroupLayout L(p[0].n_paths, p[0].n_steps);
+    // (buffers that are large enough already need no look at the card's free memory: the query takes a quarter of a
+    // millisecond during which the stream runs dry at the head of every sequence)
+    if (K >= 2 && (c->gS.cap < L.sbytes * (size_t)K || c->gstate.cap < L.per * (size_t)K)) K = seq_group_fit(c, p, K);
+    // (a buffer that has to grow is freed first, while an earlier, smaller group of the same sequence may still be
+    // running in it: hipFree waits for the device before it releases memory, so that group ends undisturbed)
+    while (K >= 2) {
+        int rc = c->gS.ensure(L.sbytes * (size_t)K);
+        if (!rc) rc = c->gstate.ensure(L.per * (size_t)K);
+        if (!rc) break;
+        if (rc != (int)hipErrorOutOfMemory && rc != (int)hipErrorMemoryAllocation) return rc;
+        K /= 2;
+    }
+    *K_out = K < 2 ? 1 : K;
+    return 0;
+}
+
+// pricings p[i0 .. i0 + Kb) as one group; their sums go to dst + 8 i
+static int enqueue_seq_group(omc_ctx* c, const omc_params* p, int i0, int Kb, double* dst)
+{
+    int rc;
+    const int64_t M = p[i0].n_paths;
+    const int N = p[i0].n_steps;
+    const SeqGroupLayout L(M, N);
+    int64_t ld = 0;
+    const double* cK = nullptr;
+    if ((rc = plan_storage(c, &p[i0], 0, &ld, &cK))) return rc;  // the group's one fold table
+    omc::LsmWorkspace w0;
+    if ((rc = prepare_lsm(c, M, N, p[i0].r, p[i0].T, true, false, &w0))) return rc;  // discount table (+ the singles)
+    if (!cK || ld != L.ld || Kb > omc::kSeqGroupMax) return fail(-4, "a grouped two-pass sequence needs folded storage.");
+    omc::SeqGroupArgs g;
+    memset(&g, 0, sizeof g);
+    omc::LsmProblem prob[omc::kSeqGroupMax];
+    omc::LsmWorkspace w[omc::kSeqGroupMax];
+    hipEvent_t* evs[omc::kSeqGroupMax];
+    int64_t ntiles = 0;
+    for (int k = 0; k < Kb; ++k) {  // the event pool grows, and may move, HERE: the members' event sets are fetched
+        hipEvent_t* grown = nullptr;  // below, once it no longer does
+        if ((rc = pricing_events(c, i0 + k, &grown))) return rc;
+    }
+    for (int k = 0; k < Kb; ++k) {
+        const omc_params& q = p[i0 + k];
+        float* S = (float*)((char*)c->gS.p + L.sbytes * (size_t)k);
+        char* st = (char*)c->gstate.p + L.per * (size_t)k;
+        w[k] = w0;
+        w[k].part1 = (double*)st; w[k].gmom = (double*)(st + L.o_gmom); w[k].betas = (double*)(st + L.o_betas);
+        w[k].crit = (uint32_t*)(st + L.o_crit); w[k].part = (double*)(st + L.o_part);
+        w[k].result = dst + 8 * (size_t)(i0 + k);
+        prob[k] = omc::LsmProblem{S, ld, M, N, q.is_put ? 1 : 0, q.K, q.r, q.T};
+        prob[k].fold_cK = cK;
+        if ((rc = pricing_events(c, i0 + k, &evs[k]))) return rc;
+        if (evs[k]) {  // a timed pricing: events around ITS generator, pass-1 sweep and (below) pass-2 sweep
+            w[k].ev_p1_end = evs[k][4]; w[k].ev_p2_end = evs[k][6];
+            HIP_TRY(hipEventRecord(evs[k][0], c->stream));
+        }
+        if ((rc = enqueue_paths(c, &q, S, ld, true))) return rc;
+        if (evs[k]) HIP_TRY(hipEventRecord(evs[k][1], c->stream));
+        HIP_TRY(omc::lsm_pass1_sweep(c->stream, prob[k], w[k], &ntiles));
+        g.slot[k] = omc::lsm_group_slot(prob[k], w[k]);
+    }
+    g.cK = cK; g.ntiles = ntiles; g.N = N; g.irr_every = w0.crit_irr_every;
+    HIP_TRY(omc::lsm_group_reduce_pass1(c->stream, g, Kb));
+    HIP_TRY(omc::lsm_group_crit_build(c->stream, g, Kb));
+    for (int k = 0; k < Kb; ++k) {
+        if (evs[k]) HIP_TRY(hipEventRecord(evs[k][5], c->stream));
+        HIP_TRY(omc::lsm_pass2_sweep(c->stream, prob[k], w[k], false, true, &g.nblk));
+    }
+    HIP_TRY(omc::lsm_group_finalize(c->stream, g, Kb));
+    if (i0 == 0) HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+    return 0;
+}
+
+int omc_seq_group_width(omc_ctx* c, const omc_params* p, int n)
+{
+    if (!c || !p || n <= 0) return 0;
+    for (int i = 0; i < n; ++i)
+        if (check_params(&p[i])) return 0;
+    const int run = seq_group_run(c, p, n);
+    const int k = seq_group_ideal(c, p, run);
+    return k < 2 ? 1 : seq_group_fit(c, p, k);
+}
+
 // n pricings back to back on the stream with NO host synchronisation in between: pricing i + 1 is
 // enqueued while pricing i runs, every pricing's sums land in their own slot of a host-mapped buffer,
 // one wait at the end.  Results are those of n omc_price_american calls; kernel times are measured on
@@ -390,13 +568,25 @@ int omc_price_american_seq(omc_ctx* c, const omc_params* p, int n, omc_result* r
         c->defer_result_allreduce = false;
         return rc;
     }
-    for (int i = 0; i < n && !overlapped && multi <= 1; ++i) {
-        hipEvent_t* evs = nullptr;
-        if ((rc = pricing_events(c, i, &evs))) break;
-        rc = enqueue_pricing(c, &p[i], nullptr, 0, dist ? local + 8 * (size_t)i : c->seq_dev + 8 * (size_t)i,
-                             evs, nullptr);
+    for (int i = 0; i < n && !overlapped && multi <= 1;) {
+        // a run of two-pass pricings of one geometry on folded storage: in groups that share their small launches; a
+        // single pricing left over, a run that is not to be grouped, and everything else, one at a time
+        int run = seq_group_run(c, &p[i], n - i), Kg = 1;
+        if (run >= 2 && (rc = seq_group_reserve(c, &p[i], run, &Kg))) break;
+        while (Kg >= 2 && run >= 2 && !rc) {
+            const int Kb = Kg < run ? Kg : run;
+            rc = enqueue_seq_group(c, p, i, Kb, c->seq_dev);
+            i += Kb;
+            run -= Kb;
+        }
+        for (; run >= 1 && !rc; ++i, --run) {
+            hipEvent_t* evs = nullptr;
+            if ((rc = pricing_events(c, i, &evs))) break;
+            rc = enqueue_pricing(c, &p[i], nullptr, 0, dist ? local + 8 * (size_t)i : c->seq_dev + 8 * (size_t)i,
+                                 evs, nullptr);
+            if (!rc && evs && i == 0 && hipEventRecord(evs[2], c->stream) != hipSuccess) rc = fail(999, "hipEventRecord failed");
+        }
         if (rc) break;
-        if (evs && i == 0 && hipEventRecord(evs[2], c->stream) != hipSuccess) { rc = fail(999, "hipEventRecord failed"); break; }
     }
     c->defer_result_allreduce = false;
     if (rc) return rc;

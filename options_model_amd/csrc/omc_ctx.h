@@ -183,6 +183,10 @@ struct omc_ctx {
     int mtab_slot = 0;
     int seq_step_k = -1;       // -1: default (what fits the Infinity Cache, <= 16), 1: off, k: at most k pricings per launch
     int seq_step_wgs = 0;      // workgroups one launch of the multi-pricing sweep may use (0: one per CU)
+    // omc_price_american_seq, two-pass flow on folded storage: the pass-1 reductions, table builds and finalizes of K
+    // pricings of one geometry share three launches; per pricing of a group its own path matrix and small buffers
+    DevBuf gS, gstate;
+    int seq_two_pass_k = -1;   // -1: by size (omc_api_seq.hip), 1: one pricing at a time, k: at most k pricings per group
     int gbm_vec = 0, heston_vec = 0;
     // antithetic-folded storage of the fused GBM two-pass pricing (omc_lsm_dev.h; option "fold_antithetic": 0 never,
     // 1 = default: pricings of at least kFoldMinPaths paths over all ranks, 2 always): two cK tables (the overlapped

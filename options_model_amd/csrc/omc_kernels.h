@@ -156,6 +156,44 @@ hipError_t lsm_pass1_moments(hipStream_t st, const LsmProblem& p, const LsmWorks
 // when write_state, leaves sums in w.result
 hipError_t lsm_pass2_apply(hipStream_t st, const LsmProblem& p, const LsmWorkspace& w,
                            bool write_state, bool solve_from_moments = false);
+// The same two calls taken apart (lsm_pass1_moments = sweep + reduction; lsm_pass2_apply = begin event + table build +
+// sweep + finalize), for callers that run the small launches of several pricings together (below):
+//   lsm_pass1_sweep   the sweep alone, w.part1 left unreduced; *ntiles = records per step (the reduction's argument)
+//   lsm_pass2_tables  whether pass 2 of (p, w) decides from exercise tables: the caller has then built w.crit and
+//                     solved the fits into w.betas (lsm_crit_build) before the sweep
+//   lsm_pass2_sweep   the sweep alone (w.ev_p2_end behind it); *nblk = partial sums per quantity it leaves in w.part
+hipError_t lsm_pass1_sweep(hipStream_t st, const LsmProblem& p, const LsmWorkspace& w, int64_t* ntiles);
+hipError_t lsm_reduce_pass1(hipStream_t st, const LsmWorkspace& w, int64_t ntiles, int N);
+bool lsm_pass2_tables(const LsmProblem& p, const LsmWorkspace& w, bool write_state);
+hipError_t lsm_pass2_sweep(hipStream_t st, const LsmProblem& p, const LsmWorkspace& w, bool write_state,
+                           bool solve_from_moments, int* nblk);
+// ---- the two-pass flow's latency-bound launches for K pricings of one geometry at once (omc_price_american_seq):
+// pass-1 reduction, table build and finalize with the pricing on grid.y.  Thin entry points around the bodies of the
+// single launches, so every pricing keeps the bits of its own.  The per-pricing pointers travel BY VALUE in the
+// kernel arguments (72 bytes x 32 pricings + the shared fields = 2.4 KB of the 4 KB a launch may carry): no table
+// upload sits on the stream between a group's sweeps and nothing has to outlive the enqueue.
+constexpr int kSeqGroupMax = 32;
+struct SeqGroupSlot {
+    const double* part1;  // pass 1's unreduced partials
+    double* gmom;         // [N+1][8]
+    double* betas;        // [N+1][4], written by the table build
+    uint32_t* crit;       // [N+1][8]
+    const double* part;   // pass 2's partial sums
+    double* result;       // [8]
+    double K, invK;
+    int is_put, pad_;
+};
+struct SeqGroupArgs {
+    SeqGroupSlot slot[kSeqGroupMax];
+    const double* cK;  // one fold table for the whole group
+    int64_t ntiles;    // lsm_pass1_sweep
+    int N, nblk;       // nblk: lsm_pass2_sweep
+    int irr_every, pad_;
+};
+SeqGroupSlot lsm_group_slot(const LsmProblem& p, const LsmWorkspace& w);
+hipError_t lsm_group_reduce_pass1(hipStream_t st, const SeqGroupArgs& g, int K);
+hipError_t lsm_group_crit_build(hipStream_t st, const SeqGroupArgs& g, int K);
+hipError_t lsm_group_finalize(hipStream_t st, const SeqGroupArgs& g, int K);
 // betas[t] = solve_poly2(gmom[t]), n = gmom[t][0] for t = 1 .. N-1: the fits pass 2 solves for itself
 hipError_t lsm_solve_betas(hipStream_t st, const double* gmom, double* betas, int N);
 // pass 2's exercise tables [N+1][8] (omc_crit.h; the stored path's words, then the partner's) of one set of fits

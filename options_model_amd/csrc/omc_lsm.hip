@@ -155,6 +155,29 @@ __global__ __launch_bounds__(kBlock) void lsm_finalize_multi_kernel(const SweepA
     lsm_finalize_body(a.part, a.gmom, a.result, a.nblk, a.N, a.pstride, a.gstride);
 }
 
+// ---- the two-pass flow's small launches for K pricings of one geometry (omc_price_american_seq): pricing = blockIdx.y,
+// its pointers from the by-value argument block; blockIdx.x is what the single launch's body expects.
+__global__ __launch_bounds__(kBlock) void lsm_reduce_pass1_group_kernel(SeqGroupArgs g)
+{
+    const SeqGroupSlot& s = g.slot[blockIdx.y];
+    lsm_reduce_pass1_body(s.part1, s.gmom, g.ntiles, g.N);
+}
+
+__global__ __launch_bounds__(128) void lsm_crit_build_group_kernel(SeqGroupArgs g)
+{
+    const SeqGroupSlot& s = g.slot[blockIdx.y];
+    CritArgs a;
+    a.gmom = s.gmom; a.betas = s.betas; a.betas_out = s.betas; a.cK = g.cK; a.tab = s.crit;
+    a.N = g.N; a.is_put = s.is_put; a.K = s.K; a.invK = s.invK; a.irr_every = g.irr_every;
+    lsm_crit_build_body(a);
+}
+
+__global__ __launch_bounds__(kBlock) void lsm_finalize_group_kernel(SeqGroupArgs g)
+{
+    const SeqGroupSlot& s = g.slot[blockIdx.y];
+    lsm_finalize_body(s.part, s.gmom, s.result, g.nblk, g.N, kPStride);
+}
+
 // ------------------------------------------------------------------ host launchers
 static inline bool vec4_ok(const LsmProblem& p)
 {
@@ -349,7 +372,7 @@ hipError_t lsm_fold_table(hipStream_t st, double* cK, int N, double c0, double g
 
 // pass 1 on the folded matrix: P = M / 2 stored columns, two tiles of 64 x VEC columns per wave and step (= 1,024 paths, as
 // in the full sweep; OMC_FOLD_TPW = 1 | 4 for experiments)
-static hipError_t lsm_pass1_moments_fold(hipStream_t st, const LsmProblem& p, const LsmWorkspace& w)
+static hipError_t lsm_pass1_sweep_fold(hipStream_t st, const LsmProblem& p, const LsmWorkspace& w, int64_t* ntiles)
 {
     Pass1Args a;
     const int64_t P = p.M / 2;
@@ -382,14 +405,15 @@ static hipError_t lsm_pass1_moments_fold(hipStream_t st, const LsmProblem& p, co
         else hipLaunchKernelGGL((lsm_pass1_fold_kernel<1, 2, 0>), grid, dim3(kBlock), 0, st, a);
     }
     if (w.ev_p1_end) (void)hipEventRecord(w.ev_p1_end, st);
-    hipLaunchKernelGGL(lsm_reduce_pass1_kernel, dim3(p.N - 1), dim3(kBlock), 0, st, w.part1, w.gmom, a.ntiles, p.N);
+    *ntiles = a.ntiles;
     return hipGetLastError();
 }
 
-hipError_t lsm_pass1_moments(hipStream_t st, const LsmProblem& p, const LsmWorkspace& w)
+hipError_t lsm_pass1_sweep(hipStream_t st, const LsmProblem& p, const LsmWorkspace& w, int64_t* ntiles)
 {
+    *ntiles = 0;
     if (p.N < 2) return hipSuccess;
-    if (p.fold_cK) return lsm_pass1_moments_fold(st, p, w);
+    if (p.fold_cK) return lsm_pass1_sweep_fold(st, p, w, ntiles);
     Pass1Args a;
     a.S = p.S; a.ld = p.ld; a.M = p.M; a.N = p.N; a.is_put = p.is_put;
     a.K = p.K; a.invK = 1.0 / p.K; a.D = w.D; a.part1 = w.part1;
@@ -433,13 +457,33 @@ hipError_t lsm_pass1_moments(hipStream_t st, const LsmProblem& p, const LsmWorks
     else if (tpw == 8) launch(integral_constant<int, 4>{}, integral_constant<int, 8>{});
     else launch(integral_constant<int, 4>{}, integral_constant<int, 4>{});
     if (w.ev_p1_end) (void)hipEventRecord(w.ev_p1_end, st);
-    hipLaunchKernelGGL(lsm_reduce_pass1_kernel, dim3(p.N - 1), dim3(kBlock), 0, st, w.part1, w.gmom,
-                       a.ntiles, p.N);
+    *ntiles = a.ntiles;
     return hipGetLastError();
 }
 
-hipError_t lsm_pass2_apply(hipStream_t st, const LsmProblem& p, const LsmWorkspace& w,
-                           bool write_state, bool solve_from_moments)
+hipError_t lsm_reduce_pass1(hipStream_t st, const LsmWorkspace& w, int64_t ntiles, int N)
+{
+    if (N < 2) return hipSuccess;
+    hipLaunchKernelGGL(lsm_reduce_pass1_kernel, dim3(N - 1), dim3(kBlock), 0, st, w.part1, w.gmom, ntiles, N);
+    return hipGetLastError();
+}
+
+hipError_t lsm_pass1_moments(hipStream_t st, const LsmProblem& p, const LsmWorkspace& w)
+{
+    int64_t ntiles = 0;
+    const hipError_t e = lsm_pass1_sweep(st, p, w, &ntiles);
+    return e != hipSuccess ? e : lsm_reduce_pass1(st, w, ntiles, p.N);
+}
+
+// exercise tables (option "pass2_tables"): built from the fits right before the sweep, which then reads the fits
+// the table kernel solved (or was given) from w.betas instead of solving all N in every workgroup
+bool lsm_pass2_tables(const LsmProblem& p, const LsmWorkspace& w, bool write_state)
+{
+    return w.crit != nullptr && p.fold_cK != nullptr && !write_state;
+}
+
+hipError_t lsm_pass2_sweep(hipStream_t st, const LsmProblem& p, const LsmWorkspace& w, bool write_state,
+                           bool solve_from_moments, int* nblk_out)
 {
     Pass2Args a;
     a.S = p.S; a.ld = p.ld; a.M = p.M; a.N = p.N; a.is_put = p.is_put;
@@ -457,16 +501,9 @@ hipError_t lsm_pass2_apply(hipStream_t st, const LsmProblem& p, const LsmWorkspa
     a.nblk = nblk; a.pstride = kPStride;
     const size_t dyn = sizeof(double) * 4 * (size_t)(p.N + 1);
     const bool v4 = vec4_ok(p);
-    if (w.ev_p2_begin) (void)hipEventRecord(w.ev_p2_begin, st);
-    // exercise tables (option "pass2_tables"): built from the fits right before the sweep, which then reads the fits
-    // the table kernel solved (or was given) from w.betas instead of solving all N in every workgroup
-    const bool tab = w.crit != nullptr && p.fold_cK != nullptr && !write_state;
-    if (tab) {
-        CritArgs c;
-        c.gmom = a.gmom; c.betas = w.betas; c.betas_out = a.betas_out; c.cK = p.fold_cK; c.tab = w.crit;
-        c.N = p.N; c.is_put = p.is_put; c.K = p.K; c.irr_every = w.crit_irr_every;
-        const hipError_t e = lsm_crit_build(st, c);
-        if (e != hipSuccess) return e;
+    *nblk_out = nblk;
+    const bool tab = lsm_pass2_tables(p, w, write_state);
+    if (tab) {  // the table launch solved the fits into w.betas
         a.gmom = nullptr;
         a.betas_out = nullptr;
         a.crit = w.crit;
@@ -497,8 +534,54 @@ hipError_t lsm_pass2_apply(hipStream_t st, const LsmProblem& p, const LsmWorkspa
         else hipLaunchKernelGGL((lsm_pass2_kernel<1, false>), dim3(nblk), dim3(kBlock), dyn, st, a);
     }
     if (w.ev_p2_end) (void)hipEventRecord(w.ev_p2_end, st);
+    return hipGetLastError();
+}
+
+hipError_t lsm_pass2_apply(hipStream_t st, const LsmProblem& p, const LsmWorkspace& w,
+                           bool write_state, bool solve_from_moments)
+{
+    if (w.ev_p2_begin) (void)hipEventRecord(w.ev_p2_begin, st);
+    const bool tab = lsm_pass2_tables(p, w, write_state);
+    if (tab) {
+        CritArgs c;
+        c.gmom = solve_from_moments ? w.gmom : nullptr; c.betas = w.betas; c.betas_out = solve_from_moments ? w.betas : nullptr;
+        c.cK = p.fold_cK; c.tab = w.crit;
+        c.N = p.N; c.is_put = p.is_put; c.K = p.K; c.irr_every = w.crit_irr_every;
+        const hipError_t e = lsm_crit_build(st, c);
+        if (e != hipSuccess) return e;
+    }
+    int nblk = 0;
+    const hipError_t e = lsm_pass2_sweep(st, p, w, write_state, solve_from_moments, &nblk);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(lsm_finalize_kernel, dim3(1), dim3(kBlock), 0, st, w.part, w.gmom, w.result,
                        nblk, p.N, kPStride);
+    return hipGetLastError();
+}
+
+SeqGroupSlot lsm_group_slot(const LsmProblem& p, const LsmWorkspace& w)
+{
+    SeqGroupSlot s;
+    s.part1 = w.part1; s.gmom = w.gmom; s.betas = w.betas; s.crit = w.crit; s.part = w.part; s.result = w.result;
+    s.K = p.K; s.invK = 1.0 / p.K; s.is_put = p.is_put; s.pad_ = 0;
+    return s;
+}
+
+hipError_t lsm_group_reduce_pass1(hipStream_t st, const SeqGroupArgs& g, int K)
+{
+    if (g.N < 2) return hipSuccess;
+    hipLaunchKernelGGL(lsm_reduce_pass1_group_kernel, dim3(g.N - 1, K), dim3(kBlock), 0, st, g);
+    return hipGetLastError();
+}
+
+hipError_t lsm_group_crit_build(hipStream_t st, const SeqGroupArgs& g, int K)
+{
+    hipLaunchKernelGGL(lsm_crit_build_group_kernel, dim3(g.N + 1, K), dim3(128), 0, st, g);
+    return hipGetLastError();
+}
+
+hipError_t lsm_group_finalize(hipStream_t st, const SeqGroupArgs& g, int K)
+{
+    hipLaunchKernelGGL(lsm_finalize_group_kernel, dim3(1, K), dim3(kBlock), 0, st, g);
     return hipGetLastError();
 }
 
