@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define OMC_ABI_VERSION 13
+#define OMC_ABI_VERSION 14
 
 typedef struct omc_ctx omc_ctx;
 
@@ -135,6 +135,8 @@ int omc_memcpy_d2h(omc_ctx* ctx, void* dst, const void* src, size_t bytes);
  * events, so a sequence yields several samples of the per-kernel times; 0 = default: the first pricing only),
  * "seq_step_k" / "seq_two_pass_k" (omc_price_american_seq: pricings per shared launch of the per-step flows / per group
  * of the two-pass flow; see omc_seq_step_width and omc_seq_group_width),
+ * "chain_fused" / "chain_k" (omc_price_american_chain: 1 / 0 (default) = the fused chain sweeps or the single-strike sweeps per
+ * entry; entries per fused launch, -1 = default, 1 .. 16; see omc_chain_width),
  * "alloc_limit" (PER PROCESS, bytes; 0 = none: no single buffer of the library -- path matrix, workspace, row scratch --
  * may grow beyond it; a larger request fails like a hipMalloc that found no room, code 2 = hipErrorOutOfMemory.  A
  * budget for a card shared with other tenants; on a distributed context such a rank-local failure is reported on
@@ -667,6 +669,47 @@ int omc_seq_step_width(omc_ctx* ctx, const omc_params* p, int n);
  * every other flow: one pricing at a time, as before.  This returns the K of the run that starts at p[0] (1 = not
  * grouped, 0 = invalid arguments). */
 int omc_seq_group_width(omc_ctx* ctx, const omc_params* p, int n);
+
+/* ---- a whole option chain from one set of paths ------------------------------------------- */
+/* n quotes of ONE expiry -- strikes and sides in e[], everything else in p (p->K and p->is_put are ignored) -- priced
+ * from one generator launch and one path matrix: the paths depend on neither the strike nor the side.  Two-pass flow
+ * (p->semantics = OMC_SEM_TWO_PASS), antithetic pairs (p->antithetic = 1), GBM or Heston, one GPU.
+ * THE CONTRACT: res[i] equals omc_price_american(ctx, p with K = e[i].K and is_put = e[i].is_put, ...) bit for bit --
+ * price, sum, sumsq, std, zero_prob, every count and `folded` -- and slice i of betas_out ([n][n_steps+1][4], host, may
+ * be NULL) equals the fits that single call makes (rows 0 and n_steps zero, as omc_price_american_greeks returns them),
+ * whatever else the chain holds, in whatever order, whatever omc_chain_width says.  Storage is chosen as by the single
+ * call (option "fold_antithetic"); on folded storage every entry has its own fold table cK_j[t] = c0_j g^t.
+ * Routes: FUSED (option "chain_fused" = 1; GBM on folded storage with "pass2_tables" on, n_steps >= 2):
+ * entries are split by side and into launches of up to omc_chain_width entries whose two sweeps read every stored spot
+ * once -- conversion to float64 and the reciprocal behind the partner's moneyness once per spot -- and form every
+ * entry's sums in the tile, block and slot geometry of the single kernels; UNFUSED (Heston, full storage,
+ * "pass2_tables" = 0, and the default, "chain_fused" = 0): the single-strike sweeps per entry on the shared matrix.  Either way the
+ * pass-1 reductions, table builds and finalizes of up to 16 entries share one launch each.
+ * Timings: res[i].ms_* repeat the chain's whole-call times, res[i].timed is 1 for i = 0 only; info (may be NULL): the
+ * route taken, the number of sweep launches per pass, and the phases -- ms_paths the generator, ms_pass1 the pass-1
+ * sweeps + reductions, ms_pass2 the table builds + pass-2 sweeps + finalizes, ms_total from the first launch to the
+ * last completion (it also holds the entries' fold tables, which every call builds anew in front of the generator).
+ * Errors: those of omc_price_american for p (nothing is launched); -7 null e / res; -3 n < 1 or n > 256; -4 an entry
+ * whose K is not finite and positive or whose is_put is not 0 / 1, or p->semantics != 2; -15 p->antithetic == 0;
+ * -10 a context with a communicator or an all-reduce hook.
+ * Options: "chain_fused" (0 = default: unfused -- 8 quotes at 1M paths x 252 steps in 1.99 ms against 3.08 ms as a
+ * sequence; 1 = fused: measured 0.3 - 5.5 % slower than unfused at the sizes of DESIGN.md 13.4, kept as an option), "chain_k" (entries per fused launch at most: -1 = default, 1 .. 16;
+ * it can only lower omc_chain_width). */
+typedef struct {
+    double K;
+    int32_t is_put, reserved;
+} omc_chain_entry;
+typedef struct {
+    int32_t folded, fused, n_launch_groups, reserved;
+    double ms_paths, ms_pass1, ms_pass2, ms_total;
+} omc_chain_info;
+#define OMC_CHAIN_MAX 256
+int omc_price_american_chain(omc_ctx* ctx, const omc_params* p, const omc_chain_entry* e, int n, omc_result* res,
+                             double* betas_out, omc_chain_info* info);
+/* entries per fused launch for a chain of n entries like p: 4, 2 or 1 (the fused pass 2 keeps every entry's exercise
+ * state in registers and its tables in LDS: 4 up to 4.2M paths, 2 beyond, where a thread takes four columns); 1 also
+ * where the chain takes the unfused route; 0 = invalid arguments */
+int omc_chain_width(omc_ctx* ctx, const omc_params* p, int n);
 
 /* ---- many small pricings in one go ------------------------------------------------------- */
 /* replaces the curve loops compute_curve_for_S0 (options_model_3.py:697-713, Options_model.py:

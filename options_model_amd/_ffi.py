@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _build
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 SEMANTICS = {"reference": 0, "textbook": 1, "two_pass": 2}
 MODELS = {"gbm": 0, "heston": 1}
@@ -91,6 +91,20 @@ class Bounds(C.Structure):
                 ("ms_fit", C.c_double), ("ms_lower", C.c_double), ("ms_upper", C.c_double), ("ms_total", C.c_double)]
 
 
+class ChainEntry(C.Structure):
+    """omc_chain_entry: strike and side of one quote of a chain (omc_price_american_chain)."""
+    _fields_ = [("K", C.c_double), ("is_put", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ChainInfo(C.Structure):
+    """omc_chain_info: storage and route of a chain, its sweep launches per pass and its phase times."""
+    _fields_ = [("folded", C.c_int32), ("fused", C.c_int32), ("n_launch_groups", C.c_int32), ("reserved", C.c_int32),
+                ("ms_paths", C.c_double), ("ms_pass1", C.c_double), ("ms_pass2", C.c_double), ("ms_total", C.c_double)]
+
+
+CHAIN_MAX = 256
+
+
 class MlpJob(C.Structure):
     """omc_mlp_job: one network of a batch trained side by side (omc_mlp_train_epoch_batch)."""
     _fields_ = [("data", C.c_void_p), ("n_rows", C.c_int64), ("batch", C.c_int64),
@@ -149,6 +163,9 @@ SIGNATURES = {
     "omc_price_american_seq": (C.c_int, [_P, C.POINTER(Params), _I, C.POINTER(Result)]),
     "omc_seq_step_width": (C.c_int, [_P, C.POINTER(Params), _I]),
     "omc_seq_group_width": (C.c_int, [_P, C.POINTER(Params), _I]),
+    "omc_price_american_chain": (C.c_int, [_P, C.POINTER(Params), C.POINTER(ChainEntry), _I, C.POINTER(Result), _P,
+                                           C.POINTER(ChainInfo)]),
+    "omc_chain_width": (C.c_int, [_P, C.POINTER(Params), _I]),
     "omc_price_american_batch": (C.c_int, [_P, C.POINTER(Params), _I, C.POINTER(Result)]),
     "omc_price_european_batch": (C.c_int, [_P, C.POINTER(Params), _I, C.POINTER(Result)]),
     "omc_price_american_contnet_batch": (C.c_int, [_P, C.POINTER(Params), _I, _I, _I, _D, C.POINTER(C.c_uint64),
@@ -862,6 +879,35 @@ class Context:
         plist = list(params_list)
         arr = (Params * len(plist))(*plist)
         return int(self.lib.omc_seq_group_width(self.handle, arr, len(plist)))
+
+    def price_american_chain(self, params: Params, strikes, is_put=True, want_betas=False):
+        """A whole chain of one expiry from one set of paths (omc_price_american_chain) -> (list of result dicts, info dict).
+        strikes: the entries' strikes; is_put: one flag for all or one per strike; params.K / params.is_put are ignored.
+        Entry i carries the bits of price_american(params with strikes[i], is_put[i]); want_betas adds its fits
+        [n_steps+1][4] as "betas"."""
+        ks = [float(k) for k in strikes]
+        n = len(ks)
+        sides = [int(bool(is_put))] * n if isinstance(is_put, (bool, int, np.integer)) else [int(bool(s)) for s in is_put]
+        if len(sides) != n:
+            raise ValueError("one side per strike.")
+        ent = (ChainEntry * max(n, 1))()
+        for i in range(n):
+            ent[i].K, ent[i].is_put = ks[i], sides[i]
+        res = (Result * max(n, 1))()
+        info = ChainInfo()
+        N = int(params.n_steps)
+        bo = np.zeros((max(n, 1), N + 1, 4)) if want_betas else None
+        _check(self.lib, self.lib.omc_price_american_chain(self.handle, C.byref(params), ent, n, res,
+                                                            bo.ctypes.data if bo is not None else None, C.byref(info)))
+        out = [res[i].as_dict() for i in range(n)]
+        if want_betas:
+            for i in range(n):
+                out[i]["betas"] = bo[i]
+        return out, {k: getattr(info, k) for k, _ in ChainInfo._fields_ if k != "reserved"}
+
+    def chain_width(self, params: Params, n: int) -> int:
+        """Entries per fused launch of a chain of n entries like params (omc_chain_width; 1 = unfused route, 0 = invalid)."""
+        return int(self.lib.omc_chain_width(self.handle, C.byref(params), int(n)))
 
     def price_american_batch(self, params_list):
         return self._batch(self.lib.omc_price_american_batch, list(params_list))

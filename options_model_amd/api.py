@@ -202,6 +202,67 @@ def price_american_option(S0, K, r, sigma, T, n_paths, n_steps, model="GBM", opt
 
 
 @dataclass
+class ChainResult:
+    """price_american_chain: one PriceResult per quote, filled as price_american_option fills it."""
+    entries: list
+    strikes: list
+    option_types: list
+    timings_ms: dict = field(default_factory=dict)  # whole chain: paths, pass1, pass2, total
+    info: dict = field(default_factory=dict)        # folded, fused, n_launch_groups
+
+    def __len__(self):
+        return len(self.entries)
+
+    def __getitem__(self, i):
+        return self.entries[i]
+
+
+def price_american_chain(S0, strikes, r, sigma, T, n_paths, n_steps, option_types="put", model="GBM", heston_params=None,
+                         heston_scheme="reference", seed=42, stream=0, device=None, ctx=None) -> ChainResult:
+    """Every quote of one expiry -- `strikes`, each a put or a call (`option_types`: one string for all, or one per
+    strike) -- from ONE set of paths (omc_price_american_chain): two-pass flow, polynomial regressor, antithetic pairs,
+    one GPU.  entries[i] equals price_american_option(S0, strikes[i], ..., option_type=option_types[i]) bit for bit."""
+    model_l = str(model).lower()
+    if model_l not in ("gbm", "heston"):
+        raise ValueError("model must be 'GBM' or 'Heston'.")
+    try:
+        ks = [float(k) for k in strikes]
+    except TypeError:
+        raise ValueError("strikes must be a sequence of numbers.") from None
+    if not ks:
+        raise ValueError("strikes must not be empty.")
+    if len(ks) > _ffi.CHAIN_MAX:
+        raise ValueError(f"a chain has at most {_ffi.CHAIN_MAX} entries.")
+    types = [option_types] * len(ks) if isinstance(option_types, str) else list(option_types)
+    if len(types) != len(ks):
+        raise ValueError("option_types must be one string or one per strike.")
+    for k, ot in zip(ks, types):
+        if not (math.isfinite(k) and k > 0):
+            raise ValueError("S0, K, T must be positive.")
+        _validate(S0, k, T, r, sigma, n_paths, n_steps, ot, need_sigma=(model_l == "gbm"))
+    M = int(n_paths) // 2 * 2
+    if M <= 0:
+        raise ValueError("num_simulations and num_time_steps must be positive integers.")
+    c = ctx or _ffi.default_context(device)
+    p = _ffi.make_params(model=model_l, is_put=True, semantics="two_pass", antithetic=True, heston_scheme=heston_scheme,
+                         n_paths=M, n_steps=int(n_steps), S0=S0, K=ks[0], r=r, sigma=sigma or 0.0, T=T, seed=seed,
+                         stream=stream, **heston_defaults(sigma, heston_params))
+    outs, info = c.price_american_chain(p, ks, [ot == "put" for ot in types])
+    entries = []
+    for out, ot in zip(outs, types):
+        var = max(out["sumsq"] / M - out["price"] ** 2, 0.0)
+        entries.append(PriceResult(price=out["price"], stderr=math.sqrt(var / M), std=out["std"],
+                                   zero_prob=out["zero_prob"], n_paths=M, n_exercised=out["n_exercised"],
+                                   sum_nitm=out["sum_nitm"], model=model_l, semantics="two_pass", option_type=ot,
+                                   timings_ms=dict(paths=out["ms_paths"], lsm=out["ms_lsm"], total=out["ms_total"])))
+    return ChainResult(entries=entries, strikes=ks, option_types=types,
+                       timings_ms=dict(paths=info["ms_paths"], pass1=info["ms_pass1"], pass2=info["ms_pass2"],
+                                       total=info["ms_total"]),
+                       info=dict(folded=bool(info["folded"]), fused=bool(info["fused"]),
+                                 n_launch_groups=info["n_launch_groups"]))
+
+
+@dataclass
 class GreeksResult:
     """price_american_greeks: the frozen-policy pathwise Greeks of the two-pass poly estimator, in raw units (per unit
     S0, S0^2, sigma, r; theta = -dV/dT per year).  Heston: vega, rho, theta are NaN."""

@@ -1,6 +1,6 @@
 // omc_api.hip -- the C ABI of libomc.so (include/omc.h): the helpers the entry points share (argument checks,
 // launch sequencing, HIP-event timing), contexts, memory, options, the all-reduce hook, RCCL and the direct peer
-// exchange.  The other entry points live in omc_api_{price,seq,batch,nn}.hip; omc_ctx.h is their common ground.
+// exchange.  The other entry points live in omc_api_{price,seq,batch,nn,bounds,chain}.hip; omc_ctx.h is their common ground.
 // No kernel code here.
 #include <sched.h>
 
@@ -91,6 +91,26 @@ int wait_stream(omc_ctx* c)
     return 0;
 }
 
+// The context's discount table D[k] = exp(-r dt k), k = 0 .. N, for (N, r, T).
+int ensure_discounts(omc_ctx* c, int N, double r, double T, double** D)
+{
+    int rc;
+    if ((rc = c->D.ensure(sizeof(double) * (size_t)(N + 1)))) return rc;
+    *D = (double*)c->D.p;
+    // discount table computed on the host in double (same libm exp as the oracle); it only
+    // depends on (N, r, T), so consecutive pricings of one contract reuse the device copy
+    if (c->D_N != N || c->D_r != r || c->D_T != T || c->D_ptr != *D) {
+        c->hD.resize((size_t)N + 1);
+        const double dt = T / N;
+        for (int k = 0; k <= N; ++k) c->hD[(size_t)k] = std::exp(-r * dt * (double)k);
+        HIP_TRY(hipMemcpyAsync(*D, c->hD.data(), sizeof(double) * (size_t)(N + 1),
+                               hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));  // hD is pageable host memory
+        c->D_N = N; c->D_r = r; c->D_T = T; c->D_ptr = *D;
+    }
+    return 0;
+}
+
 // workspace for the backward induction on M paths x N steps
 int prepare_lsm(omc_ctx* c, int64_t M, int N, double r, double T, bool two_pass,
                 bool clear_tables, omc::LsmWorkspace* w)
@@ -99,7 +119,6 @@ int prepare_lsm(omc_ctx* c, int64_t M, int N, double r, double T, bool two_pass,
     if ((rc = c->sx.ensure(sizeof(float) * (size_t)M))) return rc;
     if ((rc = c->tex.ensure(sizeof(int32_t) * (size_t)M))) return rc;
     if ((rc = c->ex.ensure(sizeof(float) * (size_t)M + 16))) return rc;
-    if ((rc = c->D.ensure(sizeof(double) * (size_t)(N + 1)))) return rc;
     if ((rc = c->part.ensure(sizeof(double) * 2 * 8 * omc::kMaxLsmBlocks))) return rc;
     if ((rc = c->gmom.ensure(sizeof(double) * 8 * (size_t)(N + 1)))) return rc;
     if ((rc = c->betas.ensure(sizeof(double) * 4 * (size_t)(N + 1)))) return rc;
@@ -121,22 +140,11 @@ int prepare_lsm(omc_ctx* c, int64_t M, int N, double r, double T, bool two_pass,
     w->sx = (float*)c->sx.p;
     w->tex = (int32_t*)c->tex.p;
     w->live = (float*)c->ex.p;
-    w->D = (double*)c->D.p;
     w->part = (double*)c->part.p;
     w->gmom = (double*)c->gmom.p;
     w->betas = (double*)c->betas.p;
     w->result = (double*)c->result.p;
-    // discount table computed on the host in double (same libm exp as the oracle); it only
-    // depends on (N, r, T), so consecutive pricings of one contract reuse the device copy
-    if (c->D_N != N || c->D_r != r || c->D_T != T || c->D_ptr != w->D) {
-        c->hD.resize((size_t)N + 1);
-        const double dt = T / N;
-        for (int k = 0; k <= N; ++k) c->hD[(size_t)k] = std::exp(-r * dt * (double)k);
-        HIP_TRY(hipMemcpyAsync(w->D, c->hD.data(), sizeof(double) * (size_t)(N + 1),
-                               hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));  // hD is pageable host memory
-        c->D_N = N; c->D_r = r; c->D_T = T; c->D_ptr = w->D;
-    }
+    if ((rc = ensure_discounts(c, N, r, T, &w->D))) return rc;
     // gmom rows 1..N-1, betas rows 1..N-1 and result[0..7] are fully written by the kernels of
     // every flow before anything reads them; rows 0 and N are only ever copied out, so they
     // are cleared just when the caller asked for the tables.
@@ -698,6 +706,8 @@ int omc_set_option(omc_ctx* c, const char* key, int64_t value)
     else if (!strcmp(key, "seq_event_stride")) c->seq_event_stride = value > 0 ? (int)value : 0;
     else if (!strcmp(key, "seq_step_k")) c->seq_step_k = value < 0 ? -1 : (int)(value > 32 ? 32 : value);
     else if (!strcmp(key, "seq_two_pass_k")) c->seq_two_pass_k = value < 0 ? -1 : (int)(value > 32 ? 32 : value);
+    else if (!strcmp(key, "chain_fused")) c->chain_fused = value ? 1 : 0;
+    else if (!strcmp(key, "chain_k")) c->chain_k = value < 1 ? -1 : (int)(value > 16 ? 16 : value);
     else if (!strcmp(key, "seq_step_wgs")) c->seq_step_wgs = value > 0 ? (int)value : 0;
     else if (!strcmp(key, "p2p_exchange")) c->p2p_use = value ? 1 : 0;
     else if (!strcmp(key, "p2p_deadline_ms") || !strcmp(key, "p2p_first_deadline_ms")) {

@@ -93,6 +93,7 @@ int bind(omc_ctx* c);
 int bind_in(omc_ctx* c);
 int wait_stream(omc_ctx* c);
 int prepare_lsm(omc_ctx* c, int64_t M, int N, double r, double T, bool two_pass, bool clear_tables, omc::LsmWorkspace* w);
+int ensure_discounts(omc_ctx* c, int N, double r, double T, double** D);  // the context's table exp(-r dt k), k = 0 .. N
 int allreduce(omc_ctx* c, double* dptr, int count);
 int allreduce_host(omc_ctx* c, double* dev, double* host, int n);
 bool p2p_active(const omc_ctx* c);
@@ -200,6 +201,10 @@ struct omc_ctx {
     DevBuf gk_part, gk_res;  // omc_price_american_greeks: per-workgroup partials, reduced sums
     DevBuf bar_part, bar_res;  // omc_price_barrier: the generator's per-workgroup partials, reduced sums
     DevBuf bnd;                // omc_price_american_bounds: outer paths, Q^ table, samples, tables, partials, sums
+    // omc_price_american_chain: per entry of a group [part1 | gmom | betas | crit | part]; the entries' fold tables + c0
+    DevBuf chain_state, chain_fold;
+    int chain_fused = 0;       // option "chain_fused": 0 = default, the single-strike sweeps per entry; 1 = the fused sweeps
+    int chain_k = -1;          // option "chain_k": entries per fused launch at most (-1: what omc_chain.hip allows)
     struct FoldKey { int N = -1; double c0 = 0, g = 0; } fold_key[2];
     int world = 1;  // ranks whose sums the hook / communicator adds up (equal shards)
     omc_allreduce_fn hook = nullptr;

@@ -167,6 +167,14 @@ hipError_t lsm_reduce_pass1(hipStream_t st, const LsmWorkspace& w, int64_t ntile
 bool lsm_pass2_tables(const LsmProblem& p, const LsmWorkspace& w, bool write_state);
 hipError_t lsm_pass2_sweep(hipStream_t st, const LsmProblem& p, const LsmWorkspace& w, bool write_state,
                            bool solve_from_moments, int* nblk);
+// launch geometry of the two sweeps on the folded matrix of p (p.fold_cK set): pass 1 -- 16-byte loads or scalar, tiles
+// per wave, tiles per step, steps per workgroup; pass 2 -- columns per thread asked for and taken (vec2), workgroups
+struct FoldGeometry {
+    bool v4 = false;
+    int tpw = 2, tchunk = 32, fvec = 2, vec2 = 1, nblk = 0;
+    int64_t ntiles = 0;
+};
+FoldGeometry lsm_fold_geometry(const LsmProblem& p);
 // ---- the two-pass flow's latency-bound launches for K pricings of one geometry at once (omc_price_american_seq):
 // pass-1 reduction, table build and finalize with the pricing on grid.y.  Thin entry points around the bodies of the
 // single launches, so every pricing keeps the bits of its own.  The per-pricing pointers travel BY VALUE in the

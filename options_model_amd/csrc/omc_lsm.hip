@@ -370,6 +370,31 @@ hipError_t lsm_fold_table(hipStream_t st, double* cK, int N, double c0, double g
     return hipGetLastError();
 }
 
+// The launch geometry of the two sweeps on the folded matrix of `p` (declared in omc_kernels.h: the chain sweeps of
+// omc_chain.hip form their sums in the very same tiles, blocks and slots).
+FoldGeometry lsm_fold_geometry(const LsmProblem& p)
+{
+    FoldGeometry g;
+    const int64_t P = p.M / 2;
+    g.v4 = (P % 4) == 0 && (p.ld % 4) == 0 && ((uintptr_t)p.S % 16) == 0;
+    static const int tpw_env = getenv("OMC_FOLD_TPW") ? atoi(getenv("OMC_FOLD_TPW")) : 0;
+    g.tpw = (g.v4 && (tpw_env == 1 || tpw_env == 4)) ? tpw_env : 2;
+    const int64_t per_wave = 64 * (int64_t)(g.v4 ? 4 : 1) * g.tpw;
+    g.ntiles = (P + per_wave - 1) / per_wave;
+    // Steps per workgroup: the folded sweep is bound by its float64 arithmetic, not by the rows it reads, so what counts is
+    // that every CU stays busy to the end -- many short workgroups (measured at C2, 245 tile-workgroups: chunks of 16-32
+    // steps 0.145-0.147 ms, 63 steps 0.156, 84 steps -- one resident round -- 0.162, 126 steps 0.183; 8M paths: 32).
+    static const int tch_env = getenv("OMC_PASS1_TCHUNK") ? atoi(getenv("OMC_PASS1_TCHUNK")) : 0;
+    g.tchunk = (tch_env >= 2 && tch_env <= kFoldMaxChunk) ? tch_env : 32;
+    static const int fvec_env = getenv("OMC_FOLD_P2_VEC") ? atoi(getenv("OMC_FOLD_P2_VEC")) : 0;
+    // columns per thread of the folded pass 2: 2 (8-byte loads, twice the threads) until the 16-byte form alone fills the
+    // chip with workgroups (measured: C2's 0.5M columns 0.131 against 0.136 ms, C3's 4M columns 1.026 against 1.008)
+    g.fvec = (fvec_env == 1 || fvec_env == 2 || fvec_env == 4) ? fvec_env : (P >= (int64_t(1) << 21) ? 4 : 2);
+    g.nblk = lsm_step_blocks(P * (4 / g.fvec));
+    g.vec2 = g.v4 && g.fvec == 4 ? 4 : (g.v4 && g.fvec == 2 ? 2 : 1);
+    return g;
+}
+
 // pass 1 on the folded matrix: P = M / 2 stored columns, two tiles of 64 x VEC columns per wave and step (= 1,024 paths, as
 // in the full sweep; OMC_FOLD_TPW = 1 | 4 for experiments)
 static hipError_t lsm_pass1_sweep_fold(hipStream_t st, const LsmProblem& p, const LsmWorkspace& w, int64_t* ntiles)
@@ -378,17 +403,12 @@ static hipError_t lsm_pass1_sweep_fold(hipStream_t st, const LsmProblem& p, cons
     const int64_t P = p.M / 2;
     a.S = p.S; a.ld = p.ld; a.M = P; a.N = p.N; a.is_put = p.is_put;
     a.K = p.K; a.invK = 1.0 / p.K; a.D = w.D; a.part1 = w.part1; a.cK = p.fold_cK;
-    const bool v4 = (P % 4) == 0 && (p.ld % 4) == 0 && ((uintptr_t)p.S % 16) == 0;
-    static const int tpw_env = getenv("OMC_FOLD_TPW") ? atoi(getenv("OMC_FOLD_TPW")) : 0;
-    const int tpw = (v4 && (tpw_env == 1 || tpw_env == 4)) ? tpw_env : 2;
-    const int64_t per_wave = 64 * (int64_t)(v4 ? 4 : 1) * tpw;
-    a.ntiles = (P + per_wave - 1) / per_wave;
-    // Steps per workgroup: the folded sweep is bound by its float64 arithmetic, not by the rows it reads, so what counts is
-    // that every CU stays busy to the end -- many short workgroups (measured at C2, 245 tile-workgroups: chunks of 16-32
-    // steps 0.145-0.147 ms, 63 steps 0.156, 84 steps -- one resident round -- 0.162, 126 steps 0.183; 8M paths: 32).
-    static const int tch_env = getenv("OMC_PASS1_TCHUNK") ? atoi(getenv("OMC_PASS1_TCHUNK")) : 0;
+    const FoldGeometry geo = lsm_fold_geometry(p);
+    const bool v4 = geo.v4;
+    const int tpw = geo.tpw;
+    a.ntiles = geo.ntiles;
     const int64_t wgs_x = (a.ntiles + 3) / 4;
-    a.tchunk = (tch_env >= 2 && tch_env <= kFoldMaxChunk) ? tch_env : 32;
+    a.tchunk = geo.tchunk;
     const dim3 grid((unsigned)wgs_x, (unsigned)((p.N - 1 + a.tchunk - 1) / a.tchunk));
     if (w.ev_p1_begin) (void)hipEventRecord(w.ev_p1_begin, st);
     if (v4 && tpw == 1) {
@@ -493,11 +513,9 @@ hipError_t lsm_pass2_sweep(hipStream_t st, const LsmProblem& p, const LsmWorkspa
         a.gmom = w.gmom;
         a.betas_out = w.betas;
     }
-    static const int fvec_env = getenv("OMC_FOLD_P2_VEC") ? atoi(getenv("OMC_FOLD_P2_VEC")) : 0;
-    // columns per thread of the folded pass 2: 2 (8-byte loads, twice the threads) until the 16-byte form alone fills the
-    // chip with workgroups (measured: C2's 0.5M columns 0.131 against 0.136 ms, C3's 4M columns 1.026 against 1.008)
-    const int fvec = (fvec_env == 1 || fvec_env == 2 || fvec_env == 4) ? fvec_env : ((p.M / 2) >= (int64_t(1) << 21) ? 4 : 2);
-    const int nblk = lsm_step_blocks(p.fold_cK ? (p.M / 2) * (4 / fvec) : p.M);
+    const FoldGeometry geo = p.fold_cK ? lsm_fold_geometry(p) : FoldGeometry{};
+    const int fvec = geo.fvec;
+    const int nblk = p.fold_cK ? geo.nblk : lsm_step_blocks(p.M);
     a.nblk = nblk; a.pstride = kPStride;
     const size_t dyn = sizeof(double) * 4 * (size_t)(p.N + 1);
     const bool v4 = vec4_ok(p);
@@ -512,7 +530,7 @@ hipError_t lsm_pass2_sweep(hipStream_t st, const LsmProblem& p, const LsmWorkspa
         if (write_state) return hipErrorInvalidValue;
         a.M = p.M / 2;
         a.cK = p.fold_cK;
-        const bool f4 = (a.M % 4) == 0 && (p.ld % 4) == 0 && ((uintptr_t)p.S % 16) == 0;
+        const bool f4 = geo.v4;
         auto launch = [&](auto vec) {
             constexpr int V = decltype(vec)::value;
             if (tab) {

@@ -599,13 +599,17 @@ __device__ __forceinline__ void lsm_pass1_body(Pass1Args a)
 // partner rows exist and what they are worth; the CPU restatement the tests check against repeats them (orc_lsm_two_pass_folded).
 // (1 / S_t: v_rcp_f64 is good to 2^-23; ONE Newton step takes it to 2^-46 = 1.4e-14 relative -- the partner's moneyness is
 //  then 1.4e-14 (absolute) from the exactly divided one, nine orders below the float32 rounding of the spot it is made from)
-__device__ __forceinline__ double fold_u(double cK_t, float s)
+// (fold_rcp: the reciprocal alone -- it depends on the spot only, so a sweep that prices several strikes from one spot forms
+//  it once and every strike's fold_u_rcp has the bits of its fold_u)
+__device__ __forceinline__ double fold_rcp(float s)
 {
     const double x = (double)s;
     double r = __builtin_amdgcn_rcp(x);
     r = fma(fma(-x, r, 1.0), r, r);
-    return fma(cK_t, r, -1.0);
+    return r;
 }
+__device__ __forceinline__ double fold_u_rcp(double cK_t, double rcp_s) { return fma(cK_t, rcp_s, -1.0); }
+__device__ __forceinline__ double fold_u(double cK_t, float s) { return fold_u_rcp(cK_t, fold_rcp(s)); }
 __device__ __forceinline__ double fold_pay(double u, double K, int is_put) { return is_put ? -K * u : K * u; }
 constexpr int kFoldMaxChunk = 64;  // steps per workgroup of the folded pass 1, at most
 
