@@ -326,6 +326,37 @@ int enqueue_lsm(omc_ctx* c, const omc::LsmProblem& p, const omc::LsmWorkspace& w
     return 0;
 }
 
+// ---- groups of two-pass pricings that share their small launches (omc_ctx.h)
+GroupLayout::GroupLayout(int64_t M, int N)
+{
+    const size_t n1 = (size_t)N + 1;
+    o_gmom = up256(sizeof(double) * 8 * n1 * omc::lsm_part1_tiles(M));
+    o_betas = o_gmom + up256(sizeof(double) * 8 * n1);
+    o_crit = o_betas + up256(sizeof(double) * 4 * n1);
+    o_part = o_crit + up256(sizeof(uint32_t) * 8 * n1);
+    per = o_part + up256(sizeof(double) * 2 * 8 * omc::kMaxLsmBlocks);
+}
+
+TwoPassGroup::TwoPassGroup(const GroupLayout& L_, void* state_, const omc::LsmWorkspace& w0_, bool tables_)
+    : L(L_), state((char*)state_), w0(w0_), tables(tables_)
+{
+    g.irr_every = w0.crit_irr_every;
+}
+
+// member K (at most kSeqGroupMax) of the group: its buffers carved from the state, its slot of the argument block
+void TwoPassGroup::add(const omc::LsmProblem& p, double* result)
+{
+    const int k = K++;
+    char* st = state + L.per * (size_t)k;
+    omc::LsmWorkspace& wk = w[k] = w0;
+    wk.part1 = (double*)st; wk.gmom = (double*)(st + L.o_gmom); wk.betas = (double*)(st + L.o_betas);
+    wk.crit = tables ? (uint32_t*)(st + L.o_crit) : nullptr; wk.part = (double*)(st + L.o_part);
+    wk.result = result;
+    prob[k] = p;
+    g.slot[k] = omc::lsm_group_slot(p, wk);
+    g.N = p.N;
+}
+
 // after a wait: did a direct exchange give up (its bounded poll ran out) -- on this rank (its sticky error word; the
 // sums are NaN then) or on ANY rank (slot 6 of the all-reduced result sums of the n pricings just waited for)?
 // Every rank of the job returns the error, not only the one whose deadline ran out.

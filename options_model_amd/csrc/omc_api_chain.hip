@@ -7,6 +7,8 @@
 //         ONE launch: the table builds   gmom[j] -> betas[j], crit[j]        (folded storage with "pass2_tables")
 //         pass-2 sweeps -> part[j]       fused / per entry, as above
 //         ONE launch: the finalizes      part[j], gmom[j] -> result slot of the entry
+// A group is a TwoPassGroup (omc_ctx.h), as in the grouped sequences: it carves the entries' buffers from the context's
+// group state and issues the three shared launches, every slot carrying its entry's own fold table.
 // The unfused sweeps ARE the single pricing's launches (lsm_pass1_sweep, lsm_pass2_sweep), the three shared launches run the
 // bodies of its small kernels, and the fused sweeps (omc_chain.hip) form every entry's sums in the single kernels' geometry:
 // res[i] carries the bits of omc_price_american(p with e[i]) on every route.  One stream, no host wait before the end.
@@ -18,20 +20,6 @@
 using namespace omc::abi;
 
 namespace {
-
-// device bytes one entry of a group owns: [part1 | gmom | betas | crit | part]
-struct ChainLayout {
-    size_t o_gmom, o_betas, o_crit, o_part, per;
-    ChainLayout(int64_t M, int N)
-    {
-        const size_t n1 = (size_t)N + 1;
-        o_gmom = up256(sizeof(double) * 8 * n1 * omc::lsm_part1_tiles(M));
-        o_betas = o_gmom + up256(sizeof(double) * 8 * n1);
-        o_crit = o_betas + up256(sizeof(double) * 4 * n1);
-        o_part = o_crit + up256(sizeof(uint32_t) * 8 * n1);
-        per = o_part + up256(sizeof(double) * 2 * 8 * omc::kMaxLsmBlocks);
-    }
-};
 
 int pow2_floor(int x)
 {
@@ -114,11 +102,11 @@ int omc_price_american_chain(omc_ctx* c, const omc_params* p, const omc_chain_en
     const bool fused = width > 0;
     const bool tables = folded && c->pass2_tables;  // lsm_pass2_tables of every entry
     const int G = std::min(n, omc::kChainGroupMax);
-    const ChainLayout L(M, N);
-    if ((rc = c->chain_state.ensure(L.per * (size_t)G))) return rc;
+    const GroupLayout L(M, N);
+    if ((rc = c->gstate.ensure(L.per * (size_t)G))) return rc;
     if ((rc = c->seq_local.ensure(sizeof(double) * 8 * (size_t)n))) return rc;
     double* dres = (double*)c->seq_local.p;
-    // (none of the single pricing's workspace: every entry's buffers are in chain_state, no per-path state is written)
+    // (none of the single pricing's workspace: every entry's buffers are in the group state, no per-path state is written)
     omc::LsmWorkspace w0;
     memset(&w0, 0, sizeof w0);
     w0.gstride = 8;
@@ -153,29 +141,16 @@ int omc_price_american_chain(omc_ctx* c, const omc_params* p, const omc_chain_en
     int launches = 0;
     for (int gi = 0; gi < ngroups; ++gi) {
         const int i0 = gi * G, Kb = std::min(G, n - i0);
-        omc::SeqGroupArgs g;
-        omc::ChainCritArgs cg;
-        memset(&g, 0, sizeof g);
-        memset(&cg, 0, sizeof cg);
-        omc::LsmProblem prob[omc::kChainGroupMax];
-        omc::LsmWorkspace w[omc::kChainGroupMax];
+        TwoPassGroup grp(L, c->gstate.p, w0, c->pass2_tables != 0);
+        const omc::LsmProblem* prob = grp.prob; const omc::LsmWorkspace* w = grp.w;  // the members, as add() leaves them
         for (int k = 0; k < Kb; ++k) {
             const omc_chain_entry& ek = e[i0 + k];
-            char* st = (char*)c->chain_state.p + L.per * (size_t)k;
-            w[k] = w0;
-            w[k].part1 = (double*)st; w[k].gmom = (double*)(st + L.o_gmom); w[k].betas = (double*)(st + L.o_betas);
-            w[k].crit = c->pass2_tables ? (uint32_t*)(st + L.o_crit) : nullptr;
-            w[k].part = (double*)(st + L.o_part);
-            w[k].result = dres + 8 * (size_t)(i0 + k);
-            prob[k] = omc::LsmProblem{S, ld, M, N, ek.is_put, ek.K, p->r, p->T};
-            prob[k].fold_cK = folded ? fold + fstride * (size_t)(i0 + k) : nullptr;
-            g.slot[k] = cg.slot[k] = omc::lsm_group_slot(prob[k], w[k]);
-            cg.cK[k] = prob[k].fold_cK;
+            omc::LsmProblem q{S, ld, M, N, ek.is_put, ek.K, p->r, p->T};
+            q.fold_cK = folded ? fold + fstride * (size_t)(i0 + k) : nullptr;
+            grp.add(q, dres + 8 * (size_t)(i0 + k));
             // rows 0 and N of the fits are only ever copied out (prepare_lsm's clear_tables)
             if (betas_out) HIP_TRY(hipMemsetAsync(w[k].betas, 0, sizeof(double) * 4 * n1, c->stream));
         }
-        g.N = cg.N = N;
-        g.irr_every = cg.irr_every = w0.crit_irr_every;
         // the fused launches of this group: entries of one side, in pieces of 4 / 2 / 1 up to the width
         struct Piece { int side, first, count; };
         std::vector<Piece> pieces;
@@ -206,20 +181,23 @@ int omc_price_american_chain(omc_ctx* c, const omc_params* p, const omc_chain_en
         };
         // ---- pass 1
         if (fused) {
-            for (const Piece& pc : pieces) HIP_TRY(omc::chain_pass1_sweep(c->stream, sweep_args(pc), prob[0], &g.ntiles));
+            for (const Piece& pc : pieces)
+                HIP_TRY(omc::chain_pass1_sweep(c->stream, sweep_args(pc), prob[0], &grp.g.ntiles));
         } else {
-            for (int k = 0; k < Kb; ++k) HIP_TRY(omc::lsm_pass1_sweep(c->stream, prob[k], w[k], &g.ntiles));
+            for (int k = 0; k < Kb; ++k) HIP_TRY(omc::lsm_pass1_sweep(c->stream, prob[k], w[k], &grp.g.ntiles));
         }
-        HIP_TRY(omc::lsm_group_reduce_pass1(c->stream, g, Kb));
+        HIP_TRY(grp.reduce_pass1(c->stream));
         HIP_TRY(hipEventRecord(c->ev_pool[2 * (size_t)gi], c->stream));
         // ---- pass 2
-        if (tables) HIP_TRY(omc::chain_crit_build(c->stream, cg, Kb));
+        if (tables) HIP_TRY(grp.build_tables(c->stream));
         if (fused) {
-            for (const Piece& pc : pieces) HIP_TRY(omc::chain_pass2_sweep(c->stream, sweep_args(pc), prob[0], &g.nblk));
+            for (const Piece& pc : pieces)
+                HIP_TRY(omc::chain_pass2_sweep(c->stream, sweep_args(pc), prob[0], &grp.g.nblk));
         } else {
-            for (int k = 0; k < Kb; ++k) HIP_TRY(omc::lsm_pass2_sweep(c->stream, prob[k], w[k], false, true, &g.nblk));
+            for (int k = 0; k < Kb; ++k)
+                HIP_TRY(omc::lsm_pass2_sweep(c->stream, prob[k], w[k], false, true, &grp.g.nblk));
         }
-        HIP_TRY(omc::lsm_group_finalize(c->stream, g, Kb));
+        HIP_TRY(grp.finalize(c->stream));
         HIP_TRY(hipEventRecord(c->ev_pool[2 * (size_t)gi + 1], c->stream));
         launches += fused ? (int)pieces.size() : Kb;
         if (betas_out)

@@ -369,6 +369,8 @@ int omc_seq_step_width(omc_ctx* c, const omc_params* p, int n)
 //     ONE launch: the K finalizes         part[k], gmom[k] -> result slot of the pricing
 // The three launches take the pricing from grid.y and run the bodies of the single launches (omc_lsm.hip), so res[i]
 // keeps the bits of omc_price_american(p[i]).  One stream, no host wait and no grid-wide barrier inside a group.
+// The members' buffers, workspaces, slots and the three launches are TwoPassGroup's (omc_ctx.h; shared with the option chain);
+// the sequence's own: a generator per member in front of its pass-1 sweep, the members' events, ONE fold table per run.
 // One card only: a distributed context all-reduces every pricing's moment table between its pass 1 and its fits.
 
 // pricing `q` can be a member of a group (the context is not distributed)
@@ -396,22 +398,11 @@ static int seq_group_run(const omc_ctx* c, const omc_params* p, int n)
     return run;
 }
 
-// device bytes one member of a group owns: its path matrix, and [part1 | gmom | betas | crit | part]
-struct SeqGroupLayout {
-    int64_t ld;
-    size_t sbytes, o_gmom, o_betas, o_crit, o_part, per;
-    SeqGroupLayout(int64_t M, int N)
-    {
-        const size_t n1 = (size_t)N + 1;
-        ld = padded_ld(M / 2);
-        sbytes = sizeof(float) * (size_t)ld * n1;
-        o_gmom = up256(sizeof(double) * 8 * n1 * omc::lsm_part1_tiles(M));
-        o_betas = o_gmom + up256(sizeof(double) * 8 * n1);
-        o_crit = o_betas + up256(sizeof(double) * 4 * n1);
-        o_part = o_crit + up256(sizeof(uint32_t) * 8 * n1);
-        per = o_part + up256(sizeof(double) * 2 * 8 * omc::kMaxLsmBlocks);
-    }
-};
+// bytes of one member's folded path matrix (its small buffers: GroupLayout)
+static size_t seq_group_matrix_bytes(const omc_params* p)
+{
+    return sizeof(float) * (size_t)padded_ld(p->n_paths / 2) * ((size_t)p->n_steps + 1);
+}
 
 // The width a run of `run` pricings like p[0] asks for.  Default (profiles/r08_seq_group_sweep.txt): sharing saves a
 // fixed ~35 us of small kernels per pricing, and the big kernels of a group run 2-3 % slower than back to back on one
@@ -433,8 +424,8 @@ static int seq_group_ideal(const omc_ctx* c, const omc_params* p, int run)
 // ... and what this card has room for: the byte budget of the per-step flows' resident matrices (seq_multi_fit)
 static int seq_group_fit(const omc_ctx* c, const omc_params* p, int k)
 {
-    const SeqGroupLayout L(p[0].n_paths, p[0].n_steps);
-    const int fit = (int)(seq_resident_budget(c, c->gS.cap + c->gstate.cap) / ((double)L.sbytes + (double)L.per));
+    const GroupLayout L(p[0].n_paths, p[0].n_steps);
+    const int fit = (int)(seq_resident_budget(c, c->gS.cap + c->gstate.cap) / ((double)seq_group_matrix_bytes(p) + (double)L.per));
     if (k > fit) k = fit;
     return k < 2 ? 1 : k;
 }
@@ -445,14 +436,15 @@ static int seq_group_reserve(omc_ctx* c, const omc_params* p, int run, int* K_ou
 {
     *K_out = 1;
     int K = seq_group_ideal(c, p, run);
-    const SeqGroupLayout L(p[0].n_paths, p[0].n_steps);
+    const GroupLayout L(p[0].n_paths, p[0].n_steps);
+    const size_t sbytes = seq_group_matrix_bytes(p);
     // (buffers that are large enough already need no look at the card's free memory: the query takes a quarter of a
     // millisecond during which the stream runs dry at the head of every sequence)
-    if (K >= 2 && (c->gS.cap < L.sbytes * (size_t)K || c->gstate.cap < L.per * (size_t)K)) K = seq_group_fit(c, p, K);
+    if (K >= 2 && (c->gS.cap < sbytes * (size_t)K || c->gstate.cap < L.per * (size_t)K)) K = seq_group_fit(c, p, K);
     // (a buffer that has to grow is freed first, while an earlier, smaller group of the same sequence may still be
     // running in it: hipFree waits for the device before it releases memory, so that group ends undisturbed)
     while (K >= 2) {
-        int rc = c->gS.ensure(L.sbytes * (size_t)K);
+        int rc = c->gS.ensure(sbytes * (size_t)K);
         if (!rc) rc = c->gstate.ensure(L.per * (size_t)K);
         if (!rc) break;
         if (rc != (int)hipErrorOutOfMemory && rc != (int)hipErrorMemoryAllocation) return rc;
@@ -468,51 +460,41 @@ static int enqueue_seq_group(omc_ctx* c, const omc_params* p, int i0, int Kb, do
     int rc;
     const int64_t M = p[i0].n_paths;
     const int N = p[i0].n_steps;
-    const SeqGroupLayout L(M, N);
+    const size_t sbytes = seq_group_matrix_bytes(&p[i0]);
     int64_t ld = 0;
     const double* cK = nullptr;
     if ((rc = plan_storage(c, &p[i0], 0, &ld, &cK))) return rc;  // the group's one fold table
     omc::LsmWorkspace w0;
     if ((rc = prepare_lsm(c, M, N, p[i0].r, p[i0].T, true, false, &w0))) return rc;  // discount table (+ the singles)
-    if (!cK || ld != L.ld || Kb > omc::kSeqGroupMax) return fail(-4, "a grouped two-pass sequence needs folded storage.");
-    omc::SeqGroupArgs g;
-    memset(&g, 0, sizeof g);
-    omc::LsmProblem prob[omc::kSeqGroupMax];
-    omc::LsmWorkspace w[omc::kSeqGroupMax];
+    if (!cK || ld != padded_ld(M / 2) || Kb > omc::kSeqGroupMax) return fail(-4, "a grouped two-pass sequence needs folded storage.");
+    TwoPassGroup grp(GroupLayout(M, N), c->gstate.p, w0, true);
     hipEvent_t* evs[omc::kSeqGroupMax];
-    int64_t ntiles = 0;
     for (int k = 0; k < Kb; ++k) {  // the event pool grows, and may move, HERE: the members' event sets are fetched
         hipEvent_t* grown = nullptr;  // below, once it no longer does
         if ((rc = pricing_events(c, i0 + k, &grown))) return rc;
     }
     for (int k = 0; k < Kb; ++k) {
         const omc_params& q = p[i0 + k];
-        float* S = (float*)((char*)c->gS.p + L.sbytes * (size_t)k);
-        char* st = (char*)c->gstate.p + L.per * (size_t)k;
-        w[k] = w0;
-        w[k].part1 = (double*)st; w[k].gmom = (double*)(st + L.o_gmom); w[k].betas = (double*)(st + L.o_betas);
-        w[k].crit = (uint32_t*)(st + L.o_crit); w[k].part = (double*)(st + L.o_part);
-        w[k].result = dst + 8 * (size_t)(i0 + k);
-        prob[k] = omc::LsmProblem{S, ld, M, N, q.is_put ? 1 : 0, q.K, q.r, q.T};
-        prob[k].fold_cK = cK;
+        float* S = (float*)((char*)c->gS.p + sbytes * (size_t)k);
+        omc::LsmProblem prob{S, ld, M, N, q.is_put ? 1 : 0, q.K, q.r, q.T};
+        prob.fold_cK = cK;
+        grp.add(prob, dst + 8 * (size_t)(i0 + k));
         if ((rc = pricing_events(c, i0 + k, &evs[k]))) return rc;
         if (evs[k]) {  // a timed pricing: events around ITS generator, pass-1 sweep and (below) pass-2 sweep
-            w[k].ev_p1_end = evs[k][4]; w[k].ev_p2_end = evs[k][6];
+            grp.w[k].ev_p1_end = evs[k][4]; grp.w[k].ev_p2_end = evs[k][6];
             HIP_TRY(hipEventRecord(evs[k][0], c->stream));
         }
         if ((rc = enqueue_paths(c, &q, S, ld, true))) return rc;
         if (evs[k]) HIP_TRY(hipEventRecord(evs[k][1], c->stream));
-        HIP_TRY(omc::lsm_pass1_sweep(c->stream, prob[k], w[k], &ntiles));
-        g.slot[k] = omc::lsm_group_slot(prob[k], w[k]);
+        HIP_TRY(omc::lsm_pass1_sweep(c->stream, prob, grp.w[k], &grp.g.ntiles));
     }
-    g.cK = cK; g.ntiles = ntiles; g.N = N; g.irr_every = w0.crit_irr_every;
-    HIP_TRY(omc::lsm_group_reduce_pass1(c->stream, g, Kb));
-    HIP_TRY(omc::lsm_group_crit_build(c->stream, g, Kb));
+    HIP_TRY(grp.reduce_pass1(c->stream));
+    HIP_TRY(grp.build_tables(c->stream));
     for (int k = 0; k < Kb; ++k) {
         if (evs[k]) HIP_TRY(hipEventRecord(evs[k][5], c->stream));
-        HIP_TRY(omc::lsm_pass2_sweep(c->stream, prob[k], w[k], false, true, &g.nblk));
+        HIP_TRY(omc::lsm_pass2_sweep(c->stream, grp.prob[k], grp.w[k], false, true, &grp.g.nblk));
     }
-    HIP_TRY(omc::lsm_group_finalize(c->stream, g, Kb));
+    HIP_TRY(grp.finalize(c->stream));
     if (i0 == 0) HIP_TRY(hipEventRecord(c->ev[2], c->stream));
     return 0;
 }

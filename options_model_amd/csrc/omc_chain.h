@@ -5,21 +5,13 @@
 
 namespace omc {
 
-constexpr int kChainGroupMax = 16;  // entries whose pass-1 reductions, table builds and finalizes share one launch each
+constexpr int kChainGroupMax = 16;  // entries per group: their pass-1 reductions, table builds and finalizes share one
+                                    // launch each (lsm_group_*, omc_kernels.h)
 constexpr int kChainWidthMax = 4;   // entries of one side per fused sweep launch
 
-// cK_j[t] = c0[j] g^t, t = 0 .. N, for j < n: table j at cK + j * stride, each by the N sequential float64 products of
-// lsm_fold_table (c0: device, n doubles)
+// cK_j[t] = c0[j] g^t, t = 0 .. N, for j < n: table j at cK + j * stride, each filled as lsm_fold_table fills its one
+// (fold_table_fill; c0: device, n doubles)
 hipError_t chain_fold_tables(hipStream_t st, double* cK, size_t stride, const double* c0, int n, int N, double g);
-
-// the table builds of a group (lsm_crit_build per entry, the entry on grid.y): as lsm_group_crit_build, with a fold table
-// per entry -- null = full storage, where the group has no tables and this is not called
-struct ChainCritArgs {
-    SeqGroupSlot slot[kChainGroupMax];
-    const double* cK[kChainGroupMax];
-    int N, irr_every;
-};
-hipError_t chain_crit_build(hipStream_t st, const ChainCritArgs& g, int K);
 
 // One fused launch: KE entries of ONE side on the folded matrix S ([N+1][ld], P stored columns).  Entry e reads its strike,
 // its fold table and -- pass 2 -- its exercise tables and fits, and leaves its partial sums in its own slabs, in the

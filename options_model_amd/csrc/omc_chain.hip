@@ -27,34 +27,12 @@ __global__ __launch_bounds__(64) void chain_fold_tables_kernel(double* __restric
 {
     const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (j >= n) return;
-    double* tab = cK + (size_t)j * stride;
-    double c = c0[j];
-    tab[0] = c;
-    for (int t = 1; t <= N; ++t) {  // (lsm_fold_table_kernel's products)
-        c *= g;
-        tab[t] = c;
-    }
+    fold_table_fill(cK + (size_t)j * stride, N, c0[j], g);
 }
 
 hipError_t chain_fold_tables(hipStream_t st, double* cK, size_t stride, const double* c0, int n, int N, double g)
 {
     hipLaunchKernelGGL(chain_fold_tables_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, cK, stride, c0, n, N, g);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------ table builds of a group, a fold table per entry
-__global__ __launch_bounds__(128) void chain_crit_build_kernel(ChainCritArgs g)
-{
-    const SeqGroupSlot& s = g.slot[blockIdx.y];
-    CritArgs a;
-    a.gmom = s.gmom; a.betas = s.betas; a.betas_out = s.betas; a.cK = g.cK[blockIdx.y]; a.tab = s.crit;
-    a.N = g.N; a.is_put = s.is_put; a.K = s.K; a.invK = s.invK; a.irr_every = g.irr_every;
-    lsm_crit_build_body(a);
-}
-
-hipError_t chain_crit_build(hipStream_t st, const ChainCritArgs& g, int K)
-{
-    hipLaunchKernelGGL(chain_crit_build_kernel, dim3(g.N + 1, K), dim3(128), 0, st, g);
     return hipGetLastError();
 }
 

@@ -128,6 +128,35 @@ int enqueue_pricing(omc_ctx* c, const omc_params* p, float* S_keep, int64_t ld, 
                     double** result_out);
 int read_kernel_times(const hipEvent_t* evs, const omc_params* p, omc_result* res, bool has_end = true);
 
+// ---- K two-pass pricings of one geometry that share their small launches (grouped sequences, option chains)
+// device bytes one member of a group owns in omc_ctx::gstate: [part1 | gmom | betas | crit | part]
+struct GroupLayout {
+    size_t o_gmom, o_betas, o_crit, o_part, per;
+    GroupLayout(int64_t M, int N);
+};
+// One group on a stream.  The caller adds its members, enqueues their sweeps from prob[k] / w[k] (lsm_pass1_sweep into
+// &g.ntiles, lsm_pass2_sweep into &g.nblk, or the chain's fused ones) and places the three shared launches between them:
+//     pass-1 sweeps;  reduce_pass1;  build_tables (members that decide from tables);  pass-2 sweeps;  finalize
+struct TwoPassGroup {
+    // `state`: room for L.per bytes per member; w0: the members' template (discount table, gstride, crit_irr_every,
+    // part1_tiles); tables: pass 2 decides from exercise tables (option "pass2_tables"), else the members carry none
+    TwoPassGroup(const GroupLayout& L, void* state, const omc::LsmWorkspace& w0, bool tables);
+    void add(const omc::LsmProblem& p, double* result);  // the next member, k = K
+    hipError_t reduce_pass1(hipStream_t st) const { return omc::lsm_group_reduce_pass1(st, g, K); }
+    hipError_t build_tables(hipStream_t st) const { return omc::lsm_group_crit_build(st, g, K); }  // folded members only
+    hipError_t finalize(hipStream_t st) const { return omc::lsm_group_finalize(st, g, K); }
+    int K = 0;
+    omc::LsmProblem prob[omc::kSeqGroupMax];
+    omc::LsmWorkspace w[omc::kSeqGroupMax];
+    omc::SeqGroupArgs g = {};
+
+private:
+    GroupLayout L;
+    char* state;
+    omc::LsmWorkspace w0;
+    bool tables;
+};
+
 }  // namespace omc::abi
 
 using omc::abi::DevBuf;
@@ -184,8 +213,9 @@ struct omc_ctx {
     int mtab_slot = 0;
     int seq_step_k = -1;       // -1: default (what fits the Infinity Cache, <= 16), 1: off, k: at most k pricings per launch
     int seq_step_wgs = 0;      // workgroups one launch of the multi-pricing sweep may use (0: one per CU)
-    // omc_price_american_seq, two-pass flow on folded storage: the pass-1 reductions, table builds and finalizes of K
-    // pricings of one geometry share three launches; per pricing of a group its own path matrix and small buffers
+    // groups of K two-pass pricings of one geometry whose pass-1 reductions, table builds and finalizes share three
+    // launches (TwoPassGroup): gstate = per member of a group [part1 | gmom | betas | crit | part] (GroupLayout), for
+    // omc_price_american_seq's groups and omc_price_american_chain's alike; gS = the sequence's K path matrices
     DevBuf gS, gstate;
     int seq_two_pass_k = -1;   // -1: by size (omc_api_seq.hip), 1: one pricing at a time, k: at most k pricings per group
     int gbm_vec = 0, heston_vec = 0;
@@ -201,8 +231,7 @@ struct omc_ctx {
     DevBuf gk_part, gk_res;  // omc_price_american_greeks: per-workgroup partials, reduced sums
     DevBuf bar_part, bar_res;  // omc_price_barrier: the generator's per-workgroup partials, reduced sums
     DevBuf bnd;                // omc_price_american_bounds: outer paths, Q^ table, samples, tables, partials, sums
-    // omc_price_american_chain: per entry of a group [part1 | gmom | betas | crit | part]; the entries' fold tables + c0
-    DevBuf chain_state, chain_fold;
+    DevBuf chain_fold;         // omc_price_american_chain: the entries' fold tables + c0 (their small buffers: gstate)
     int chain_fused = 0;       // option "chain_fused": 0 = default, the single-strike sweeps per entry; 1 = the fused sweeps
     int chain_k = -1;          // option "chain_k": entries per fused launch at most (-1: what omc_chain.hip allows)
     struct FoldKey { int N = -1; double c0 = 0, g = 0; } fold_key[2];

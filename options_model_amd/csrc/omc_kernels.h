@@ -175,11 +175,11 @@ struct FoldGeometry {
     int64_t ntiles = 0;
 };
 FoldGeometry lsm_fold_geometry(const LsmProblem& p);
-// ---- the two-pass flow's latency-bound launches for K pricings of one geometry at once (omc_price_american_seq):
-// pass-1 reduction, table build and finalize with the pricing on grid.y.  Thin entry points around the bodies of the
-// single launches, so every pricing keeps the bits of its own.  The per-pricing pointers travel BY VALUE in the
-// kernel arguments (72 bytes x 32 pricings + the shared fields = 2.4 KB of the 4 KB a launch may carry): no table
-// upload sits on the stream between a group's sweeps and nothing has to outlive the enqueue.
+// ---- the two-pass flow's latency-bound launches for K pricings of one geometry at once (omc_price_american_seq,
+// omc_price_american_chain): pass-1 reduction, table build and finalize with the pricing on grid.y.  Thin entry points
+// around the bodies of the single launches, so every pricing keeps the bits of its own.  The per-pricing pointers travel
+// BY VALUE in the kernel arguments (80 bytes x 32 pricings + the shared fields = 2.6 KB of the 4 KB a launch may carry):
+// no table upload sits on the stream between a group's sweeps and nothing has to outlive the enqueue.
 constexpr int kSeqGroupMax = 32;
 struct SeqGroupSlot {
     const double* part1;  // pass 1's unreduced partials
@@ -188,19 +188,21 @@ struct SeqGroupSlot {
     uint32_t* crit;       // [N+1][8]
     const double* part;   // pass 2's partial sums
     double* result;       // [8]
+    const double* cK;     // the pricing's fold table (LsmProblem::fold_cK); null = full storage: no table build
     double K, invK;
     int is_put, pad_;
 };
 struct SeqGroupArgs {
     SeqGroupSlot slot[kSeqGroupMax];
-    const double* cK;  // one fold table for the whole group
     int64_t ntiles;    // lsm_pass1_sweep
     int N, nblk;       // nblk: lsm_pass2_sweep
     int irr_every, pad_;
 };
+static_assert(sizeof(SeqGroupSlot) == 80 && sizeof(SeqGroupArgs) == 80 * kSeqGroupMax + 24 && sizeof(SeqGroupArgs) <= 4096,
+              "the group's argument block travels by value in the kernel arguments");
 SeqGroupSlot lsm_group_slot(const LsmProblem& p, const LsmWorkspace& w);
 hipError_t lsm_group_reduce_pass1(hipStream_t st, const SeqGroupArgs& g, int K);
-hipError_t lsm_group_crit_build(hipStream_t st, const SeqGroupArgs& g, int K);
+hipError_t lsm_group_crit_build(hipStream_t st, const SeqGroupArgs& g, int K);  // every slot has its cK
 hipError_t lsm_group_finalize(hipStream_t st, const SeqGroupArgs& g, int K);
 // betas[t] = solve_poly2(gmom[t]), n = gmom[t][0] for t = 1 .. N-1: the fits pass 2 solves for itself
 hipError_t lsm_solve_betas(hipStream_t st, const double* gmom, double* betas, int N);

@@ -78,16 +78,10 @@ __global__ __launch_bounds__(kBlock) void lsm_crit_check_kernel(const uint32_t* 
     lsm_crit_check_body(tab, betas, cK, N, is_put, K, invK, mism);
 }
 
-// cK[t] = c0 g^t, t = 0 .. N, by N sequential float64 multiplications (IEEE: the host oracle repeats them exactly)
+// cK[t] = c0 g^t, t = 0 .. N (fold_table_fill)
 __global__ void lsm_fold_table_kernel(double* __restrict__ cK, int N, double c0, double g)
 {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    double c = c0;
-    cK[0] = c;
-    for (int t = 1; t <= N; ++t) {
-        c *= g;
-        cK[t] = c;
-    }
+    if (threadIdx.x == 0 && blockIdx.x == 0) fold_table_fill(cK, N, c0, g);
 }
 
 template <int VEC>
@@ -167,7 +161,7 @@ __global__ __launch_bounds__(128) void lsm_crit_build_group_kernel(SeqGroupArgs 
 {
     const SeqGroupSlot& s = g.slot[blockIdx.y];
     CritArgs a;
-    a.gmom = s.gmom; a.betas = s.betas; a.betas_out = s.betas; a.cK = g.cK; a.tab = s.crit;
+    a.gmom = s.gmom; a.betas = s.betas; a.betas_out = s.betas; a.cK = s.cK; a.tab = s.crit;
     a.N = g.N; a.is_put = s.is_put; a.K = s.K; a.invK = s.invK; a.irr_every = g.irr_every;
     lsm_crit_build_body(a);
 }
@@ -580,6 +574,7 @@ SeqGroupSlot lsm_group_slot(const LsmProblem& p, const LsmWorkspace& w)
 {
     SeqGroupSlot s;
     s.part1 = w.part1; s.gmom = w.gmom; s.betas = w.betas; s.crit = w.crit; s.part = w.part; s.result = w.result;
+    s.cK = p.fold_cK;
     s.K = p.K; s.invK = 1.0 / p.K; s.is_put = p.is_put; s.pad_ = 0;
     return s;
 }

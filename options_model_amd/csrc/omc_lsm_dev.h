@@ -611,6 +611,17 @@ __device__ __forceinline__ double fold_rcp(float s)
 __device__ __forceinline__ double fold_u_rcp(double cK_t, double rcp_s) { return fma(cK_t, rcp_s, -1.0); }
 __device__ __forceinline__ double fold_u(double cK_t, float s) { return fold_u_rcp(cK_t, fold_rcp(s)); }
 __device__ __forceinline__ double fold_pay(double u, double K, int is_put) { return is_put ? -K * u : K * u; }
+// A fold table tab[t] = c0 g^t, t = 0 .. N, by N sequential float64 multiplications (IEEE: the host oracle repeats them
+// exactly); one thread fills one table
+__device__ __forceinline__ void fold_table_fill(double* __restrict__ tab, int N, double c0, double g)
+{
+    double c = c0;
+    tab[0] = c;
+    for (int t = 1; t <= N; ++t) {
+        c *= g;
+        tab[t] = c;
+    }
+}
 constexpr int kFoldMaxChunk = 64;  // steps per workgroup of the folded pass 1, at most
 
 // Pass 1 on the folded matrix: as lsm_pass1_body, every loaded spot contributing its own row and its partner's.

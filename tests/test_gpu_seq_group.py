@@ -53,6 +53,19 @@ def test_every_member_of_a_group_returns_its_own_bits(gctx, M, N, n):
     assert len({s["price"] for s in singles}) == n
 
 
+def test_a_full_argument_block_and_a_pricing_left_over(gctx):
+    """32 members fill the by-value argument block of the shared launches to its last slot (the other tests stop at 7,
+    and never read the tail of the block); the 33rd pricing is left over and priced alone."""
+    ps = _run(65_536, 9, 33)
+    gctx.set_option("seq_two_pass_k", 32)
+    assert gctx.seq_group_width(ps) == 32
+    outs = gctx.price_american_seq(ps)
+    assert len(outs) == 33
+    for p, o in zip(ps, outs):
+        _same(o, gctx.price_american(p))
+    assert len({o["price"] for o in outs}) == 33
+
+
 def test_mixed_sequence_groups_its_runs_and_leaves_the_rest_alone(gctx):
     from options_model_amd import _ffi
     run_a = _run(131_072, 30, 3)
