@@ -357,6 +357,52 @@ typedef struct {
 int omc_price_barrier(omc_ctx* ctx, const omc_params* p, const omc_barrier* b, omc_barrier_result* out, float* S_keep,
                       int64_t ld);
 
+/* ---- dividends: a continuous yield and discrete cash / proportional dividends ------------- */
+/* omc_price_american on a stock that pays dividends: two-pass flow (p->semantics = OMC_SEM_TWO_PASS), antithetic pairs
+ * (p->antithetic = 1), one GPU, GBM and Heston (every scheme), the polynomial regression.
+ * Continuous yield q (finite, any sign): the paths drift at rq = p->r - q (one float64 subtraction; the generators' and
+ *   the fold table's rate), every discount factor stays at p->r.  A yield-only pricing (n_div = 0) runs
+ *   omc_price_american's kernels under its storage rule (option "fold_antithetic"; S_keep forces full storage); with
+ *   q = 0 its `base` is omc_price_american's result bit for bit.
+ * Discrete dividends d[i] = (t, amount, kind), 0 < t <= T:
+ *   OMC_DIV_PROPORTIONAL  amount = delta in [0, 1): the spot becomes s (1 - delta);
+ *   OMC_DIV_CASH          amount = c >= 0: the spot becomes max(s - c, 0) -- a dividend is paid only as far as the spot
+ *                         covers it, and a spot at 0 stays at 0.
+ *   Ex-dividend step k = clamp((int)ceil(t * n_steps / T - 1e-9), 1, n_steps), in float64.  Row k of the path matrix holds
+ *   the EX-dividend spot: exercising at step k earns the ex-dividend payoff, the last cum-dividend exercise date is k - 1.
+ *   Per-step table, composed on the host in float64: the dividends stable-sorted by k (input order within a step), from
+ *   (m, c) = (1, 0): proportional m *= 1 - delta, c *= 1 - delta; cash c += amount; then mul[k] = (float)m, cash[k] =
+ *   (float)c.  On a step with an entry, after the model's own step, both partners of a pair become
+ *   s = fmaxf(fmaf(s, mul[k], -cash[k]), 0) in float32; the Heston variance is untouched.  Steps without an entry are the
+ *   vanilla generator's operations: rows 0 .. first_div_step - 1 carry the bits of omc_gbm_paths_f32 /
+ *   omc_heston_paths_f32 at rate rq, and a dividend of amount 0 changes no bit of a non-negative spot.
+ *   Any discrete dividend means FULL storage (base.folded = 0), in the library's own matrix or S_keep ([n_steps+1][ld],
+ *   ld >= n_paths).  A spot of exactly 0 is an ordinary entry for the sweeps.  A schedule that takes
+ *   EVERY path to 0 leaves a singular regression: the result is what the sweeps give for an all-equal column, no more.
+ * omc_dividend_schedule: host only (no context, no device work): the argument checks of omc_price_american_div and the
+ *   table -- mul, cash, has [n_steps+1] (1 / 0 / 0 where no dividend goes ex; row 0 never has one); any of the three may
+ *   be NULL.
+ * Errors (nothing is launched): omc_params checks as omc_price_american; -17 q not finite; -18 n_div < 0; -19 d NULL
+ * with n_div > 0; -20 a t outside (0, T]; -21 an amount negative or not finite; -22 a proportional amount >= 1; -23 an
+ * unknown kind; -24 p->antithetic = 0; -11 p->semantics != OMC_SEM_TWO_PASS; -10 a distributed context (one GPU);
+ * -7 null ctx / out; -6 ld < n_paths. */
+enum { OMC_DIV_PROPORTIONAL = 0, OMC_DIV_CASH = 1 };
+typedef struct {
+    double t, amount;    /* ex-dividend time in (0, T]; delta (proportional) or currency units (cash) */
+    int32_t kind;        /* OMC_DIV_*                                                                 */
+    int32_t reserved;
+} omc_dividend;
+typedef struct {
+    omc_result base;        /* as omc_price_american returns it (folded = 0 with any discrete dividend)            */
+    double ms_div_paths;    /* HIP-event time of the path generator of this call                                   */
+    int32_t n_div_steps;    /* time steps on which at least one dividend goes ex (0: yield only)                   */
+    int32_t first_div_step; /* the first of them (0: none)                                                         */
+} omc_div_result;
+int omc_dividend_schedule(const omc_params* p, double q, const omc_dividend* d, int n_div, float* mul, float* cash,
+                          int32_t* has);
+int omc_price_american_div(omc_ctx* ctx, const omc_params* p, double q, const omc_dividend* d, int n_div,
+                           omc_div_result* out, float* S_keep, int64_t ld);
+
 /* ---- Andersen-Broadie price bounds for American options ----------------------------------- */
 /* A lower and an upper bound on the value of the Bermudan put / call on the pricing grid, both from ONE frozen exercise
  * policy: the lower bound applies the policy as a stopping rule on fresh paths, the upper bound is the Andersen-Broadie

@@ -19,11 +19,22 @@ MODELS = {"gbm": 0, "heston": 1}
 HESTON_SCHEMES = {"reference": 0, "clamp": 0, "full_truncation": 1, "calibrator": 2}
 BARRIER_KINDS = {"down-and-out": 0, "up-and-out": 1, "down-and-in": 2, "up-and-in": 3}
 MONITORING = {"discrete": 0, "continuous": 1}
+DIVIDEND_KINDS = {"proportional": 0, "cash": 1}
+# argument errors of the dividend entry points (include/omc.h): raised as DividendError
+DIVIDEND_ERRORS = range(-24, -16)
 BOUND_POLICIES = {"reference": 0, "textbook": 1, "two_pass": 2, "given": 3}
 
 
 class OmcError(RuntimeError):
     pass
+
+
+class DividendError(OmcError, ValueError):
+    """An argument of the dividend entry points the library refuses (codes -17 .. -24 of include/omc.h)."""
+
+    def __init__(self, code, msg):
+        super().__init__(msg)
+        self.code = code
 
 
 class Params(C.Structure):
@@ -73,6 +84,17 @@ class BarrierResult(C.Structure):
     _fields_ = [("base", Result),
                 ("euro_out", C.c_double), ("euro_out_se", C.c_double), ("euro_in", C.c_double),
                 ("euro_in_se", C.c_double), ("hit_prob", C.c_double), ("ms_barrier_paths", C.c_double)]
+
+
+class Dividend(C.Structure):
+    """omc_dividend: ex-dividend time t in (0, T], amount (delta or currency units), kind (DIVIDEND_KINDS)."""
+    _fields_ = [("t", C.c_double), ("amount", C.c_double), ("kind", C.c_int32), ("reserved", C.c_int32)]
+
+
+class DivResult(C.Structure):
+    """omc_div_result: the pricing plus the generator's time and the dividend steps of the schedule."""
+    _fields_ = [("base", Result), ("ms_div_paths", C.c_double), ("n_div_steps", C.c_int32),
+                ("first_div_step", C.c_int32)]
 
 
 class BoundsConfig(C.Structure):
@@ -156,6 +178,9 @@ SIGNATURES = {
     "omc_pass2_tables_check": (C.c_int, [_P, _I, _D, _I, _P, _P, _I, _P, _P]),
     "omc_price_european": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Result)]),
     "omc_price_barrier": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Barrier), C.POINTER(BarrierResult), _P, _I64]),
+    "omc_dividend_schedule": (C.c_int, [C.POINTER(Params), _D, C.POINTER(Dividend), _I, _P, _P, _P]),
+    "omc_price_american_div": (C.c_int, [_P, C.POINTER(Params), _D, C.POINTER(Dividend), _I, C.POINTER(DivResult), _P,
+                                         _I64]),
     "omc_price_american_bounds": (C.c_int, [_P, C.POINTER(Params), C.POINTER(BoundsConfig), _P, _P, _P, _P,
                                             C.POINTER(Bounds)]),
     "omc_heston_price_strikes": (C.c_int, [_P, _I64, _I] + [_D] * 8 + [_U64, _U64, _I, _P, _I, _I, _P, _P]),
@@ -267,6 +292,8 @@ def _check(lib, rc):
     if rc == 0:
         return
     msg = (lib.omc_last_error() or b"").decode(errors="replace")
+    if rc in DIVIDEND_ERRORS:
+        raise DividendError(rc, msg)
     if rc < 0:
         raise ValueError(msg)
     raise OmcError(f"HIP error {rc}: {msg}")
@@ -278,6 +305,33 @@ def comm_unique_id() -> bytes:
     buf = C.create_string_buffer(128)
     _check(lib, lib.omc_comm_unique_id(buf, 128))
     return buf.raw
+
+
+def dividend_array(dividends):
+    """[(t, amount) | (t, amount, kind)] -> a ctypes array of omc_dividend (or None when empty) and its length; a bare
+    (t, amount) is a cash dividend; kind: a key of DIVIDEND_KINDS or its code."""
+    items = []
+    for d in dividends:
+        if len(d) not in (2, 3):
+            raise ValueError("a dividend is (t, amount) or (t, amount, kind).")
+        t, amount, kind = (tuple(d) + ("cash",))[:3]
+        e = Dividend()
+        e.t, e.amount = float(t), float(amount)
+        e.kind = DIVIDEND_KINDS.get(kind, -1) if isinstance(kind, str) else int(kind)
+        items.append(e)
+    return ((Dividend * len(items))(*items) if items else None), len(items)
+
+
+def dividend_schedule(params: Params, q, dividends):
+    """omc_dividend_schedule -> (mul float32 [n_steps+1], cash float32 [n_steps+1], has bool [n_steps+1]): the per-step
+    table of a dividend schedule and the argument checks of Context.price_american_div.  Host only: no GPU is needed."""
+    lib = load_library()
+    arr, n = dividend_array(dividends)
+    N = max(int(params.n_steps), 0)
+    mul, cash, has = np.empty(N + 1, np.float32), np.empty(N + 1, np.float32), np.empty(N + 1, np.int32)
+    _check(lib, lib.omc_dividend_schedule(C.byref(params), float(q), arr, n, mul.ctypes.data, cash.ctypes.data,
+                                          has.ctypes.data))
+    return mul, cash, has.astype(bool)
 
 
 def device_count() -> int:
@@ -643,6 +697,19 @@ class Context:
                                                      keep_paths.shape[1] if keep_paths else 0))
         d = out.base.as_dict()
         d.update({k: getattr(out, k) for k, _ in BarrierResult._fields_ if k != "base"})
+        return d
+
+    def price_american_div(self, params: Params, q=0.0, dividends=(), S_keep: DeviceArray | None = None):
+        """American option on a stock with a dividend yield q and discrete dividends (omc_price_american_div) -> dict: the
+        base pricing's keys (as price_american returns them) plus ms_div_paths, n_div_steps, first_div_step.  dividends:
+        [(t, amount) | (t, amount, "cash" | "proportional")]; S_keep: device [n_steps+1][ld] receiving the path matrix."""
+        arr, n = dividend_array(dividends)
+        out = DivResult()
+        _check(self.lib, self.lib.omc_price_american_div(self.handle, C.byref(params), float(q), arr, n, C.byref(out),
+                                                          S_keep.ptr if S_keep else None,
+                                                          S_keep.shape[1] if S_keep else 0))
+        d = out.base.as_dict()
+        d.update({k: getattr(out, k) for k, _ in DivResult._fields_ if k != "base"})
         return d
 
     def price_american_bounds(self, params: Params, policy="textbook", n_lower=1_000_000, n_outer=8192, n_inner=1024,

@@ -394,6 +394,69 @@ def price_barrier_option(S0, K, r, sigma, T, n_paths, n_steps, barrier, barrier_
 
 
 @dataclass
+class DividendResult:
+    """price_american_dividends: price / stderr (the convention of PriceResult), the exercise counts, the storage the
+    pricing ran on and the time steps on which a dividend went ex."""
+    price: float
+    stderr: float
+    std: float
+    zero_prob: float
+    n_paths: int
+    n_exercised: int
+    sum_nitm: int
+    folded: bool
+    dividend_steps: int
+    dividend_yield: float
+    model: str
+    option_type: str
+    timings_ms: dict = field(default_factory=dict)
+    info: dict = field(default_factory=dict)  # first_dividend_step, n_dividends
+
+    def __float__(self):
+        return float(self.price)
+
+
+def price_american_dividends(S0, K, r, sigma, T, n_paths, n_steps, dividend_yield=0.0, dividends=(), model="GBM",
+                             option_type="put", heston_params=None, seed=42, device=None) -> DividendResult:
+    """American option on a stock that pays dividends (omc_price_american_div): the two-pass poly
+    LSM of price_american_option on paths that drift at r - dividend_yield and drop by every discrete dividend on its
+    ex-dividend step.  dividends: items (t, amount) -- a cash dividend -- or (t, amount, "cash" | "proportional"), with
+    0 < t <= T; a proportional amount is the fraction of the spot paid out, in [0, 1).  Antithetic paths, one GPU."""
+    model_l = str(model).lower()
+    if model_l not in ("gbm", "heston"):
+        raise ValueError("model must be 'GBM' or 'Heston'.")
+    q = float(dividend_yield)
+    if not math.isfinite(q):
+        raise ValueError("dividend_yield must be finite.")
+    divs = []
+    for d in dividends:
+        d = tuple(d)
+        if len(d) not in (2, 3):
+            raise ValueError("a dividend is (t, amount) or (t, amount, 'cash' | 'proportional').")
+        kind = d[2] if len(d) == 3 else "cash"
+        if kind not in _ffi.DIVIDEND_KINDS:
+            raise ValueError("a dividend's kind must be 'cash' or 'proportional'.")
+        divs.append((float(d[0]), float(d[1]), kind))
+    _validate(S0, K, T, r, sigma, n_paths, n_steps, option_type, need_sigma=(model_l == "gbm"))
+    M = int(n_paths) // 2 * 2
+    if M <= 0:
+        raise ValueError("num_simulations and num_time_steps must be positive integers.")
+    c = _ffi.default_context(device)
+    p = _ffi.make_params(model=model_l, is_put=(option_type == "put"), semantics="two_pass", antithetic=True,
+                         n_paths=M, n_steps=int(n_steps), S0=S0, K=K, r=r, sigma=sigma or 0.0, T=T, seed=seed,
+                         **heston_defaults(sigma, heston_params))
+    out = c.price_american_div(p, q, divs)
+    var = max(out["sumsq"] / M - out["price"] ** 2, 0.0)
+    return DividendResult(price=out["price"], stderr=math.sqrt(var / M), std=out["std"], zero_prob=out["zero_prob"],
+                          n_paths=M, n_exercised=out["n_exercised"], sum_nitm=out["sum_nitm"],
+                          folded=bool(out["folded"]), dividend_steps=out["n_div_steps"], dividend_yield=q, model=model_l,
+                          option_type=option_type,
+                          timings_ms=dict(paths=out["ms_div_paths"], pass1=out["ms_pass1"], pass2=out["ms_pass2"],
+                                          lsm=out["ms_lsm"], total=out["ms_total"]),
+                          info=dict(first_dividend_step=out["first_div_step"], n_dividends=len(divs)))
+
+
+@dataclass
 class BoundsResult:
     """price_american_bounds: Andersen-Broadie bounds on the value of the BERMUDAN option with exercise dates t = 1..n_steps
     of the grid dt = T / n_steps, all values discounted to t = 0 (Z_t = exp(-r t dt) max(phi(S_t), 0)) -- the textbook

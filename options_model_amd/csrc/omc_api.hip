@@ -1,6 +1,6 @@
 // omc_api.hip -- the C ABI of libomc.so (include/omc.h): the helpers the entry points share (argument checks,
 // launch sequencing, HIP-event timing), contexts, memory, options, the all-reduce hook, RCCL and the direct peer
-// exchange.  The other entry points live in omc_api_{price,seq,batch,nn,bounds,chain}.hip; omc_ctx.h is their common ground.
+// exchange.  The other entry points live in omc_api_{price,seq,batch,nn,bounds,chain,dividend}.hip; omc_ctx.h is their common ground.
 // No kernel code here.
 #include <sched.h>
 
@@ -510,10 +510,12 @@ int ensure_paths(omc_ctx* c, const omc_params* p, Storage how, float** S, int64_
 
 // Enqueue one whole pricing (paths + backward induction) on the context's stream; its 8 result sums
 // go to `result_dev` (device-visible memory) or, when null, to the workspace's device buffer, which is
-// returned through *result_out.  Events are recorded only when `timed`.
+// returned through *result_out.  Events are recorded only when `timed`.  `gen` (null: p itself) holds the parameters of
+// the generator / fold-table side: p with the drift rate of the paths where that is not the discount rate.
 int enqueue_pricing(omc_ctx* c, const omc_params* p, float* S_keep, int64_t ld, double* result_dev,
-                    hipEvent_t* evs, double** result_out)
+                    hipEvent_t* evs, double** result_out, const omc_params* gen)
 {
+    if (!gen) gen = p;
     const bool timed = evs != nullptr;
     int rc;
     const int64_t M = p->n_paths;
@@ -522,7 +524,7 @@ int enqueue_pricing(omc_ctx* c, const omc_params* p, float* S_keep, int64_t ld, 
     const double* cK = nullptr;
     if (S) {
         if (ld < M) return fail(-6, "leading dimension smaller than n_paths.");
-    } else if ((rc = ensure_paths(c, p, Storage::planned, &S, &ld, &cK))) {
+    } else if ((rc = ensure_paths(c, gen, Storage::planned, &S, &ld, &cK))) {
         return rc;
     }
     omc::LsmWorkspace w;
@@ -534,12 +536,35 @@ int enqueue_pricing(omc_ctx* c, const omc_params* p, float* S_keep, int64_t ld, 
         w.ev_p1_end = evs[4]; w.ev_p2_begin = evs[5]; w.ev_p2_end = evs[6];
         HIP_TRY(hipEventRecord(evs[0], c->stream));
     }
-    if ((rc = enqueue_paths(c, p, S, ld, cK != nullptr))) return rc;
+    if ((rc = enqueue_paths(c, gen, S, ld, cK != nullptr))) return rc;
     if (timed) HIP_TRY(hipEventRecord(evs[1], c->stream));
     if (result_dev) w.result = result_dev;
     if ((rc = enqueue_lsm(c, prob, w, p->semantics, false))) return rc;
     if (result_out) *result_out = w.result;
     return 0;
+}
+
+// omc_price_american behind its argument checks: one timed pricing on the context's stream and its result (gen: as
+// enqueue_pricing)
+int price_fused(omc_ctx* c, const omc_params* p, const omc_params* gen, omc_result* res, float* S_keep, int64_t ld)
+{
+    int rc;
+    // Single GPU: the finalize kernel stores its 8 sums straight into host-mapped pinned memory (no copy
+    // kernel, no extra dependent launch).  With an all-reduce hook the sums stay in device memory for
+    // the collective and are copied afterwards.
+    const bool zero_copy = c->hres_dev && !c->distributed();
+    double* hres = c->hres_pin ? c->hres_pin : c->hres;
+    double* result = nullptr;
+    if ((rc = enqueue_pricing(c, p, S_keep, ld, zero_copy ? c->hres_dev : nullptr, c->ev, &result, gen))) return rc;
+    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+    if (!zero_copy)
+        HIP_TRY(hipMemcpyAsync(hres, result, sizeof(double) * 8, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = wait_stream(c))) return rc;
+    if ((rc = check_p2p(c, hres, 1))) return rc;
+    fill_result(res, hres, c->distributed() ? p->n_paths * c->world : p->n_paths,
+                c->distributed() ? c->world : 1);  // distributed: sums are global
+    res->folded = (!S_keep && fold_applies(c, p)) ? 1 : 0;
+    return read_kernel_times(c->ev, p, res);
 }
 
 // HIP-event times of a pricing with enqueue_pricing's events: evs[0] paths evs[1] backward induction evs[2] (when

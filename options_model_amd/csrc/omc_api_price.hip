@@ -192,22 +192,7 @@ int omc_price_american(omc_ctx* c, const omc_params* p, omc_result* res, float* 
     if ((rc = S_keep ? bind_in(c) : bind(c))) return rc;  // only a caller-provided path matrix is borrowed memory
     if ((rc = check_params(p))) return rc;
     if (!res) return fail(-7, "null result pointer.");
-    // Single GPU: the finalize kernel stores its 8 sums straight into host-mapped pinned memory (no copy
-    // kernel, no extra dependent launch).  With an all-reduce hook the sums stay in device memory for
-    // the collective and are copied afterwards.
-    const bool zero_copy = c->hres_dev && !c->distributed();
-    double* hres = c->hres_pin ? c->hres_pin : c->hres;
-    double* result = nullptr;
-    if ((rc = enqueue_pricing(c, p, S_keep, ld, zero_copy ? c->hres_dev : nullptr, c->ev, &result))) return rc;
-    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
-    if (!zero_copy)
-        HIP_TRY(hipMemcpyAsync(hres, result, sizeof(double) * 8, hipMemcpyDeviceToHost, c->stream));
-    if ((rc = wait_stream(c))) return rc;
-    if ((rc = check_p2p(c, hres, 1))) return rc;
-    fill_result(res, hres, c->distributed() ? p->n_paths * c->world : p->n_paths,
-                c->distributed() ? c->world : 1);  // distributed: sums are global
-    res->folded = (!S_keep && fold_applies(c, p)) ? 1 : 0;
-    return read_kernel_times(c->ev, p, res);
+    return price_fused(c, p, nullptr, res, S_keep, ld);
 }
 
 int omc_pass2_tables_check(omc_ctx* c, int is_put, double K, int n_steps, const double* betas, const double* cK,

@@ -124,8 +124,10 @@ int enqueue_paths(omc_ctx* c, const omc_params* p, float* S, int64_t ld, bool fo
 bool fold_applies(const omc_ctx* c, const omc_params* p);
 int plan_storage(omc_ctx* c, const omc_params* p, int slot, int64_t* ld, const double** cK);
 int ensure_paths(omc_ctx* c, const omc_params* p, Storage how, float** S, int64_t* ld, const double** cK = nullptr);
+// gen: the parameters the generator and the fold table take (null: p; a dividend yield hands p with r - q as its rate)
 int enqueue_pricing(omc_ctx* c, const omc_params* p, float* S_keep, int64_t ld, double* result_dev, hipEvent_t* evs,
-                    double** result_out);
+                    double** result_out, const omc_params* gen = nullptr);
+int price_fused(omc_ctx* c, const omc_params* p, const omc_params* gen, omc_result* res, float* S_keep, int64_t ld);
 int read_kernel_times(const hipEvent_t* evs, const omc_params* p, omc_result* res, bool has_end = true);
 
 // ---- K two-pass pricings of one geometry that share their small launches (grouped sequences, option chains)
@@ -230,6 +232,7 @@ struct omc_ctx {
     DevBuf foldC;
     DevBuf gk_part, gk_res;  // omc_price_american_greeks: per-workgroup partials, reduced sums
     DevBuf bar_part, bar_res;  // omc_price_barrier: the generator's per-workgroup partials, reduced sums
+    DevBuf div_tab;            // omc_price_american_div: the dividend steps of the call (omc::DivEntry)
     DevBuf bnd;                // omc_price_american_bounds: outer paths, Q^ table, samples, tables, partials, sums
     DevBuf chain_fold;         // omc_price_american_chain: the entries' fold tables + c0 (their small buffers: gstate)
     int chain_fused = 0;       // option "chain_fused": 0 = default, the single-strike sweeps per entry; 1 = the fused sweeps
