@@ -403,6 +403,56 @@ int omc_dividend_schedule(const omc_params* p, double q, const omc_dividend* d, 
 int omc_price_american_div(omc_ctx* ctx, const omc_params* p, double q, const omc_dividend* d, int n_div,
                            omc_div_result* out, float* S_keep, int64_t ld);
 
+/* ---- jump-diffusion: Merton (GBM) and Bates (Heston) paths -------------------------------- */
+/* omc_price_american on a stock whose price jumps: compound-Poisson lognormal jumps on top of GBM (Merton) or of any
+ * Heston scheme (Bates), with a continuous dividend yield q.  Two-pass flow (p->semantics = OMC_SEM_TWO_PASS),
+ * antithetic pairs (p->antithetic = 1), one GPU, the polynomial regression.
+ * Parameters: lambda >= 0 jumps per year; a jump multiplies the spot by exp(J), J ~ N(mu_j, sigma_j^2), sigma_j >= 0;
+ *   q as in omc_price_american_div.
+ * Compensator and drift: kappa = exp(mu_j + sigma_j^2 / 2) - 1; the generator's drift rate is
+ *   rj = (p->r - q) - lambda * kappa, formed once in float64 in exactly that order; rj goes wherever the generator takes
+ *   a rate, every discount factor stays at p->r.
+ * Jump count of a step: exact Poisson by inversion on integers.  With x = lambda * T / n_steps the host builds 16
+ *   thresholds in float64: p_0 = exp(-x), p_n = p_{n-1} * x / n, c_n = p_0 + .. + p_n,
+ *   thr[n] = min(2^24, floor(c_n * 2^24 + 0.5)) as uint32.  For step t = 1..N of a pair, w = the top 24 bits (word >> 8)
+ *   of word (t-1) & 3 of the Philox4x32-10 block at counter (pair lo, pair hi, 0x40000000 | ((t-1) >> 2), stream), key =
+ *   the seed as everywhere; the count is n = #{k : w >= thr[k]}, 0 .. 16.  x > 1 is refused (at x = 1 the mass beyond 16
+ *   jumps is below 1e-14).  The normals use counter word 2 below 2^30 and the barrier's uniforms 0x80000000 | blk, so
+ *   the families never share a counter.
+ * Jump size, only where n > 0: z_J = the first value of box_muller(o.x, o.y) of the Philox block o at counter
+ *   (pair lo, pair hi, 0xC0000000 | t, stream); the log2 jump in float32 is
+ *   jl = fmaf(sqrtf((float)n) * sj2, z_J, (float)n * mj2), mj2 = (float)(mu_j log2 e), sj2 = (float)(sigma_j log2 e).
+ * Both partners of a pair share n and z_J: only the diffusion is antithetic.
+ * Step rule: GBM s *= exp2(fma(b, z, a) + jl), partner s' *= exp2(fma(-b, z, a) + jl); Heston, after the scheme's own
+ *   step, s *= exp2(jl) and s' *= exp2(jl), the variance untouched.  A step with n = 0 executes the vanilla generator's
+ *   operations and nothing else: every column carries the bits of omc_gbm_paths_f32 / omc_heston_paths_f32 at rate rj up
+ *   to its own first jump, and with mu_j = sigma_j = 0 no bit differs from the vanilla matrix at rate p->r - q for any
+ *   lambda.
+ * lambda = 0 delegates to the yield-only route of omc_price_american_div (its storage rule, omc_price_american's bits at
+ *   q = 0); any lambda > 0 means FULL storage (base.folded = 0), in the library's own matrix or S_keep
+ *   ([n_steps+1][ld], ld >= n_paths): with jumps the partner's spot is no function of the stored one.
+ * omc_jump_table: host only (no context, no device work): the argument checks of omc_price_american_jump and the table;
+ *   any of thr, kappa, drift_rate may be NULL.
+ * Errors (nothing is launched): omc_params checks as omc_price_american; -25 j NULL; -17 q not finite; -26 lambda
+ * negative or not finite; -27 mu_j not finite, or sigma_j negative or not finite; -28 lambda * T / n_steps > 1;
+ * -24 p->antithetic = 0; -11 p->semantics != OMC_SEM_TWO_PASS; -10 a distributed context (one GPU); -7 null ctx / out;
+ * -6 ld < n_paths. */
+typedef struct {
+    double lambda, mu_j, sigma_j; /* jumps per year; mean and standard deviation of a jump's log size */
+} omc_jump;
+typedef struct {
+    omc_result base;       /* as omc_price_american returns it (folded = 0 with lambda > 0)                        */
+    double ms_jump_paths;  /* HIP-event time of the path generator of this call                                    */
+    double kappa;          /* exp(mu_j + sigma_j^2 / 2) - 1                                                        */
+    double drift_rate;     /* rj = (r - q) - lambda kappa                                                          */
+    int32_t n_thresholds;  /* entries of the table below 2^24: the largest count a step can carry (0: lambda = 0)  */
+    int32_t reserved;
+} omc_jump_result;
+int omc_jump_table(const omc_params* p, const omc_jump* j, double q, uint32_t thr[16], double* kappa,
+                   double* drift_rate);
+int omc_price_american_jump(omc_ctx* ctx, const omc_params* p, const omc_jump* j, double q, omc_jump_result* out,
+                            float* S_keep, int64_t ld);
+
 /* ---- Andersen-Broadie price bounds for American options ----------------------------------- */
 /* A lower and an upper bound on the value of the Bermudan put / call on the pricing grid, both from ONE frozen exercise
  * policy: the lower bound applies the policy as a stopping rule on fresh paths, the upper bound is the Andersen-Broadie

@@ -97,6 +97,17 @@ class DivResult(C.Structure):
                 ("first_div_step", C.c_int32)]
 
 
+class Jump(C.Structure):
+    """omc_jump: lambda (jumps per year), mu_j and sigma_j (mean and standard deviation of a jump's log size)."""
+    _fields_ = [("lambda_", C.c_double), ("mu_j", C.c_double), ("sigma_j", C.c_double)]
+
+
+class JumpResult(C.Structure):
+    """omc_jump_result: the pricing plus the generator's time, the compensator, the drift rate and the largest count."""
+    _fields_ = [("base", Result), ("ms_jump_paths", C.c_double), ("kappa", C.c_double), ("drift_rate", C.c_double),
+                ("n_thresholds", C.c_int32), ("reserved", C.c_int32)]
+
+
 class BoundsConfig(C.Structure):
     """omc_bounds_config: policy (BOUND_POLICIES), the three sizes and the three Philox streams."""
     _fields_ = [("policy", C.c_int32), ("reserved", C.c_int32), ("n_lower", C.c_int64), ("n_outer", C.c_int64),
@@ -181,6 +192,8 @@ SIGNATURES = {
     "omc_dividend_schedule": (C.c_int, [C.POINTER(Params), _D, C.POINTER(Dividend), _I, _P, _P, _P]),
     "omc_price_american_div": (C.c_int, [_P, C.POINTER(Params), _D, C.POINTER(Dividend), _I, C.POINTER(DivResult), _P,
                                          _I64]),
+    "omc_jump_table": (C.c_int, [C.POINTER(Params), C.POINTER(Jump), _D, _P, C.POINTER(_D), C.POINTER(_D)]),
+    "omc_price_american_jump": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Jump), _D, C.POINTER(JumpResult), _P, _I64]),
     "omc_price_american_bounds": (C.c_int, [_P, C.POINTER(Params), C.POINTER(BoundsConfig), _P, _P, _P, _P,
                                             C.POINTER(Bounds)]),
     "omc_heston_price_strikes": (C.c_int, [_P, _I64, _I] + [_D] * 8 + [_U64, _U64, _I, _P, _I, _I, _P, _P]),
@@ -332,6 +345,26 @@ def dividend_schedule(params: Params, q, dividends):
     _check(lib, lib.omc_dividend_schedule(C.byref(params), float(q), arr, n, mul.ctypes.data, cash.ctypes.data,
                                           has.ctypes.data))
     return mul, cash, has.astype(bool)
+
+
+def make_jump(jump) -> Jump:
+    """(lambda, mu_j, sigma_j) or a Jump -> Jump"""
+    if isinstance(jump, Jump):
+        return jump
+    lam, mu, sig = jump
+    return Jump(float(lam), float(mu), float(sig))
+
+
+def jump_table(params: Params, jump, q=0.0):
+    """omc_jump_table -> (thr uint32 [16], kappa, drift_rate): the Poisson thresholds of a step, the compensator and
+    the generator's drift rate, after the argument checks of Context.price_american_jump.  jump: (lambda, mu_j,
+    sigma_j).  Host only: no GPU is needed."""
+    lib = load_library()
+    thr = np.empty(16, np.uint32)
+    kappa, rate = C.c_double(), C.c_double()
+    _check(lib, lib.omc_jump_table(C.byref(params), C.byref(make_jump(jump)), float(q), thr.ctypes.data, C.byref(kappa),
+                                   C.byref(rate)))
+    return thr, kappa.value, rate.value
 
 
 def device_count() -> int:
@@ -710,6 +743,18 @@ class Context:
                                                           S_keep.shape[1] if S_keep else 0))
         d = out.base.as_dict()
         d.update({k: getattr(out, k) for k, _ in DivResult._fields_ if k != "base"})
+        return d
+
+    def price_american_jump(self, params: Params, jump, q=0.0, S_keep: DeviceArray | None = None):
+        """American option under jump-diffusion (omc_price_american_jump: Merton on GBM, Bates on Heston) -> dict: the
+        base pricing's keys (as price_american returns them) plus ms_jump_paths, kappa, drift_rate, n_thresholds.
+        jump: (lambda, mu_j, sigma_j); q: dividend yield; S_keep: device [n_steps+1][ld] receiving the path matrix."""
+        out = JumpResult()
+        _check(self.lib, self.lib.omc_price_american_jump(self.handle, C.byref(params), C.byref(make_jump(jump)), float(q),
+                                                           C.byref(out), S_keep.ptr if S_keep else None,
+                                                           S_keep.shape[1] if S_keep else 0))
+        d = out.base.as_dict()
+        d.update({k: getattr(out, k) for k, _ in JumpResult._fields_ if k not in ("base", "reserved")})
         return d
 
     def price_american_bounds(self, params: Params, policy="textbook", n_lower=1_000_000, n_outer=8192, n_inner=1024,

@@ -457,6 +457,74 @@ def price_american_dividends(S0, K, r, sigma, T, n_paths, n_steps, dividend_yiel
 
 
 @dataclass
+class JumpResult:
+    """price_american_jumps: price / stderr (the convention of PriceResult), the exercise counts, the compensator
+    kappa = E[e^J] - 1 and the drift rate (r - q) - lambda kappa the paths ran at."""
+    price: float
+    stderr: float
+    std: float
+    zero_prob: float
+    n_paths: int
+    n_exercised: int
+    sum_nitm: int
+    folded: bool
+    kappa: float
+    drift_rate: float
+    jump_intensity: float
+    jump_mean: float
+    jump_vol: float
+    dividend_yield: float
+    model: str
+    option_type: str
+    timings_ms: dict = field(default_factory=dict)
+    info: dict = field(default_factory=dict)  # max_jumps_per_step
+
+    def __float__(self):
+        return float(self.price)
+
+
+def price_american_jumps(S0, K, r, sigma, T, n_paths, n_steps, jump_intensity, jump_mean=0.0, jump_vol=0.0,
+                         dividend_yield=0.0, model="GBM", option_type="put", heston_params=None, seed=42,
+                         device=None) -> JumpResult:
+    """American option under jump-diffusion (omc_price_american_jump): the two-pass poly LSM of
+    price_american_option on paths that carry compound-Poisson jumps -- jump_intensity jumps per year, each multiplying
+    the spot by exp(J), J ~ N(jump_mean, jump_vol^2) -- and drift at r - dividend_yield - jump_intensity (E[e^J] - 1).
+    model "GBM" is Merton's jump-diffusion, "Heston" is Bates's model.  jump_intensity * T / n_steps may not exceed 1.
+    Antithetic paths, one GPU."""
+    model_l = str(model).lower()
+    if model_l not in ("gbm", "heston"):
+        raise ValueError("model must be 'GBM' or 'Heston'.")
+    lam, mu, sj, q = float(jump_intensity), float(jump_mean), float(jump_vol), float(dividend_yield)
+    if not (math.isfinite(lam) and lam >= 0.0):
+        raise ValueError("jump_intensity must be finite and non-negative.")
+    if not math.isfinite(mu):
+        raise ValueError("jump_mean must be finite.")
+    if not (math.isfinite(sj) and sj >= 0.0):
+        raise ValueError("jump_vol must be finite and non-negative.")
+    if not math.isfinite(q):
+        raise ValueError("dividend_yield must be finite.")
+    _validate(S0, K, T, r, sigma, n_paths, n_steps, option_type, need_sigma=(model_l == "gbm"))
+    if lam * float(T) / int(n_steps) > 1.0:
+        raise ValueError("jump_intensity * T / n_steps must not exceed 1: use more time steps.")
+    M = int(n_paths) // 2 * 2
+    if M <= 0:
+        raise ValueError("num_simulations and num_time_steps must be positive integers.")
+    c = _ffi.default_context(device)
+    p = _ffi.make_params(model=model_l, is_put=(option_type == "put"), semantics="two_pass", antithetic=True,
+                         n_paths=M, n_steps=int(n_steps), S0=S0, K=K, r=r, sigma=sigma or 0.0, T=T, seed=seed,
+                         **heston_defaults(sigma, heston_params))
+    out = c.price_american_jump(p, (lam, mu, sj), q)
+    var = max(out["sumsq"] / M - out["price"] ** 2, 0.0)
+    return JumpResult(price=out["price"], stderr=math.sqrt(var / M), std=out["std"], zero_prob=out["zero_prob"],
+                      n_paths=M, n_exercised=out["n_exercised"], sum_nitm=out["sum_nitm"], folded=bool(out["folded"]),
+                      kappa=out["kappa"], drift_rate=out["drift_rate"], jump_intensity=lam, jump_mean=mu, jump_vol=sj,
+                      dividend_yield=q, model=model_l, option_type=option_type,
+                      timings_ms=dict(paths=out["ms_jump_paths"], pass1=out["ms_pass1"], pass2=out["ms_pass2"],
+                                      lsm=out["ms_lsm"], total=out["ms_total"]),
+                      info=dict(max_jumps_per_step=out["n_thresholds"]))
+
+
+@dataclass
 class BoundsResult:
     """price_american_bounds: Andersen-Broadie bounds on the value of the BERMUDAN option with exercise dates t = 1..n_steps
     of the grid dt = T / n_steps, all values discounted to t = 0 (Z_t = exp(-r t dt) max(phi(S_t), 0)) -- the textbook

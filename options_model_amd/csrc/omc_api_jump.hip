@@ -1,0 +1,117 @@
+// omc_api_jump.hip -- American options under jump-diffusion (include/omc.h): Merton (GBM) and
+// Bates (Heston) paths with compound-Poisson lognormal jumps and a continuous dividend yield q.  The jump generator
+// (omc_jump.hip) writes the full-storage matrix at the compensated drift rate; the unchanged two-pass flow
+// (enqueue_lsm) prices it.  lambda = 0 is the yield-only route of omc_price_american_div.
+#include <algorithm>
+
+#include "omc_ctx.h"
+#include "omc_jump.h"
+
+using namespace omc::abi;
+
+namespace {
+
+struct JumpTable {
+    uint32_t thr[omc::kJumpThr];
+    double kappa, drift_rate;
+    int n_thr;  // entries below 2^24
+};
+
+// The argument checks of both entry points and the host side of the jump law, all in float64.
+int compose_jump(const omc_params* p, const omc_jump* j, double q, JumpTable* t)
+{
+    int rc;
+    if ((rc = check_params(p))) return rc;
+    if (!j) return fail(-25, "null jump parameters.");
+    if (!std::isfinite(q)) return fail(-17, "dividend yield q must be finite.");
+    if (!(std::isfinite(j->lambda) && j->lambda >= 0.0)) return fail(-26, "jump intensity lambda must be finite and non-negative.");
+    if (!std::isfinite(j->mu_j)) return fail(-27, "jump mean mu_j must be finite.");
+    if (!(std::isfinite(j->sigma_j) && j->sigma_j >= 0.0)) return fail(-27, "jump volatility sigma_j must be finite and non-negative.");
+    const double x = j->lambda * p->T / p->n_steps;
+    if (!(x <= 1.0)) return fail(-28, "lambda * T / n_steps must not exceed 1: use more time steps.");
+    if (!p->antithetic) return fail(-24, "jump paths are antithetic pairs (antithetic = 1).");
+    if (p->semantics != OMC_SEM_TWO_PASS) return fail(-11, "jump-diffusion is priced by the two-pass flow (semantics 2).");
+    t->kappa = std::exp(j->mu_j + j->sigma_j * j->sigma_j / 2.0) - 1.0;
+    t->drift_rate = (p->r - q) - j->lambda * t->kappa;
+    double pn = std::exp(-x), cn = 0.0;
+    t->n_thr = 0;
+    for (int n = 0; n < omc::kJumpThr; ++n) {
+        if (n > 0) pn = pn * x / n;
+        cn += pn;
+        t->thr[n] = (uint32_t)std::min(16777216.0, std::floor(cn * 16777216.0 + 0.5));
+        t->n_thr += t->thr[n] < 16777216u ? 1 : 0;
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int omc_jump_table(const omc_params* p, const omc_jump* j, double q, uint32_t thr[16], double* kappa, double* drift_rate)
+{
+    JumpTable t;
+    int rc;
+    if ((rc = compose_jump(p, j, q, &t))) return rc;
+    if (thr) memcpy(thr, t.thr, sizeof t.thr);
+    if (kappa) *kappa = t.kappa;
+    if (drift_rate) *drift_rate = t.drift_rate;
+    return 0;
+}
+
+int omc_price_american_jump(omc_ctx* c, const omc_params* p, const omc_jump* j, double q, omc_jump_result* out,
+                            float* S_keep, int64_t ld)
+{
+    int rc;
+    if ((rc = S_keep ? bind_in(c) : bind(c))) return rc;
+    if (!out) return fail(-7, "null result pointer.");
+    JumpTable t;
+    if ((rc = compose_jump(p, j, q, &t))) return rc;
+    if (c->distributed()) return fail(-10, "jump-diffusion pricing runs on one GPU.");
+    if (S_keep && ld < p->n_paths) return fail(-6, "leading dimension smaller than n_paths.");
+    const int64_t M = p->n_paths;
+    const int N = p->n_steps;
+    memset(out, 0, sizeof *out);
+    out->kappa = t.kappa;
+    out->drift_rate = t.drift_rate;
+    if (j->lambda == 0.0) {  // no jumps: the yield-only route of omc_price_american_div, under its storage rule
+        omc_params gen = *p;
+        gen.r = p->r - q;
+        if ((rc = price_fused(c, p, &gen, &out->base, S_keep, ld))) return rc;
+        out->ms_jump_paths = out->base.ms_paths;
+        return 0;
+    }
+    float* S = S_keep;
+    if (!S && (rc = ensure_paths(c, p, Storage::full_only, &S, &ld))) return rc;
+    omc::JumpGen g{};
+    g.model = p->model == OMC_MODEL_GBM ? 0 : 1; g.scheme = p->heston_scheme;
+    g.n_paths = M; g.n_steps = N;
+    g.S0 = p->S0; g.r = t.drift_rate; g.sigma = p->sigma; g.T = p->T;
+    g.v0 = p->v0; g.kappa = p->kappa; g.theta = p->theta; g.xi = p->xi; g.rho = p->rho;
+    g.seed = p->seed; g.pair_offset = p->pair_offset; g.stream = (uint32_t)p->stream;
+    g.vec_hint = g.model == 0 ? c->gbm_vec : c->heston_vec;
+    memcpy(g.law.thr, t.thr, sizeof t.thr);
+    const double L2E = 1.4426950408889634074;
+    g.law.mj2 = (float)(j->mu_j * L2E);
+    g.law.sj2 = (float)(j->sigma_j * L2E);
+    g.S = S; g.ld = ld;
+    omc::LsmWorkspace w;
+    if ((rc = prepare_lsm(c, M, N, p->r, p->T, true, false, &w))) return rc;
+    HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+    HIP_TRY(omc::launch_jump_paths(c->stream, g));
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    omc::LsmProblem prob{S, ld, M, N, p->is_put ? 1 : 0, p->K, p->r, p->T};
+    w.ev_p1_end = c->ev[4]; w.ev_p2_begin = c->ev[5]; w.ev_p2_end = c->ev[6];
+    if ((rc = enqueue_lsm(c, prob, w, OMC_SEM_TWO_PASS, false))) return rc;
+    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+    HIP_TRY(hipMemcpyAsync(c->hres, w.result, sizeof(double) * 8, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = wait_stream(c))) return rc;
+    fill_result(&out->base, c->hres, M);
+    out->base.folded = 0;
+    if ((rc = read_kernel_times(c->ev, p, &out->base))) return rc;
+    out->ms_jump_paths = out->base.ms_paths;
+    out->n_thresholds = t.n_thr;
+    return 0;
+}
+
+}  // extern "C"
