@@ -453,6 +453,69 @@ int omc_jump_table(const omc_params* p, const omc_jump* j, double q, uint32_t th
 int omc_price_american_jump(omc_ctx* ctx, const omc_params* p, const omc_jump* j, double q, omc_jump_result* out,
                             float* S_keep, int64_t ld);
 
+/* ---- multi-asset options: basket, best-of and worst-of ------------------------------------ */
+/* omc_price_american on an INDEX X_t of d correlated GBM assets, 1 <= d <= 8: the payoff is max(K - X, 0) (p->is_put) or
+ * max(X - K, 0), and the two-pass flow regresses on [1, u, u^2] of the index -- the exercise policy is a function of the
+ * index alone.  Two-pass flow (p->semantics = OMC_SEM_TWO_PASS), antithetic pairs (p->antithetic = 1), one GPU, GBM
+ * (p->model = OMC_MODEL_GBM), FULL storage (base.folded = 0).  K, is_put, r, T, the sizes, seed, stream and pair_offset
+ * come from omc_params; p->S0 and p->sigma are NOT read (the omc_params checks run on a copy that carries X_0 and sigma[0]
+ * in their place).
+ * Per asset i: S0[i] > 0, sigma[i] > 0, a continuous yield q[i] (finite, any sign), a weight w[i] > 0 (finite, not
+ *   normalised); rho[i * d + j] is the correlation matrix, row-major in the first d * d entries; kind is OMC_BASKET_*.
+ * Host constants, float64 then rounded once: dt = T / n_steps; rq_i = p->r - q[i];
+ *   a_i = (float)((rq_i - sigma_i^2 / 2) dt log2 e), b_i = (float)(sigma_i sqrt(dt) log2 e) -- omc_gbm_paths_f32's at rate
+ *   rq_i; wf_i = (float)w[i], s0f_i = (float)S0[i]; L = the lower Cholesky factor of rho, row by row (Cholesky-Banachiewicz:
+ *   for j <= i, t = rho[i][j] - sum_{k<j} L[i][k] L[j][k], k ascending; L[i][i] = sqrt(t), L[i][j] = t / L[j][j]), from the
+ *   lower triangle of rho, Lf = (float)L.  rho is refused when an entry is not finite, a diagonal entry is off 1 by more
+ *   than 1e-12, |rho[i][j] - rho[j][i]| > 1e-12, or a pivot t is <= 1e-12.
+ * Normals: asset k of pair p at Philox block blk takes the four normals of the vanilla GBM generator at the pair index
+ *   pair_offset + p + ((uint64_t)k << 40), counter word 2 = blk: the asset tag sits in the PAIR index, so the tagged
+ *   families of the barrier and jump generators are untouched, asset k's independent normals are omc_gbm_normals_f32's at
+ *   pair_offset + (k << 40), and a call with pair_offset + n_paths / 2 > 2^40 is refused.
+ * Correlation, float32, fixed order: y_i = Lf[i][0] z_0, then y_i = fmaf(Lf[i][k], z_k, y_i), k = 1 .. i (Lf[0][0] is
+ *   1.0f exactly, so y_0 = z_0).
+ * Step: e_i = fmaf(b_i, y_i, a_i), s_i *= exp2(e_i); the partner flips EVERY asset's normal: e'_i = fmaf(-b_i, y_i, a_i),
+ *   s'_i *= exp2(e'_i) -- omc_gbm_paths_f32's step per asset.
+ * Index, float32, from the registers the asset rows are stored from:
+ *   OMC_BASKET_ARITHMETIC  X = wf_0 s_0, then X = fmaf(wf_k, s_k, X), k ascending;
+ *   OMC_BASKET_BEST_OF     X = wf_0 s_0, then X = fmaxf(X, wf_k s_k);   OMC_BASKET_WORST_OF the same with fminf;
+ *   OMC_BASKET_GEOMETRIC   a state of its own: g_0 = (float)prod_i S0[i]^w[i] (float64 product, i ascending), and per step
+ *                          g *= exp2(E), E = wf_0 e_0, then E = fmaf(wf_k, e_k, E) (the partner from its own e'_k).
+ *   Row 0 holds the index of the initial spots by the same rule (geometric: g_0).
+ * Storage: the index goes to the context's full-storage matrix or to S_keep ([n_steps+1][ld], ld >= n_paths); with
+ *   assets_keep the per-asset matrices go to that buffer, [d][n_steps+1][ld] (the same ld; without S_keep, ld as passed).
+ *   Columns p and p + n_paths / 2 are the partners, as everywhere else.
+ * What follows: with d = 1, w = 1 and any kind the index matrix is omc_gbm_paths_f32's at rate r - q[0], bit for bit;
+ *   with rho = I asset k's matrix is omc_gbm_paths_f32(S0[k], r - q[k], sigma[k], pair_offset + (k << 40)), bit for bit,
+ *   and asset 0's is that for any rho; the geometric index is a GBM from G_0 = prod S0[i]^w[i] with
+ *   sigma_G^2 = sum_ij w_i w_j sigma_i sigma_j rho_ij and yield q_G = r - sum_i w_i (r - q_i - sigma_i^2 / 2) - sigma_G^2 / 2.
+ * The default flow is the reference's two-pass rule, which sits above the Andersen-Broadie upper bound for a vanilla put
+ *   (DESIGN.md section 12): these prices are not comparable with literature tables of textbook LSM.
+ * omc_basket_table: host only (no context, no device work): the argument checks of omc_price_american_basket and the
+ *   constants -- L_packed [d (d+1) / 2] (row i at i (i+1) / 2, float64), a, b [d], x0 (the index of the initial spots in
+ *   float64: sum w_i S0_i, max / min of w_i S0_i, or G_0), geo [3] = G_0, sigma_G, q_G; any output may be NULL.
+ * Errors (nothing is launched): -7 null ctx / params / out; -12 p->model not GBM; -29 basket NULL or n_assets outside
+ * 1 .. 8; -30 a bad per-asset field; -32 unknown kind; -31 rho refused; then the omc_params checks as omc_price_american
+ * (on the copy); -24 p->antithetic = 0; -11 p->semantics != OMC_SEM_TWO_PASS; -33 pair_offset + n_paths / 2 > 2^40;
+ * -10 a distributed context (one GPU); -6 ld < n_paths (S_keep or assets_keep given). */
+enum { OMC_BASKET_ARITHMETIC = 0, OMC_BASKET_GEOMETRIC = 1, OMC_BASKET_BEST_OF = 2, OMC_BASKET_WORST_OF = 3 };
+#define OMC_BASKET_MAX_ASSETS 8
+typedef struct {
+    int32_t n_assets, kind;                 /* d in 1 .. 8; OMC_BASKET_*                                       */
+    double S0[8], sigma[8], q[8], w[8];     /* per asset: spot, volatility, continuous yield, weight           */
+    double rho[64];                         /* correlation matrix, row-major [d][d] in the first d * d entries */
+} omc_basket;
+typedef struct {
+    omc_result base;        /* as omc_price_american returns it on the index matrix (folded = 0)                   */
+    double ms_basket_paths; /* HIP-event time of the path generator of this call                                   */
+    double index0;          /* the index of the initial spots, float64 (x0 of omc_basket_table)                    */
+    int32_t n_assets, kind;
+} omc_basket_result;
+int omc_basket_table(const omc_params* p, const omc_basket* b, double* L_packed, float* a, float* b_out, double* x0,
+                     double* geo);
+int omc_price_american_basket(omc_ctx* ctx, const omc_params* p, const omc_basket* b, omc_basket_result* out,
+                              float* S_keep, float* assets_keep, int64_t ld);
+
 /* ---- Andersen-Broadie price bounds for American options ----------------------------------- */
 /* A lower and an upper bound on the value of the Bermudan put / call on the pricing grid, both from ONE frozen exercise
  * policy: the lower bound applies the policy as a stopping rule on fresh paths, the upper bound is the Andersen-Broadie

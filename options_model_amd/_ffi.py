@@ -22,6 +22,8 @@ MONITORING = {"discrete": 0, "continuous": 1}
 DIVIDEND_KINDS = {"proportional": 0, "cash": 1}
 # argument errors of the dividend entry points (include/omc.h): raised as DividendError
 DIVIDEND_ERRORS = range(-24, -16)
+BASKET_KINDS = {"basket": 0, "arithmetic": 0, "geometric": 1, "best-of": 2, "worst-of": 3}
+BASKET_MAX_ASSETS = 8
 BOUND_POLICIES = {"reference": 0, "textbook": 1, "two_pass": 2, "given": 3}
 
 
@@ -106,6 +108,18 @@ class JumpResult(C.Structure):
     """omc_jump_result: the pricing plus the generator's time, the compensator, the drift rate and the largest count."""
     _fields_ = [("base", Result), ("ms_jump_paths", C.c_double), ("kappa", C.c_double), ("drift_rate", C.c_double),
                 ("n_thresholds", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Basket(C.Structure):
+    """omc_basket: n_assets (1 .. 8), kind (BASKET_KINDS), per-asset S0 / sigma / q / w, and rho row-major [d][d]."""
+    _fields_ = [("n_assets", C.c_int32), ("kind", C.c_int32), ("S0", C.c_double * 8), ("sigma", C.c_double * 8),
+                ("q", C.c_double * 8), ("w", C.c_double * 8), ("rho", C.c_double * 64)]
+
+
+class BasketResult(C.Structure):
+    """omc_basket_result: the pricing of the index matrix plus the generator's time and the index of the initial spots."""
+    _fields_ = [("base", Result), ("ms_basket_paths", C.c_double), ("index0", C.c_double), ("n_assets", C.c_int32),
+                ("kind", C.c_int32)]
 
 
 class BoundsConfig(C.Structure):
@@ -194,6 +208,9 @@ SIGNATURES = {
                                          _I64]),
     "omc_jump_table": (C.c_int, [C.POINTER(Params), C.POINTER(Jump), _D, _P, C.POINTER(_D), C.POINTER(_D)]),
     "omc_price_american_jump": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Jump), _D, C.POINTER(JumpResult), _P, _I64]),
+    "omc_basket_table": (C.c_int, [C.POINTER(Params), C.POINTER(Basket), _P, _P, _P, C.POINTER(_D), _P]),
+    "omc_price_american_basket": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Basket), C.POINTER(BasketResult), _P, _P,
+                                            _I64]),
     "omc_price_american_bounds": (C.c_int, [_P, C.POINTER(Params), C.POINTER(BoundsConfig), _P, _P, _P, _P,
                                             C.POINTER(Bounds)]),
     "omc_heston_price_strikes": (C.c_int, [_P, _I64, _I] + [_D] * 8 + [_U64, _U64, _I, _P, _I, _I, _P, _P]),
@@ -365,6 +382,45 @@ def jump_table(params: Params, jump, q=0.0):
     _check(lib, lib.omc_jump_table(C.byref(params), C.byref(make_jump(jump)), float(q), thr.ctypes.data, C.byref(kappa),
                                    C.byref(rate)))
     return thr, kappa.value, rate.value
+
+
+def make_basket(spots, sigmas, yields=None, weights=None, correlation=None, kind="basket") -> Basket:
+    """per-asset sequences, a [d][d] correlation (None: identity) and a kind (a key of BASKET_KINDS or its code) -> Basket.
+    Defaults: yields 0, weights 1.  Only the shapes are checked here; the values are the library's to refuse."""
+    S0 = np.atleast_1d(np.asarray(spots, np.float64))
+    d = S0.size
+    if S0.ndim != 1 or not 1 <= d <= BASKET_MAX_ASSETS:
+        raise ValueError(f"a basket has 1 .. {BASKET_MAX_ASSETS} assets.")
+
+    def per_asset(x, default, name):
+        a = np.full(d, default, np.float64) if x is None else np.atleast_1d(np.asarray(x, np.float64))
+        if a.shape != (d,):
+            raise ValueError(f"{name} must have one entry per asset ({d}).")
+        return a
+    rho = np.eye(d) if correlation is None else np.asarray(correlation, np.float64)
+    if rho.shape != (d, d):
+        raise ValueError(f"correlation must be a {d} x {d} matrix.")
+    b = Basket()
+    b.n_assets = d
+    b.kind = BASKET_KINDS.get(kind, -1) if isinstance(kind, str) else int(kind)
+    b.S0[:d], b.sigma[:d] = list(S0), list(per_asset(sigmas, 0.0, "sigmas"))
+    b.q[:d], b.w[:d] = list(per_asset(yields, 0.0, "yields")), list(per_asset(weights, 1.0, "weights"))
+    b.rho[:d * d] = list(rho.ravel())
+    return b
+
+
+def basket_table(params: Params, basket: Basket):
+    """omc_basket_table -> (L float64 [d][d] lower Cholesky factor, a float32 [d], b float32 [d], x0, (G0, sigma_G, q_G)),
+    after the argument checks of Context.price_american_basket.  Host only: no GPU is needed."""
+    lib = load_library()
+    d = min(max(int(basket.n_assets), 1), BASKET_MAX_ASSETS)
+    Lp, a, b = np.zeros(d * (d + 1) // 2), np.zeros(d, np.float32), np.zeros(d, np.float32)
+    x0, geo = C.c_double(), np.zeros(3)
+    _check(lib, lib.omc_basket_table(C.byref(params), C.byref(basket), Lp.ctypes.data, a.ctypes.data, b.ctypes.data,
+                                     C.byref(x0), geo.ctypes.data))
+    L = np.zeros((d, d))
+    L[np.tril_indices(d)] = Lp
+    return L, a, b, x0.value, tuple(geo)
 
 
 def device_count() -> int:
@@ -755,6 +811,26 @@ class Context:
                                                            S_keep.shape[1] if S_keep else 0))
         d = out.base.as_dict()
         d.update({k: getattr(out, k) for k, _ in JumpResult._fields_ if k not in ("base", "reserved")})
+        return d
+
+    def price_american_basket(self, params: Params, basket: Basket, S_keep: DeviceArray | None = None,
+                              assets_keep: DeviceArray | None = None):
+        """American option on the index of several correlated GBM assets (omc_price_american_basket) -> dict: the base
+        pricing's keys (as price_american returns them) plus ms_basket_paths, index0, n_assets, kind.  params.S0 and
+        params.sigma are not read.  S_keep: device [n_steps+1][ld] receiving the index matrix; assets_keep: device
+        [n_assets][n_steps+1][ld] receiving the asset matrices (the same ld when both are given)."""
+        ld = (S_keep or assets_keep).shape[-1] if (S_keep or assets_keep) else 0
+        if assets_keep is not None:
+            if assets_keep.shape[:2] != (int(basket.n_assets), int(params.n_steps) + 1):
+                raise ValueError("assets_keep must have shape (n_assets, n_steps + 1, ld).")
+            if S_keep is not None and S_keep.shape[1] != assets_keep.shape[2]:
+                raise ValueError("S_keep and assets_keep must share their leading dimension.")
+        out = BasketResult()
+        _check(self.lib, self.lib.omc_price_american_basket(self.handle, C.byref(params), C.byref(basket), C.byref(out),
+                                                             S_keep.ptr if S_keep else None,
+                                                             assets_keep.ptr if assets_keep else None, ld))
+        d = out.base.as_dict()
+        d.update({k: getattr(out, k) for k, _ in BasketResult._fields_ if k != "base"})
         return d
 
     def price_american_bounds(self, params: Params, policy="textbook", n_lower=1_000_000, n_outer=8192, n_inner=1024,

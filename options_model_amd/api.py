@@ -525,6 +525,88 @@ def price_american_jumps(S0, K, r, sigma, T, n_paths, n_steps, jump_intensity, j
 
 
 @dataclass
+class BasketResult:
+    """price_american_basket: price / stderr (the convention of PriceResult), the exercise counts and the index of the
+    initial spots.  The exercise policy behind the price is a function of the INDEX alone."""
+    price: float
+    stderr: float
+    std: float
+    zero_prob: float
+    n_paths: int
+    n_exercised: int
+    sum_nitm: int
+    index0: float
+    n_assets: int
+    kind: str
+    option_type: str
+    timings_ms: dict = field(default_factory=dict)
+    info: dict = field(default_factory=dict)  # weights, geometric (G0, sigma_G, q_G)
+
+    def __float__(self):
+        return float(self.price)
+
+
+_BASKET_KINDS = ("basket", "geometric", "best-of", "worst-of")
+
+
+def price_american_basket(spots, K, r, sigmas, T, n_paths, n_steps, correlation=None, weights=None, dividend_yields=None,
+                          kind="basket", option_type="put", seed=None, device=None) -> BasketResult:
+    """American option on an index of 1 .. 8 correlated GBM assets (omc_price_american_basket): the
+    two-pass poly LSM of price_american_option on the matrix of the index X_t -- kind "basket" sum w_i S_i, "geometric"
+    prod S_i^w_i, "best-of" max w_i S_i, "worst-of" min w_i S_i -- with the payoff max(K - X, 0) or max(X - K, 0).  The
+    regression is on the index, so the exercise policy is a function of the index alone: the usual dominant regressor for
+    baskets, a deliberately simple policy for best-of / worst-of.  correlation: [d][d], default identity; weights: default
+    1 / d for "basket" and "geometric", 1 for "best-of" and "worst-of"; dividend_yields: default 0; seed: default 42.
+    The flow is the reference's two-pass rule: not comparable with tables of textbook LSM.
+    Antithetic paths, one GPU."""
+    if kind not in _BASKET_KINDS:
+        raise ValueError(f"kind must be one of {list(_BASKET_KINDS)}.")
+    try:
+        S0 = [float(x) for x in spots]
+        sig = [float(x) for x in sigmas]
+    except TypeError:
+        raise ValueError("spots and sigmas must be sequences with one entry per asset.") from None
+    d = len(S0)
+    if not 1 <= d <= _ffi.BASKET_MAX_ASSETS:
+        raise ValueError(f"a basket has 1 .. {_ffi.BASKET_MAX_ASSETS} assets.")
+    if len(sig) != d:
+        raise ValueError("sigmas must have one entry per asset.")
+    w = [1.0 / d if kind in ("basket", "geometric") else 1.0] * d if weights is None else [float(x) for x in weights]
+    q = [0.0] * d if dividend_yields is None else [float(x) for x in dividend_yields]
+    if len(w) != d or len(q) != d:
+        raise ValueError("weights and dividend_yields must have one entry per asset.")
+    if not all(math.isfinite(x) and x > 0.0 for x in S0):
+        raise ValueError("every spot must be finite and positive.")
+    if not all(math.isfinite(x) and x > 0.0 for x in sig):
+        raise ValueError("every sigma must be finite and positive.")
+    if not all(math.isfinite(x) and x > 0.0 for x in w):
+        raise ValueError("every weight must be finite and positive.")
+    if not all(math.isfinite(x) for x in q):
+        raise ValueError("every dividend yield must be finite.")
+    rho = [[1.0 if i == j else 0.0 for j in range(d)] for i in range(d)] if correlation is None else \
+        [[float(x) for x in row] for row in correlation]
+    if len(rho) != d or any(len(row) != d for row in rho):
+        raise ValueError(f"correlation must be a {d} x {d} matrix.")
+    _validate(S0[0], K, T, r, sig[0], n_paths, n_steps, option_type)
+    M = int(n_paths) // 2 * 2
+    if M <= 0:
+        raise ValueError("num_simulations and num_time_steps must be positive integers.")
+    p = _ffi.make_params(model="gbm", is_put=(option_type == "put"), semantics="two_pass", antithetic=True, n_paths=M,
+                         n_steps=int(n_steps), S0=S0[0], K=K, r=r, sigma=sig[0], T=T, seed=42 if seed is None else int(seed))
+    b = _ffi.make_basket(S0, sig, q, w, rho, kind)
+    _, _, _, _, geo = _ffi.basket_table(p, b)  # host only: the library's own checks (the correlation matrix among them)
+    c = _ffi.default_context(device)
+    out = c.price_american_basket(p, b)
+    var = max(out["sumsq"] / M - out["price"] ** 2, 0.0)
+    return BasketResult(price=out["price"], stderr=math.sqrt(var / M), std=out["std"], zero_prob=out["zero_prob"],
+                        n_paths=M, n_exercised=out["n_exercised"], sum_nitm=out["sum_nitm"], index0=out["index0"],
+                        n_assets=d, kind=kind, option_type=option_type,
+                        timings_ms=dict(paths=out["ms_basket_paths"], pass1=out["ms_pass1"], pass2=out["ms_pass2"],
+                                        lsm=out["ms_lsm"], total=out["ms_total"]),
+                        info=dict(weights=w, geometric=dict(G0=geo[0], sigma_G=geo[1], q_G=geo[2])))
+
+
+@dataclass
 class BoundsResult:
     """price_american_bounds: Andersen-Broadie bounds on the value of the BERMUDAN option with exercise dates t = 1..n_steps
     of the grid dt = T / n_steps, all values discounted to t = 0 (Z_t = exp(-r t dt) max(phi(S_t), 0)) -- the textbook

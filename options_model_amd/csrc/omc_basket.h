@@ -1,0 +1,47 @@
+// omc_basket.h -- host interface of the multi-asset path generator (omc_basket.hip): d correlated GBM assets simulated in
+// registers, the index of a basket / best-of / worst-of option stored as the path matrix the two-pass sweeps price
+// (DESIGN.md section 16).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace omc {
+
+constexpr int kBasketMax = 8;                                  // assets at most
+constexpr int kBasketTri = kBasketMax * (kBasketMax + 1) / 2;  // entries of the packed lower triangle
+
+// What the kernel needs of the basket, by value in its argument block (wave-uniform: scalar registers; no device table).
+//   a, b    per asset: the exponent of a step is fmaf(b y, a)  (include/omc.h)
+//   w, s0   (float)weight, (float)spot
+//   L       (float) lower Cholesky factor of the correlation matrix, packed: row i at i (i + 1) / 2
+//   g0      (float)prod S0_i^w_i, the geometric index of the initial spots
+//   kind    OMC_BASKET_*
+struct BasketLaw {
+    float a[kBasketMax], b[kBasketMax], w[kBasketMax], s0[kBasketMax];
+    float L[kBasketTri];
+    float g0;
+    int kind;
+};
+
+struct BasketGen {
+    int d;              // assets, 1 .. kBasketMax
+    int64_t n_paths;    // antithetic: pairs = n_paths / 2
+    int n_steps;
+    uint64_t seed, pair_offset;
+    uint32_t stream;
+    int vec_hint;       // pairs per thread at most: 1, 2, 4; 0 = auto (option "gbm_vec")
+    BasketLaw law;
+    float* S;           // device: the index matrix [N+1][ld], full storage
+    int64_t ld;
+    float* assets;      // device, or null: the asset matrices [d][N+1][ld_assets]
+    int64_t ld_assets;
+};
+
+// pairs per thread an instantiation for d assets holds at most (so that none spills: DESIGN.md 16.3)
+constexpr int basket_vec_cap(int d) { return d <= 2 ? 4 : d <= 4 ? 2 : 1; }
+
+// the generator: rows 0 .. N of both partners of every pair
+hipError_t launch_basket_paths(hipStream_t st, const BasketGen& a);
+
+}  // namespace omc

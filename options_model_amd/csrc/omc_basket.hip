@@ -1,0 +1,219 @@
+// omc_basket.hip -- path generator of the multi-asset options: basket (arithmetic / geometric), best-of and worst-of,
+// DESIGN.md section 16.
+//
+// basket_paths_kernel<D, VEC, KEEP> writes the full-storage matrix of the INDEX X_t of D correlated GBM assets, which the
+// unchanged two-pass LSM sweeps then price.  A lane owns VEC antithetic pairs for all steps and holds the 2 D VEC asset
+// spots (and the 2 VEC geometric states) in registers; only the index leaves, and with KEEP the asset rows too.  Asset k
+// draws the vanilla generator's normals at the pair index pair + (k << 40) (include/omc.h): one Philox block per asset
+// per pair per four steps.  The correlated normals y_i = sum_{k <= i} Lf[i][k] z_k are accumulated while the z_k are
+// generated, k ascending -- the order the header fixes -- so a lane never holds more than one asset's raw normals.  The
+// step of an asset is gbm_paths_body's (omc_paths_dev.h): same counters, same operations.
+//
+// The per-asset constants, the packed Cholesky factor and the kind come by value in the argument block: scalar
+// registers, no table in memory.  D is a template parameter so that every loop over assets unrolls and every index of
+// the constants is a compile-time one; the kind is wave-uniform and switched on where the index is formed.  No
+// grid-stride loop, no LDS; every write is a VEC-wide vector store.
+#include "omc_basket.h"
+#include "omc_paths_dev.h"
+
+#include "../../include/omc.h"
+
+namespace omc {
+
+struct BasketArgs {
+    float* S;       // index matrix [N+1][ld]
+    float* A;       // asset matrices [D][N+1][lda] (KEEP only)
+    int64_t ld, lda, P;
+    int n_steps;
+    uint32_t k0, k1, stream;
+    uint64_t pair_offset;
+};
+
+// the index of one path from its asset spots (KIND arithmetic, best-of or worst-of; the geometric kind has its own state)
+template <int KIND, int D>
+__device__ __forceinline__ float basket_index(const BasketLaw& c, const float (&s)[D])
+{
+    float x = c.w[0] * s[0];
+#pragma unroll
+    for (int k = 1; k < D; ++k) {
+        if constexpr (KIND == OMC_BASKET_ARITHMETIC) x = __builtin_fmaf(c.w[k], s[k], x);
+        else if constexpr (KIND == OMC_BASKET_BEST_OF) x = fmaxf(x, c.w[k] * s[k]);
+        else x = fminf(x, c.w[k] * s[k]);
+    }
+    return x;
+}
+
+template <int D, int VEC, bool KEEP>
+__global__ __launch_bounds__(kBlock) void basket_paths_kernel(BasketArgs g, BasketLaw c)
+{
+    const int64_t P = g.P, ld = g.ld;
+    const int64_t p0 = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * VEC;
+    if (p0 >= P) return;  // (P % VEC == 0: a thread's pairs all exist or none does)
+    const int kind = c.kind;
+    const bool geo = kind == OMC_BASKET_GEOMETRIC;
+    float s[VEC][D], sa[VEC][D], gs[VEC], ga[VEC];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+#pragma unroll
+        for (int k = 0; k < D; ++k) s[v][k] = sa[v][k] = c.s0[k];
+        gs[v] = ga[v] = c.g0;
+    }
+    float* row = g.S + p0;
+    float* arow = KEEP ? g.A + p0 : nullptr;
+    const int64_t astride = KEEP ? (int64_t)(g.n_steps + 1) * g.lda : 0;  // one asset's matrix
+
+    auto store_rows = [&]() {
+        float x[VEC], xa[VEC];
+        if (geo) {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) {
+                x[v] = gs[v];
+                xa[v] = ga[v];
+            }
+        } else if (kind == OMC_BASKET_ARITHMETIC) {  // (the kind is wave-uniform: one scalar branch per row, not per pair)
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) {
+                x[v] = basket_index<OMC_BASKET_ARITHMETIC, D>(c, s[v]);
+                xa[v] = basket_index<OMC_BASKET_ARITHMETIC, D>(c, sa[v]);
+            }
+        } else if (kind == OMC_BASKET_BEST_OF) {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) {
+                x[v] = basket_index<OMC_BASKET_BEST_OF, D>(c, s[v]);
+                xa[v] = basket_index<OMC_BASKET_BEST_OF, D>(c, sa[v]);
+            }
+        } else {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) {
+                x[v] = basket_index<OMC_BASKET_WORST_OF, D>(c, s[v]);
+                xa[v] = basket_index<OMC_BASKET_WORST_OF, D>(c, sa[v]);
+            }
+        }
+        store_vec<VEC>(row, x);
+        store_vec<VEC>(row + P, xa);
+        if constexpr (KEEP) {
+#pragma unroll
+            for (int k = 0; k < D; ++k) {
+                float t[VEC], ta[VEC];
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) {
+                    t[v] = s[v][k];
+                    ta[v] = sa[v][k];
+                }
+                store_vec<VEC>(arow + k * astride, t);
+                store_vec<VEC>(arow + k * astride + P, ta);
+            }
+        }
+    };
+    store_rows();
+
+    const int n_steps = g.n_steps;
+    const int nblk = (n_steps + 3) >> 2;
+    int t = 0;
+    for (int blk = 0; blk < nblk; ++blk) {
+        float y[VEC][D][4];  // the correlated normals of the block's four steps
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) {
+                float z[4];
+                normals4(g.pair_offset + (uint64_t)(p0 + v) + ((uint64_t)k << 40), (uint32_t)blk, g.stream, g.k0, g.k1, z);
+#pragma unroll
+                for (int i = k; i < D; ++i) {
+                    const float l = c.L[i * (i + 1) / 2 + k];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        if (i == 0) y[v][i][j] = z[j];  // Lf[0][0] = 1.0f exactly
+                        else if (k == 0) y[v][i][j] = l * z[j];
+                        else y[v][i][j] = __builtin_fmaf(l, z[j], y[v][i][j]);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (++t > n_steps) break;
+            row += ld;
+            if constexpr (KEEP) arow += g.lda;
+            if (geo) {
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) {
+                    float E = 0.0f, Ea = 0.0f;
+#pragma unroll
+                    for (int k = 0; k < D; ++k) {
+                        const float e = __builtin_fmaf(c.b[k], y[v][k][j], c.a[k]);
+                        const float ea = __builtin_fmaf(-c.b[k], y[v][k][j], c.a[k]);
+                        s[v][k] = s[v][k] * fast_exp2(e);
+                        sa[v][k] = sa[v][k] * fast_exp2(ea);
+                        E = k == 0 ? c.w[0] * e : __builtin_fmaf(c.w[k], e, E);
+                        Ea = k == 0 ? c.w[0] * ea : __builtin_fmaf(c.w[k], ea, Ea);
+                    }
+                    gs[v] = gs[v] * fast_exp2(E);
+                    ga[v] = ga[v] * fast_exp2(Ea);
+                }
+            } else {
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) {
+#pragma unroll
+                    for (int k = 0; k < D; ++k) {
+                        s[v][k] = s[v][k] * fast_exp2(__builtin_fmaf(c.b[k], y[v][k][j], c.a[k]));
+                        sa[v][k] = sa[v][k] * fast_exp2(__builtin_fmaf(-c.b[k], y[v][k][j], c.a[k]));
+                    }
+                }
+            }
+            store_rows();
+        }
+    }
+}
+
+template <int D, int VEC>
+static void launch_basket(hipStream_t st, const BasketArgs& g, const BasketLaw& law, bool keep)
+{
+    const dim3 block(kBlock), grid((unsigned)((g.P / VEC + kBlock - 1) / kBlock));
+    if (keep) hipLaunchKernelGGL((basket_paths_kernel<D, VEC, true>), grid, block, 0, st, g, law);
+    else hipLaunchKernelGGL((basket_paths_kernel<D, VEC, false>), grid, block, 0, st, g, law);
+}
+
+template <int D>
+static void launch_basket_d(hipStream_t st, const BasketArgs& g, const BasketLaw& law, bool keep, int vec)
+{
+    constexpr int CAP = basket_vec_cap(D);
+    if constexpr (CAP >= 4) {
+        if (vec == 4) return launch_basket<D, 4>(st, g, law, keep);
+    }
+    if constexpr (CAP >= 2) {
+        if (vec >= 2) return launch_basket<D, 2>(st, g, law, keep);
+    }
+    launch_basket<D, 1>(st, g, law, keep);
+}
+
+hipError_t launch_basket_paths(hipStream_t st, const BasketGen& a)
+{
+    const int64_t P = a.n_paths / 2;
+    if (P <= 0) return hipSuccess;
+    if (a.d < 1 || a.d > kBasketMax) return hipErrorInvalidValue;
+    int vec = a.vec_hint >= 4 || a.vec_hint <= 0 ? 4 : a.vec_hint >= 2 ? 2 : 1;
+    if (vec > basket_vec_cap(a.d)) vec = basket_vec_cap(a.d);
+    // VEC-wide stores need every row start and the antithetic half aligned (as launch_gbm_paths), in both buffers
+    auto aligned = [&](const float* S, int64_t ld, int v) { return (ld % v) == 0 && ((uintptr_t)S % (4 * v)) == 0; };
+    while (vec > 1 && !((P % vec) == 0 && aligned(a.S, a.ld, vec) &&
+                        (!a.assets || (aligned(a.assets, a.ld_assets, vec) && ((int64_t)(a.n_steps + 1) * a.ld_assets) % vec == 0))))
+        vec >>= 1;
+    BasketArgs g{};
+    g.S = a.S; g.A = a.assets; g.ld = a.ld; g.lda = a.ld_assets; g.P = P; g.n_steps = a.n_steps;
+    g.k0 = (uint32_t)a.seed; g.k1 = (uint32_t)(a.seed >> 32); g.stream = a.stream; g.pair_offset = a.pair_offset;
+    const bool keep = a.assets != nullptr;
+    switch (a.d) {
+    case 1: launch_basket_d<1>(st, g, a.law, keep, vec); break;
+    case 2: launch_basket_d<2>(st, g, a.law, keep, vec); break;
+    case 3: launch_basket_d<3>(st, g, a.law, keep, vec); break;
+    case 4: launch_basket_d<4>(st, g, a.law, keep, vec); break;
+    case 5: launch_basket_d<5>(st, g, a.law, keep, vec); break;
+    case 6: launch_basket_d<6>(st, g, a.law, keep, vec); break;
+    case 7: launch_basket_d<7>(st, g, a.law, keep, vec); break;
+    default: launch_basket_d<8>(st, g, a.law, keep, vec); break;
+    }
+    return hipGetLastError();
+}
+
+}  // namespace omc
