@@ -63,6 +63,13 @@ class Result(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+def _with_base(out):
+    """A result struct that extends omc_result as one dict: the base pricing's keys plus its own fields."""
+    d = out.base.as_dict()
+    d.update({k: getattr(out, k) for k, _ in out._fields_ if k not in ("base", "reserved")})
+    return d
+
+
 class Greeks(C.Structure):
     """omc_greeks: the base pricing plus the frozen-policy pathwise Greeks (omc_price_american_greeks)."""
     _fields_ = [("base", Result),
@@ -763,8 +770,7 @@ class Context:
         _check(self.lib, self.lib.omc_price_american_greeks(self.handle, C.byref(params), float(bump),
                                                              b.ctypes.data if b is not None else None,
                                                              bo.ctypes.data if bo is not None else None, C.byref(g)))
-        d = g.base.as_dict()
-        d.update({k: getattr(g, k) for k, _ in Greeks._fields_ if k != "base"})
+        d = _with_base(g)
         if want_betas:
             d["betas"] = bo
         return d
@@ -784,9 +790,7 @@ class Context:
         _check(self.lib, self.lib.omc_price_barrier(self.handle, C.byref(params), C.byref(b), C.byref(out),
                                                      keep_paths.ptr if keep_paths else None,
                                                      keep_paths.shape[1] if keep_paths else 0))
-        d = out.base.as_dict()
-        d.update({k: getattr(out, k) for k, _ in BarrierResult._fields_ if k != "base"})
-        return d
+        return _with_base(out)
 
     def price_american_div(self, params: Params, q=0.0, dividends=(), S_keep: DeviceArray | None = None):
         """American option on a stock with a dividend yield q and discrete dividends (omc_price_american_div) -> dict: the
@@ -797,9 +801,7 @@ class Context:
         _check(self.lib, self.lib.omc_price_american_div(self.handle, C.byref(params), float(q), arr, n, C.byref(out),
                                                           S_keep.ptr if S_keep else None,
                                                           S_keep.shape[1] if S_keep else 0))
-        d = out.base.as_dict()
-        d.update({k: getattr(out, k) for k, _ in DivResult._fields_ if k != "base"})
-        return d
+        return _with_base(out)
 
     def price_american_jump(self, params: Params, jump, q=0.0, S_keep: DeviceArray | None = None):
         """American option under jump-diffusion (omc_price_american_jump: Merton on GBM, Bates on Heston) -> dict: the
@@ -809,9 +811,7 @@ class Context:
         _check(self.lib, self.lib.omc_price_american_jump(self.handle, C.byref(params), C.byref(make_jump(jump)), float(q),
                                                            C.byref(out), S_keep.ptr if S_keep else None,
                                                            S_keep.shape[1] if S_keep else 0))
-        d = out.base.as_dict()
-        d.update({k: getattr(out, k) for k, _ in JumpResult._fields_ if k not in ("base", "reserved")})
-        return d
+        return _with_base(out)
 
     def price_american_basket(self, params: Params, basket: Basket, S_keep: DeviceArray | None = None,
                               assets_keep: DeviceArray | None = None):
@@ -829,9 +829,7 @@ class Context:
         _check(self.lib, self.lib.omc_price_american_basket(self.handle, C.byref(params), C.byref(basket), C.byref(out),
                                                              S_keep.ptr if S_keep else None,
                                                              assets_keep.ptr if assets_keep else None, ld))
-        d = out.base.as_dict()
-        d.update({k: getattr(out, k) for k, _ in BasketResult._fields_ if k != "base"})
-        return d
+        return _with_base(out)
 
     def price_american_bounds(self, params: Params, policy="textbook", n_lower=1_000_000, n_outer=8192, n_inner=1024,
                               stream_lower=None, stream_outer=None, stream_inner=None, betas=None, want_q=False,

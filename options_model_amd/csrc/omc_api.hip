@@ -589,6 +589,53 @@ int read_kernel_times(const hipEvent_t* evs, const omc_params* p, omc_result* re
     return 0;
 }
 
+// ------------------------------------------------------------------ generate, then the two-pass sweeps
+omc::PathSpec path_spec(const omc_ctx* c, const omc_params* p, double drift_rate, float* S, int64_t ld)
+{
+    omc::PathSpec g{};
+    g.model = p->model == OMC_MODEL_GBM ? 0 : 1; g.scheme = p->heston_scheme;
+    g.n_paths = p->n_paths; g.n_steps = p->n_steps;
+    g.S0 = p->S0; g.r = drift_rate; g.sigma = p->sigma; g.T = p->T;
+    g.v0 = p->v0; g.kappa = p->kappa; g.theta = p->theta; g.xi = p->xi; g.rho = p->rho;
+    g.seed = p->seed; g.pair_offset = p->pair_offset; g.stream = (uint32_t)p->stream;
+    g.vec_hint = g.model == 0 ? c->gbm_vec : c->heston_vec;
+    g.S = S; g.ld = ld;
+    return g;
+}
+
+int take_full_matrix(omc_ctx* c, const omc_params* p, float* S_keep, float** S, int64_t* ld)
+{
+    if (S_keep && *ld < p->n_paths) return fail(-6, "leading dimension smaller than n_paths.");
+    *S = S_keep;
+    return S_keep ? 0 : ensure_paths(c, p, Storage::full_only, S, ld);
+}
+
+int enqueue_generated(omc_ctx* c, const omc_params* p, const float* S, int64_t ld,
+                      const std::function<hipError_t(hipStream_t)>& gen)
+{
+    int rc;
+    omc::LsmWorkspace w;
+    if ((rc = prepare_lsm(c, p->n_paths, p->n_steps, p->r, p->T, true, false, &w))) return rc;
+    HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+    HIP_TRY(gen(c->stream));
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    omc::LsmProblem prob{S, ld, p->n_paths, p->n_steps, p->is_put ? 1 : 0, p->K, p->r, p->T};
+    w.ev_p1_end = c->ev[4]; w.ev_p2_begin = c->ev[5]; w.ev_p2_end = c->ev[6];
+    if ((rc = enqueue_lsm(c, prob, w, OMC_SEM_TWO_PASS, false))) return rc;
+    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+    HIP_TRY(hipMemcpyAsync(c->hres, w.result, sizeof(double) * 8, hipMemcpyDeviceToHost, c->stream));
+    return 0;
+}
+
+int finish_generated(omc_ctx* c, const omc_params* p, omc_result* base)
+{
+    int rc;
+    if ((rc = wait_stream(c))) return rc;
+    fill_result(base, c->hres, p->n_paths);
+    base->folded = 0;
+    return read_kernel_times(c->ev, p, base);
+}
+
 }  // namespace omc::abi
 
 using namespace omc::abi;

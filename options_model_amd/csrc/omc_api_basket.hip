@@ -83,12 +83,8 @@ int compose_basket(const omc_params* p, const omc_basket* k, BasketTable* t)
     const uint64_t lim = (uint64_t)1 << 40, pairs = (uint64_t)(p->n_paths / 2);
     if (p->pair_offset > lim || pairs > lim - p->pair_offset)
         return fail(-33, "pair_offset + n_paths / 2 must not exceed 2^40 (the asset tag sits above it).");
-    const double dt = p->T / p->n_steps, L2E = 1.4426950408889634074;
-    for (int i = 0; i < d; ++i) {
-        const double rq = p->r - k->q[i];  // one float64 subtraction, as omc_price_american_div forms its rate
-        t->a[i] = (float)((rq - 0.5 * k->sigma[i] * k->sigma[i]) * dt * L2E);
-        t->b[i] = (float)(k->sigma[i] * std::sqrt(dt) * L2E);
-    }
+    for (int i = 0; i < d; ++i)  // (the rate: one float64 subtraction, as omc_price_american_div forms its own)
+        omc::gbm_step_constants(p->r - k->q[i], k->sigma[i], p->T, p->n_steps, &t->a[i], &t->b[i]);
     return 0;
 }
 
@@ -122,20 +118,17 @@ int omc_price_american_basket(omc_ctx* c, const omc_params* p, const omc_basket*
     BasketTable t;
     if ((rc = compose_basket(p, b, &t))) return rc;
     if (c->distributed()) return fail(-10, "multi-asset pricing runs on one GPU.");
-    if ((S_keep || assets_keep) && ld < p->n_paths) return fail(-6, "leading dimension smaller than n_paths.");
-    const int64_t M = p->n_paths;
-    const int N = p->n_steps;
+    if (assets_keep && ld < p->n_paths) return fail(-6, "leading dimension smaller than n_paths.");
+    float* S;
+    int64_t ld_index = ld;  // (the library's own index matrix has its own leading dimension)
+    if ((rc = take_full_matrix(c, p, S_keep, &S, &ld_index))) return rc;
     memset(out, 0, sizeof *out);
     out->index0 = t.x0;
     out->n_assets = t.d;
     out->kind = b->kind;
-    float* S = S_keep;
-    int64_t ld_index = ld;
-    if (!S && (rc = ensure_paths(c, p, Storage::full_only, &S, &ld_index))) return rc;
     omc::BasketGen g{};
-    g.d = t.d; g.n_paths = M; g.n_steps = N;
-    g.seed = p->seed; g.pair_offset = p->pair_offset; g.stream = (uint32_t)p->stream;
-    g.vec_hint = c->gbm_vec;
+    g.paths = path_spec(c, p, p->r, S, ld_index);
+    g.d = t.d;
     for (int i = 0; i < t.d; ++i) {
         g.law.a[i] = t.a[i];
         g.law.b[i] = t.b[i];
@@ -145,22 +138,9 @@ int omc_price_american_basket(omc_ctx* c, const omc_params* p, const omc_basket*
     for (int i = 0; i < t.d * (t.d + 1) / 2; ++i) g.law.L[i] = (float)t.L[i];
     g.law.g0 = (float)t.G0;
     g.law.kind = b->kind;
-    g.S = S; g.ld = ld_index;
     g.assets = assets_keep; g.ld_assets = ld;
-    omc::LsmWorkspace w;
-    if ((rc = prepare_lsm(c, M, N, p->r, p->T, true, false, &w))) return rc;
-    HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-    HIP_TRY(omc::launch_basket_paths(c->stream, g));
-    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-    omc::LsmProblem prob{S, ld_index, M, N, p->is_put ? 1 : 0, p->K, p->r, p->T};
-    w.ev_p1_end = c->ev[4]; w.ev_p2_begin = c->ev[5]; w.ev_p2_end = c->ev[6];
-    if ((rc = enqueue_lsm(c, prob, w, OMC_SEM_TWO_PASS, false))) return rc;
-    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
-    HIP_TRY(hipMemcpyAsync(c->hres, w.result, sizeof(double) * 8, hipMemcpyDeviceToHost, c->stream));
-    if ((rc = wait_stream(c))) return rc;
-    fill_result(&out->base, c->hres, M);
-    out->base.folded = 0;
-    if ((rc = read_kernel_times(c->ev, p, &out->base))) return rc;
+    if ((rc = enqueue_generated(c, p, S, ld_index, [&](hipStream_t st) { return omc::launch_basket_paths(st, g); }))) return rc;
+    if ((rc = finish_generated(c, p, &out->base))) return rc;
     out->ms_basket_paths = out->base.ms_paths;
     return 0;
 }

@@ -52,11 +52,9 @@ extern "C" int omc_price_american_bounds(omc_ctx* c, const omc_params* p, const 
     double* res = (double*)(b + o_res);
 
     omc::BoundsArgs a{};
-    const double dt = p->T / N, L2E = 1.4426950408889634074;
     a.N = N; a.is_put = p->is_put ? 1 : 0; a.K = p->K; a.invK = 1.0 / p->K;
-    a.s0 = (float)p->S0;  // launch_gbm_paths' constants, so every spot is the generator's
-    a.a = (float)((p->r - 0.5 * p->sigma * p->sigma) * dt * L2E);
-    a.b = (float)(p->sigma * std::sqrt(dt) * L2E);
+    a.s0 = (float)p->S0;  // the generator's start value and step constants, so every spot is the generator's
+    omc::gbm_step_constants(p->r, p->sigma, p->T, N, &a.a, &a.b);
     a.k0 = (uint32_t)p->seed; a.k1 = (uint32_t)(p->seed >> 32);
     a.D = w.D; a.betas = w.betas; a.tab = (uint32_t*)(b + o_tab);
     a.n_lower = nl; a.stream_lower = (uint32_t)cfg->stream_lower;

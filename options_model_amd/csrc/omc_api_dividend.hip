@@ -86,8 +86,6 @@ int omc_price_american_div(omc_ctx* c, const omc_params* p, double q, const omc_
     std::vector<int32_t> has;
     if ((rc = compose_schedule(p, q, d, n_div, &mul, &cash, &has))) return rc;
     if (c->distributed()) return fail(-10, "dividend pricing runs on one GPU.");
-    if (S_keep && ld < p->n_paths) return fail(-6, "leading dimension smaller than n_paths.");
-    const int64_t M = p->n_paths;
     const int N = p->n_steps;
     omc_params gen = *p;  // the generator / fold-table side drifts at r - q; the sweeps discount at p->r
     gen.r = p->r - q;
@@ -110,32 +108,13 @@ int omc_price_american_div(omc_ctx* c, const omc_params* p, double q, const omc_
     }
     tab[n_ent] = omc::DivEntry{omc::kDivNoStep, 1.0f, 0.0f, 0};
     if ((rc = c->div_tab.ensure(c->h_table.size()))) return rc;
-    float* S = S_keep;
-    if (!S && (rc = ensure_paths(c, p, Storage::full_only, &S, &ld))) return rc;
-    omc::DividendGen g{};
-    g.model = p->model == OMC_MODEL_GBM ? 0 : 1; g.scheme = p->heston_scheme;
-    g.n_paths = M; g.n_steps = N;
-    g.S0 = p->S0; g.r = gen.r; g.sigma = p->sigma; g.T = p->T;
-    g.v0 = p->v0; g.kappa = p->kappa; g.theta = p->theta; g.xi = p->xi; g.rho = p->rho;
-    g.seed = p->seed; g.pair_offset = p->pair_offset; g.stream = (uint32_t)p->stream;
-    g.vec_hint = g.model == 0 ? c->gbm_vec : c->heston_vec;
-    g.tab = (const omc::DivEntry*)c->div_tab.p;
-    g.S = S; g.ld = ld;
-    omc::LsmWorkspace w;
-    if ((rc = prepare_lsm(c, M, N, p->r, p->T, true, false, &w))) return rc;
+    float* S;
+    if ((rc = take_full_matrix(c, p, S_keep, &S, &ld))) return rc;
+    const omc::DividendGen g{path_spec(c, p, gen.r, S, ld), (const omc::DivEntry*)c->div_tab.p};
+    // (the table's copy stays ahead of event 0: ms_div_paths is the generator alone)
     HIP_TRY(hipMemcpyAsync(c->div_tab.p, tab, c->h_table.size(), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-    HIP_TRY(omc::launch_dividend_paths(c->stream, g));
-    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-    omc::LsmProblem prob{S, ld, M, N, p->is_put ? 1 : 0, p->K, p->r, p->T};
-    w.ev_p1_end = c->ev[4]; w.ev_p2_begin = c->ev[5]; w.ev_p2_end = c->ev[6];
-    if ((rc = enqueue_lsm(c, prob, w, OMC_SEM_TWO_PASS, false))) return rc;
-    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
-    HIP_TRY(hipMemcpyAsync(c->hres, w.result, sizeof(double) * 8, hipMemcpyDeviceToHost, c->stream));
-    if ((rc = wait_stream(c))) return rc;
-    fill_result(&out->base, c->hres, M);
-    out->base.folded = 0;
-    if ((rc = read_kernel_times(c->ev, p, &out->base))) return rc;
+    if ((rc = enqueue_generated(c, p, S, ld, [&](hipStream_t st) { return omc::launch_dividend_paths(st, g); }))) return rc;
+    if ((rc = finish_generated(c, p, &out->base))) return rc;
     out->ms_div_paths = out->base.ms_paths;
     out->n_div_steps = (int32_t)n_ent;
     out->first_div_step = first;

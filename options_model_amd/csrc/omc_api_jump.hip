@@ -68,9 +68,6 @@ int omc_price_american_jump(omc_ctx* c, const omc_params* p, const omc_jump* j, 
     JumpTable t;
     if ((rc = compose_jump(p, j, q, &t))) return rc;
     if (c->distributed()) return fail(-10, "jump-diffusion pricing runs on one GPU.");
-    if (S_keep && ld < p->n_paths) return fail(-6, "leading dimension smaller than n_paths.");
-    const int64_t M = p->n_paths;
-    const int N = p->n_steps;
     memset(out, 0, sizeof *out);
     out->kappa = t.kappa;
     out->drift_rate = t.drift_rate;
@@ -81,34 +78,15 @@ int omc_price_american_jump(omc_ctx* c, const omc_params* p, const omc_jump* j, 
         out->ms_jump_paths = out->base.ms_paths;
         return 0;
     }
-    float* S = S_keep;
-    if (!S && (rc = ensure_paths(c, p, Storage::full_only, &S, &ld))) return rc;
-    omc::JumpGen g{};
-    g.model = p->model == OMC_MODEL_GBM ? 0 : 1; g.scheme = p->heston_scheme;
-    g.n_paths = M; g.n_steps = N;
-    g.S0 = p->S0; g.r = t.drift_rate; g.sigma = p->sigma; g.T = p->T;
-    g.v0 = p->v0; g.kappa = p->kappa; g.theta = p->theta; g.xi = p->xi; g.rho = p->rho;
-    g.seed = p->seed; g.pair_offset = p->pair_offset; g.stream = (uint32_t)p->stream;
-    g.vec_hint = g.model == 0 ? c->gbm_vec : c->heston_vec;
+    float* S;
+    if ((rc = take_full_matrix(c, p, S_keep, &S, &ld))) return rc;
+    omc::JumpGen g{path_spec(c, p, t.drift_rate, S, ld), {}};
     memcpy(g.law.thr, t.thr, sizeof t.thr);
     const double L2E = 1.4426950408889634074;
     g.law.mj2 = (float)(j->mu_j * L2E);
     g.law.sj2 = (float)(j->sigma_j * L2E);
-    g.S = S; g.ld = ld;
-    omc::LsmWorkspace w;
-    if ((rc = prepare_lsm(c, M, N, p->r, p->T, true, false, &w))) return rc;
-    HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-    HIP_TRY(omc::launch_jump_paths(c->stream, g));
-    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-    omc::LsmProblem prob{S, ld, M, N, p->is_put ? 1 : 0, p->K, p->r, p->T};
-    w.ev_p1_end = c->ev[4]; w.ev_p2_begin = c->ev[5]; w.ev_p2_end = c->ev[6];
-    if ((rc = enqueue_lsm(c, prob, w, OMC_SEM_TWO_PASS, false))) return rc;
-    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
-    HIP_TRY(hipMemcpyAsync(c->hres, w.result, sizeof(double) * 8, hipMemcpyDeviceToHost, c->stream));
-    if ((rc = wait_stream(c))) return rc;
-    fill_result(&out->base, c->hres, M);
-    out->base.folded = 0;
-    if ((rc = read_kernel_times(c->ev, p, &out->base))) return rc;
+    if ((rc = enqueue_generated(c, p, S, ld, [&](hipStream_t st) { return omc::launch_jump_paths(st, g); }))) return rc;
+    if ((rc = finish_generated(c, p, &out->base))) return rc;
     out->ms_jump_paths = out->base.ms_paths;
     out->n_thresholds = t.n_thr;
     return 0;

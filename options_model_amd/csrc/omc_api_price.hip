@@ -364,40 +364,31 @@ int omc_price_barrier(omc_ctx* c, const omc_params* p, const omc_barrier* b, omc
     if (c->distributed()) return fail(-10, "barrier pricing runs on one GPU.");
     if (S_keep && ld < p->n_paths) return fail(-6, "leading dimension smaller than n_paths.");
     const int64_t M = p->n_paths;
-    const int N = p->n_steps;
     float* S = S_keep;
     if (b->american && !S && (rc = ensure_paths(c, p, Storage::full_only, &S, &ld))) return rc;
     omc::BarrierGen g{};
-    g.model = p->model == OMC_MODEL_GBM ? 0 : 1; g.scheme = p->heston_scheme;
-    g.n_paths = M; g.n_steps = N;
-    g.S0 = p->S0; g.r = p->r; g.sigma = p->sigma; g.T = p->T;
-    g.v0 = p->v0; g.kappa = p->kappa; g.theta = p->theta; g.xi = p->xi; g.rho = p->rho;
-    g.seed = p->seed; g.pair_offset = p->pair_offset; g.stream = (uint32_t)p->stream;
+    g.paths = path_spec(c, p, p->r, S, S ? ld : 0);
     g.is_put = p->is_put ? 1 : 0; g.up = up;
     g.knock_in = (b->kind == OMC_BARRIER_DOWN_IN || b->kind == OMC_BARRIER_UP_IN) ? 1 : 0;
     g.continuous = b->monitoring == OMC_MONITOR_CONTINUOUS ? 1 : 0;
     g.K = p->K; g.H = b->H;
-    g.S = S; g.ld = S ? ld : 0;
     const int64_t nblk = omc::barrier_blocks(g);
     if ((rc = c->bar_part.ensure(sizeof(double) * omc::kBarrierQ * (size_t)nblk))) return rc;
     if ((rc = c->bar_res.ensure(sizeof(double) * omc::kBarrierQ))) return rc;
     g.part = (double*)c->bar_part.p;
     g.result = (double*)c->bar_res.p;
-    omc::LsmWorkspace w;
-    if (b->american && (rc = prepare_lsm(c, M, N, p->r, p->T, true, false, &w))) return rc;
-    HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-    HIP_TRY(omc::launch_barrier_paths(c->stream, g));
-    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    const auto gen = [&](hipStream_t st) { return omc::launch_barrier_paths(st, g); };
     if (b->american) {
-        omc::LsmProblem prob{S, ld, M, N, p->is_put ? 1 : 0, p->K, p->r, p->T};
-        w.ev_p1_end = c->ev[4]; w.ev_p2_begin = c->ev[5]; w.ev_p2_end = c->ev[6];
-        if ((rc = enqueue_lsm(c, prob, w, OMC_SEM_TWO_PASS, false))) return rc;
-        HIP_TRY(hipEventRecord(c->ev[2], c->stream));
-        HIP_TRY(hipMemcpyAsync(c->hres, w.result, sizeof(double) * 8, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = enqueue_generated(c, p, S, ld, gen))) return rc;
+    } else {
+        HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+        HIP_TRY(gen(c->stream));
+        HIP_TRY(hipEventRecord(c->ev[1], c->stream));
     }
     double h[omc::kBarrierQ];
     HIP_TRY(hipMemcpyAsync(h, g.result, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    if ((rc = wait_stream(c))) return rc;
+    omc_result american;
+    if ((rc = b->american ? finish_generated(c, p, &american) : wait_stream(c))) return rc;
     memset(out, 0, sizeof *out);
     const double Md = (double)M;
     mean_and_se(h[0], h[1], Md, &out->euro_out, &out->euro_out_se);
@@ -407,9 +398,7 @@ int omc_price_barrier(omc_ctx* c, const omc_params* p, const omc_barrier* b, omc
     HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
     out->ms_barrier_paths = ms;
     if (b->american) {
-        fill_result(&out->base, c->hres, M);
-        out->base.folded = 0;
-        if ((rc = read_kernel_times(c->ev, p, &out->base))) return rc;
+        out->base = american;
     } else {  // the European option of `kind`
         const int q = g.knock_in ? 2 : 0;
         const double e[8] = {h[q], h[q + 1], 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};

@@ -5,6 +5,8 @@
 
 #include <cstdint>
 
+#include "omc_kernels.h"
+
 namespace omc {
 
 // Sums the generator leaves in its result buffer (kBarrierQ doubles, float64, fixed order), over both partners of
@@ -13,20 +15,12 @@ namespace omc {
 constexpr int kBarrierQ = 8;
 
 struct BarrierGen {
-    // the model (as launch_gbm_paths / launch_heston_paths take it)
-    int model, scheme;  // model 0 GBM, 1 Heston (scheme 0, 1, 2)
-    int64_t n_paths;    // antithetic: pairs = n_paths / 2
-    int n_steps;
-    double S0, r, sigma, T, v0, kappa, theta, xi, rho;
-    uint64_t seed, pair_offset;
-    uint32_t stream;
+    // S = the encoded matrix [N+1][ld] (null: sums only, nothing stored); vec_hint is not read (barrier_vec)
+    PathSpec paths;
     // the contract
     int is_put, up, knock_in, continuous;
     double K, H;
-    // outputs: S = encoded matrix [N+1][ld] (null: sums only, nothing stored); part = per-workgroup partials
-    // [kBarrierQ][barrier_blocks(..)], result = kBarrierQ doubles
-    float* S;
-    int64_t ld;
+    // outputs: part = per-workgroup partials [kBarrierQ][barrier_blocks(..)], result = kBarrierQ doubles
     double* part;
     double* result;
 };

@@ -30,8 +30,6 @@
 
 namespace omc {
 
-HestonC make_heston(double r, double T, int n_steps, double kappa, double theta, double xi, double rho);
-
 struct BarArgs {
     PathArgs g;  // S (null for STORE = false), ld, P = pairs, n_steps, s_init, a, b, v_init, hc, Philox key / stream / offset
     int is_put, knock_in;
@@ -123,7 +121,7 @@ __device__ __forceinline__ void barrier_paths_body(const BarArgs& A)
                             xa[v] = xna;
                         }
                     } else {
-                        heston_pair_step<MODEL - 1>(g.hc, z[v][2 * i], z[v][2 * i + 1], s[v], va[v], sa[v], vb[v]);
+                        pair_step<MODEL>(g, z[v], i, s[v], va[v], sa[v], vb[v]);
                     }
                     h[v] |= sg * s[v] <= sthr;
                     ha[v] |= sg * sa[v] <= sthr;
@@ -206,68 +204,51 @@ float barrier_threshold(double H, int up)
 
 int barrier_vec(const BarrierGen& a)
 {
-    return ((a.n_paths / 2) % 4) == 0 ? 4 : 1;  // from the geometry only: both kernels reduce in the same order
+    return ((a.paths.n_paths / 2) % 4) == 0 ? 4 : 1;  // from the geometry only: both kernels reduce in the same order
 }
 
 int64_t barrier_blocks(const BarrierGen& a)
 {
     const int64_t per = (int64_t)kBlock * barrier_vec(a);
-    const int64_t P = a.n_paths / 2;
+    const int64_t P = a.paths.n_paths / 2;
     return P > 0 ? (P + per - 1) / per : 1;
 }
 
 hipError_t launch_barrier_paths(hipStream_t st, const BarrierGen& a)
 {
-    const double dt = a.T / a.n_steps, L2E = 1.4426950408889634074;
+    const PathSpec& s = a.paths;
     const int vec = barrier_vec(a);
     const int64_t nblk = barrier_blocks(a);
     BarArgs A{};
-    PathArgs& g = A.g;
-    g.S = a.S; g.ld = a.ld; g.P = a.n_paths / 2; g.n_steps = a.n_steps;
-    g.s_init = (float)a.S0; g.v_init = (float)a.v0;
-    g.a = (float)((a.r - 0.5 * a.sigma * a.sigma) * dt * L2E);
-    g.b = (float)(a.sigma * sqrt(dt) * L2E);
-    if (a.model != 0) g.hc = make_heston(a.r, a.T, a.n_steps, a.kappa, a.theta, a.xi, a.rho);
-    g.k0 = (uint32_t)a.seed; g.k1 = (uint32_t)(a.seed >> 32); g.stream = a.stream; g.pair_offset = a.pair_offset;
+    A.g = make_path_args(s, s.n_paths / 2);
     A.is_put = a.is_put; A.knock_in = a.knock_in;
-    const bool vstore = a.S && vec > 1 && (g.ld % vec) == 0 && ((uintptr_t)a.S % (4 * vec)) == 0;
+    const bool vstore = s.S && vec > 1 && store_aligned(vec, A.g.P, s.S, s.ld);
     const float thr = barrier_threshold(a.H, a.up);
     A.sg = a.up ? -1.0f : 1.0f;
     A.sthr = a.up ? -thr : thr;
     A.dead = barrier_dead_spot(a.K, a.is_put);
-    A.x0 = (float)std::log2((double)(float)a.S0 / a.H);
-    A.cbr = a.model == 0 ? (float)(-2.0 * 0.69314718055994530942 / (a.sigma * a.sigma * dt)) : 0.0f;
-    A.K = a.K; A.df = exp(-a.r * a.T); A.part = a.part;
+    A.x0 = (float)std::log2((double)(float)s.S0 / a.H);
+    A.cbr = s.model == 0 ? (float)(-2.0 * 0.69314718055994530942 / (s.sigma * s.sigma * (s.T / s.n_steps))) : 0.0f;
+    A.K = a.K; A.df = exp(-s.r * s.T); A.part = a.part;
     const dim3 grid((unsigned)nblk), block(kBlock);
-    auto go = [&](auto model, auto store, auto mon) {
-        constexpr int MO = decltype(model)::value, MN = decltype(mon)::value;
-        constexpr bool STO = decltype(store)::value;
-        bool launched = false;
-        if constexpr (STO) {  // (VEC-wide stores only where there are stores)
-            if (vec == 4 && vstore) {
-                hipLaunchKernelGGL((barrier_paths_kernel<MO, STO, MN, 4, true>), grid, block, 0, st, A);
-                launched = true;
+    auto go = [&](auto store, auto mon) {
+        for_model(s.model, s.scheme, [&](auto model) {
+            constexpr int MO = decltype(model)::value, MN = decltype(mon)::value;
+            constexpr bool STO = decltype(store)::value;
+            if constexpr (MN == 0 || MO == 0) {  // (continuous monitoring is GBM only)
+                if (STO && vec == 4 && vstore)  // (VEC-wide stores only where there are stores)
+                    hipLaunchKernelGGL((barrier_paths_kernel<MO, STO, MN, 4, STO>), grid, block, 0, st, A);
+                else if (vec == 4) hipLaunchKernelGGL((barrier_paths_kernel<MO, STO, MN, 4, false>), grid, block, 0, st, A);
+                else hipLaunchKernelGGL((barrier_paths_kernel<MO, STO, MN, 1, false>), grid, block, 0, st, A);
             }
-        }
-        if (launched) return;
-        if (vec == 4) hipLaunchKernelGGL((barrier_paths_kernel<MO, STO, MN, 4, false>), grid, block, 0, st, A);
-        else hipLaunchKernelGGL((barrier_paths_kernel<MO, STO, MN, 1, false>), grid, block, 0, st, A);
+        });
     };
-    auto by_model = [&](auto store) {
-        using std::integral_constant;
-        if (a.model == 0) {
-            if (a.continuous) go(integral_constant<int, 0>{}, store, integral_constant<int, 1>{});
-            else go(integral_constant<int, 0>{}, store, integral_constant<int, 0>{});
-        } else if (a.scheme == 0) {
-            go(integral_constant<int, 1>{}, store, integral_constant<int, 0>{});
-        } else if (a.scheme == 1) {
-            go(integral_constant<int, 2>{}, store, integral_constant<int, 0>{});
-        } else {
-            go(integral_constant<int, 3>{}, store, integral_constant<int, 0>{});
-        }
+    auto by_monitoring = [&](auto store) {
+        if (s.model == 0 && a.continuous) go(store, std::integral_constant<int, 1>{});
+        else go(store, std::integral_constant<int, 0>{});
     };
-    if (a.S) by_model(std::integral_constant<bool, true>{});
-    else by_model(std::integral_constant<bool, false>{});
+    if (s.S) by_monitoring(std::true_type{});
+    else by_monitoring(std::false_type{});
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(barrier_finalize_kernel, dim3(1), dim3(kBlock), 0, st, (const double*)a.part, nblk, a.result);

@@ -6,6 +6,8 @@
 
 #include <cstdint>
 
+#include "omc_kernels.h"
+
 namespace omc {
 
 constexpr int kBasketMax = 8;                                  // assets at most
@@ -25,15 +27,11 @@ struct BasketLaw {
 };
 
 struct BasketGen {
+    // geometry, Philox coordinates, vec_hint (pairs per thread at most, option "gbm_vec") and S = the index matrix
+    // [N+1][ld], full storage; its single-asset model fields are not read: the assets are in `law`
+    PathSpec paths;
     int d;              // assets, 1 .. kBasketMax
-    int64_t n_paths;    // antithetic: pairs = n_paths / 2
-    int n_steps;
-    uint64_t seed, pair_offset;
-    uint32_t stream;
-    int vec_hint;       // pairs per thread at most: 1, 2, 4; 0 = auto (option "gbm_vec")
     BasketLaw law;
-    float* S;           // device: the index matrix [N+1][ld], full storage
-    int64_t ld;
     float* assets;      // device, or null: the asset matrices [d][N+1][ld_assets]
     int64_t ld_assets;
 };

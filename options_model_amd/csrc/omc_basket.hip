@@ -189,19 +189,18 @@ static void launch_basket_d(hipStream_t st, const BasketArgs& g, const BasketLaw
 
 hipError_t launch_basket_paths(hipStream_t st, const BasketGen& a)
 {
-    const int64_t P = a.n_paths / 2;
+    const PathSpec& s = a.paths;
+    const int64_t P = s.n_paths / 2;
     if (P <= 0) return hipSuccess;
     if (a.d < 1 || a.d > kBasketMax) return hipErrorInvalidValue;
-    int vec = a.vec_hint >= 4 || a.vec_hint <= 0 ? 4 : a.vec_hint >= 2 ? 2 : 1;
+    int vec = s.vec_hint >= 4 || s.vec_hint <= 0 ? 4 : s.vec_hint >= 2 ? 2 : 1;
     if (vec > basket_vec_cap(a.d)) vec = basket_vec_cap(a.d);
-    // VEC-wide stores need every row start and the antithetic half aligned (as launch_gbm_paths), in both buffers
-    auto aligned = [&](const float* S, int64_t ld, int v) { return (ld % v) == 0 && ((uintptr_t)S % (4 * v)) == 0; };
-    while (vec > 1 && !((P % vec) == 0 && aligned(a.S, a.ld, vec) &&
-                        (!a.assets || (aligned(a.assets, a.ld_assets, vec) && ((int64_t)(a.n_steps + 1) * a.ld_assets) % vec == 0))))
-        vec >>= 1;
+    // VEC-wide stores in both buffers (asset k's matrix starts k (N + 1) ld_assets floats in: aligned where its rows are)
+    vec = store_vec_width(vec, P, s.S, s.ld);
+    if (a.assets) vec = store_vec_width(vec, P, a.assets, a.ld_assets);
     BasketArgs g{};
-    g.S = a.S; g.A = a.assets; g.ld = a.ld; g.lda = a.ld_assets; g.P = P; g.n_steps = a.n_steps;
-    g.k0 = (uint32_t)a.seed; g.k1 = (uint32_t)(a.seed >> 32); g.stream = a.stream; g.pair_offset = a.pair_offset;
+    g.S = s.S; g.A = a.assets; g.ld = s.ld; g.lda = a.ld_assets; g.P = P; g.n_steps = s.n_steps;
+    g.k0 = (uint32_t)s.seed; g.k1 = (uint32_t)(s.seed >> 32); g.stream = s.stream; g.pair_offset = s.pair_offset;
     const bool keep = a.assets != nullptr;
     switch (a.d) {
     case 1: launch_basket_d<1>(st, g, a.law, keep, vec); break;

@@ -19,8 +19,6 @@
 
 namespace omc {
 
-HestonC make_heston(double r, double T, int n_steps, double kappa, double theta, double xi, double rho);
-
 // One per problem, built on the host, read-only on the device.
 struct BatchProb {
     PathArgs path;
@@ -277,7 +275,6 @@ void batch_build(const BatchItem* items, int n, bool american, bool two_pass, ch
                  BatchExtents* ext)
 {
     BatchProb* tab = (BatchProb*)table_host;
-    const double L2E = 1.4426950408889634074;
     size_t o = 0, dk = 0;
     BatchExtents e{};
     e.vec4 = batch_vec4(items, n) ? 1 : 0;
@@ -295,8 +292,7 @@ void batch_build(const BatchItem* items, int n, bool american, bool two_pass, ch
         p.path.S = american ? (float*)(slab + L.S) : nullptr;
         p.path.ld = L.ld; p.path.P = P; p.path.n_steps = N;
         p.path.s_init = (float)it.S0; p.path.v_init = (float)it.v0;
-        p.path.a = (float)((it.r - 0.5 * it.sigma * it.sigma) * dt * L2E);
-        p.path.b = (float)(it.sigma * sqrt(dt) * L2E);
+        gbm_step_constants(it.r, it.sigma, it.T, N, &p.path.a, &p.path.b);
         p.path.hc = make_heston(it.r, it.T, N, it.kappa, it.theta, it.xi, it.rho);
         p.path.k0 = (uint32_t)it.seed; p.path.k1 = (uint32_t)(it.seed >> 32);
         p.path.stream = (uint32_t)it.stream; p.path.pair_offset = it.pair_offset;

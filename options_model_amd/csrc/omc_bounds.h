@@ -12,7 +12,7 @@ namespace omc {
 struct BoundsArgs {
     int N, is_put;
     double K, invK;
-    float s0, a, b;           // the generator's float32 start value and step constants (launch_gbm_paths)
+    float s0, a, b;           // the generator's float32 start value and step constants (gbm_step_constants)
     uint32_t k0, k1;          // Philox key = seed
     const double* D;          // [N+1] exp(-r dt t): Z_t = D[t] max(phi(S_t), 0)
     const double* betas;      // [N+1][4] the policy (float64 fallback on irregular steps)

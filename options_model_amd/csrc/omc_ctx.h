@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -129,6 +130,18 @@ int enqueue_pricing(omc_ctx* c, const omc_params* p, float* S_keep, int64_t ld, 
                     double** result_out, const omc_params* gen = nullptr);
 int price_fused(omc_ctx* c, const omc_params* p, const omc_params* gen, omc_result* res, float* S_keep, int64_t ld);
 int read_kernel_times(const hipEvent_t* evs, const omc_params* p, omc_result* res, bool has_end = true);
+
+// ---- a generator of its own that writes a full-storage matrix, then the unchanged two-pass sweeps (dividends, jumps,
+// multi-asset, barrier): DESIGN.md section 14, "adding a generator"
+// which paths: `p` with `drift_rate` as the rate of the paths, the width hint of p's model, the matrix S [N+1][ld]
+omc::PathSpec path_spec(const omc_ctx* c, const omc_params* p, double drift_rate, float* S, int64_t ld);
+// the matrix the generator writes: the caller's S_keep (refusal -6 when *ld < n_paths) or the context's own, in full
+int take_full_matrix(omc_ctx* c, const omc_params* p, float* S_keep, float** S, int64_t* ld);
+// events 0 and 1 around gen(stream), the two-pass flow on S with its pass events, event 2, the eight sums -> c->hres
+int enqueue_generated(omc_ctx* c, const omc_params* p, const float* S, int64_t ld,
+                      const std::function<hipError_t(hipStream_t)>& gen);
+// waits for the stream; *base from c->hres (full storage: folded = 0) with the kernel times
+int finish_generated(omc_ctx* c, const omc_params* p, omc_result* base);
 
 // ---- K two-pass pricings of one geometry that share their small launches (grouped sequences, option chains)
 // device bytes one member of a group owns in omc_ctx::gstate: [part1 | gmom | betas | crit | part]

@@ -5,6 +5,8 @@
 
 #include <cstdint>
 
+#include "omc_kernels.h"
+
 namespace omc {
 
 // One dividend step of the composed schedule: after the model's own step `step` the spot becomes
@@ -18,18 +20,8 @@ static_assert(sizeof(DivEntry) == 16, "one 16-byte uniform load per dividend ste
 constexpr int32_t kDivNoStep = 0x7fffffff;
 
 struct DividendGen {
-    // the model (as launch_gbm_paths / launch_heston_paths take it); r is the DRIFT rate (r - q)
-    int model, scheme;  // model 0 GBM, 1 Heston (scheme 0, 1, 2)
-    int64_t n_paths;    // antithetic: pairs = n_paths / 2
-    int n_steps;
-    double S0, r, sigma, T, v0, kappa, theta, xi, rho;
-    uint64_t seed, pair_offset;
-    uint32_t stream;
-    int vec_hint;       // pairs per thread: 1, 2, 4; 0 = auto (options "gbm_vec" / "heston_vec")
-    // device: the dividend steps in step order + the closing entry; S = the matrix [N+1][ld], full storage
-    const DivEntry* tab;
-    float* S;
-    int64_t ld;
+    PathSpec paths;       // r is the DRIFT rate r - q; S = the matrix [N+1][ld], full storage
+    const DivEntry* tab;  // device: the dividend steps in step order + the closing entry
 };
 
 // the generator: rows 0 .. N of both partners of every pair, ex-dividend spots on the dividend steps

@@ -17,8 +17,6 @@
 
 namespace omc {
 
-HestonC make_heston(double r, double T, int n_steps, double kappa, double theta, double xi, double rho);
-
 // MODEL 0 GBM, 1/2/3 Heston scheme 0/1/2.  VEC-wide stores: the launcher picks a VEC every row start is aligned to.
 template <int MODEL, int VEC>
 __global__ __launch_bounds__(kBlock) void dividend_paths_kernel(PathArgs g, const DivEntry* __restrict__ tab)
@@ -75,32 +73,18 @@ __global__ __launch_bounds__(kBlock) void dividend_paths_kernel(PathArgs g, cons
 
 hipError_t launch_dividend_paths(hipStream_t st, const DividendGen& a)
 {
-    const double dt = a.T / a.n_steps, L2E = 1.4426950408889634074;
-    const int64_t P = a.n_paths / 2;
+    const PathSpec& s = a.paths;
+    const int64_t P = s.n_paths / 2;
     if (P <= 0) return hipSuccess;
-    int vec = a.vec_hint > 0 ? a.vec_hint : 4;
-    // VEC-wide stores need every row start and the antithetic half aligned (as launch_gbm_paths)
-    while (vec > 1 && !((P % vec) == 0 && (a.ld % vec) == 0 && ((uintptr_t)a.S % (4 * vec)) == 0)) vec >>= 1;
-    PathArgs g{};
-    g.S = a.S; g.ld = a.ld; g.P = P; g.n_steps = a.n_steps;
-    g.s_init = (float)a.S0; g.v_init = (float)a.v0;
-    g.a = (float)((a.r - 0.5 * a.sigma * a.sigma) * dt * L2E);
-    g.b = (float)(a.sigma * sqrt(dt) * L2E);
-    if (a.model != 0) g.hc = make_heston(a.r, a.T, a.n_steps, a.kappa, a.theta, a.xi, a.rho);
-    g.k0 = (uint32_t)a.seed; g.k1 = (uint32_t)(a.seed >> 32); g.stream = a.stream; g.pair_offset = a.pair_offset;
-    auto go = [&](auto model) {
-        constexpr int MO = decltype(model)::value;
-        const dim3 block(kBlock);
-        auto grid = [&](int v) { return dim3((unsigned)((P / v + kBlock - 1) / kBlock)); };
-        if (vec == 4) hipLaunchKernelGGL((dividend_paths_kernel<MO, 4>), grid(4), block, 0, st, g, a.tab);
-        else if (vec == 2) hipLaunchKernelGGL((dividend_paths_kernel<MO, 2>), grid(2), block, 0, st, g, a.tab);
-        else hipLaunchKernelGGL((dividend_paths_kernel<MO, 1>), grid(1), block, 0, st, g, a.tab);
-    };
-    using std::integral_constant;
-    if (a.model == 0) go(integral_constant<int, 0>{});
-    else if (a.scheme == 0) go(integral_constant<int, 1>{});
-    else if (a.scheme == 1) go(integral_constant<int, 2>{});
-    else go(integral_constant<int, 3>{});
+    const PathArgs g = make_path_args(s, P);
+    const int width = store_vec_width(s.vec_hint, P, s.S, s.ld);  // (so P % VEC == 0 and every store is VEC wide)
+    for_model(s.model, s.scheme, [&](auto model) {
+        for_vec(width, [&](auto vec) {
+            constexpr int MO = decltype(model)::value, V = decltype(vec)::value;
+            hipLaunchKernelGGL((dividend_paths_kernel<MO, V>), dim3((unsigned)((P / V + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                               st, g, a.tab);
+        });
+    });
     return hipGetLastError();
 }
 

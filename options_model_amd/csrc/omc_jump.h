@@ -5,6 +5,8 @@
 
 #include <cstdint>
 
+#include "omc_kernels.h"
+
 namespace omc {
 
 constexpr int kJumpThr = 16;  // thresholds of the Poisson inversion: a step carries 0 .. 16 jumps
@@ -18,17 +20,8 @@ struct JumpLaw {
 };
 
 struct JumpGen {
-    // the model (as launch_gbm_paths / launch_heston_paths take it); r is the DRIFT rate (r - q) - lambda kappa
-    int model, scheme;  // model 0 GBM (Merton), 1 Heston (Bates; scheme 0, 1, 2)
-    int64_t n_paths;    // antithetic: pairs = n_paths / 2
-    int n_steps;
-    double S0, r, sigma, T, v0, kappa, theta, xi, rho;
-    uint64_t seed, pair_offset;
-    uint32_t stream;
-    int vec_hint;       // pairs per thread: 1, 2, 4; 0 = auto (options "gbm_vec" / "heston_vec")
+    PathSpec paths;  // r is the DRIFT rate (r - q) - lambda kappa; S = the matrix [N+1][ld], full storage
     JumpLaw law;
-    float* S;           // device: the matrix [N+1][ld], full storage
-    int64_t ld;
 };
 
 // the generator: rows 0 .. N of both partners of every pair

@@ -25,6 +25,43 @@ inline hipError_t set_max_dynamic_lds(std::atomic<uint64_t>& mask, const void* k
 }
 
 // ---- omc_paths.hip
+// Which paths a generator writes: the model, the geometry, the Philox coordinates and the matrix.  The single-problem
+// generators' descriptors (DividendGen, JumpGen, BarrierGen) embed it; the API layer fills it (path_spec, omc_ctx.h).
+struct PathSpec {
+    int model, scheme;  // model 0 GBM, 1 Heston (scheme 0, 1, 2)
+    int64_t n_paths;    // antithetic: pairs = n_paths / 2
+    int n_steps;
+    double S0, r, sigma, T, v0, kappa, theta, xi, rho;  // r: the DRIFT rate of the paths
+    uint64_t seed, pair_offset;
+    uint32_t stream;
+    int vec_hint;       // pairs per thread: 1, 2, 4; 0 = auto (options "gbm_vec" / "heston_vec")
+    float* S;           // device: the matrix [N+1][ld]
+    int64_t ld;
+};
+
+// The two float32 constants of a GBM step, s *= exp2(fma(+-b, z, a)): the only definition.  Every launcher that needs
+// them and the fold table (gbm_fold_constants) take them from here.
+inline void gbm_step_constants(double r, double sigma, double T, int n_steps, float* a, float* b)
+{
+    const double dt = T / n_steps, L2E = 1.4426950408889634074;
+    *a = (float)((r - 0.5 * sigma * sigma) * dt * L2E);
+    *b = (float)(sigma * std::sqrt(dt) * L2E);
+}
+
+// VEC-wide stores of a generator's rows need the pair count (the antithetic half starts P columns in), the leading
+// dimension and the base address aligned to VEC floats
+inline bool store_aligned(int vec, int64_t P, const float* S, int64_t ld)
+{
+    return (P % vec) == 0 && (ld % vec) == 0 && ((uintptr_t)S % (4 * vec)) == 0;
+}
+// pairs per thread: the hint (0 = 4), halved until the stores are aligned
+inline int store_vec_width(int hint, int64_t P, const float* S, int64_t ld)
+{
+    int vec = hint > 0 ? hint : 4;
+    while (vec > 1 && !store_aligned(vec, P, S, ld)) vec >>= 1;
+    return vec;
+}
+
 hipError_t launch_gbm_paths(hipStream_t st, float* S, int64_t ld, int64_t n_paths, int n_steps,
                             double S0, double r, double sigma, double T, uint64_t seed,
                             uint32_t stream, uint64_t pair_offset, int antithetic, int vec_hint);
@@ -111,11 +148,11 @@ struct LsmWorkspace {
 size_t lsm_part1_tiles(int64_t M);
 // LsmProblem::fold_cK: cK[t] = c0 g^t for t = 0 .. N (c0 = S0^2 / K, g = exp(2 drift dt)), N sequential products
 hipError_t lsm_fold_table(hipStream_t st, double* cK, int N, double c0, double g);
-// its two constants, from the float32 drift exponent and start value the generator itself uses (launch_gbm_paths)
+// its two constants, from the generator's own float32 drift exponent (gbm_step_constants) and start value
 inline void gbm_fold_constants(double S0, double K, double r, double sigma, double T, int n_steps, double* c0, double* g)
 {
-    const double dt = T / n_steps, L2E = 1.4426950408889634074;
-    const float a = (float)((r - 0.5 * sigma * sigma) * dt * L2E);
+    float a, b;
+    gbm_step_constants(r, sigma, T, n_steps, &a, &b);
     const float s0 = (float)S0;
     *c0 = (double)s0 * (double)s0 / K;
     *g = std::exp2(2.0 * (double)a);

@@ -114,6 +114,18 @@ HestonC make_heston(double r, double T, int n_steps, double kappa, double theta,
     return c;
 }
 
+// (the float32 constants a, b of a GBM step: gbm_step_constants, omc_kernels.h)
+PathArgs make_path_args(const PathSpec& s, int64_t P)
+{
+    PathArgs g{};
+    g.S = s.S; g.ld = s.ld; g.P = P; g.n_steps = s.n_steps;
+    g.s_init = (float)s.S0; g.v_init = (float)s.v0;
+    gbm_step_constants(s.r, s.sigma, s.T, s.n_steps, &g.a, &g.b);
+    if (s.model != 0) g.hc = make_heston(s.r, s.T, s.n_steps, s.kappa, s.theta, s.xi, s.rho);
+    g.k0 = (uint32_t)s.seed; g.k1 = (uint32_t)(s.seed >> 32); g.stream = s.stream; g.pair_offset = s.pair_offset;
+    return g;
+}
+
 static inline unsigned grid_for(int64_t work_items)
 {
     return (unsigned)((work_items + kBlock - 1) / kBlock);
@@ -123,31 +135,18 @@ hipError_t launch_gbm_paths(hipStream_t st, float* S, int64_t ld, int64_t n_path
                             double S0, double r, double sigma, double T, uint64_t seed,
                             uint32_t stream, uint64_t pair_offset, int antithetic, int vec_hint)
 {
-    const double dt = T / n_steps, L2E = 1.4426950408889634074;
-    const float a = (float)((r - 0.5 * sigma * sigma) * dt * L2E);
-    const float b = (float)(sigma * sqrt(dt) * L2E);
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    PathSpec s{};
+    s.n_paths = n_paths; s.n_steps = n_steps; s.S0 = S0; s.r = r; s.sigma = sigma; s.T = T;
+    s.seed = seed; s.pair_offset = pair_offset; s.stream = stream; s.S = S; s.ld = ld;
     const int64_t P = antithetic ? n_paths / 2 : n_paths;
     if (P <= 0) return hipSuccess;
-    int vec = vec_hint > 0 ? vec_hint : 4;
-    // VEC-wide stores need every row start (and the antithetic half) aligned
-    while (vec > 1 && !((P % vec) == 0 && (ld % vec) == 0 && ((uintptr_t)S % (4 * vec)) == 0)) vec >>= 1;
-    PathArgs g{};
-    g.S = S; g.ld = ld; g.P = P; g.n_steps = n_steps; g.s_init = (float)S0; g.a = a; g.b = b;
-    g.k0 = k0; g.k1 = k1; g.stream = stream; g.pair_offset = pair_offset;
-#define OMC_LAUNCH_GBM(V, A)                                                                       \
-    hipLaunchKernelGGL((gbm_paths_kernel<V, A>), dim3(grid_for((P + V - 1) / V)), dim3(kBlock), 0, \
-                       st, g)
-    if (antithetic) {
-        if (vec == 4) OMC_LAUNCH_GBM(4, true);
-        else if (vec == 2) OMC_LAUNCH_GBM(2, true);
-        else OMC_LAUNCH_GBM(1, true);
-    } else {
-        if (vec == 4) OMC_LAUNCH_GBM(4, false);
-        else if (vec == 2) OMC_LAUNCH_GBM(2, false);
-        else OMC_LAUNCH_GBM(1, false);
-    }
-#undef OMC_LAUNCH_GBM
+    const PathArgs g = make_path_args(s, P);
+    for_vec(store_vec_width(vec_hint, P, S, ld), [&](auto vec) {
+        constexpr int V = decltype(vec)::value;
+        const dim3 grid(grid_for((P + V - 1) / V)), block(kBlock);
+        if (antithetic) hipLaunchKernelGGL((gbm_paths_kernel<V, true>), grid, block, 0, st, g);
+        else hipLaunchKernelGGL((gbm_paths_kernel<V, false>), grid, block, 0, st, g);
+    });
     return hipGetLastError();
 }
 
@@ -156,32 +155,21 @@ hipError_t launch_heston_paths(hipStream_t st, float* S, int64_t ld, int64_t n_p
                                double theta, double xi, double rho, uint64_t seed, uint32_t stream,
                                uint64_t pair_offset, int scheme, int vec_hint)
 {
-    const HestonC c = make_heston(r, T, n_steps, kappa, theta, xi, rho);
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    PathSpec s{};
+    s.model = 1; s.scheme = scheme; s.n_paths = n_paths; s.n_steps = n_steps; s.S0 = S0; s.r = r; s.T = T;
+    s.v0 = v0; s.kappa = kappa; s.theta = theta; s.xi = xi; s.rho = rho;
+    s.seed = seed; s.pair_offset = pair_offset; s.stream = stream; s.S = S; s.ld = ld;
     const int64_t P = n_paths / 2;
     if (P <= 0) return hipSuccess;
-    int vec = vec_hint > 0 ? vec_hint : 4;
-    while (vec > 1 && !((P % vec) == 0 && (ld % vec) == 0 && ((uintptr_t)S % (4 * vec)) == 0)) vec >>= 1;
-    PathArgs g{};
-    g.S = S; g.ld = ld; g.P = P; g.n_steps = n_steps; g.s_init = (float)S0; g.v_init = (float)v0;
-    g.hc = c; g.k0 = k0; g.k1 = k1; g.stream = stream; g.pair_offset = pair_offset;
-#define OMC_LAUNCH_HES(V, SC)                                                                     \
-    hipLaunchKernelGGL((heston_paths_kernel<V, SC>), dim3(grid_for((P + V - 1) / V)),             \
-                       dim3(kBlock), 0, st, g)
-    if (scheme == 0) {
-        if (vec == 4) OMC_LAUNCH_HES(4, 0);
-        else if (vec == 2) OMC_LAUNCH_HES(2, 0);
-        else OMC_LAUNCH_HES(1, 0);
-    } else if (scheme == 1) {
-        if (vec == 4) OMC_LAUNCH_HES(4, 1);
-        else if (vec == 2) OMC_LAUNCH_HES(2, 1);
-        else OMC_LAUNCH_HES(1, 1);
-    } else {
-        if (vec == 4) OMC_LAUNCH_HES(4, 2);
-        else if (vec == 2) OMC_LAUNCH_HES(2, 2);
-        else OMC_LAUNCH_HES(1, 2);
-    }
-#undef OMC_LAUNCH_HES
+    const PathArgs g = make_path_args(s, P);
+    const int width = store_vec_width(vec_hint, P, S, ld);
+    for_model(1, scheme, [&](auto model) {
+        for_vec(width, [&](auto vec) {
+            constexpr int V = decltype(vec)::value, MO = decltype(model)::value;
+            if constexpr (MO > 0)  // (MODEL = SCHEME + 1)
+                hipLaunchKernelGGL((heston_paths_kernel<V, MO - 1>), dim3(grid_for((P + V - 1) / V)), dim3(kBlock), 0, st, g);
+        });
+    });
     return hipGetLastError();
 }
 
@@ -189,9 +177,8 @@ hipError_t launch_gbm_from_normals(hipStream_t st, float* S, int64_t ld, int64_t
                                    int n_steps, double S0, double r, double sigma, double T,
                                    const float* Z, int64_t ldz, int antithetic)
 {
-    const double dt = T / n_steps, L2E = 1.4426950408889634074;
-    const float a = (float)((r - 0.5 * sigma * sigma) * dt * L2E);
-    const float b = (float)(sigma * sqrt(dt) * L2E);
+    float a, b;
+    gbm_step_constants(r, sigma, T, n_steps, &a, &b);
     const int64_t P = antithetic ? n_paths / 2 : n_paths;
     if (P <= 0) return hipSuccess;
     if (antithetic)
@@ -423,13 +410,11 @@ hipError_t launch_terminal(hipStream_t st, double* part, int* nblk_out, int mode
                            double xi, double rho, int is_put, uint64_t seed, uint32_t stream,
                            uint64_t pair_offset)
 {
-    const double dt = T / n_steps, L2E = 1.4426950408889634074;
     TermArgs a;
     a.P = (model == 0 && !antithetic) ? n_paths : n_paths / 2;
     a.n_steps = n_steps; a.is_put = is_put;
     a.s_init = (float)S0; a.v_init = (float)v0;
-    a.a = (float)((r - 0.5 * sigma * sigma) * dt * L2E);
-    a.b = (float)(sigma * sqrt(dt) * L2E);
+    gbm_step_constants(r, sigma, T, n_steps, &a.a, &a.b);
     a.hc = make_heston(r, T, n_steps, kappa, theta, xi, rho);
     a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.stream = stream;
     a.pair_offset = pair_offset; a.K = K; a.df = exp(-r * T); a.part = part;

@@ -2,6 +2,8 @@
 // launchers (omc_paths.hip) and the batched launchers (omc_batch.hip).  Bodies only look at
 // blockIdx.x; the batch dimension is resolved by the __global__ wrapper.
 #pragma once
+#include <type_traits>
+
 #include "omc_device.h"
 #include "omc_kernels.h"
 
@@ -37,6 +39,32 @@ struct PathArgs {
     uint32_t k0, k1, stream;
     uint64_t pair_offset;
 };
+
+// ---- host side of the single-problem launchers (definitions: omc_paths.hip)
+HestonC make_heston(double r, double T, int n_steps, double kappa, double theta, double xi, double rho);
+// the argument block of `s` for P pairs (or P single paths): the only fill of PathArgs for the single-problem launchers
+PathArgs make_path_args(const PathSpec& s, int64_t P);
+
+// a run-time model / scheme or pairs-per-thread as a compile-time constant: f(std::integral_constant<int, MODEL>{}),
+// MODEL 0 GBM, 1/2/3 Heston scheme 0/1/2; f(std::integral_constant<int, VEC>{}), VEC 4, 2 or 1
+template <class F>
+inline void for_model(int model, int scheme, F&& f)
+{
+    using std::integral_constant;
+    if (model == 0) f(integral_constant<int, 0>{});
+    else if (scheme == 0) f(integral_constant<int, 1>{});
+    else if (scheme == 1) f(integral_constant<int, 2>{});
+    else f(integral_constant<int, 3>{});
+}
+
+template <class F>
+inline void for_vec(int vec, F&& f)
+{
+    using std::integral_constant;
+    if (vec == 4) f(integral_constant<int, 4>{});
+    else if (vec == 2) f(integral_constant<int, 2>{});
+    else f(integral_constant<int, 1>{});
+}
 
 template <int VEC, bool ANTI>
 __device__ __forceinline__ void gbm_paths_body(const PathArgs& g)
@@ -135,6 +163,21 @@ __device__ __forceinline__ void heston_pair_step(const HestonC& c, float z1, flo
         const float az = c.l2e_sqdt * z1;
         heston_path_step<SCHEME>(c, tw, az, s, v);
         heston_path_step<SCHEME>(c, -tw, -az, sa, vb);
+    }
+}
+
+// ---- what the exotic generators (dividend, jump, barrier) share with the bodies here
+// The vanilla step of one antithetic pair from its Philox block z: MODEL 0 GBM, step i = 0 .. 3 of the block (gbm_paths_body's
+// operations); MODEL 1/2/3 Heston scheme 0/1/2, step i = 0, 1 of the block (heston_paths_body's)
+template <int MODEL>
+__device__ __forceinline__ void pair_step(const PathArgs& g, const float (&z)[4], int i, float& s, float& v, float& sa,
+                                          float& vb)
+{
+    if constexpr (MODEL == 0) {
+        s = s * fast_exp2(__builtin_fmaf(g.b, z[i], g.a));
+        sa = sa * fast_exp2(__builtin_fmaf(-g.b, z[i], g.a));
+    } else {
+        heston_pair_step<MODEL - 1>(g.hc, z[2 * i], z[2 * i + 1], s, v, sa, vb);
     }
 }
 
