@@ -240,7 +240,7 @@ static int enqueue_sweep_graph(omc_ctx* c, const omc::LsmProblem& p, const omc::
         HIP_TRY(hipMemcpyAsync(c->sweep_args.p, slot, nb, hipMemcpyHostToDevice, c->stream));
         c->sweep_img.swap(img);
     }
-    const int vec4 = ((p.M % 4) == 0 && (p.ld % 4) == 0 && ((uintptr_t)p.S % 16) == 0) ? 1 : 0;
+    const int vec4 = omc::rows_aligned(4, p.M, p.S, p.ld) ? 1 : 0;  // the launcher's own rule (lsm_step_impl)
     if (!c->sweep_exec || c->sg_M != p.M || c->sg_N != p.N || c->sg_sem != semantics || c->sg_vec4 != vec4 ||
         c->sg_ld != p.ld || c->sg_args != c->sweep_args.p) {
         drop_sweep_graph(c);

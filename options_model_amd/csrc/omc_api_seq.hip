@@ -289,7 +289,7 @@ static int enqueue_seq_step_multi(omc_ctx* c, const omc_params* p, int n, int K,
     omc::LsmWorkspace w0;
     if ((rc = prepare_lsm(c, M, N, p[0].r, p[0].T, false, false, &w0))) return rc;  // discount table (+ unused singles)
     const bool ext = c->distributed();
-    const bool vec4 = (M % 4) == 0;  // ld is a multiple of 64 and every matrix starts 256-byte aligned
+    const bool vec4 = omc::state_vec4(M);  // ld is a multiple of 64 and every matrix starts 256-byte aligned
     char* state = (char*)c->mstate.p;
     double* gmomK = (double*)state;
     for (int i0 = 0; i0 < n; i0 += K) {

@@ -222,7 +222,7 @@ hipError_t launch_barrier_paths(hipStream_t st, const BarrierGen& a)
     BarArgs A{};
     A.g = make_path_args(s, s.n_paths / 2);
     A.is_put = a.is_put; A.knock_in = a.knock_in;
-    const bool vstore = s.S && vec > 1 && store_aligned(vec, A.g.P, s.S, s.ld);
+    const bool vstore = s.S && vec > 1 && rows_aligned(vec, A.g.P, s.S, s.ld);
     const float thr = barrier_threshold(a.H, a.up);
     A.sg = a.up ? -1.0f : 1.0f;
     A.sthr = a.up ? -thr : thr;
@@ -231,24 +231,20 @@ hipError_t launch_barrier_paths(hipStream_t st, const BarrierGen& a)
     A.cbr = s.model == 0 ? (float)(-2.0 * 0.69314718055994530942 / (s.sigma * s.sigma * (s.T / s.n_steps))) : 0.0f;
     A.K = a.K; A.df = exp(-s.r * s.T); A.part = a.part;
     const dim3 grid((unsigned)nblk), block(kBlock);
-    auto go = [&](auto store, auto mon) {
-        for_model(s.model, s.scheme, [&](auto model) {
-            constexpr int MO = decltype(model)::value, MN = decltype(mon)::value;
-            constexpr bool STO = decltype(store)::value;
-            if constexpr (MN == 0 || MO == 0) {  // (continuous monitoring is GBM only)
-                if (STO && vec == 4 && vstore)  // (VEC-wide stores only where there are stores)
-                    hipLaunchKernelGGL((barrier_paths_kernel<MO, STO, MN, 4, STO>), grid, block, 0, st, A);
-                else if (vec == 4) hipLaunchKernelGGL((barrier_paths_kernel<MO, STO, MN, 4, false>), grid, block, 0, st, A);
-                else hipLaunchKernelGGL((barrier_paths_kernel<MO, STO, MN, 1, false>), grid, block, 0, st, A);
-            }
+    for_flag(s.S != nullptr, [&](auto store) {
+        for_int<1, 0>(s.model == 0 && a.continuous ? 1 : 0, [&](auto mon) {
+            for_model(s.model, s.scheme, [&](auto model) {
+                constexpr int MO = decltype(model)::value, MN = decltype(mon)::value;
+                constexpr bool STO = decltype(store)::value;
+                if constexpr (MN == 0 || MO == 0) {  // (continuous monitoring is GBM only)
+                    if (STO && vec == 4 && vstore)  // (VEC-wide stores only where there are stores)
+                        hipLaunchKernelGGL((barrier_paths_kernel<MO, STO, MN, 4, STO>), grid, block, 0, st, A);
+                    else if (vec == 4) hipLaunchKernelGGL((barrier_paths_kernel<MO, STO, MN, 4, false>), grid, block, 0, st, A);
+                    else hipLaunchKernelGGL((barrier_paths_kernel<MO, STO, MN, 1, false>), grid, block, 0, st, A);
+                }
+            });
         });
-    };
-    auto by_monitoring = [&](auto store) {
-        if (s.model == 0 && a.continuous) go(store, std::integral_constant<int, 1>{});
-        else go(store, std::integral_constant<int, 0>{});
-    };
-    if (s.S) by_monitoring(std::true_type{});
-    else by_monitoring(std::false_type{});
+    });
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(barrier_finalize_kernel, dim3(1), dim3(kBlock), 0, st, (const double*)a.part, nblk, a.result);

@@ -315,23 +315,20 @@ void batch_build(const BatchItem* items, int n, bool american, bool two_pass, ch
         double* D = disc_dev + dk;
         for (int k = 0; k <= N; ++k) disc_host[dk + (size_t)k] = exp(-it.r * dt * (double)k);
         dk += (size_t)N + 1;
-        StepArgs& s = p.step;
-        s.S = p.path.S; s.ld = L.ld; s.M = M; s.N = N; s.is_put = it.is_put; s.K = it.K; s.invK = 1.0 / it.K;
-        s.sx = (float*)(slab + L.sx); s.tex = (int32_t*)(slab + L.tex); s.live = (float*)(slab + L.ex); s.D = D;
-        s.part = part;
-        s.gmom = (double*)(slab + L.gmom); s.betas = (double*)(slab + L.betas);
-        s.t = 0; s.nblk = L.nblk_sweep; s.external = 0; s.pstride = L.pstride; s.gstride = 8; s.cont = nullptr; s.ldc = 0;
-        Pass1Args& a1 = p.p1;
-        a1.S = s.S; a1.ld = L.ld; a1.M = M; a1.N = N; a1.is_put = it.is_put; a1.K = it.K; a1.invK = s.invK;
-        a1.D = D; a1.part1 = two_pass ? (double*)(slab + L.part1) : nullptr; a1.ntiles = L.ntiles; a1.tchunk = 16;
-        Pass2Args& a2 = p.p2;
-        a2.S = s.S; a2.ld = L.ld; a2.M = M; a2.N = N; a2.is_put = it.is_put; a2.K = it.K; a2.invK = s.invK;
-        a2.D = D; a2.betas = s.betas; a2.sx = s.sx; a2.tex = s.tex; a2.part = part;
-        a2.nblk = L.nblk_blocks; a2.pstride = L.pstride;
-        FinalArgs& f = p.fin;
-        f.sx = s.sx; f.tex = s.tex; f.M = M; f.N = N; f.is_put = it.is_put; f.tval = it.semantics == 1 ? 0 : 1;
-        f.live = it.semantics == 0 ? s.live : nullptr; f.fill_state = 0;
-        f.K = it.K; f.D = D; f.part = part; f.nblk = L.nblk_blocks; f.pstride = L.pstride;
+        // the member as a single problem on its part of the slab: the argument blocks are the single path's (omc_lsm.hip),
+        // then what the layout decides
+        const LsmProblem lp{p.path.S, L.ld, M, N, it.is_put, it.K, it.r, it.T};
+        LsmWorkspace lw{};
+        lw.sx = (float*)(slab + L.sx); lw.tex = (int32_t*)(slab + L.tex); lw.live = (float*)(slab + L.ex); lw.D = D;
+        lw.part = part; lw.gmom = (double*)(slab + L.gmom); lw.betas = (double*)(slab + L.betas);
+        lw.part1 = two_pass ? (double*)(slab + L.part1) : nullptr;
+        p.step = step_args(lp, lw, 0, false);
+        p.step.nblk = L.nblk_sweep; p.step.pstride = L.pstride;
+        p.p1 = pass1_args(lp, lw, L.ntiles, 16);
+        p.p2 = pass2_args(lp, lw, L.nblk_blocks);
+        p.p2.pstride = L.pstride;
+        p.fin = final_args(lp, lw, it.semantics == 1 ? 0 : 1, it.semantics == 0, false);
+        p.fin.nblk = L.nblk_blocks; p.fin.pstride = L.pstride;
         p.fin_nblk = L.nblk_blocks;
         e.max_steps = std::max(e.max_steps, N);
         e.path_blocks = std::max<int64_t>(e.path_blocks, (P + kBlock - 1) / kBlock);
@@ -347,16 +344,30 @@ hipError_t batch_paths(hipStream_t st, const void* table_dev, int n, const Batch
     const BatchProb* pr = (const BatchProb*)table_dev;
     const int vec = e.vec4 ? 4 : 1;
     const dim3 grid((unsigned)((e.path_blocks + vec - 1) / vec), (unsigned)n), block(kBlock);
-#define OMC_BP(V, G) hipLaunchKernelGGL((paths_batch_kernel<V, G>), grid, block, 0, st, pr)
-    if (vec == 4) {
-        if (gen == 0) OMC_BP(4, 0); else if (gen == 1) OMC_BP(4, 1); else if (gen == 2) OMC_BP(4, 2);
-        else if (gen == 3) OMC_BP(4, 3); else OMC_BP(4, 4);
-    } else {
-        if (gen == 0) OMC_BP(1, 0); else if (gen == 1) OMC_BP(1, 1); else if (gen == 2) OMC_BP(1, 2);
-        else if (gen == 3) OMC_BP(1, 3); else OMC_BP(1, 4);
-    }
-#undef OMC_BP
+    for_vec4(e.vec4 != 0, [&](auto v) {
+        for_int<0, 1, 2, 3, 4>(gen, [&](auto g) {
+            hipLaunchKernelGGL((paths_batch_kernel<decltype(v)::value, decltype(g)::value>), grid, block, 0, st, pr);
+        });
+    });
     return hipGetLastError();
+}
+
+// one time step / the valuation of every member
+static void batch_step(hipStream_t st, const BatchProb* pr, int n, const BatchExtents& e, int semantics, size_t dyn, int t)
+{
+    const dim3 gs((unsigned)e.sweep_blocks, 1, (unsigned)n);
+    for_step(semantics, e.vec4 != 0, [&](auto sem, auto vec, auto block) {
+        constexpr int SEM = decltype(sem)::value, VEC = decltype(vec)::value, BLOCK = decltype(block)::value;
+        hipLaunchKernelGGL((lsm_step_batch_kernel<SEM, VEC, BLOCK>), gs, dim3(BLOCK), dyn, st, pr, t);
+    });
+}
+
+static void batch_final(hipStream_t st, const BatchProb* pr, int n, const BatchExtents& e)
+{
+    const dim3 gf((unsigned)e.block_blocks, 1, (unsigned)n);
+    for_vec4(e.vec4 != 0, [&](auto v) {
+        hipLaunchKernelGGL((lsm_final_batch_kernel<decltype(v)::value>), gf, dim3(kBlock), 0, st, pr);
+    });
 }
 
 hipError_t batch_lsm(hipStream_t st, const void* table_dev, int n, const BatchExtents& e, int semantics)
@@ -367,35 +378,21 @@ hipError_t batch_lsm(hipStream_t st, const void* table_dev, int n, const BatchEx
     if (semantics == 2) {
         if (Nmax >= 2) {
             const dim3 g1((unsigned)e.tile_blocks, (unsigned)((Nmax - 1 + 15) / 16), z);
-            if (e.vec4) hipLaunchKernelGGL((lsm_pass1_batch_kernel<4>), g1, dim3(kBlock), 0, st, pr);
-            else hipLaunchKernelGGL((lsm_pass1_batch_kernel<1>), g1, dim3(kBlock), 0, st, pr);
+            for_vec4(e.vec4 != 0, [&](auto v) {
+                hipLaunchKernelGGL((lsm_pass1_batch_kernel<decltype(v)::value>), g1, dim3(kBlock), 0, st, pr);
+            });
             hipLaunchKernelGGL(lsm_reduce_pass1_batch_kernel, dim3(Nmax - 1, 1, z), dim3(kBlock), 0, st, pr);
             hipLaunchKernelGGL(lsm_solve_all_batch_kernel, dim3((Nmax + 255) / 256, 1, z), dim3(256), 0, st, pr);
         }
         const size_t dyn = sizeof(double) * 4 * (size_t)(Nmax + 1);
         const dim3 g2((unsigned)e.block_blocks, 1, z);
-        if (e.vec4) hipLaunchKernelGGL((lsm_pass2_batch_kernel<4>), g2, dim3(kBlock), dyn, st, pr);
-        else hipLaunchKernelGGL((lsm_pass2_batch_kernel<1>), g2, dim3(kBlock), dyn, st, pr);
+        for_vec4(e.vec4 != 0, [&](auto v) {
+            hipLaunchKernelGGL((lsm_pass2_batch_kernel<decltype(v)::value>), g2, dim3(kBlock), dyn, st, pr);
+        });
     } else {
-        const bool big = lsm_step_block_threads() == 1024;
-        const dim3 gs((unsigned)e.sweep_blocks, 1, z), bs(big ? 1024 : 512);
         const size_t dyn = semantics == 1 ? sizeof(double) * (size_t)(Nmax + 1) : 0;
-#define OMC_BSTEP(SEM, VEC)                                                                              \
-    do {                                                                                                 \
-        if (big) hipLaunchKernelGGL((lsm_step_batch_kernel<SEM, VEC, 1024>), gs, bs, dyn, st, pr, t);    \
-        else hipLaunchKernelGGL((lsm_step_batch_kernel<SEM, VEC, 512>), gs, bs, dyn, st, pr, t);         \
-    } while (0)
-        for (int t = Nmax; t >= 1; --t) {
-            if (semantics == 0) {
-                if (e.vec4) OMC_BSTEP(0, 4); else OMC_BSTEP(0, 1);
-            } else {
-                if (e.vec4) OMC_BSTEP(1, 4); else OMC_BSTEP(1, 1);
-            }
-        }
-#undef OMC_BSTEP
-        const dim3 gf((unsigned)e.block_blocks, 1, z);
-        if (e.vec4) hipLaunchKernelGGL((lsm_final_batch_kernel<4>), gf, dim3(kBlock), 0, st, pr);
-        else hipLaunchKernelGGL((lsm_final_batch_kernel<1>), gf, dim3(kBlock), 0, st, pr);
+        for (int t = Nmax; t >= 1; --t) batch_step(st, pr, n, e, semantics, dyn, t);
+        batch_final(st, pr, n, e);
     }
     hipLaunchKernelGGL(lsm_finalize_batch_kernel, dim3(1, 1, z), dim3(kBlock), 0, st, pr, 1);
     return hipGetLastError();
@@ -405,11 +402,9 @@ hipError_t batch_terminal(hipStream_t st, const void* table_dev, int n, const Ba
 {
     const BatchProb* pr = (const BatchProb*)table_dev;
     const dim3 grid((unsigned)e.term_blocks, 1, (unsigned)n);
-    if (gen == 0) hipLaunchKernelGGL((terminal_batch_kernel<0>), grid, dim3(kBlock), 0, st, pr);
-    else if (gen == 1) hipLaunchKernelGGL((terminal_batch_kernel<1>), grid, dim3(kBlock), 0, st, pr);
-    else if (gen == 2) hipLaunchKernelGGL((terminal_batch_kernel<2>), grid, dim3(kBlock), 0, st, pr);
-    else if (gen == 3) hipLaunchKernelGGL((terminal_batch_kernel<3>), grid, dim3(kBlock), 0, st, pr);
-    else hipLaunchKernelGGL((terminal_batch_kernel<4>), grid, dim3(kBlock), 0, st, pr);
+    for_int<0, 1, 2, 3, 4>(gen, [&](auto g) {
+        hipLaunchKernelGGL((terminal_batch_kernel<decltype(g)::value>), grid, dim3(kBlock), 0, st, pr);
+    });
     hipLaunchKernelGGL(lsm_finalize_batch_kernel, dim3(1, 1, (unsigned)n), dim3(kBlock), 0, st, pr, 0);
     return hipGetLastError();
 }
@@ -514,8 +509,6 @@ hipError_t batch_contnet(hipStream_t st, const void* table_dev, const void* cn_t
     const int H = cn_padded_width(hidden);
     const unsigned z = (unsigned)n;
     const int Nmax = e.max_steps;
-    const bool big = lsm_step_block_threads() == 1024;
-    const dim3 gs((unsigned)e.sweep_blocks, 1, z), bs(big ? 1024 : 512);
     // workgroups per problem in the trainer's launches: enough to fill the chip when the batch is small, few when
     // the batch itself does (a regression set is mostly a small fraction of the paths: surplus workgroups only exit)
     // trainer launches: a lone problem gets one workgroup per possible tile; a batch shares a fixed pool of
@@ -523,15 +516,6 @@ hipError_t batch_contnet(hipStream_t st, const void* table_dev, const void* cn_t
     const int tiles_max = (int)((max_paths + 31) / 32);
     const bool listed = n > 1 && tile_prefix_dev != nullptr && H <= 64;  // (the 128-unit instance of the list kernel spills)
     const int gx = listed ? 4096 : tiles_max;
-    auto step = [&](int t) {
-        if (big) {
-            if (e.vec4) hipLaunchKernelGGL((lsm_step_batch_kernel<0, 4, 1024>), gs, bs, 0, st, pr, t);
-            else hipLaunchKernelGGL((lsm_step_batch_kernel<0, 1, 1024>), gs, bs, 0, st, pr, t);
-        } else {
-            if (e.vec4) hipLaunchKernelGGL((lsm_step_batch_kernel<0, 4, 512>), gs, bs, 0, st, pr, t);
-            else hipLaunchKernelGGL((lsm_step_batch_kernel<0, 1, 512>), gs, bs, 0, st, pr, t);
-        }
-    };
     for (int t = Nmax; t >= 1; --t) {
         if (t < Nmax) {  // (at t = Nmax no problem has a regression step: t == N is the initialising launch)
             const dim3 gc((unsigned)max_cn_blocks, z);
@@ -552,11 +536,9 @@ hipError_t batch_contnet(hipStream_t st, const void* table_dev, const void* cn_t
                                      : cn_forward_batch<128>(st, pr, cp, n, max_paths, t);
             if (err != hipSuccess) return err;
         }
-        step(t);
+        batch_step(st, pr, n, e, 0, 0, t);
     }
-    const dim3 gf((unsigned)e.block_blocks, 1, z);
-    if (e.vec4) hipLaunchKernelGGL((lsm_final_batch_kernel<4>), gf, dim3(kBlock), 0, st, pr);
-    else hipLaunchKernelGGL((lsm_final_batch_kernel<1>), gf, dim3(kBlock), 0, st, pr);
+    batch_final(st, pr, n, e);
     hipLaunchKernelGGL(lsm_finalize_batch_kernel, dim3(1, 1, z), dim3(kBlock), 0, st, pr, 0);
     hipLaunchKernelGGL(cn_total_batch_kernel, dim3((n + 255) / 256), dim3(256), 0, st, pr, cp, n);
     return hipGetLastError();

@@ -318,7 +318,6 @@ int chain_fused_width(const LsmProblem& p)
 {
     if (!p.fold_cK || p.N < 2) return 0;
     const FoldGeometry geo = lsm_fold_geometry(p);
-    if (geo.tpw != 2) return 0;  // (an experiment's tile shape: the single sweeps only)
     const size_t per_entry = sizeof(uint32_t) * 8 * (size_t)(p.N + 1);
     int w = kChainWidthMax;
     // (registers: 4 x columns-per-thread state words and 16 accumulator registers per entry; beyond 8 entry-columns per
@@ -330,17 +329,15 @@ int chain_fused_width(const LsmProblem& p)
 
 hipError_t chain_pass1_sweep(hipStream_t st, const ChainSweepArgs& a, const LsmProblem& p, int64_t* ntiles)
 {
-    const FoldGeometry geo = lsm_fold_geometry(p);
-    *ntiles = geo.ntiles;
-    if (p.N < 2 || geo.tpw != 2 || a.KE < 1 || a.KE > kChainWidthMax) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((geo.ntiles + 3) / 4), (unsigned)((p.N - 1 + geo.tchunk - 1) / geo.tchunk));
-    if (geo.v4) {
-        if (a.is_put) hipLaunchKernelGGL((lsm_pass1_fold_chain_kernel<4, 2, 1>), grid, dim3(kBlock), 0, st, a, geo.ntiles, geo.tchunk);
-        else hipLaunchKernelGGL((lsm_pass1_fold_chain_kernel<4, 2, 0>), grid, dim3(kBlock), 0, st, a, geo.ntiles, geo.tchunk);
-    } else {
-        if (a.is_put) hipLaunchKernelGGL((lsm_pass1_fold_chain_kernel<1, 2, 1>), grid, dim3(kBlock), 0, st, a, geo.ntiles, geo.tchunk);
-        else hipLaunchKernelGGL((lsm_pass1_fold_chain_kernel<1, 2, 0>), grid, dim3(kBlock), 0, st, a, geo.ntiles, geo.tchunk);
-    }
+    const Pass1Geometry g = lsm_fold_geometry(p).p1;
+    *ntiles = g.ntiles;
+    if (p.N < 2 || a.KE < 1 || a.KE > kChainWidthMax) return hipErrorInvalidValue;
+    for_vec4(g.v4, [&](auto vec) {
+        for_put(a.is_put, [&](auto put) {
+            constexpr int VEC = decltype(vec)::value, PUT = decltype(put)::value;
+            hipLaunchKernelGGL((lsm_pass1_fold_chain_kernel<VEC, kFoldTpw, PUT>), g.grid, dim3(kBlock), 0, st, a, g.ntiles, g.tchunk);
+        });
+    });
     return hipGetLastError();
 }
 
@@ -357,28 +354,23 @@ static hipError_t launch_pass2_chain(hipStream_t st, const ChainSweepArgs& a, in
     return hipGetLastError();
 }
 
-template <int VEC, int PUT>
-static hipError_t launch_pass2_chain_ke(hipStream_t st, const ChainSweepArgs& a, int nblk, size_t dyn)
-{
-    switch (a.KE) {
-    case 1: return launch_pass2_chain<VEC, PUT, 1>(st, a, nblk, dyn);
-    case 2: return launch_pass2_chain<VEC, PUT, 2>(st, a, nblk, dyn);
-    case 4:
-        if constexpr (VEC <= 2) return launch_pass2_chain<VEC, PUT, 4>(st, a, nblk, dyn);
-        return hipErrorInvalidValue;
-    default: return hipErrorInvalidValue;
-    }
-}
-
 hipError_t chain_pass2_sweep(hipStream_t st, const ChainSweepArgs& a, const LsmProblem& p, int* nblk)
 {
     const FoldGeometry geo = lsm_fold_geometry(p);
     *nblk = geo.nblk;
     const size_t dyn = sizeof(uint32_t) * 8 * (size_t)(p.N + 1) * (size_t)a.KE;
     if (dyn > kChainLdsBudget - sizeof(double) * kNQ * kRedStride) return hipErrorInvalidValue;
-    if (geo.vec2 == 4) return a.is_put ? launch_pass2_chain_ke<4, 1>(st, a, geo.nblk, dyn) : launch_pass2_chain_ke<4, 0>(st, a, geo.nblk, dyn);
-    if (geo.vec2 == 2) return a.is_put ? launch_pass2_chain_ke<2, 1>(st, a, geo.nblk, dyn) : launch_pass2_chain_ke<2, 0>(st, a, geo.nblk, dyn);
-    return a.is_put ? launch_pass2_chain_ke<1, 1>(st, a, geo.nblk, dyn) : launch_pass2_chain_ke<1, 0>(st, a, geo.nblk, dyn);
+    if (a.KE != 1 && a.KE != 2 && a.KE != 4) return hipErrorInvalidValue;
+    return for_vec(geo.vec2, [&](auto vec) {
+        return for_put(a.is_put, [&](auto put) {
+            return for_int<1, 2, 4>(a.KE, [&](auto ke) {
+                constexpr int VEC = decltype(vec)::value, PUT = decltype(put)::value, KE = decltype(ke)::value;
+                // (four entries at four columns per thread would spill: chain_fused_width never asks for them)
+                if constexpr (VEC <= 2 || KE < 4) return launch_pass2_chain<VEC, PUT, KE>(st, a, geo.nblk, dyn);
+                else return hipErrorInvalidValue;
+            });
+        });
+    });
 }
 
 }  // namespace omc

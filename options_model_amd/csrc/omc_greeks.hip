@@ -189,7 +189,7 @@ __global__ __launch_bounds__(kBlock) void lsm_greeks_finalize_kernel(const doubl
 
 int greeks_vec(const GreeksArgs& a)
 {
-    return ((a.cols % 2) == 0 && (a.ld % 2) == 0 && ((uintptr_t)a.S % 8) == 0) ? 2 : 1;
+    return rows_aligned(2, a.cols, a.S, a.ld) ? 2 : 1;
 }
 
 int64_t greeks_blocks(const GreeksArgs& a)
@@ -202,20 +202,16 @@ hipError_t lsm_greeks(hipStream_t st, const GreeksArgs& a, hipEvent_t ev_begin, 
 {
     const int64_t nblk = greeks_blocks(a);
     const size_t dyn = sizeof(double) * 4 * (size_t)(a.N + 1);
-    const bool v2 = greeks_vec(a) == 2, fold = a.cK != nullptr;
     if (ev_begin) (void)hipEventRecord(ev_begin, st);
-    auto launch = [&](auto vec, auto fo) {
-        constexpr int V = decltype(vec)::value;
-        constexpr bool F = decltype(fo)::value;
-        if (a.is_put) hipLaunchKernelGGL((lsm_greeks_kernel<V, F, 1>), dim3((unsigned)nblk), dim3(kBlock), dyn, st, a);
-        else hipLaunchKernelGGL((lsm_greeks_kernel<V, F, 0>), dim3((unsigned)nblk), dim3(kBlock), dyn, st, a);
-    };
-    using std::integral_constant;
-    using std::bool_constant;
-    if (fold && v2) launch(integral_constant<int, 2>{}, bool_constant<true>{});
-    else if (fold) launch(integral_constant<int, 1>{}, bool_constant<true>{});
-    else if (v2) launch(integral_constant<int, 2>{}, bool_constant<false>{});
-    else launch(integral_constant<int, 1>{}, bool_constant<false>{});
+    for_int<2, 1>(greeks_vec(a), [&](auto vec) {
+        for_flag(a.cK != nullptr, [&](auto fold) {
+            for_put(a.is_put, [&](auto put) {
+                constexpr int VEC = decltype(vec)::value, PUT = decltype(put)::value;
+                hipLaunchKernelGGL((lsm_greeks_kernel<VEC, decltype(fold)::value, PUT>), dim3((unsigned)nblk), dim3(kBlock), dyn,
+                                   st, a);
+            });
+        });
+    });
     if (ev_end) (void)hipEventRecord(ev_end, st);
     hipLaunchKernelGGL(lsm_greeks_finalize_kernel, dim3(3), dim3(kBlock), 0, st, a.part, nblk, a.gmom, a.N, a.result);
     return hipGetLastError();

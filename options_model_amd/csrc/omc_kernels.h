@@ -6,6 +6,8 @@
 #include <atomic>
 #include <cmath>
 
+#include "omc_dispatch.h"
+
 namespace omc {
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a property of a kernel ON A DEVICE: a process that prices on
@@ -48,17 +50,21 @@ inline void gbm_step_constants(double r, double sigma, double T, int n_steps, fl
     *b = (float)(sigma * std::sqrt(dt) * L2E);
 }
 
-// VEC-wide stores of a generator's rows need the pair count (the antithetic half starts P columns in), the leading
-// dimension and the base address aligned to VEC floats
-inline bool store_aligned(int vec, int64_t P, const float* S, int64_t ld)
+// The alignment rule of VEC-wide accesses to the rows of a path matrix, stated once: a generator's stores and a sweep's loads
+// need the column count (for the generators the pair count: the antithetic half starts P columns in), the leading dimension
+// and the base address aligned to VEC floats
+inline bool rows_aligned(int vec, int64_t cols, const float* S, int64_t ld)
 {
-    return (P % vec) == 0 && (ld % vec) == 0 && ((uintptr_t)S % (4 * vec)) == 0;
+    return (cols % vec) == 0 && (ld % vec) == 0 && ((uintptr_t)S % (4 * vec)) == 0;
 }
+// A different rule: 16-byte accesses to the per-path state arrays (sx, tex, live: no leading dimension, bases from the
+// workspace allocator) of the valuation kernels need only the path count
+inline bool state_vec4(int64_t M) { return (M % 4) == 0; }
 // pairs per thread: the hint (0 = 4), halved until the stores are aligned
 inline int store_vec_width(int hint, int64_t P, const float* S, int64_t ld)
 {
     int vec = hint > 0 ? hint : 4;
-    while (vec > 1 && !store_aligned(vec, P, S, ld)) vec >>= 1;
+    while (vec > 1 && !rows_aligned(vec, P, S, ld)) vec >>= 1;
     return vec;
 }
 
@@ -170,7 +176,15 @@ hipError_t lsm_step(hipStream_t st, const LsmProblem& p, const LsmWorkspace& w, 
 hipError_t lsm_reduce_step_moments(hipStream_t st, const LsmWorkspace& w, int t, int nblk);
 int lsm_step_blocks(int64_t M);   // grid of pass 2 / valuation sweeps (256-thread blocks)
 int lsm_sweep_blocks(int64_t M);  // grid of the per-step sweep
-int lsm_step_block_threads();     // its workgroup size (1024; OMC_STEP_BLOCK=512 for experiments)
+constexpr int kStepThreads = 1024;  // its workgroup size: one workgroup per CU, 256 partials
+// the template arguments of the per-step kernels: f(SEM, VEC, BLOCK)
+template <class F>
+inline void for_step(int semantics, bool v4, F&& f)
+{
+    for_int<0, 1>(semantics, [&](auto sem) {
+        for_vec4(v4, [&](auto vec) { f(sem, vec, std::integral_constant<int, kStepThreads>{}); });
+    });
+}
 // The whole per-step sweep with its arguments in a device block (lsm_sweep_args_bytes, filled from
 // lsm_sweep_args_image): capturable into a HIP graph whose replays serve every pricing of the same
 // geometry (M, N, semantics, ld, alignment of S).
@@ -204,12 +218,21 @@ hipError_t lsm_reduce_pass1(hipStream_t st, const LsmWorkspace& w, int64_t ntile
 bool lsm_pass2_tables(const LsmProblem& p, const LsmWorkspace& w, bool write_state);
 hipError_t lsm_pass2_sweep(hipStream_t st, const LsmProblem& p, const LsmWorkspace& w, bool write_state,
                            bool solve_from_moments, int* nblk);
-// launch geometry of the two sweeps on the folded matrix of p (p.fold_cK set): pass 1 -- 16-byte loads or scalar, tiles
-// per wave, tiles per step, steps per workgroup; pass 2 -- columns per thread asked for and taken (vec2), workgroups
-struct FoldGeometry {
+// tiles of 64 x VEC columns a wave of pass 1 takes per step: full storage, folded storage (both 1,024 paths at VEC 4)
+constexpr int kPass1Tpw = 4, kFoldTpw = 2;
+// launch geometry of pass 1 on the full matrix of p: 16-byte loads or scalar, tiles per step, steps per workgroup, grid
+struct Pass1Geometry {
     bool v4 = false;
-    int tpw = 2, tchunk = 32, fvec = 2, vec2 = 1, nblk = 0;
+    int tchunk = 32;
     int64_t ntiles = 0;
+    dim3 grid;
+};
+Pass1Geometry lsm_pass1_geometry(const LsmProblem& p);
+// launch geometry of the two sweeps on the folded matrix of p (p.fold_cK set): pass 1 as above, on the M / 2 stored columns;
+// pass 2 -- columns per thread asked for and taken (vec2), workgroups
+struct FoldGeometry {
+    Pass1Geometry p1;
+    int fvec = 2, vec2 = 1, nblk = 0;
 };
 FoldGeometry lsm_fold_geometry(const LsmProblem& p);
 // ---- the two-pass flow's latency-bound launches for K pricings of one geometry at once (omc_price_american_seq,

@@ -173,11 +173,6 @@ __global__ __launch_bounds__(kBlock) void lsm_finalize_group_kernel(SeqGroupArgs
 }
 
 // ------------------------------------------------------------------ host launchers
-static inline bool vec4_ok(const LsmProblem& p)
-{
-    return (p.M % 4) == 0 && (p.ld % 4) == 0 && ((uintptr_t)p.S % 16) == 0;
-}
-
 int lsm_step_blocks(int64_t M)
 {
     const int64_t per_block = (int64_t)kBlock * 4;
@@ -186,20 +181,9 @@ int lsm_step_blocks(int64_t M)
     return (int)(b > kMaxLsmBlocks ? kMaxLsmBlocks : b);
 }
 
-int lsm_step_block_threads()
-{
-    // threads per workgroup of the per-step sweep: 1024 (one workgroup per CU, 256 partials) or 512
-    static const int v = [] {
-        const char* e = getenv("OMC_STEP_BLOCK");
-        const int x = e ? atoi(e) : 0;
-        return x == 512 ? 512 : 1024;
-    }();
-    return v;
-}
-
 int lsm_sweep_blocks(int64_t M)
 {
-    const int64_t per_block = (int64_t)lsm_step_block_threads() * 4;
+    const int64_t per_block = (int64_t)kStepThreads * 4;
     int64_t b = (M + per_block - 1) / per_block;
     if (b < 1) b = 1;
     return (int)(b > kStepMaxBlocks ? kStepMaxBlocks : b);
@@ -211,45 +195,74 @@ size_t lsm_part1_tiles(int64_t M)
     return (size_t)((M + kBlock - 1) / kBlock);
 }
 
-static void fill_step_args(StepArgs& a, const LsmProblem& p, const LsmWorkspace& w, int t, bool external_moments)
+// ---- the argument blocks (declared in omc_lsm_dev.h)
+// the view of the contract that StepArgs, Pass1Args and Pass2Args share
+template <class Args>
+static void set_contract(Args& a, const LsmProblem& p, const LsmWorkspace& w)
 {
     a.S = p.S; a.ld = p.ld; a.M = p.M; a.N = p.N; a.is_put = p.is_put;
-    a.K = p.K; a.invK = 1.0 / p.K;
-    a.sx = w.sx; a.tex = w.tex; a.live = w.live; a.D = w.D; a.part = w.part; a.gmom = w.gmom; a.betas = w.betas;
+    a.K = p.K; a.invK = 1.0 / p.K; a.D = w.D;
+}
+
+StepArgs step_args(const LsmProblem& p, const LsmWorkspace& w, int t, bool external_moments)
+{
+    StepArgs a{};
+    set_contract(a, p, w);
+    a.sx = w.sx; a.tex = w.tex; a.live = w.live; a.part = w.part; a.gmom = w.gmom; a.betas = w.betas;
     a.t = t; a.nblk = lsm_sweep_blocks(p.M); a.external = external_moments ? 1 : 0;
     a.pstride = kPStride;
     a.gstride = w.gstride;
     a.cont = w.cont; a.ldc = w.ldc;
+    return a;
 }
 
-template <int SEM, int VEC, int BLOCK>
-static void launch_step(hipStream_t st, const StepArgs& a, const StepArgs* ind, int t, size_t dyn)
+Pass1Args pass1_args(const LsmProblem& p, const LsmWorkspace& w, int64_t ntiles, int tchunk)
 {
-    const dim3 grid(a.nblk), block(BLOCK);
-    if (ind) hipLaunchKernelGGL((lsm_step_ind_kernel<SEM, VEC, BLOCK>), grid, block, dyn, st, ind, t);
-    else hipLaunchKernelGGL((lsm_step_kernel<SEM, VEC, BLOCK>), grid, block, dyn, st, a);
+    Pass1Args a{};
+    set_contract(a, p, w);
+    a.part1 = w.part1; a.ntiles = ntiles; a.tchunk = tchunk;
+    if (p.fold_cK) {  // the folded matrix: M / 2 stored columns
+        a.M = p.M / 2;
+        a.cK = p.fold_cK;
+    }
+    return a;
+}
+
+Pass2Args pass2_args(const LsmProblem& p, const LsmWorkspace& w, int nblk)
+{
+    Pass2Args a{};
+    set_contract(a, p, w);
+    a.betas = w.betas; a.sx = w.sx; a.tex = w.tex; a.part = w.part;
+    a.nblk = nblk; a.pstride = kPStride;
+    if (p.fold_cK) {  // the folded matrix: M / 2 stored columns, both partners decided from every spot; no state arrays
+        a.M = p.M / 2;
+        a.cK = p.fold_cK;
+    }
+    return a;
+}
+
+FinalArgs final_args(const LsmProblem& p, const LsmWorkspace& w, int tval, bool use_flags, bool fill_state)
+{
+    FinalArgs a{};
+    a.sx = w.sx; a.tex = w.tex; a.live = use_flags ? w.live : nullptr;
+    a.M = p.M; a.N = p.N; a.is_put = p.is_put; a.tval = tval; a.fill_state = fill_state ? 1 : 0;
+    a.K = p.K; a.D = w.D; a.part = w.part;
+    a.nblk = lsm_step_blocks(p.M); a.pstride = kPStride;
+    return a;
 }
 
 // `ind` != null: the kernel reads its arguments from that device block (see lsm_step_args)
 static hipError_t lsm_step_impl(hipStream_t st, const LsmProblem& p, const LsmWorkspace& w, int semantics,
                                 int t, bool external_moments, const StepArgs* ind)
 {
-    StepArgs a;
-    fill_step_args(a, p, w, t, external_moments);
-    const bool v4 = vec4_ok(p);
+    const StepArgs a = step_args(p, w, t, external_moments);
     const size_t dyn = semantics == 1 ? sizeof(double) * (size_t)(p.N + 1) : 0;
-    const bool big = lsm_step_block_threads() == 1024;
-#define OMC_STEP(SEM, VEC)                                                       \
-    do {                                                                         \
-        if (big) launch_step<SEM, VEC, 1024>(st, a, ind, t, dyn);               \
-        else launch_step<SEM, VEC, 512>(st, a, ind, t, dyn);                    \
-    } while (0)
-    if (semantics == 0) {
-        if (v4) OMC_STEP(0, 4); else OMC_STEP(0, 1);
-    } else {
-        if (v4) OMC_STEP(1, 4); else OMC_STEP(1, 1);
-    }
-#undef OMC_STEP
+    for_step(semantics, rows_aligned(4, p.M, p.S, p.ld), [&](auto sem, auto vec, auto block) {
+        constexpr int SEM = decltype(sem)::value, VEC = decltype(vec)::value, BLOCK = decltype(block)::value;
+        const dim3 grid(a.nblk), threads(BLOCK);
+        if (ind) hipLaunchKernelGGL((lsm_step_ind_kernel<SEM, VEC, BLOCK>), grid, threads, dyn, st, ind, t);
+        else hipLaunchKernelGGL((lsm_step_kernel<SEM, VEC, BLOCK>), grid, threads, dyn, st, a);
+    });
     return hipGetLastError();
 }
 
@@ -261,23 +274,14 @@ hipError_t lsm_step(hipStream_t st, const LsmProblem& p, const LsmWorkspace& w, 
 
 size_t lsm_sweep_args_bytes() { return sizeof(SweepArgs); }
 
-static void fill_final_args(FinalArgs& a, const LsmProblem& p, const LsmWorkspace& w, int tval, bool use_flags,
-                            bool fill_state)
-{
-    a.sx = w.sx; a.tex = w.tex; a.live = use_flags ? w.live : nullptr;
-    a.M = p.M; a.N = p.N; a.is_put = p.is_put; a.tval = tval; a.fill_state = fill_state ? 1 : 0;
-    a.K = p.K; a.D = w.D; a.part = w.part;
-    a.nblk = lsm_step_blocks(p.M); a.pstride = kPStride;
-}
-
 // host image of the device argument block the indirect kernels read
 void lsm_sweep_args_image(const LsmProblem& p, const LsmWorkspace& w, int semantics, bool fill_state, void* out,
                           bool external_moments)
 {
     SweepArgs s;
     memset(&s, 0, sizeof s);
-    fill_step_args(s.step, p, w, 0, external_moments);
-    fill_final_args(s.fin, p, w, semantics == 1 ? 0 : 1, semantics == 0, fill_state);
+    s.step = step_args(p, w, 0, external_moments);
+    s.fin = final_args(p, w, semantics == 1 ? 0 : 1, semantics == 0, fill_state);
     s.fz.part = w.part; s.fz.gmom = w.gmom; s.fz.result = w.result;
     s.fz.nblk = s.fin.nblk; s.fz.N = p.N; s.fz.pstride = kPStride; s.fz.gstride = w.gstride;
     memcpy(out, &s, sizeof s);
@@ -301,18 +305,10 @@ hipError_t lsm_step_multi(hipStream_t st, const void* table_dev, int K, int G, i
     const SweepArgs* tab = (const SweepArgs*)table_dev;
     const dim3 grid((unsigned)(K * G));
     const size_t dyn = semantics == 1 ? sizeof(double) * (size_t)(N + 1) : 0;
-    const bool big = lsm_step_block_threads() == 1024;
-#define OMC_STEPM(SEM, VEC)                                                                                    \
-    do {                                                                                                       \
-        if (big) hipLaunchKernelGGL((lsm_step_multi_kernel<SEM, VEC, 1024>), grid, dim3(1024), dyn, st, tab, G, t); \
-        else hipLaunchKernelGGL((lsm_step_multi_kernel<SEM, VEC, 512>), grid, dim3(512), dyn, st, tab, G, t);  \
-    } while (0)
-    if (semantics == 0) {
-        if (vec4) OMC_STEPM(0, 4); else OMC_STEPM(0, 1);
-    } else {
-        if (vec4) OMC_STEPM(1, 4); else OMC_STEPM(1, 1);
-    }
-#undef OMC_STEPM
+    for_step(semantics, vec4, [&](auto sem, auto vec, auto block) {
+        constexpr int SEM = decltype(sem)::value, VEC = decltype(vec)::value, BLOCK = decltype(block)::value;
+        hipLaunchKernelGGL((lsm_step_multi_kernel<SEM, VEC, BLOCK>), grid, dim3(BLOCK), dyn, st, tab, G, t);
+    });
     return hipGetLastError();
 }
 
@@ -327,8 +323,9 @@ hipError_t lsm_final_multi(hipStream_t st, const void* table_dev, int K, int64_t
 {
     const SweepArgs* tab = (const SweepArgs*)table_dev;
     const int nblk = lsm_step_blocks(M);
-    if ((M % 4) == 0) hipLaunchKernelGGL((lsm_final_multi_kernel<4>), dim3(nblk, 1, K), dim3(kBlock), 0, st, tab);
-    else hipLaunchKernelGGL((lsm_final_multi_kernel<1>), dim3(nblk, 1, K), dim3(kBlock), 0, st, tab);
+    for_vec4(state_vec4(M), [&](auto vec) {
+        hipLaunchKernelGGL((lsm_final_multi_kernel<decltype(vec)::value>), dim3(nblk, 1, K), dim3(kBlock), 0, st, tab);
+    });
     hipLaunchKernelGGL(lsm_finalize_multi_kernel, dim3(K), dim3(kBlock), 0, st, tab);
     return hipGetLastError();
 }
@@ -345,8 +342,9 @@ hipError_t lsm_sweep_indirect(hipStream_t st, const LsmProblem& p, const LsmWork
         if (e != hipSuccess) return e;
     }
     const int nblk = lsm_step_blocks(p.M);
-    if ((p.M % 4) == 0) hipLaunchKernelGGL((lsm_final_ind_kernel<4>), dim3(nblk), dim3(kBlock), 0, st, &sa->fin);
-    else hipLaunchKernelGGL((lsm_final_ind_kernel<1>), dim3(nblk), dim3(kBlock), 0, st, &sa->fin);
+    for_vec4(state_vec4(p.M), [&](auto vec) {
+        hipLaunchKernelGGL((lsm_final_ind_kernel<decltype(vec)::value>), dim3(nblk), dim3(kBlock), 0, st, &sa->fin);
+    });
     hipLaunchKernelGGL(lsm_finalize_ind_kernel, dim3(1), dim3(kBlock), 0, st, &sa->fz);
     return hipGetLastError();
 }
@@ -364,80 +362,27 @@ hipError_t lsm_fold_table(hipStream_t st, double* cK, int N, double c0, double g
     return hipGetLastError();
 }
 
-// The launch geometry of the two sweeps on the folded matrix of `p` (declared in omc_kernels.h: the chain sweeps of
-// omc_chain.hip form their sums in the very same tiles, blocks and slots).
-FoldGeometry lsm_fold_geometry(const LsmProblem& p)
+// steps per workgroup of a pass-1 sweep: `tchunk`, or what OMC_PASS1_TCHUNK asks for when that is 2 .. max (the only
+// tuning knob left: tools/soak_tchunk.py walks the chunk lengths with it)
+static int pass1_tchunk(int tchunk, int max)
 {
-    FoldGeometry g;
-    const int64_t P = p.M / 2;
-    g.v4 = (P % 4) == 0 && (p.ld % 4) == 0 && ((uintptr_t)p.S % 16) == 0;
-    static const int tpw_env = getenv("OMC_FOLD_TPW") ? atoi(getenv("OMC_FOLD_TPW")) : 0;
-    g.tpw = (g.v4 && (tpw_env == 1 || tpw_env == 4)) ? tpw_env : 2;
-    const int64_t per_wave = 64 * (int64_t)(g.v4 ? 4 : 1) * g.tpw;
-    g.ntiles = (P + per_wave - 1) / per_wave;
-    // Steps per workgroup: the folded sweep is bound by its float64 arithmetic, not by the rows it reads, so what counts is
-    // that every CU stays busy to the end -- many short workgroups (measured at C2, 245 tile-workgroups: chunks of 16-32
-    // steps 0.145-0.147 ms, 63 steps 0.156, 84 steps -- one resident round -- 0.162, 126 steps 0.183; 8M paths: 32).
-    static const int tch_env = getenv("OMC_PASS1_TCHUNK") ? atoi(getenv("OMC_PASS1_TCHUNK")) : 0;
-    g.tchunk = (tch_env >= 2 && tch_env <= kFoldMaxChunk) ? tch_env : 32;
-    static const int fvec_env = getenv("OMC_FOLD_P2_VEC") ? atoi(getenv("OMC_FOLD_P2_VEC")) : 0;
-    // columns per thread of the folded pass 2: 2 (8-byte loads, twice the threads) until the 16-byte form alone fills the
-    // chip with workgroups (measured: C2's 0.5M columns 0.131 against 0.136 ms, C3's 4M columns 1.026 against 1.008)
-    g.fvec = (fvec_env == 1 || fvec_env == 2 || fvec_env == 4) ? fvec_env : (P >= (int64_t(1) << 21) ? 4 : 2);
-    g.nblk = lsm_step_blocks(P * (4 / g.fvec));
-    g.vec2 = g.v4 && g.fvec == 4 ? 4 : (g.v4 && g.fvec == 2 ? 2 : 1);
-    return g;
+    static const int env = getenv("OMC_PASS1_TCHUNK") ? atoi(getenv("OMC_PASS1_TCHUNK")) : 0;
+    return (env >= 2 && env <= max) ? env : tchunk;
 }
 
-// pass 1 on the folded matrix: P = M / 2 stored columns, two tiles of 64 x VEC columns per wave and step (= 1,024 paths, as
-// in the full sweep; OMC_FOLD_TPW = 1 | 4 for experiments)
-static hipError_t lsm_pass1_sweep_fold(hipStream_t st, const LsmProblem& p, const LsmWorkspace& w, int64_t* ntiles)
+static dim3 pass1_grid(int64_t ntiles, int N, int tchunk)
 {
-    Pass1Args a;
-    const int64_t P = p.M / 2;
-    a.S = p.S; a.ld = p.ld; a.M = P; a.N = p.N; a.is_put = p.is_put;
-    a.K = p.K; a.invK = 1.0 / p.K; a.D = w.D; a.part1 = w.part1; a.cK = p.fold_cK;
-    const FoldGeometry geo = lsm_fold_geometry(p);
-    const bool v4 = geo.v4;
-    const int tpw = geo.tpw;
-    a.ntiles = geo.ntiles;
-    const int64_t wgs_x = (a.ntiles + 3) / 4;
-    a.tchunk = geo.tchunk;
-    const dim3 grid((unsigned)wgs_x, (unsigned)((p.N - 1 + a.tchunk - 1) / a.tchunk));
-    if (w.ev_p1_begin) (void)hipEventRecord(w.ev_p1_begin, st);
-    if (v4 && tpw == 1) {
-        if (p.is_put) hipLaunchKernelGGL((lsm_pass1_fold_kernel<4, 1, 1>), grid, dim3(kBlock), 0, st, a);
-        else hipLaunchKernelGGL((lsm_pass1_fold_kernel<4, 1, 0>), grid, dim3(kBlock), 0, st, a);
-    } else if (v4 && tpw == 4) {
-        if (p.is_put) hipLaunchKernelGGL((lsm_pass1_fold_kernel<4, 4, 1>), grid, dim3(kBlock), 0, st, a);
-        else hipLaunchKernelGGL((lsm_pass1_fold_kernel<4, 4, 0>), grid, dim3(kBlock), 0, st, a);
-    } else if (v4) {
-        if (p.is_put) hipLaunchKernelGGL((lsm_pass1_fold_kernel<4, 2, 1>), grid, dim3(kBlock), 0, st, a);
-        else hipLaunchKernelGGL((lsm_pass1_fold_kernel<4, 2, 0>), grid, dim3(kBlock), 0, st, a);
-    } else {
-        if (p.is_put) hipLaunchKernelGGL((lsm_pass1_fold_kernel<1, 2, 1>), grid, dim3(kBlock), 0, st, a);
-        else hipLaunchKernelGGL((lsm_pass1_fold_kernel<1, 2, 0>), grid, dim3(kBlock), 0, st, a);
-    }
-    if (w.ev_p1_end) (void)hipEventRecord(w.ev_p1_end, st);
-    *ntiles = a.ntiles;
-    return hipGetLastError();
+    return dim3((unsigned)((ntiles + 3) / 4), (unsigned)((N - 1 + tchunk - 1) / tchunk));
 }
 
-hipError_t lsm_pass1_sweep(hipStream_t st, const LsmProblem& p, const LsmWorkspace& w, int64_t* ntiles)
+// The launch geometry of pass 1 on the full matrix of `p`: kPass1Tpw tiles of 64 x VEC columns per wave and step
+// (defaults measured on MI355X)
+Pass1Geometry lsm_pass1_geometry(const LsmProblem& p)
 {
-    *ntiles = 0;
-    if (p.N < 2) return hipSuccess;
-    if (p.fold_cK) return lsm_pass1_sweep_fold(st, p, w, ntiles);
-    Pass1Args a;
-    a.S = p.S; a.ld = p.ld; a.M = p.M; a.N = p.N; a.is_put = p.is_put;
-    a.K = p.K; a.invK = 1.0 / p.K; a.D = w.D; a.part1 = w.part1;
-    const bool v4 = vec4_ok(p);
-    // tuning knobs (defaults measured on MI355X): tiles per wave, steps per block
-    static const int tpw_env = getenv("OMC_PASS1_TPW") ? atoi(getenv("OMC_PASS1_TPW")) : 0;
-    static const int tch_env = getenv("OMC_PASS1_TCHUNK") ? atoi(getenv("OMC_PASS1_TCHUNK")) : 0;
-    const int tpw = (v4 && (tpw_env == 1 || tpw_env == 2 || tpw_env == 8)) ? tpw_env : 4;
-    const int64_t per_wave = 64 * (int64_t)(v4 ? 4 : 1) * tpw;  // paths per wave per step
-    a.ntiles = (p.M + per_wave - 1) / per_wave;
+    Pass1Geometry g;
+    g.v4 = rows_aligned(4, p.M, p.S, p.ld);
+    const int64_t per_wave = 64 * (int64_t)(g.v4 ? 4 : 1) * kPass1Tpw;  // paths per wave per step
+    g.ntiles = (p.M + per_wave - 1) / per_wave;
     // Steps per workgroup.  The kernel holds 3 waves per SIMD (152 VGPRs), i.e. 3 workgroups per CU: when all the
     // workgroups of a launch fit on the chip at once there is no partly filled last round of dispatch (measured at
     // C2, 245 tile-workgroups: 8 chunks of 32 steps = 2.55 rounds 0.214 ms, 4 x 63 = 1.28 rounds 0.230, 3 x 84 =
@@ -450,26 +395,58 @@ hipError_t lsm_pass1_sweep(hipStream_t st, const LsmProblem& p, const LsmWorkspa
         return n > 0 ? n : 256;
     }();
     int tchunk = 32;
-    const int64_t wgs_x = (a.ntiles + 3) / 4;
+    const int64_t wgs_x = (g.ntiles + 3) / 4;
     if (wgs_x <= 3 * (int64_t)cus && p.N > 2) {
         const int chunks = (int)((3 * (int64_t)cus) / wgs_x);
         const int t = (p.N - 1 + chunks - 1) / chunks;
         if (t <= 126 && t >= 32) tchunk = t;
     }
-    a.tchunk = (tch_env >= 2 && tch_env <= kPass1MaxChunk) ? tch_env : tchunk;
-    const dim3 grid((unsigned)((a.ntiles + 3) / 4), (unsigned)((p.N - 1 + a.tchunk - 1) / a.tchunk));
+    g.tchunk = pass1_tchunk(tchunk, kPass1MaxChunk);
+    g.grid = pass1_grid(g.ntiles, p.N, g.tchunk);
+    return g;
+}
+
+// The launch geometry of the two sweeps on the folded matrix of `p` (declared in omc_kernels.h: the chain sweeps of
+// omc_chain.hip form their sums in the very same tiles, blocks and slots).  Pass 1: P = M / 2 stored columns, kFoldTpw
+// tiles of 64 x VEC columns per wave and step (= 1,024 paths, as in the full sweep).
+FoldGeometry lsm_fold_geometry(const LsmProblem& p)
+{
+    FoldGeometry g;
+    const int64_t P = p.M / 2;
+    g.p1.v4 = rows_aligned(4, P, p.S, p.ld);
+    const int64_t per_wave = 64 * (int64_t)(g.p1.v4 ? 4 : 1) * kFoldTpw;
+    g.p1.ntiles = (P + per_wave - 1) / per_wave;
+    // Steps per workgroup: the folded sweep is bound by its float64 arithmetic, not by the rows it reads, so what counts is
+    // that every CU stays busy to the end -- many short workgroups (measured at C2, 245 tile-workgroups: chunks of 16-32
+    // steps 0.145-0.147 ms, 63 steps 0.156, 84 steps -- one resident round -- 0.162, 126 steps 0.183; 8M paths: 32).
+    g.p1.tchunk = pass1_tchunk(32, kFoldMaxChunk);
+    g.p1.grid = pass1_grid(g.p1.ntiles, p.N, g.p1.tchunk);
+    // columns per thread of the folded pass 2: 2 (8-byte loads, twice the threads) until the 16-byte form alone fills the
+    // chip with workgroups (measured: C2's 0.5M columns 0.131 against 0.136 ms, C3's 4M columns 1.026 against 1.008)
+    g.fvec = P >= (int64_t(1) << 21) ? 4 : 2;
+    g.nblk = lsm_step_blocks(P * (4 / g.fvec));
+    g.vec2 = g.p1.v4 ? g.fvec : 1;
+    return g;
+}
+
+// pass 1, full or folded storage: geometry, arguments, dispatch
+hipError_t lsm_pass1_sweep(hipStream_t st, const LsmProblem& p, const LsmWorkspace& w, int64_t* ntiles)
+{
+    *ntiles = 0;
+    if (p.N < 2) return hipSuccess;
+    const Pass1Geometry g = p.fold_cK ? lsm_fold_geometry(p).p1 : lsm_pass1_geometry(p);
+    const Pass1Args a = pass1_args(p, w, g.ntiles, g.tchunk);
     if (w.ev_p1_begin) (void)hipEventRecord(w.ev_p1_begin, st);
-    auto launch = [&](auto vec, auto tp) {
-        constexpr int V = decltype(vec)::value, T = decltype(tp)::value;
-        if (p.is_put) hipLaunchKernelGGL((lsm_pass1_kernel<V, T, 1>), grid, dim3(kBlock), 0, st, a);
-        else hipLaunchKernelGGL((lsm_pass1_kernel<V, T, 0>), grid, dim3(kBlock), 0, st, a);
-    };
-    using std::integral_constant;
-    if (!v4) launch(integral_constant<int, 1>{}, integral_constant<int, 4>{});
-    else if (tpw == 1) launch(integral_constant<int, 4>{}, integral_constant<int, 1>{});
-    else if (tpw == 2) launch(integral_constant<int, 4>{}, integral_constant<int, 2>{});
-    else if (tpw == 8) launch(integral_constant<int, 4>{}, integral_constant<int, 8>{});
-    else launch(integral_constant<int, 4>{}, integral_constant<int, 4>{});
+    for_flag(p.fold_cK != nullptr, [&](auto fold) {
+        for_vec4(g.v4, [&](auto vec) {
+            for_put(p.is_put, [&](auto put) {
+                constexpr int VEC = decltype(vec)::value, PUT = decltype(put)::value;
+                if constexpr (decltype(fold)::value)
+                    hipLaunchKernelGGL((lsm_pass1_fold_kernel<VEC, kFoldTpw, PUT>), g.grid, dim3(kBlock), 0, st, a);
+                else hipLaunchKernelGGL((lsm_pass1_kernel<VEC, kPass1Tpw, PUT>), g.grid, dim3(kBlock), 0, st, a);
+            });
+        });
+    });
     if (w.ev_p1_end) (void)hipEventRecord(w.ev_p1_end, st);
     *ntiles = a.ntiles;
     return hipGetLastError();
@@ -499,51 +476,36 @@ bool lsm_pass2_tables(const LsmProblem& p, const LsmWorkspace& w, bool write_sta
 hipError_t lsm_pass2_sweep(hipStream_t st, const LsmProblem& p, const LsmWorkspace& w, bool write_state,
                            bool solve_from_moments, int* nblk_out)
 {
-    Pass2Args a;
-    a.S = p.S; a.ld = p.ld; a.M = p.M; a.N = p.N; a.is_put = p.is_put;
-    a.K = p.K; a.invK = 1.0 / p.K; a.D = w.D; a.betas = w.betas; a.sx = w.sx; a.tex = w.tex;
-    a.part = w.part;
-    if (solve_from_moments) {
+    const bool fold = p.fold_cK != nullptr;
+    const FoldGeometry geo = fold ? lsm_fold_geometry(p) : FoldGeometry{};
+    const int nblk = fold ? geo.nblk : lsm_step_blocks(p.M);
+    *nblk_out = nblk;
+    if (fold && write_state) return hipErrorInvalidValue;  // (the folded sweep keeps no state arrays)
+    Pass2Args a = pass2_args(p, w, nblk);
+    const bool tab = lsm_pass2_tables(p, w, write_state);
+    if (tab) {  // the table launch solved the fits into w.betas
+        a.crit = w.crit;
+    } else if (solve_from_moments) {
         a.gmom = w.gmom;
         a.betas_out = w.betas;
     }
-    const FoldGeometry geo = p.fold_cK ? lsm_fold_geometry(p) : FoldGeometry{};
-    const int fvec = geo.fvec;
-    const int nblk = p.fold_cK ? geo.nblk : lsm_step_blocks(p.M);
-    a.nblk = nblk; a.pstride = kPStride;
     const size_t dyn = sizeof(double) * 4 * (size_t)(p.N + 1);
-    const bool v4 = vec4_ok(p);
-    *nblk_out = nblk;
-    const bool tab = lsm_pass2_tables(p, w, write_state);
-    if (tab) {  // the table launch solved the fits into w.betas
-        a.gmom = nullptr;
-        a.betas_out = nullptr;
-        a.crit = w.crit;
-    }
-    if (p.fold_cK) {  // the folded matrix: M / 2 stored columns, both partners decided from every spot; no state arrays
-        if (write_state) return hipErrorInvalidValue;
-        a.M = p.M / 2;
-        a.cK = p.fold_cK;
-        const bool f4 = geo.v4;
-        auto launch = [&](auto vec) {
-            constexpr int V = decltype(vec)::value;
-            if (tab) {
-                if (p.is_put) hipLaunchKernelGGL((lsm_pass2_fold_kernel<V, 1, true>), dim3(nblk), dim3(kBlock), dyn, st, a);
-                else hipLaunchKernelGGL((lsm_pass2_fold_kernel<V, 0, true>), dim3(nblk), dim3(kBlock), dyn, st, a);
-            } else {
-                if (p.is_put) hipLaunchKernelGGL((lsm_pass2_fold_kernel<V, 1, false>), dim3(nblk), dim3(kBlock), dyn, st, a);
-                else hipLaunchKernelGGL((lsm_pass2_fold_kernel<V, 0, false>), dim3(nblk), dim3(kBlock), dyn, st, a);
-            }
-        };
-        if (f4 && fvec == 4) launch(std::integral_constant<int, 4>{});
-        else if (f4 && fvec == 2) launch(std::integral_constant<int, 2>{});
-        else launch(std::integral_constant<int, 1>{});
-    } else if (v4) {
-        if (write_state) hipLaunchKernelGGL((lsm_pass2_kernel<4, true>), dim3(nblk), dim3(kBlock), dyn, st, a);
-        else hipLaunchKernelGGL((lsm_pass2_kernel<4, false>), dim3(nblk), dim3(kBlock), dyn, st, a);
+    const dim3 grid(nblk), block(kBlock);
+    if (fold) {
+        for_vec(geo.vec2, [&](auto vec) {
+            for_put(p.is_put, [&](auto put) {
+                for_flag(tab, [&](auto tb) {
+                    constexpr int VEC = decltype(vec)::value, PUT = decltype(put)::value;
+                    hipLaunchKernelGGL((lsm_pass2_fold_kernel<VEC, PUT, decltype(tb)::value>), grid, block, dyn, st, a);
+                });
+            });
+        });
     } else {
-        if (write_state) hipLaunchKernelGGL((lsm_pass2_kernel<1, true>), dim3(nblk), dim3(kBlock), dyn, st, a);
-        else hipLaunchKernelGGL((lsm_pass2_kernel<1, false>), dim3(nblk), dim3(kBlock), dyn, st, a);
+        for_vec4(rows_aligned(4, p.M, p.S, p.ld), [&](auto vec) {
+            for_flag(write_state, [&](auto ws) {
+                hipLaunchKernelGGL((lsm_pass2_kernel<decltype(vec)::value, decltype(ws)::value>), grid, block, dyn, st, a);
+            });
+        });
     }
     if (w.ev_p2_end) (void)hipEventRecord(w.ev_p2_end, st);
     return hipGetLastError();
@@ -564,10 +526,7 @@ hipError_t lsm_pass2_apply(hipStream_t st, const LsmProblem& p, const LsmWorkspa
     }
     int nblk = 0;
     const hipError_t e = lsm_pass2_sweep(st, p, w, write_state, solve_from_moments, &nblk);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(lsm_finalize_kernel, dim3(1), dim3(kBlock), 0, st, w.part, w.gmom, w.result,
-                       nblk, p.N, kPStride);
-    return hipGetLastError();
+    return e != hipSuccess ? e : lsm_finalize(st, w.part, w.gmom, w.result, nblk, p.N);
 }
 
 SeqGroupSlot lsm_group_slot(const LsmProblem& p, const LsmWorkspace& w)
@@ -635,14 +594,11 @@ hipError_t lsm_finalize(hipStream_t st, const double* part, const double* gmom, 
 hipError_t lsm_final_reduce(hipStream_t st, const LsmProblem& p, const LsmWorkspace& w, int tval, bool use_flags,
                             bool fill_state)
 {
-    FinalArgs a;
-    fill_final_args(a, p, w, tval, use_flags, fill_state);
-    const int nblk = a.nblk;
-    if ((p.M % 4) == 0) hipLaunchKernelGGL((lsm_final_kernel<4>), dim3(nblk), dim3(kBlock), 0, st, a);
-    else hipLaunchKernelGGL((lsm_final_kernel<1>), dim3(nblk), dim3(kBlock), 0, st, a);
-    hipLaunchKernelGGL(lsm_finalize_kernel, dim3(1), dim3(kBlock), 0, st, w.part, w.gmom, w.result,
-                       nblk, p.N, kPStride);
-    return hipGetLastError();
+    const FinalArgs a = final_args(p, w, tval, use_flags, fill_state);
+    for_vec4(state_vec4(p.M), [&](auto vec) {
+        hipLaunchKernelGGL((lsm_final_kernel<decltype(vec)::value>), dim3(a.nblk), dim3(kBlock), 0, st, a);
+    });
+    return lsm_finalize(st, w.part, w.gmom, w.result, a.nblk, p.N);
 }
 
 }  // namespace omc

@@ -1320,4 +1320,13 @@ __device__ __forceinline__ void lsm_finalize_body(const double* __restrict__ par
     if (tid < 64 && (tid & 7) == 0) result[tid >> 3] = s;
 }
 
+// ---- host side: the only fill of the four argument blocks (definitions: omc_lsm.hip), each from (problem, workspace) with
+// the single-problem geometry (lsm_sweep_blocks / lsm_step_blocks slots, stride kPStride); the batched launchers
+// (omc_batch.hip) call the same and then set what their layout decides.  pass1_args / pass2_args take the folded case from
+// p.fold_cK: M = stored columns, cK.
+StepArgs step_args(const LsmProblem& p, const LsmWorkspace& w, int t, bool external_moments);
+Pass1Args pass1_args(const LsmProblem& p, const LsmWorkspace& w, int64_t ntiles, int tchunk);
+Pass2Args pass2_args(const LsmProblem& p, const LsmWorkspace& w, int nblk);
+FinalArgs final_args(const LsmProblem& p, const LsmWorkspace& w, int tval, bool use_flags, bool fill_state);
+
 }  // namespace omc

@@ -5,6 +5,7 @@
 #include <type_traits>
 
 #include "omc_device.h"
+#include "omc_dispatch.h"
 #include "omc_kernels.h"
 
 namespace omc {
@@ -44,27 +45,7 @@ struct PathArgs {
 HestonC make_heston(double r, double T, int n_steps, double kappa, double theta, double xi, double rho);
 // the argument block of `s` for P pairs (or P single paths): the only fill of PathArgs for the single-problem launchers
 PathArgs make_path_args(const PathSpec& s, int64_t P);
-
-// a run-time model / scheme or pairs-per-thread as a compile-time constant: f(std::integral_constant<int, MODEL>{}),
-// MODEL 0 GBM, 1/2/3 Heston scheme 0/1/2; f(std::integral_constant<int, VEC>{}), VEC 4, 2 or 1
-template <class F>
-inline void for_model(int model, int scheme, F&& f)
-{
-    using std::integral_constant;
-    if (model == 0) f(integral_constant<int, 0>{});
-    else if (scheme == 0) f(integral_constant<int, 1>{});
-    else if (scheme == 1) f(integral_constant<int, 2>{});
-    else f(integral_constant<int, 3>{});
-}
-
-template <class F>
-inline void for_vec(int vec, F&& f)
-{
-    using std::integral_constant;
-    if (vec == 4) f(integral_constant<int, 4>{});
-    else if (vec == 2) f(integral_constant<int, 2>{});
-    else f(integral_constant<int, 1>{});
-}
+// (model / scheme and pairs per thread as compile-time constants: for_model, for_vec of omc_dispatch.h)
 
 template <int VEC, bool ANTI>
 __device__ __forceinline__ void gbm_paths_body(const PathArgs& g)

@@ -11,6 +11,7 @@
 #include "../../include/omc.h"
 #include "../../options_model_amd/csrc/omc_batch.h"
 #include "../../options_model_amd/csrc/omc_kernels.h"
+#include "../../options_model_amd/csrc/omc_lsm_dev.h"
 
 #define REQUIRE(cond)                                                                 \
     do {                                                                              \
@@ -142,6 +143,43 @@ int main()
         REQUIRE(img == img2);  // no uninitialised padding leaks into the compared image
         omc::lsm_sweep_args_image(lp, w, 0, true, img2.data());
         REQUIRE(img != img2);
+    }
+    // ---- the sweeps' geometry functions and argument constructors (host arithmetic; without a device the CU count
+    // of the full pass 1 falls back to 256)
+    {
+        omc::LsmProblem lp{(const float*)0x1000, 1024, 1000, 50, 1, 100.0, 0.05, 1.0};
+        omc::LsmWorkspace w;
+        memset((void*)&w, 0, sizeof w);
+        w.gstride = 8;
+        REQUIRE(omc::rows_aligned(4, lp.M, lp.S, lp.ld) && !omc::rows_aligned(4, lp.M, lp.S, 1023) &&
+                !omc::rows_aligned(4, 1002, lp.S, lp.ld) && !omc::rows_aligned(4, lp.M, (const float*)0x1004, lp.ld));
+        REQUIRE(omc::state_vec4(1004) && !omc::state_vec4(1002));
+        const omc::Pass1Geometry g = omc::lsm_pass1_geometry(lp);
+        REQUIRE(g.v4 && g.ntiles == 1 && g.tchunk >= 32 && g.tchunk <= 126 && g.grid.x == 1);
+        REQUIRE(g.grid.y == (unsigned)((lp.N - 1 + g.tchunk - 1) / g.tchunk));
+        lp.ld = 1023;  // the leading dimension alone forces the scalar kernels: four times the tiles
+        REQUIRE(!omc::lsm_pass1_geometry(lp).v4 && omc::lsm_pass1_geometry(lp).ntiles == 4);
+        lp.ld = 1024;
+        const omc::Pass1Args a1 = omc::pass1_args(lp, w, g.ntiles, g.tchunk);
+        REQUIRE(a1.M == 1000 && a1.cK == nullptr && a1.ntiles == 1 && a1.tchunk == g.tchunk && a1.invK == 1.0 / 100.0);
+        const omc::Pass2Args a2 = omc::pass2_args(lp, w, 7);
+        REQUIRE(a2.M == 1000 && a2.cK == nullptr && a2.gmom == nullptr && a2.crit == nullptr && a2.nblk == 7 &&
+                a2.pstride == omc::kPStride);
+        const omc::StepArgs as = omc::step_args(lp, w, 3, true);
+        REQUIRE(as.t == 3 && as.external == 1 && as.nblk == omc::lsm_sweep_blocks(1000) && as.gstride == 8);
+        const omc::FinalArgs af = omc::final_args(lp, w, 1, false, true);
+        REQUIRE(af.live == nullptr && af.fill_state == 1 && af.nblk == omc::lsm_step_blocks(1000));
+        // folded storage: M / 2 stored columns in both blocks and in the geometry
+        const double cK[51] = {0};
+        lp.fold_cK = cK;
+        const omc::FoldGeometry fg = omc::lsm_fold_geometry(lp);
+        REQUIRE(fg.p1.v4 && fg.p1.ntiles == 1 && fg.p1.tchunk == 32 && fg.p1.grid.y == 2 && fg.fvec == 2 && fg.vec2 == 2 &&
+                fg.nblk == omc::lsm_step_blocks(1000));
+        REQUIRE(omc::pass1_args(lp, w, 1, 32).M == 500 && omc::pass1_args(lp, w, 1, 32).cK == cK);
+        REQUIRE(omc::pass2_args(lp, w, fg.nblk).M == 500 && omc::pass2_args(lp, w, fg.nblk).cK == cK);
+        lp.M = 1004;  // 502 stored columns: scalar loads
+        REQUIRE(!omc::lsm_fold_geometry(lp).p1.v4 && omc::lsm_fold_geometry(lp).vec2 == 1 &&
+                omc::lsm_fold_geometry(lp).p1.ntiles == 4);
     }
     printf("host_driver ok\n");
     return 0;

@@ -283,16 +283,20 @@ def test_lsm_frozen_betas_replay(ctx, golden):
     assert np.allclose(cf, pf["poly_mid_put_twopass_cf"], rtol=2e-6, atol=1e-5)
 
 
-def test_lsm_unaligned_leading_dimension(ctx):
-    """ld not a multiple of 4 -> scalar kernels; same answer as the vector path."""
-    M, N = 1002, 9
+@pytest.mark.parametrize("is_put", [True, False], ids=["put", "call"])
+@pytest.mark.parametrize("sem", ["reference", "textbook", "two_pass"])
+@pytest.mark.parametrize("M", [1002, 1004])
+def test_lsm_unaligned_leading_dimension(ctx, M, sem, is_put):
+    """ld = M + 3, not a multiple of 4 -> scalar kernels in every flow and for both payoff sides; same answer as the vector
+    path.  M = 1004 is a multiple of 4: there the leading dimension alone forces them."""
+    N = 9
     So = orc.gbm_paths(M, N, 100.0, R, SIG, T, 5)
     pad = np.zeros((N + 1, M + 3), np.float32)
     pad[:, :M] = So
     Sd = ctx.to_device(pad)
-    a = ctx.lsm_poly(Sd, K, R, T, True, "reference", want_state=True, n_paths=M)
+    a = ctx.lsm_poly(Sd, K, R, T, is_put, sem, want_state=True, n_paths=M)
     Sd.free()
-    ref = orc.lsm_poly(So, K, R, T, True, "reference")
+    ref = orc.lsm_poly(So, K, R, T, is_put, sem)
     assert np.array_equal(a["tex"], ref["tex"])
     assert abs(a["price"] - ref["price"]) <= 1e-9 * ref["price"]
 
