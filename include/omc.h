@@ -572,6 +572,51 @@ int omc_price_american_bounds(omc_ctx* ctx, const omc_params* p, const omc_bound
                               double* q_out /* NULL or host [n_outer][N]: Q^_t, for tests */,
                               double* samples_out /* NULL or host [n_outer] */, omc_bounds* out);
 
+/* ---- Andersen-Broadie price bounds for multi-asset American options ------------------------ */
+/* omc_price_american_bounds on the INDEX X_t of d correlated GBM assets, 1 <= d <= 8, arithmetic basket, best-of or
+ * worst-of: a lower and an upper bound on the Bermudan value of the game Z_t = exp(-r t dt) max(phi(X_t), 0), t = 1..N,
+ * both from one frozen policy that is a function of the index alone.  What the bounds bracket is the TRUE value of the
+ * multi-asset game (any policy); how far the lower bound sits below it is what the index-alone policy costs.
+ * Arguments: p and b as omc_price_american_basket takes them (its checks run unchanged: GBM, antithetic = 1,
+ *   p->semantics = OMC_SEM_TWO_PASS, pair_offset + n_paths / 2 <= 2^40; p->S0, p->sigma not read); cfg, betas, betas_out,
+ *   q_out, samples_out as omc_price_american_bounds takes them.
+ * Policy: the rule of omc_lsm_apply_frozen on u = X / K - 1 with a table betas [N+1][4].  cfg->policy = OMC_SEM_REFERENCE /
+ *   OMC_SEM_TEXTBOOK / OMC_SEM_TWO_PASS: the fits omc_lsm_poly makes with that semantics on the index matrix that
+ *   omc_price_american_basket's generator writes for p at (p->seed, p->stream, p->pair_offset); OMC_POLICY_GIVEN: `betas`.
+ *   Decisions come from the stored-path exercise tables, on irregular dates from the float64 rule: the same decisions.
+ * Paths: every spot is the basket generator's (the section above): asset k of generator pair g draws the vanilla normals at
+ *   pair index g + ((uint64_t)k << 40), the correlated normals accumulate with k ascending in the same fmaf chain, the step
+ *   is s_k *= exp2(fmaf(+-b_k, y_k, a_k)), the index is formed from the asset spots by the kind's float32 rule.
+ * Lower bound: pairs 0 .. n_lower/2 - 1 of stream_lower (pair_offset 0): the index rows are bit for bit the S_keep of
+ *   omc_price_american_basket(n_paths = n_lower, stream = stream_lower, pair_offset = 0); each partner stops at the first
+ *   date the rule fires; the standard error comes from pair means.
+ * Outer paths: that generator at stream_outer, pair_offset 0, n_paths = n_outer: the index matrix [N+1][n_outer] and the
+ *   asset matrices A_k [N+1][n_outer] (S_keep and assets_keep of such a call).
+ * Inner simulations: inner pair j of item (i, t) is generator pair gbase + j on stream_inner, gbase = (i (N+1) + t)
+ *   n_inner/2, started at the outer ASSET spots A_k[t][i]; inner step n consumes generator row n - 1.  The inner index
+ *   spots are bit for bit rows 0 .. N-t of the S_keep that omc_price_american_basket writes for b with S0[k] = A_k[t][i],
+ *   n_paths = n_inner, stream = stream_inner, pair_offset = gbase and the same T, n_steps, K, weights and rho.
+ * Q^, L^, M^, the samples, upper, se_*, ci_*, n_exercised_lower and ms_* are omc_price_american_bounds' with X in the
+ *   place of S.  inner_path_steps counts PATH steps (a step of all d assets of one inner path is one).  The inner
+ *   simulations run as launches of at most 2^30 / d worst-case inner path steps.  float64 sums in a fixed order: identical
+ *   calls return identical bits.
+ * With d = 1, w[0] = 1 and q[0] = 0 (arithmetic, best-of or worst-of) every output has the bits of
+ *   omc_price_american_bounds for (S0[0], sigma[0]); with d = 1 and a yield q[0] these are the bounds of a single asset
+ *   with a continuous dividend yield.  A geometric index is one GBM: price it with d = 1 from (G0, sigma_G, q_G) of
+ *   omc_basket_table and w = 1 (kind OMC_BASKET_GEOMETRIC is refused here).
+ * Errors (nothing is launched): -7 null cfg / out; omc_price_american_basket's own (-7, -12, -29 .. -33, the omc_params
+ * checks, -24, -11); -34 kind OMC_BASKET_GEOMETRIC; -10 a distributed context; then -4, -7 (betas NULL with
+ * OMC_POLICY_GIVEN), -3 and -16 as omc_price_american_bounds. */
+typedef struct {
+    omc_bounds bounds;
+    double index0;          /* the index of the initial spots, float64 (x0 of omc_basket_table) */
+    int32_t n_assets, kind;
+} omc_basket_bounds;
+int omc_price_american_basket_bounds(omc_ctx* ctx, const omc_params* p, const omc_basket* b, const omc_bounds_config* cfg,
+                                     const double* betas /* policy == OMC_POLICY_GIVEN: host [N+1][4] */,
+                                     double* betas_out, double* q_out /* NULL or host [n_outer][N] */,
+                                     double* samples_out /* NULL or host [n_outer] */, omc_basket_bounds* out);
+
 /* ---- calibrator inner loop -------------------------------------- */
 /* replaces HestonPricer.price_options_batch / price_european_option
  * (options_model_3/heston_calibration.py:259-312) for ONE expiry: simulate n_paths antithetic

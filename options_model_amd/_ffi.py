@@ -145,6 +145,11 @@ class Bounds(C.Structure):
                 ("ms_fit", C.c_double), ("ms_lower", C.c_double), ("ms_upper", C.c_double), ("ms_total", C.c_double)]
 
 
+class BasketBounds(C.Structure):
+    """omc_basket_bounds: omc_bounds of the index of a basket plus the index of the initial spots, n_assets and kind."""
+    _fields_ = [("bounds", Bounds), ("index0", C.c_double), ("n_assets", C.c_int32), ("kind", C.c_int32)]
+
+
 class ChainEntry(C.Structure):
     """omc_chain_entry: strike and side of one quote of a chain (omc_price_american_chain)."""
     _fields_ = [("K", C.c_double), ("is_put", C.c_int32), ("reserved", C.c_int32)]
@@ -220,6 +225,8 @@ SIGNATURES = {
                                             _I64]),
     "omc_price_american_bounds": (C.c_int, [_P, C.POINTER(Params), C.POINTER(BoundsConfig), _P, _P, _P, _P,
                                             C.POINTER(Bounds)]),
+    "omc_price_american_basket_bounds": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Basket), C.POINTER(BoundsConfig), _P,
+                                                   _P, _P, _P, C.POINTER(BasketBounds)]),
     "omc_heston_price_strikes": (C.c_int, [_P, _I64, _I] + [_D] * 8 + [_U64, _U64, _I, _P, _I, _I, _P, _P]),
     "omc_heston_price_surface": (C.c_int, [_P, _I64, _I] + [_D] * 7 + [_U64, _I, _P, _P, _I, _P, _P, _I, _I, _P, _P]),
     "omc_price_american_seq": (C.c_int, [_P, C.POINTER(Params), _I, C.POINTER(Result)]),
@@ -838,6 +845,21 @@ class Context:
         omc_bounds plus `betas` (the policy used, [n_steps+1][4]) and, when asked, `q` ([n_outer][n_steps]: Q^_t) and
         `samples` ([n_outer]).  policy: a key of BOUND_POLICIES or its code; betas: the table of policy "given".  Streams
         default to params.stream + 1 / 2 / 3."""
+        return self._bounds(params, None, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner,
+                            betas, want_q, want_samples)
+
+    def price_american_basket_bounds(self, params: Params, basket: Basket, policy="textbook", n_lower=1_000_000,
+                                     n_outer=8192, n_inner=1024, stream_lower=None, stream_outer=None, stream_inner=None,
+                                     betas=None, want_q=False, want_samples=False):
+        """Andersen-Broadie bounds of the Bermudan game on the INDEX of 1 .. 8 correlated GBM assets
+        (omc_price_american_basket_bounds; arithmetic basket, best-of, worst-of) -> the dict of price_american_bounds plus
+        index0, n_assets, kind.  params and basket as price_american_basket takes them; the policy is a function of the
+        index alone.  Streams default to params.stream + 1 / 2 / 3."""
+        return self._bounds(params, basket, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner,
+                            betas, want_q, want_samples)
+
+    def _bounds(self, params, basket, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner, betas,
+                want_q, want_samples):
         N = int(params.n_steps)
         cfg = BoundsConfig()
         cfg.policy = BOUND_POLICIES.get(policy, -1) if isinstance(policy, str) else int(policy)
@@ -854,11 +876,19 @@ class Context:
         bo = np.zeros((N + 1, 4))
         q = np.zeros((max(int(n_outer), 0), N)) if want_q else None
         smp = np.zeros(max(int(n_outer), 0)) if want_samples else None
-        out = Bounds()
-        _check(self.lib, self.lib.omc_price_american_bounds(
-            self.handle, C.byref(params), C.byref(cfg), b.ctypes.data if b is not None else None, bo.ctypes.data,
-            q.ctypes.data if q is not None else None, smp.ctypes.data if smp is not None else None, C.byref(out)))
-        d = {k: getattr(out, k) for k, _ in Bounds._fields_}
+        tail = (b.ctypes.data if b is not None else None, bo.ctypes.data, q.ctypes.data if q is not None else None,
+                smp.ctypes.data if smp is not None else None)
+        if basket is None:
+            out = Bounds()
+            _check(self.lib, self.lib.omc_price_american_bounds(self.handle, C.byref(params), C.byref(cfg), *tail,
+                                                                C.byref(out)))
+            d = {k: getattr(out, k) for k, _ in Bounds._fields_}
+        else:
+            bb = BasketBounds()
+            _check(self.lib, self.lib.omc_price_american_basket_bounds(self.handle, C.byref(params), C.byref(basket),
+                                                                       C.byref(cfg), *tail, C.byref(bb)))
+            d = {k: getattr(bb.bounds, k) for k, _ in Bounds._fields_}
+            d.update(index0=bb.index0, n_assets=bb.n_assets, kind=bb.kind)
         d["betas"] = bo
         if want_q:
             d["q"] = q

@@ -549,16 +549,8 @@ class BasketResult:
 _BASKET_KINDS = ("basket", "geometric", "best-of", "worst-of")
 
 
-def price_american_basket(spots, K, r, sigmas, T, n_paths, n_steps, correlation=None, weights=None, dividend_yields=None,
-                          kind="basket", option_type="put", seed=None, device=None) -> BasketResult:
-    """American option on an index of 1 .. 8 correlated GBM assets (omc_price_american_basket, DESIGN.md section 16): the
-    two-pass poly LSM of price_american_option on the matrix of the index X_t -- kind "basket" sum w_i S_i, "geometric"
-    prod S_i^w_i, "best-of" max w_i S_i, "worst-of" min w_i S_i -- with the payoff max(K - X, 0) or max(X - K, 0).  The
-    regression is on the index, so the exercise policy is a function of the index alone: the usual dominant regressor for
-    baskets, a deliberately simple policy for best-of / worst-of.  correlation: [d][d], default identity; weights: default
-    1 / d for "basket" and "geometric", 1 for "best-of" and "worst-of"; dividend_yields: default 0; seed: default 42.
-    The flow is the reference's two-pass rule (DESIGN.md section 12): not comparable with tables of textbook LSM.
-    Antithetic paths, one GPU."""
+def _basket_args(spots, sigmas, weights, dividend_yields, correlation, kind):
+    """The per-asset arguments of the multi-asset entry points, checked and with their defaults -> (S0, sigma, q, w, rho)."""
     if kind not in _BASKET_KINDS:
         raise ValueError(f"kind must be one of {list(_BASKET_KINDS)}.")
     try:
@@ -587,6 +579,21 @@ def price_american_basket(spots, K, r, sigmas, T, n_paths, n_steps, correlation=
         [[float(x) for x in row] for row in correlation]
     if len(rho) != d or any(len(row) != d for row in rho):
         raise ValueError(f"correlation must be a {d} x {d} matrix.")
+    return S0, sig, q, w, rho
+
+
+def price_american_basket(spots, K, r, sigmas, T, n_paths, n_steps, correlation=None, weights=None, dividend_yields=None,
+                          kind="basket", option_type="put", seed=None, device=None) -> BasketResult:
+    """American option on an index of 1 .. 8 correlated GBM assets (omc_price_american_basket, DESIGN.md section 16): the
+    two-pass poly LSM of price_american_option on the matrix of the index X_t -- kind "basket" sum w_i S_i, "geometric"
+    prod S_i^w_i, "best-of" max w_i S_i, "worst-of" min w_i S_i -- with the payoff max(K - X, 0) or max(X - K, 0).  The
+    regression is on the index, so the exercise policy is a function of the index alone: the usual dominant regressor for
+    baskets, a deliberately simple policy for best-of / worst-of.  correlation: [d][d], default identity; weights: default
+    1 / d for "basket" and "geometric", 1 for "best-of" and "worst-of"; dividend_yields: default 0; seed: default 42.
+    The flow is the reference's two-pass rule (DESIGN.md section 12): not comparable with tables of textbook LSM.
+    Antithetic paths, one GPU."""
+    S0, sig, q, w, rho = _basket_args(spots, sigmas, weights, dividend_yields, correlation, kind)
+    d = len(S0)
     _validate(S0[0], K, T, r, sig[0], n_paths, n_steps, option_type)
     M = int(n_paths) // 2 * 2
     if M <= 0:
@@ -661,6 +668,58 @@ def price_american_bounds(S0, K, r, sigma, T, n_paths, n_steps, option_type="put
                         option_type=option_type,
                         timings_ms=dict(fit=out["ms_fit"], lower=out["ms_lower"], upper=out["ms_upper"],
                                         total=out["ms_total"]))
+
+
+@dataclass
+class BasketBoundsResult(BoundsResult):
+    """price_american_basket_bounds: BoundsResult for the index of a basket, with the index of the initial spots, the number
+    of assets and the kind.  The policy is a function of the index alone, so `lower` is what that policy earns; `upper`
+    bounds the value of the multi-asset game under ANY policy."""
+    index0: float = 0.0
+    n_assets: int = 1
+    kind: str = "basket"
+
+
+def price_american_basket_bounds(spots, K, r, sigmas, T, n_paths, n_steps, correlation=None, weights=None,
+                                 dividend_yields=None, kind="basket", option_type="put", policy="textbook",
+                                 n_lower=1_000_000, n_outer=8192, n_inner=1024, seed=42, stream=0, betas=None, device=None,
+                                 ctx=None) -> BasketBoundsResult:
+    """Lower and upper bounds on the Bermudan value of an option on an index of 1 .. 8 correlated GBM assets
+    (omc_price_american_basket_bounds): price_american_bounds with the assets, kinds and defaults of
+    price_american_basket.  The policy (`policy` / `betas` as price_american_bounds takes them) regresses on the index
+    alone; the lower-bound, outer and inner paths use Philox streams stream + 1, + 2, + 3.  With one asset and a dividend
+    yield these are the bounds of a single stock with a continuous yield.  kind="geometric": the geometric index is itself
+    one GBM, so the call is made with ONE asset (G0, sigma_G, q_G) of weight 1 -- n_assets of the result is then 1 and
+    index0 is G0.  One GPU."""
+    if policy not in _ffi.BOUND_POLICIES:
+        raise ValueError(f"policy must be one of {sorted(_ffi.BOUND_POLICIES)}.")
+    if (policy == "given") != (betas is not None):
+        raise ValueError("betas must be given exactly when policy='given'.")
+    for name, v in (("n_lower", n_lower), ("n_outer", n_outer), ("n_inner", n_inner)):
+        if int(v) < 2 or int(v) % 2:
+            raise ValueError(f"{name} must be an even integer >= 2 (antithetic pairs).")
+    S0, sig, q, w, rho = _basket_args(spots, sigmas, weights, dividend_yields, correlation, kind)
+    _validate(S0[0], K, T, r, sig[0], n_paths, n_steps, option_type)
+    M = int(n_paths) // 2 * 2
+    if M <= 0:
+        raise ValueError("num_simulations and num_time_steps must be positive integers.")
+    p = _ffi.make_params(model="gbm", is_put=(option_type == "put"), semantics="two_pass", antithetic=True, n_paths=M,
+                         n_steps=int(n_steps), S0=S0[0], K=K, r=r, sigma=sig[0], T=T, seed=seed, stream=stream)
+    b = _ffi.make_basket(S0, sig, q, w, rho, kind)
+    if kind == "geometric":  # one GBM: (G0, sigma_G, q_G) of the library's own table
+        G0, sigma_G, q_G = _ffi.basket_table(p, b)[4]
+        b = _ffi.make_basket([G0], [sigma_G], [q_G], [1.0], None, "basket")
+    c = ctx or _ffi.default_context(device)
+    out = c.price_american_basket_bounds(p, b, policy=policy, n_lower=int(n_lower), n_outer=int(n_outer),
+                                         n_inner=int(n_inner), betas=betas)
+    return BasketBoundsResult(lower=out["lower"], se_lower=out["se_lower"], upper=out["upper"], se_upper=out["se_upper"],
+                              ci_lo=out["ci_lo"], ci_hi=out["ci_hi"], n_lower=out["n_lower"], n_outer=out["n_outer"],
+                              n_inner=out["n_inner"], n_exercised_lower=out["n_exercised_lower"],
+                              inner_path_steps=out["inner_path_steps"], policy=policy, betas=out["betas"],
+                              option_type=option_type,
+                              timings_ms=dict(fit=out["ms_fit"], lower=out["ms_lower"], upper=out["ms_upper"],
+                                              total=out["ms_total"]),
+                              index0=out["index0"], n_assets=out["n_assets"], kind=kind)
 
 
 _job = {}

@@ -9,16 +9,9 @@
 
 using namespace omc::abi;
 
-namespace {
+namespace omc::abi {
 
-struct BasketTable {
-    int d;
-    double L[omc::kBasketTri];  // packed lower triangle: row i at i (i + 1) / 2
-    float a[omc::kBasketMax], b[omc::kBasketMax];
-    double x0, G0, sigma_G, q_G;
-};
-
-// The argument checks of both entry points and the host constants, all in float64.
+// The argument checks of the multi-asset entry points and the host constants, all in float64.
 int compose_basket(const omc_params* p, const omc_basket* k, BasketTable* t)
 {
     int rc;
@@ -88,7 +81,22 @@ int compose_basket(const omc_params* p, const omc_basket* k, BasketTable* t)
     return 0;
 }
 
-}  // namespace
+omc::BasketLaw basket_law(const BasketTable& t, const omc_basket* k)
+{
+    omc::BasketLaw law{};
+    for (int i = 0; i < t.d; ++i) {
+        law.a[i] = t.a[i];
+        law.b[i] = t.b[i];
+        law.w[i] = (float)k->w[i];
+        law.s0[i] = (float)k->S0[i];
+    }
+    for (int i = 0; i < t.d * (t.d + 1) / 2; ++i) law.L[i] = (float)t.L[i];
+    law.g0 = (float)t.G0;
+    law.kind = k->kind;
+    return law;
+}
+
+}  // namespace omc::abi
 
 extern "C" {
 
@@ -129,15 +137,7 @@ int omc_price_american_basket(omc_ctx* c, const omc_params* p, const omc_basket*
     omc::BasketGen g{};
     g.paths = path_spec(c, p, p->r, S, ld_index);
     g.d = t.d;
-    for (int i = 0; i < t.d; ++i) {
-        g.law.a[i] = t.a[i];
-        g.law.b[i] = t.b[i];
-        g.law.w[i] = (float)b->w[i];
-        g.law.s0[i] = (float)b->S0[i];
-    }
-    for (int i = 0; i < t.d * (t.d + 1) / 2; ++i) g.law.L[i] = (float)t.L[i];
-    g.law.g0 = (float)t.G0;
-    g.law.kind = b->kind;
+    g.law = basket_law(t, b);
     g.assets = assets_keep; g.ld_assets = ld;
     if ((rc = enqueue_generated(c, p, S, ld_index, [&](hipStream_t st) { return omc::launch_basket_paths(st, g); }))) return rc;
     if ((rc = finish_generated(c, p, &out->base))) return rc;

@@ -1,5 +1,6 @@
 // omc_api_bounds.hip -- Andersen-Broadie price bounds of American options (include/omc.h): the policy
 // fit, the lower-bound sweep, the outer paths, the inner simulations in launches over blocks of outer paths, the walk.
+// run_bounds is that flow, shared with the multi-asset entry point (omc_api_basket_bounds.hip, section 17).
 #include "omc_bounds.h"
 #include "omc_ctx.h"
 
@@ -8,18 +9,15 @@ using namespace omc::abi;
 namespace {
 constexpr double kMaxItemPairs = 4294967296.0;   // n_outer (N+1) n_inner
 constexpr double kMaxInnerSteps = 549755813888.0;  // 2^39: n_outer n_inner N (N+1) / 2, a never-exercising policy's steps
-constexpr double kLaunchSteps = 1073741824.0;    // 2^30 worst-case inner steps per launch of the inner kernel
+constexpr double kLaunchSteps = 1073741824.0;    // 2^30 / d worst-case inner path steps per launch of the inner kernel
 }  // namespace
 
-extern "C" int omc_price_american_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg,
-                                         const double* betas, double* betas_out, double* q_out, double* samples_out,
-                                         omc_bounds* out)
+namespace omc::abi {
+
+int run_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg, const double* betas, double* betas_out,
+               double* q_out, double* samples_out, omc_bounds* out, const BoundsFlow& f)
 {
     int rc;
-    if ((rc = bind(c))) return rc;
-    if (!cfg || !out) return fail(-7, "null bounds config or result pointer.");
-    if ((rc = check_params(p))) return rc;
-    if (p->model != OMC_MODEL_GBM) return fail(-12, "price bounds are available for GBM only.");
     if (c->distributed()) return fail(-10, "price bounds run on one GPU.");
     const int policy = cfg->policy;
     if (policy != OMC_SEM_REFERENCE && policy != OMC_SEM_TEXTBOOK && policy != OMC_SEM_TWO_PASS && policy != OMC_POLICY_GIVEN)
@@ -39,9 +37,10 @@ extern "C" int omc_price_american_bounds(omc_ctx* c, const omc_params* p, const 
     omc::LsmWorkspace w;
     if ((rc = prepare_lsm(c, M, N, p->r, p->T, policy == OMC_SEM_TWO_PASS, true, &w))) return rc;
     if (!fitted && (rc = upload_fits(c, w, betas, N))) return rc;
-    // the workspace: outer paths [N+1][n_outer] f32 | Q^ [n_outer][N] | samples [n_outer] | tables [N+1][8] u32 |
-    // partials [8][kPStride] | sums [16] | inner step count
-    const size_t o_q = up256(sizeof(float) * (size_t)(N + 1) * (size_t)no);
+    // the workspace: outer paths [N+1][n_outer] f32 | the flow's own room | Q^ [n_outer][N] | samples [n_outer] | tables
+    // [N+1][8] u32 | partials [8][kPStride] | sums [16] | inner step count
+    const size_t o_extra = up256(sizeof(float) * (size_t)(N + 1) * (size_t)no);
+    const size_t o_q = o_extra + up256(f.extra_bytes);
     const size_t o_smp = o_q + up256(sizeof(double) * (size_t)no * (size_t)N);
     const size_t o_tab = o_smp + up256(sizeof(double) * (size_t)no);
     const size_t o_part = o_tab + up256(sizeof(uint32_t) * 8 * (size_t)(N + 1));
@@ -51,10 +50,8 @@ extern "C" int omc_price_american_bounds(omc_ctx* c, const omc_params* p, const 
     char* b = (char*)c->bnd.p;
     double* res = (double*)(b + o_res);
 
-    omc::BoundsArgs a{};
+    omc::BoundsArgs a{};  // (s0, a, b: the single-asset flow's, set in its bind)
     a.N = N; a.is_put = p->is_put ? 1 : 0; a.K = p->K; a.invK = 1.0 / p->K;
-    a.s0 = (float)p->S0;  // the generator's start value and step constants, so every spot is the generator's
-    omc::gbm_step_constants(p->r, p->sigma, p->T, N, &a.a, &a.b);
     a.k0 = (uint32_t)p->seed; a.k1 = (uint32_t)(p->seed >> 32);
     a.D = w.D; a.betas = w.betas; a.tab = (uint32_t*)(b + o_tab);
     a.n_lower = nl; a.stream_lower = (uint32_t)cfg->stream_lower;
@@ -62,13 +59,14 @@ extern "C" int omc_price_american_bounds(omc_ctx* c, const omc_params* p, const 
     a.q = (double*)(b + o_q); a.samples = (double*)(b + o_smp);
     a.steps = (unsigned long long*)(b + o_steps);
     a.part = (double*)(b + o_part);
+    f.bind(a, b + o_extra);
 
     HIP_TRY(hipEventRecord(c->ev[0], st));
     if (fitted) {  // omc_lsm_poly's fits on the paths of p
         float* S = nullptr;
         int64_t ld = 0;
         if ((rc = ensure_paths(c, p, Storage::full_only, &S, &ld))) return rc;
-        if ((rc = enqueue_paths(c, p, S, ld, false))) return rc;
+        if ((rc = f.fit_paths(S, ld))) return rc;
         omc::LsmProblem prob{S, ld, M, N, a.is_put, p->K, p->r, p->T};
         if ((rc = enqueue_lsm(c, prob, w, policy, false))) return rc;
     }
@@ -77,15 +75,14 @@ extern "C" int omc_price_american_bounds(omc_ctx* c, const omc_params* p, const 
     ct.betas = w.betas; ct.tab = (uint32_t*)a.tab;
     ct.N = N; ct.is_put = a.is_put; ct.K = p->K; ct.irr_every = c->pass2_irr_every;
     HIP_TRY(omc::lsm_crit_build(st, ct));
-    HIP_TRY(omc::bounds_lower(st, a, res));
+    HIP_TRY(f.lower(st, res));
     HIP_TRY(hipEventRecord(c->ev[2], st));
-    HIP_TRY(omc::launch_gbm_paths(st, (float*)a.So, no, no, N, p->S0, p->r, p->sigma, p->T, p->seed,
-                                  (uint32_t)cfg->stream_outer, 0, 1, c->gbm_vec));
+    HIP_TRY(f.outer(st));
     HIP_TRY(hipMemsetAsync(a.steps, 0, sizeof(unsigned long long), st));
-    // launches over blocks of outer paths, each at most kLaunchSteps inner steps even if the policy never exercises
-    int64_t blk = (int64_t)(kLaunchSteps / work1);
+    // launches over blocks of outer paths, each at most kLaunchSteps / d inner path steps even if the policy never exercises
+    int64_t blk = (int64_t)(kLaunchSteps / (double)f.d / work1);
     blk = blk < 1 ? 1 : (blk > no ? no : blk);
-    for (int64_t i0 = 0; i0 < no; i0 += blk) HIP_TRY(omc::bounds_inner(st, a, i0, no - i0 < blk ? no - i0 : blk));
+    for (int64_t i0 = 0; i0 < no; i0 += blk) HIP_TRY(f.inner(st, i0, no - i0 < blk ? no - i0 : blk));
     HIP_TRY(omc::bounds_walk(st, a, res + 8));
     HIP_TRY(hipEventRecord(c->ev[3], st));
     double h[16];
@@ -115,4 +112,32 @@ extern "C" int omc_price_american_bounds(omc_ctx* c, const omc_params* p, const 
     HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[3]));
     out->ms_total = ms;
     return 0;
+}
+
+}  // namespace omc::abi
+
+extern "C" int omc_price_american_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg,
+                                         const double* betas, double* betas_out, double* q_out, double* samples_out,
+                                         omc_bounds* out)
+{
+    int rc;
+    if ((rc = bind(c))) return rc;
+    if (!cfg || !out) return fail(-7, "null bounds config or result pointer.");
+    if ((rc = check_params(p))) return rc;
+    if (p->model != OMC_MODEL_GBM) return fail(-12, "price bounds are available for GBM only.");
+    omc::BoundsArgs a{};
+    BoundsFlow f;
+    f.fit_paths = [&](float* S, int64_t ld) { return enqueue_paths(c, p, S, ld, false); };
+    f.bind = [&](const omc::BoundsArgs& common, char*) {
+        a = common;
+        a.s0 = (float)p->S0;  // the generator's start value and step constants, so every spot is the generator's
+        omc::gbm_step_constants(p->r, p->sigma, p->T, p->n_steps, &a.a, &a.b);
+    };
+    f.lower = [&](hipStream_t st, double* res) { return omc::bounds_lower(st, a, res); };
+    f.outer = [&](hipStream_t st) {
+        return omc::launch_gbm_paths(st, (float*)a.So, a.n_outer, a.n_outer, a.N, p->S0, p->r, p->sigma, p->T, p->seed,
+                                     (uint32_t)cfg->stream_outer, 0, 1, c->gbm_vec);
+    };
+    f.inner = [&](hipStream_t st, int64_t i0, int64_t ni) { return omc::bounds_inner(st, a, i0, ni); };
+    return run_bounds(c, p, cfg, betas, betas_out, q_out, samples_out, out, f);
 }

@@ -14,32 +14,9 @@
 // bits -- and, on the steps the table builder marks irregular, the float64 rule itself.  Both give the same decisions.
 // Sums: float64, per lane in a fixed order, per wave / workgroup in a fixed tree, then lsm_finalize: identical calls
 // return identical bits (the inner step count is an integer atomic sum, exact in any order).
-#include "omc_bounds.h"
-#include "omc_lsm_dev.h"
+#include "omc_bounds_dev.h"
 
 namespace omc {
-
-// does a path at spot s stop at date d?  iv = the date's table (lo0, lo1, len0, len1); an irregular date decides with
-// the float64 rule of omc_lsm_apply_frozen
-__device__ __forceinline__ bool bd_stop(float s, int d, uint4 iv, const BoundsArgs& a)
-{
-    if (d >= a.N) return true;
-    if (iv.x == kCritIrregular) return exercises(pay_stored(s, a.K, a.invK, a.is_put), fit_given(a.betas, d, a.N));
-    return crit_in(iv, __float_as_uint(s));
-}
-
-__device__ __forceinline__ double bd_value(float s, int d, const BoundsArgs& a)
-{
-    const double p = payoff_d(s, a.K, a.is_put);
-    return a.D[d] * (p > 0.0 ? p : 0.0);
-}
-
-// the stored-path tables [N+1][8] -> LDS [N+1][4]
-__device__ __forceinline__ void bd_load_tables(const BoundsArgs& a, uint4* sh)
-{
-    for (int t = threadIdx.x; t <= a.N; t += blockDim.x) sh[t] = *reinterpret_cast<const uint4*>(a.tab + (size_t)t * 8);
-    __syncthreads();
-}
 
 // ------------------------------------------------------------------ lower bound
 __global__ __launch_bounds__(kBlock) void bounds_lower_kernel(BoundsArgs a, int nblk)
@@ -97,13 +74,6 @@ hipError_t bounds_lower(hipStream_t st, const BoundsArgs& a, double* result)
 }
 
 // ------------------------------------------------------------------ inner simulations
-__device__ __forceinline__ double wave_sum_f64(double x)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
-    return x;
-}
-
 // items q = t * ni + (i - i0): all outer paths of the earliest date first, so the longest items start first
 __global__ __launch_bounds__(kBlock) void bounds_inner_kernel(BoundsArgs a, int64_t i0, int64_t ni)
 {

@@ -11,6 +11,8 @@
 #include <vector>
 
 #include "../../include/omc.h"
+#include "omc_basket.h"
+#include "omc_bounds.h"
 #include "omc_comm.h"
 #include "omc_kernels.h"
 #include "omc_p2p.h"
@@ -142,6 +144,35 @@ int enqueue_generated(omc_ctx* c, const omc_params* p, const float* S, int64_t l
                       const std::function<hipError_t(hipStream_t)>& gen);
 // waits for the stream; *base from c->hres (full storage: folded = 0) with the kernel times
 int finish_generated(omc_ctx* c, const omc_params* p, omc_result* base);
+
+// ---- multi-asset options: what omc_price_american_basket and omc_price_american_basket_bounds share (omc_api_basket.hip)
+struct BasketTable {
+    int d;
+    double L[omc::kBasketTri];  // packed lower triangle: row i at i (i + 1) / 2
+    float a[omc::kBasketMax], b[omc::kBasketMax];
+    double x0, G0, sigma_G, q_G;
+};
+// the argument checks of include/omc.h's multi-asset section and the host constants: 0, or the code with the message set
+int compose_basket(const omc_params* p, const omc_basket* k, BasketTable* t);
+omc::BasketLaw basket_law(const BasketTable& t, const omc_basket* k);  // what the kernels take by value
+
+// ---- Andersen-Broadie bounds: the flow omc_price_american_bounds and omc_price_american_basket_bounds share
+// (omc_api_bounds.hip).  The caller has checked its params; what differs between one asset and several is where the
+// paths come from and which kernels simulate the fresh ones.
+struct BoundsFlow {
+    int d = 1;               // assets: an inner launch covers at most 2^30 / d worst-case inner path steps
+    size_t extra_bytes = 0;  // room in the workspace beside the outer matrix (the outer asset matrices)
+    // the paths of p (the policy fit's) into S [N+1][ld], on the context's stream
+    std::function<int(float* S, int64_t ld)> fit_paths;
+    // called once, before anything is enqueued: the common arguments are filled, `extra` is the caller's room
+    std::function<void(const omc::BoundsArgs& a, char* extra)> bind;
+    std::function<hipError_t(hipStream_t, double* result)> lower;
+    std::function<hipError_t(hipStream_t)> outer;  // the outer paths into a.So (and what the caller keeps in `extra`)
+    std::function<hipError_t(hipStream_t, int64_t i0, int64_t ni)> inner;
+};
+// the cfg checks (-10, -4, -7, -3, -16), the policy, the sweeps, the walk, the read-back and *out
+int run_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg, const double* betas, double* betas_out,
+               double* q_out, double* samples_out, omc_bounds* out, const BoundsFlow& f);
 
 // ---- K two-pass pricings of one geometry that share their small launches (grouped sequences, option chains)
 // device bytes one member of a group owns in omc_ctx::gstate: [part1 | gmom | betas | crit | part]
