@@ -6,12 +6,21 @@
 
 #include <cstdint>
 
+#include "omc_dispatch.h"
 #include "omc_kernels.h"
 
 namespace omc {
 
 constexpr int kBasketMax = 8;                                  // assets at most
 constexpr int kBasketTri = kBasketMax * (kBasketMax + 1) / 2;  // entries of the packed lower triangle
+
+// the asset count as a compile-time constant: the one list of the counts the kernels are built for (callers check the range)
+template <class F>
+inline auto for_assets(int d, F&& f)
+{
+    static_assert(kBasketMax == 8, "one instantiation per asset count");
+    return for_int<1, 2, 3, 4, 5, 6, 7, 8>(d, f);
+}
 
 // What the kernel needs of the basket, by value in its argument block (wave-uniform: scalar registers; no device table).
 //   a, b    per asset: the exponent of a step is fmaf(b y, a)  (include/omc.h)

@@ -7,16 +7,16 @@
 // draws the vanilla generator's normals at the pair index pair + (k << 40) (include/omc.h): one Philox block per asset
 // per pair per four steps.  The correlated normals y_i = sum_{k <= i} Lf[i][k] z_k are accumulated while the z_k are
 // generated, k ascending -- the order the header fixes -- so a lane never holds more than one asset's raw normals.  The
-// step of an asset is gbm_paths_body's (omc_paths_dev.h): same counters, same operations.
+// step of an asset is gbm_paths_body's (omc_paths_dev.h): same counters, same operations.  The correlation and the index
+// rule are omc_basket_dev.h's, which the bound kernels (omc_basket_bounds.hip) use too.
 //
 // The per-asset constants, the packed Cholesky factor and the kind come by value in the argument block: scalar
 // registers, no table in memory.  D is a template parameter so that every loop over assets unrolls and every index of
 // the constants is a compile-time one; the kind is wave-uniform and switched on where the index is formed.  No
 // grid-stride loop, no LDS; every write is a VEC-wide vector store.
 #include "omc_basket.h"
+#include "omc_basket_dev.h"
 #include "omc_paths_dev.h"
-
-#include "../../include/omc.h"
 
 namespace omc {
 
@@ -28,20 +28,6 @@ struct BasketArgs {
     uint32_t k0, k1, stream;
     uint64_t pair_offset;
 };
-
-// the index of one path from its asset spots (KIND arithmetic, best-of or worst-of; the geometric kind has its own state)
-template <int KIND, int D>
-__device__ __forceinline__ float basket_index(const BasketLaw& c, const float (&s)[D])
-{
-    float x = c.w[0] * s[0];
-#pragma unroll
-    for (int k = 1; k < D; ++k) {
-        if constexpr (KIND == OMC_BASKET_ARITHMETIC) x = __builtin_fmaf(c.w[k], s[k], x);
-        else if constexpr (KIND == OMC_BASKET_BEST_OF) x = fmaxf(x, c.w[k] * s[k]);
-        else x = fminf(x, c.w[k] * s[k]);
-    }
-    return x;
-}
 
 template <int D, int VEC, bool KEEP>
 __global__ __launch_bounds__(kBlock) void basket_paths_kernel(BasketArgs g, BasketLaw c)
@@ -118,16 +104,7 @@ __global__ __launch_bounds__(kBlock) void basket_paths_kernel(BasketArgs g, Bask
             for (int v = 0; v < VEC; ++v) {
                 float z[4];
                 normals4(g.pair_offset + (uint64_t)(p0 + v) + ((uint64_t)k << 40), (uint32_t)blk, g.stream, g.k0, g.k1, z);
-#pragma unroll
-                for (int i = k; i < D; ++i) {
-                    const float l = c.L[i * (i + 1) / 2 + k];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        if (i == 0) y[v][i][j] = z[j];  // Lf[0][0] = 1.0f exactly
-                        else if (k == 0) y[v][i][j] = l * z[j];
-                        else y[v][i][j] = __builtin_fmaf(l, z[j], y[v][i][j]);
-                    }
-                }
+                basket_correlate<D>(c, k, z, y[v]);
             }
         }
 #pragma unroll
@@ -152,6 +129,8 @@ __global__ __launch_bounds__(kBlock) void basket_paths_kernel(BasketArgs g, Bask
                     ga[v] = ga[v] * fast_exp2(Ea);
                 }
             } else {
+                // basket_step's arithmetic (omc_basket_dev.h), which this loop must match: it is restated here, beside the
+                // geometric branch, because through the helper the D >= 2 kernels come out with another schedule
 #pragma unroll
                 for (int v = 0; v < VEC; ++v) {
 #pragma unroll
@@ -202,16 +181,7 @@ hipError_t launch_basket_paths(hipStream_t st, const BasketGen& a)
     g.S = s.S; g.A = a.assets; g.ld = s.ld; g.lda = a.ld_assets; g.P = P; g.n_steps = s.n_steps;
     g.k0 = (uint32_t)s.seed; g.k1 = (uint32_t)(s.seed >> 32); g.stream = s.stream; g.pair_offset = s.pair_offset;
     const bool keep = a.assets != nullptr;
-    switch (a.d) {
-    case 1: launch_basket_d<1>(st, g, a.law, keep, vec); break;
-    case 2: launch_basket_d<2>(st, g, a.law, keep, vec); break;
-    case 3: launch_basket_d<3>(st, g, a.law, keep, vec); break;
-    case 4: launch_basket_d<4>(st, g, a.law, keep, vec); break;
-    case 5: launch_basket_d<5>(st, g, a.law, keep, vec); break;
-    case 6: launch_basket_d<6>(st, g, a.law, keep, vec); break;
-    case 7: launch_basket_d<7>(st, g, a.law, keep, vec); break;
-    default: launch_basket_d<8>(st, g, a.law, keep, vec); break;
-    }
+    for_assets(a.d, [&](auto d) { launch_basket_d<d()>(st, g, a.law, keep, vec); });
     return hipGetLastError();
 }
 

@@ -1,132 +1,87 @@
 // omc_basket_bounds.hip -- Andersen-Broadie price bounds on the index of D correlated GBM assets.
 //
-// The two sweeps of omc_bounds.hip that simulate paths, with D assets per partner:
-//   lower   bounds_lower_kernel's shape: one thread per antithetic pair of fresh paths, both partners' D spots in
-//           registers, each partner stopped at the first date the rule fires on its INDEX.
-//   inner   bounds_inner_kernel's shape, the hot path: a wave per (outer path, date) item, a lane per antithetic inner
-//           pair, four steps per Philox block per asset, finished lanes refilled from the item's unstarted pairs (ballot +
-//           mbcnt), a fixed xor-shuffle sum, an integer atomic step count.  The item's D start spots are the outer ASSET
-//           spots A_k[t][i]: loaded once per item, wave-uniform, kept in scalar registers.
-// Every spot is the basket generator's (omc_basket.hip, include/omc.h): asset k of pair g draws normals4(g + (k << 40)),
-// the correlated normals accumulate with k ascending in the generator's fmaf chain, the step is s *= exp2(fmaf(+-b_k, y_k,
-// a_k)), the index is the generator's rule for the kind.  These three are restated here, not shared, so the generator's
-// instruction streams stay what they were.  The law and the kind come by value; D is a template parameter so that every
-// loop over assets unrolls and no array is indexed at run time (no scratch: section 17.3).
+// The two sweeps of omc_bounds.hip that simulate paths, with D assets per partner: the same bodies (bounds_lower_body,
+// bounds_inner_body: omc_bounds_dev.h) with the path law below -- except the D = 1 inner kernel, which keeps a restated body
+// (see there).
+//   lower   one thread per antithetic pair of fresh paths, both partners' D spots in registers, each partner stopped at the
+//           first date the rule fires on its INDEX.
+//   inner   the hot path: a wave per (outer path, date) item, a lane per antithetic inner pair, four steps per Philox
+//           block per asset.  The item's D start spots are the outer ASSET spots A_k[t][i]: loaded once per item,
+//           wave-uniform, kept in scalar registers.
+// Every spot is the basket generator's (omc_basket.hip, include/omc.h), from the generator's own helpers
+// (omc_basket_dev.h): asset k of pair g draws normals4(g + (k << 40)), the correlated normals accumulate with k ascending
+// in one fmaf chain, the step is s *= exp2(fmaf(+-b_k, y_k, a_k)), the index is the rule of the kind.  The law and the
+// kind come by value; D is a template parameter so that every loop over assets unrolls and no array is indexed at run
+// time (no scratch: section 17.3).
 // With D = 1 and w = 1 both kernels perform the vanilla kernels' operations in the vanilla order: the same bits.
 // The outer walk, the exercise tables and the finalize are omc_bounds.hip's / omc_lsm.hip's, on the index matrix.
 #include "omc_basket_bounds.h"
+#include "omc_basket_dev.h"
 #include "omc_bounds_dev.h"
-
-#include "../../include/omc.h"
 
 namespace omc {
 
-// the correlated normals of one pair's Philox block `blk`: y[i][j] for asset i, step j of the block
+// the path law of D correlated GBM assets (the Model of omc_bounds_dev.h); the policy sees the index
 template <int D>
-__device__ __forceinline__ void bb_normals(const BasketLaw& c, uint64_t pair, uint32_t blk, uint32_t stream, uint32_t k0,
-                                           uint32_t k1, float (&y)[D][4])
-{
+struct BasketBoundsModel {
+    struct Start { float v[D]; };
+    struct Spots { float a[D], b[D]; };
+    using Normals = float[D][4];
+    const BasketBoundsArgs& g;
+    __device__ __forceinline__ Start lower_start() const
+    {
+        Start s0;
 #pragma unroll
-    for (int k = 0; k < D; ++k) {
-        float z[4];
-        normals4(pair + ((uint64_t)k << 40), blk, stream, k0, k1, z);
-#pragma unroll
-        for (int i = k; i < D; ++i) {
-            const float l = c.L[i * (i + 1) / 2 + k];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (i == 0) y[i][j] = z[j];  // Lf[0][0] = 1.0f exactly
-                else if (k == 0) y[i][j] = l * z[j];
-                else y[i][j] = __builtin_fmaf(l, z[j], y[i][j]);
-            }
-        }
+        for (int k = 0; k < D; ++k) s0.v[k] = g.law.s0[k];
+        return s0;
     }
-}
-
-template <int KIND, int D>
-__device__ __forceinline__ float bb_index_of(const BasketLaw& c, const float (&s)[D])
-{
-    float x = c.w[0] * s[0];
+    // the outer asset spots A_k[t][i]: one address per wave, held as scalars
+    __device__ __forceinline__ Start inner_start(int t, int64_t i) const
+    {
+        const size_t astride = (size_t)(g.v.N + 1) * (size_t)g.v.n_outer;  // one asset's outer matrix
+        Start s0;
 #pragma unroll
-    for (int k = 1; k < D; ++k) {
-        if constexpr (KIND == OMC_BASKET_ARITHMETIC) x = __builtin_fmaf(c.w[k], s[k], x);
-        else if constexpr (KIND == OMC_BASKET_BEST_OF) x = fmaxf(x, c.w[k] * s[k]);
-        else x = fminf(x, c.w[k] * s[k]);
+        for (int k = 0; k < D; ++k)
+            s0.v[k] = __int_as_float(
+                __builtin_amdgcn_readfirstlane(__float_as_int(g.Ao[(size_t)k * astride + (size_t)t * g.v.n_outer + i])));
+        return s0;
     }
-    return x;
-}
-
-// (the kind is wave-uniform: a scalar branch)
-template <int D>
-__device__ __forceinline__ float bb_index(const BasketLaw& c, const float (&s)[D])
-{
-    if (c.kind == OMC_BASKET_ARITHMETIC) return bb_index_of<OMC_BASKET_ARITHMETIC, D>(c, s);
-    if (c.kind == OMC_BASKET_BEST_OF) return bb_index_of<OMC_BASKET_BEST_OF, D>(c, s);
-    return bb_index_of<OMC_BASKET_WORST_OF, D>(c, s);
-}
-
-// one step of both partners' assets with the block's normals of step u
-template <int D>
-__device__ __forceinline__ void bb_step(const BasketLaw& c, float (&sa)[D], float (&sb)[D], const float (&y)[D][4], int u)
-{
+    __device__ __forceinline__ void reset(Spots& s, const Start& s0) const
+    {
 #pragma unroll
-    for (int k = 0; k < D; ++k) {
-        sa[k] = sa[k] * fast_exp2(__builtin_fmaf(c.b[k], y[k][u], c.a[k]));
-        sb[k] = sb[k] * fast_exp2(__builtin_fmaf(-c.b[k], y[k][u], c.a[k]));
+        for (int k = 0; k < D; ++k) s.a[k] = s.b[k] = s0.v[k];
     }
-}
+    __device__ __forceinline__ void draw(uint64_t pair, uint32_t blk, uint32_t stream, Normals& y) const
+    {
+        basket_normals<D>(g.law, pair, blk, stream, g.v.k0, g.v.k1, y);
+    }
+    __device__ __forceinline__ void step(Spots& s, const Normals& y, int u) const { basket_step<D>(g.law, s.a, s.b, y, u); }
+    __device__ __forceinline__ float index_a(const Spots& s) const { return basket_law_index<D>(g.law, s.a); }
+    __device__ __forceinline__ float index_b(const Spots& s) const { return basket_law_index<D>(g.law, s.b); }
+};
 
-// ------------------------------------------------------------------ lower bound
 template <int D>
 __global__ __launch_bounds__(kBlock) void basket_bounds_lower_kernel(BasketBoundsArgs g, int nblk)
 {
     extern __shared__ uint4 sh_bt[];
     __shared__ double red[kNQ * kRedStride];
-    const BoundsArgs& a = g.v;
-    const BasketLaw& c = g.law;
-    bd_load_tables(a, sh_bt);
-    const int N = a.N;
-    double acc[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) acc[q] = 0.0;
-    const int64_t P = a.n_lower / 2;
-    for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p < P; p += (int64_t)nblk * kBlock) {
-        float sa[D], sb[D], xa = 0.0f, xb = 0.0f;  // the partners' asset spots; the index each stopped at
-#pragma unroll
-        for (int k = 0; k < D; ++k) sa[k] = sb[k] = c.s0[k];
-        int da = 0, db = 0;  // stop dates, 0 while live
-        for (int blk = 0; 4 * blk < N && (da == 0 || db == 0); ++blk) {
-            float y[D][4];
-            bb_normals<D>(c, (uint64_t)p, (uint32_t)blk, a.stream_lower, a.k0, a.k1, y);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int d = 4 * blk + u + 1;
-                if (d > N) break;
-                bb_step<D>(c, sa, sb, y, u);
-                const float ia = bb_index<D>(c, sa), ib = bb_index<D>(c, sb);
-                const uint4 iv = sh_bt[d];
-                const bool ea = da == 0 && bd_stop(ia, d, iv, a);
-                const bool eb = db == 0 && bd_stop(ib, d, iv, a);
-                xa = ea ? ia : xa;
-                da = ea ? d : da;
-                xb = eb ? ib : xb;
-                db = eb ? d : db;
-            }
-        }
-        const double m = 0.5 * (bd_value(xa, da, a) + bd_value(xb, db, a));
-        acc[0] += m;
-        acc[1] += m * m;
-        acc[2] += (da < N ? 1.0 : 0.0) + (db < N ? 1.0 : 0.0);
-    }
-    const double s = block_reduce8(acc, red);
-    if (threadIdx.x < 64 && (threadIdx.x & 7) == 0) a.part[(size_t)(threadIdx.x >> 3) * kPStride + blockIdx.x] = s;
+    bounds_lower_body(g.v, BasketBoundsModel<D>{g}, nblk, sh_bt, red);
 }
 
-// ------------------------------------------------------------------ inner simulations
-// items q = t * ni + (i - i0): all outer paths of the earliest date first, so the longest items start first
 template <int D>
 __global__ __launch_bounds__(kBlock) void basket_bounds_inner_kernel(BasketBoundsArgs g, int64_t i0, int64_t ni)
 {
+    extern __shared__ uint4 sh_bt[];
+    bounds_inner_body(g.v, BasketBoundsModel<D>{g}, i0, ni, sh_bt);
+}
+
+// D = 1 keeps the body it had before the shared one, restated: through bounds_inner_body this one kernel measured 0.5 - 1.2 %
+// slower on the upper phase (profiles/bounds_body_time.txt), beyond the run-to-run noise; its instruction
+// stream is the earlier one.  A change to bounds_inner_body's refill must be made here too.
+template <>
+__global__ __launch_bounds__(kBlock) void basket_bounds_inner_kernel<1>(BasketBoundsArgs g, int64_t i0, int64_t ni)
+{
+    constexpr int D = 1;
     extern __shared__ uint4 sh_bt[];
     const BoundsArgs& a = g.v;
     const BasketLaw& c = g.law;
@@ -157,14 +112,14 @@ __global__ __launch_bounds__(kBlock) void basket_bounds_inner_kernel(BasketBound
         while (__builtin_amdgcn_ballot_w64(act)) {
             if (act) {
                 float y[D][4];
-                bb_normals<D>(c, gbase + (uint64_t)j, (uint32_t)(k >> 2), a.stream_inner, a.k0, a.k1, y);
+                basket_normals<D>(c, gbase + (uint64_t)j, (uint32_t)(k >> 2), a.stream_inner, a.k0, a.k1, y);
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     if (da == 0 || db == 0) {
                         ++k;
                         const int d = t + k;
-                        bb_step<D>(c, sa, sb, y, u);
-                        const float ia = bb_index<D>(c, sa), ib = bb_index<D>(c, sb);
+                        basket_step<D>(c, sa, sb, y, u);
+                        const float ia = basket_law_index<D>(c, sa), ib = basket_law_index<D>(c, sb);
                         const uint4 iv = sh_bt[d];
                         const bool ea = da == 0 && bd_stop(ia, d, iv, a);
                         const bool eb = db == 0 && bd_stop(ib, d, iv, a);
@@ -198,39 +153,14 @@ __global__ __launch_bounds__(kBlock) void basket_bounds_inner_kernel(BasketBound
 }
 
 // ------------------------------------------------------------------ launchers
-template <int D>
-static void launch_lower(hipStream_t st, const BasketBoundsArgs& a, int nblk)
-{
-    hipLaunchKernelGGL((basket_bounds_lower_kernel<D>), dim3(nblk), dim3(kBlock), sizeof(uint4) * (size_t)(a.v.N + 1), st, a,
-                       nblk);
-}
-
-template <int D>
-static void launch_inner(hipStream_t st, const BasketBoundsArgs& a, unsigned grid, int64_t i0, int64_t ni)
-{
-    hipLaunchKernelGGL((basket_bounds_inner_kernel<D>), dim3(grid), dim3(kBlock), sizeof(uint4) * (size_t)(a.v.N + 1), st, a,
-                       i0, ni);
-}
-
-#define OMC_BASKET_D_SWITCH(d, call)  \
-    switch (d) {                      \
-    case 1: call(1); break;           \
-    case 2: call(2); break;           \
-    case 3: call(3); break;           \
-    case 4: call(4); break;           \
-    case 5: call(5); break;           \
-    case 6: call(6); break;           \
-    case 7: call(7); break;           \
-    default: call(8); break;          \
-    }
-
 hipError_t basket_bounds_lower(hipStream_t st, const BasketBoundsArgs& a, double* result)
 {
     if (a.d < 1 || a.d > kBasketMax) return hipErrorInvalidValue;
     const int nblk = (int)bounds_lower_blocks(a.v);  // the vanilla sweep's grid
-#define OMC_CALL(D) launch_lower<D>(st, a, nblk)
-    OMC_BASKET_D_SWITCH(a.d, OMC_CALL)
-#undef OMC_CALL
+    for_assets(a.d, [&](auto d) {
+        hipLaunchKernelGGL((basket_bounds_lower_kernel<d()>), dim3(nblk), dim3(kBlock), sizeof(uint4) * (size_t)(a.v.N + 1), st,
+                           a, nblk);
+    });
     return lsm_finalize(st, a.v.part, nullptr, result, nblk, 0);
 }
 
@@ -240,9 +170,10 @@ hipError_t basket_bounds_inner(hipStream_t st, const BasketBoundsArgs& a, int64_
     const int64_t items = ni * a.v.N;
     int64_t g = (items + 3) / 4;
     if (g > 2048) g = 2048;
-#define OMC_CALL(D) launch_inner<D>(st, a, (unsigned)g, i0, ni)
-    OMC_BASKET_D_SWITCH(a.d, OMC_CALL)
-#undef OMC_CALL
+    for_assets(a.d, [&](auto d) {
+        hipLaunchKernelGGL((basket_bounds_inner_kernel<d()>), dim3((unsigned)g), dim3(kBlock),
+                           sizeof(uint4) * (size_t)(a.v.N + 1), st, a, i0, ni);
+    });
     return hipGetLastError();
 }
 

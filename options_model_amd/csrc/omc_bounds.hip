@@ -14,49 +14,41 @@
 // bits -- and, on the steps the table builder marks irregular, the float64 rule itself.  Both give the same decisions.
 // Sums: float64, per lane in a fixed order, per wave / workgroup in a fixed tree, then lsm_finalize: identical calls
 // return identical bits (the inner step count is an integer atomic sum, exact in any order).
+// The lower and the inner sweep are bounds_lower_body / bounds_inner_body (omc_bounds_dev.h), which the multi-asset
+// kernels share; this file supplies their path law, one GBM asset, and the walk.
 #include "omc_bounds_dev.h"
 
 namespace omc {
+
+// the path law of one GBM asset (the Model of omc_bounds_dev.h): the generator's counters and spot recurrence; the
+// policy sees the spot
+struct GbmBoundsModel {
+    using Start = float;
+    struct Spots { float a, b; };
+    using Normals = float[4];
+    const BoundsArgs& a;
+    __device__ __forceinline__ Start lower_start() const { return a.s0; }
+    __device__ __forceinline__ Start inner_start(int t, int64_t i) const { return a.So[(size_t)t * a.n_outer + i]; }
+    __device__ __forceinline__ void reset(Spots& s, Start s0) const { s.a = s.b = s0; }
+    __device__ __forceinline__ void draw(uint64_t pair, uint32_t blk, uint32_t stream, Normals& z) const
+    {
+        normals4(pair, blk, stream, a.k0, a.k1, z);
+    }
+    __device__ __forceinline__ void step(Spots& s, const Normals& z, int u) const
+    {
+        s.a = s.a * fast_exp2(__builtin_fmaf(a.b, z[u], a.a));
+        s.b = s.b * fast_exp2(__builtin_fmaf(-a.b, z[u], a.a));
+    }
+    __device__ __forceinline__ float index_a(const Spots& s) const { return s.a; }
+    __device__ __forceinline__ float index_b(const Spots& s) const { return s.b; }
+};
 
 // ------------------------------------------------------------------ lower bound
 __global__ __launch_bounds__(kBlock) void bounds_lower_kernel(BoundsArgs a, int nblk)
 {
     extern __shared__ uint4 sh_bt[];
     __shared__ double red[kNQ * kRedStride];
-    bd_load_tables(a, sh_bt);
-    const int N = a.N;
-    double acc[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) acc[q] = 0.0;
-    const int64_t P = a.n_lower / 2;
-    for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p < P; p += (int64_t)nblk * kBlock) {
-        float sa = a.s0, sb = a.s0, xa = a.s0, xb = a.s0;
-        int da = 0, db = 0;  // stop dates, 0 while live
-        for (int blk = 0; 4 * blk < N && (da == 0 || db == 0); ++blk) {
-            float z[4];
-            normals4((uint64_t)p, (uint32_t)blk, a.stream_lower, a.k0, a.k1, z);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int d = 4 * blk + u + 1;
-                if (d > N) break;
-                sa = sa * fast_exp2(__builtin_fmaf(a.b, z[u], a.a));
-                sb = sb * fast_exp2(__builtin_fmaf(-a.b, z[u], a.a));
-                const uint4 iv = sh_bt[d];
-                const bool ea = da == 0 && bd_stop(sa, d, iv, a);
-                const bool eb = db == 0 && bd_stop(sb, d, iv, a);
-                xa = ea ? sa : xa;
-                da = ea ? d : da;
-                xb = eb ? sb : xb;
-                db = eb ? d : db;
-            }
-        }
-        const double m = 0.5 * (bd_value(xa, da, a) + bd_value(xb, db, a));
-        acc[0] += m;
-        acc[1] += m * m;
-        acc[2] += (da < N ? 1.0 : 0.0) + (db < N ? 1.0 : 0.0);
-    }
-    const double s = block_reduce8(acc, red);
-    if (threadIdx.x < 64 && (threadIdx.x & 7) == 0) a.part[(size_t)(threadIdx.x >> 3) * kPStride + blockIdx.x] = s;
+    bounds_lower_body(a, GbmBoundsModel{a}, nblk, sh_bt, red);
 }
 
 int64_t bounds_lower_blocks(const BoundsArgs& a)
@@ -74,67 +66,10 @@ hipError_t bounds_lower(hipStream_t st, const BoundsArgs& a, double* result)
 }
 
 // ------------------------------------------------------------------ inner simulations
-// items q = t * ni + (i - i0): all outer paths of the earliest date first, so the longest items start first
 __global__ __launch_bounds__(kBlock) void bounds_inner_kernel(BoundsArgs a, int64_t i0, int64_t ni)
 {
     extern __shared__ uint4 sh_bt[];
-    bd_load_tables(a, sh_bt);
-    const int N = a.N;
-    const int lane = (int)(threadIdx.x & 63);
-    const int64_t H = a.half_inner;
-    const int64_t n_items = ni * N;
-    const int64_t nwaves = (int64_t)gridDim.x * (kBlock / 64);
-    unsigned long long steps = 0;
-    for (int64_t item = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); item < n_items; item += nwaves) {
-        const int t = (int)(item / ni);
-        const int64_t i = i0 + (item - (int64_t)t * ni);
-        const float s0 = a.So[(size_t)t * a.n_outer + i];
-        const uint64_t gbase = ((uint64_t)i * (uint64_t)(N + 1) + (uint64_t)t) * (uint64_t)H;
-        int64_t j = lane, next = 64;  // this lane's pair; the item's first unstarted pair
-        bool act = j < H;
-        float sa = s0, sb = s0, xa = s0, xb = s0;
-        int k = 0, da = 0, db = 0;  // steps taken by the pair; stop dates of its partners (0 while live)
-        double acc = 0.0;
-        while (__builtin_amdgcn_ballot_w64(act)) {
-            if (act) {
-                float z[4];
-                normals4(gbase + (uint64_t)j, (uint32_t)(k >> 2), a.stream_inner, a.k0, a.k1, z);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    if (da == 0 || db == 0) {
-                        ++k;
-                        const int d = t + k;
-                        sa = sa * fast_exp2(__builtin_fmaf(a.b, z[u], a.a));
-                        sb = sb * fast_exp2(__builtin_fmaf(-a.b, z[u], a.a));
-                        const uint4 iv = sh_bt[d];
-                        const bool ea = da == 0 && bd_stop(sa, d, iv, a);
-                        const bool eb = db == 0 && bd_stop(sb, d, iv, a);
-                        xa = ea ? sa : xa;
-                        da = ea ? d : da;
-                        xb = eb ? sb : xb;
-                        db = eb ? d : db;
-                    }
-                }
-            }
-            const bool done = act && da != 0 && db != 0;
-            const uint64_t m = __builtin_amdgcn_ballot_w64(done);
-            if (done) {
-                acc += bd_value(xa, da, a) + bd_value(xb, db, a);
-                steps += (unsigned long long)(da - t) + (unsigned long long)(db - t);
-                // the finished lanes take the next pairs in lane order (mbcnt: finished lanes below this one)
-                j = next + (int64_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-                act = j < H;
-                sa = sb = xa = xb = s0;
-                k = da = db = 0;
-            }
-            next += __popcll(m);
-        }
-        const double q = wave_sum_f64(acc);
-        if (lane == 0) a.q[(size_t)i * N + t] = q / (double)(2 * H);
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) steps += __shfl_xor(steps, off, 64);
-    if (lane == 0 && steps) atomicAdd(a.steps, steps);
+    bounds_inner_body(a, GbmBoundsModel{a}, i0, ni, sh_bt);
 }
 
 hipError_t bounds_inner(hipStream_t st, const BoundsArgs& a, int64_t i0, int64_t ni)

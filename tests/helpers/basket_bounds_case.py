@@ -19,6 +19,23 @@ KINDS = ("basket", "best-of", "worst-of")
 POLICIES = ("textbook", "two_pass", "reference", "given")
 
 
+RHO3 = np.array([[1.0, 0.5, 0.2], [0.5, 1.0, -0.3], [0.2, -0.3, 1.0]])
+
+
+def equi(d, c):
+    return np.full((d, d), c) + (1.0 - c) * np.eye(d)
+
+
+def unequal_basket(d, kind):
+    """unequal spots, sigmas, yields and weights; a non-trivial correlation"""
+    S0 = [96.0 + 3.0 * k for k in range(d)]
+    sig = [0.16 + 0.03 * k for k in range(d)]
+    q = [0.01 * ((k * 3) % 5) for k in range(d)]
+    w = [(0.7 + 0.1 * k) / d for k in range(d)] if kind == "basket" else [1.04 - 0.02 * k for k in range(d)]
+    rho = {2: np.array([[1.0, -0.4], [-0.4, 1.0]]), 3: RHO3}.get(d, equi(d, 0.3))
+    return _ffi.make_basket(S0, sig, q, w, rho, kind)
+
+
 def with_fields(s, **kw):
     """a copy of a ctypes structure with some fields replaced"""
     c = type(s).from_buffer_copy(bytes(s))

@@ -29,26 +29,13 @@ pytestmark = pytest.mark.gpu
 
 K, R = 100.0, 0.05
 POLICIES = ["textbook", "two_pass", "reference", "given"]
-RHO3 = np.array([[1.0, 0.5, 0.2], [0.5, 1.0, -0.3], [0.2, -0.3, 1.0]])
-
-
-def equi(d, c):
-    return np.full((d, d), c) + (1.0 - c) * np.eye(d)
+RHO3 = bc.RHO3
+_basket = bc.unequal_basket  # unequal spots, sigmas, yields and weights; a non-trivial correlation
 
 
 def _params(is_put=True, N=8, M=4096, stream=0, model="gbm", T=1.0, S0=100.0, sigma=0.2, seed=42):
     return _ffi.make_params(model=model, is_put=is_put, semantics="two_pass", n_paths=M, n_steps=N, S0=S0, K=K, r=R,
                             sigma=sigma, T=T, seed=seed, stream=stream)
-
-
-def _basket(d, kind):
-    """unequal spots, sigmas, yields and weights; a non-trivial correlation"""
-    S0 = [96.0 + 3.0 * k for k in range(d)]
-    sig = [0.16 + 0.03 * k for k in range(d)]
-    q = [0.01 * ((k * 3) % 5) for k in range(d)]
-    w = [(0.7 + 0.1 * k) / d for k in range(d)] if kind == "basket" else [1.04 - 0.02 * k for k in range(d)]
-    rho = {2: np.array([[1.0, -0.4], [-0.4, 1.0]]), 3: RHO3}.get(d, equi(d, 0.3))
-    return _ffi.make_basket(S0, sig, q, w, rho, kind)
 
 
 # ------------------------------------------------------------------ 1. one asset: the vanilla entry, bit for bit
