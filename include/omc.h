@@ -617,6 +617,44 @@ int omc_price_american_basket_bounds(omc_ctx* ctx, const omc_params* p, const om
                                      double* betas_out, double* q_out /* NULL or host [n_outer][N] */,
                                      double* samples_out /* NULL or host [n_outer] */, omc_basket_bounds* out);
 
+/* ---- ... with a policy on the index and the runner-up ------------------------------------- */
+/* omc_price_american_basket_bounds' game, paths, estimators and outputs (the section above, word for word: Z_t, the Philox
+ * coordinates of the lower, outer and inner paths, Q^, L^, M^, the samples, the standard errors from pair means,
+ * inner_path_steps, the launches of at most 2^30 / d worst-case inner path steps) with a second policy family: a rule on TWO
+ * regressors, the index and the runner-up.  The lower bound of a best-of option is the only out-of-sample price of such a
+ * product, and the index alone leaves it percent short; which asset is second closes most of that.
+ * Products: OMC_BASKET_BEST_OF and OMC_BASKET_WORST_OF with 2 <= d <= 8.
+ * Regressors: v_k = w_k * s_k, the float32 product the index rule forms.  X = the index (max or min of the v_k, the bits
+ *   of the generator's index matrix).  Y = the second order statistic of the v_k in the same direction -- second largest for
+ *   best-of, second smallest for worst-of --, counted with multiplicity: Y = X when two assets tie.  Y is a value, so no
+ *   evaluation order changes it.  u = fma((double)X, 1/K, -1), w = fma((double)Y, 1/K, -1).
+ * Policy table: betas [N+1][8] = (c0, c1, c2, c3, c4, c5, n, 0) per date,
+ *     cont = fma(w, fma(w, c4, fma(u, c5, c3)), fma(u, fma(u, c2, c1), c0))     = c0 + c1 u + c2 u^2 + c3 w + c4 w^2 + c5 u w
+ *   At 1 <= t < N a path exercises iff n_t > 0.5, imm = phi(X) > 0 and imm > cont, all in float64; at N it takes its payoff.
+ *   There are no float32 exercise tables (the rule is two-dimensional): option "pass2_tables_irregular_every" has no effect.
+ *   With c3 = c4 = c5 = 0 the rule is omc_price_american_basket_bounds' with (c0, c1, c2, n), and so is every output bit.
+ * cfg->policy = OMC_SEM_TEXTBOOK: fitted here by classic Longstaff-Schwartz on the p->n_paths paths of the basket generator
+ *   at (p->seed, p->stream, p->pair_offset), index and assets kept.  Per-path state (x_ex, tex), initialised to (X_N, N).
+ *   For t = N-1 .. 1: the regression set is the paths with phi(X_t) > 0, the target y = D[tex - t] max(phi(x_ex), 0)
+ *   (D[k] = exp(-r dt k)), the features f = (u, u^2, w, w^2, uw) of (X_t, Y_t).  The sums n, sum f, sum f f', sum y,
+ *   sum f y (27 numbers) are float64 in a fixed order.  The centred system C = sum f f' - sum f sum f' / n,
+ *   c = sum f y - sum f sum y / n is solved by LDL' without pivoting in the order of f; feature j (counted from 0) and
+ *   every later one get coefficient 0 when n < j + 1.5 or the pivot is not above 1e-12 |C_jj| + 1e-300;
+ *   c0 = ybar - sum c_k fbar_k, n_t = n (a date with n < 0.5 gets a row of zeros: nobody exercises there).  Every path,
+ *   in the set or not, then applies the rule of date t and updates (x_ex, tex).  n_0 = n_N = 0.
+ * cfg->policy = OMC_POLICY_GIVEN: the caller's table `betas`, host [N+1][8].  betas_out: NULL or host [N+1][8].
+ * Errors (nothing is launched): omc_price_american_basket_bounds' own, and -35 kind OMC_BASKET_ARITHMETIC or one asset
+ * (OMC_BASKET_GEOMETRIC keeps -34); -4 also for OMC_SEM_REFERENCE and OMC_SEM_TWO_PASS; -16 also for more than 512 dates
+ * (the kernels keep the policy rows, 64 bytes per date, in LDS; omc_price_american_basket_bounds has no such cap).
+ * Memory: the fit keeps the asset matrices of its paths, n_assets (N+1) n_paths floats on the device; a request the card
+ * cannot hold fails as a HIP allocation error (a positive code), as for every workspace of the library. */
+int omc_price_american_basket_bounds_runnerup(omc_ctx* ctx, const omc_params* p, const omc_basket* b,
+                                              const omc_bounds_config* cfg,
+                                              const double* betas /* policy == OMC_POLICY_GIVEN: host [N+1][8] */,
+                                              double* betas_out /* NULL or host [N+1][8] */,
+                                              double* q_out /* NULL or host [n_outer][N] */,
+                                              double* samples_out /* NULL or host [n_outer] */, omc_basket_bounds* out);
+
 /* ---- calibrator inner loop -------------------------------------- */
 /* replaces HestonPricer.price_options_batch / price_european_option
  * (options_model_3/heston_calibration.py:259-312) for ONE expiry: simulate n_paths antithetic

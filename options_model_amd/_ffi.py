@@ -25,6 +25,22 @@ DIVIDEND_ERRORS = range(-24, -16)
 BASKET_KINDS = {"basket": 0, "arithmetic": 0, "geometric": 1, "best-of": 2, "worst-of": 3}
 BASKET_MAX_ASSETS = 8
 BOUND_POLICIES = {"reference": 0, "textbook": 1, "two_pass": 2, "given": 3}
+BOUND_REGRESSORS = ("index", "index+runner-up")  # what the policy of the multi-asset bounds sees
+
+
+def check_runnerup(regressors, policy, kind, n_assets):
+    """The argument checks of regressors="index+runner-up" (omc_price_american_basket_bounds_runnerup), raised as
+    ValueError before anything touches the device.  kind: a key of BASKET_KINDS or its code."""
+    if regressors not in BOUND_REGRESSORS:
+        raise ValueError(f"regressors must be one of {list(BOUND_REGRESSORS)}.")
+    if regressors == "index":
+        return
+    if BOUND_POLICIES.get(policy, policy) not in (BOUND_POLICIES["textbook"], BOUND_POLICIES["given"]):
+        raise ValueError("regressors='index+runner-up' takes policy 'textbook' or 'given'.")
+    if BASKET_KINDS.get(kind, kind) not in (BASKET_KINDS["best-of"], BASKET_KINDS["worst-of"]):
+        raise ValueError("regressors='index+runner-up' is for kind 'best-of' or 'worst-of'.")
+    if int(n_assets) < 2:
+        raise ValueError("regressors='index+runner-up' needs at least two assets.")
 
 
 class OmcError(RuntimeError):
@@ -227,6 +243,9 @@ SIGNATURES = {
                                             C.POINTER(Bounds)]),
     "omc_price_american_basket_bounds": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Basket), C.POINTER(BoundsConfig), _P,
                                                    _P, _P, _P, C.POINTER(BasketBounds)]),
+    "omc_price_american_basket_bounds_runnerup": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Basket),
+                                                            C.POINTER(BoundsConfig), _P, _P, _P, _P,
+                                                            C.POINTER(BasketBounds)]),
     "omc_heston_price_strikes": (C.c_int, [_P, _I64, _I] + [_D] * 8 + [_U64, _U64, _I, _P, _I, _I, _P, _P]),
     "omc_heston_price_surface": (C.c_int, [_P, _I64, _I] + [_D] * 7 + [_U64, _I, _P, _P, _I, _P, _P, _I, _I, _P, _P]),
     "omc_price_american_seq": (C.c_int, [_P, C.POINTER(Params), _I, C.POINTER(Result)]),
@@ -850,16 +869,20 @@ class Context:
 
     def price_american_basket_bounds(self, params: Params, basket: Basket, policy="textbook", n_lower=1_000_000,
                                      n_outer=8192, n_inner=1024, stream_lower=None, stream_outer=None, stream_inner=None,
-                                     betas=None, want_q=False, want_samples=False):
+                                     betas=None, want_q=False, want_samples=False, regressors="index"):
         """Andersen-Broadie bounds of the Bermudan game on the INDEX of 1 .. 8 correlated GBM assets
         (omc_price_american_basket_bounds; arithmetic basket, best-of, worst-of) -> the dict of price_american_bounds plus
         index0, n_assets, kind.  params and basket as price_american_basket takes them; the policy is a function of the
-        index alone.  Streams default to params.stream + 1 / 2 / 3."""
+        index alone.  Streams default to params.stream + 1 / 2 / 3.
+        regressors="index+runner-up" (omc_price_american_basket_bounds_runnerup; best-of and worst-of on 2 .. 8 assets,
+        policy "textbook" or "given"): the policy sees the index and the second order statistic of the weighted spots, and
+        `betas` (given and returned) is [n_steps+1][8] = c0 .. c5, n, 0."""
+        check_runnerup(regressors, policy, int(basket.kind), int(basket.n_assets))
         return self._bounds(params, basket, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner,
-                            betas, want_q, want_samples)
+                            betas, want_q, want_samples, 8 if regressors == "index+runner-up" else 4)
 
     def _bounds(self, params, basket, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner, betas,
-                want_q, want_samples):
+                want_q, want_samples, cols=4):
         N = int(params.n_steps)
         cfg = BoundsConfig()
         cfg.policy = BOUND_POLICIES.get(policy, -1) if isinstance(policy, str) else int(policy)
@@ -871,9 +894,9 @@ class Context:
         b = None
         if betas is not None:
             b = np.ascontiguousarray(betas, np.float64)
-            if b.shape != (N + 1, 4):
-                raise ValueError(f"betas must have shape ({N + 1}, 4), got {b.shape}.")
-        bo = np.zeros((N + 1, 4))
+            if b.shape != (N + 1, cols):
+                raise ValueError(f"betas must have shape ({N + 1}, {cols}), got {b.shape}.")
+        bo = np.zeros((N + 1, cols))
         q = np.zeros((max(int(n_outer), 0), N)) if want_q else None
         smp = np.zeros(max(int(n_outer), 0)) if want_samples else None
         tail = (b.ctypes.data if b is not None else None, bo.ctypes.data, q.ctypes.data if q is not None else None,
@@ -885,8 +908,9 @@ class Context:
             d = {k: getattr(out, k) for k, _ in Bounds._fields_}
         else:
             bb = BasketBounds()
-            _check(self.lib, self.lib.omc_price_american_basket_bounds(self.handle, C.byref(params), C.byref(basket),
-                                                                       C.byref(cfg), *tail, C.byref(bb)))
+            entry = self.lib.omc_price_american_basket_bounds if cols == 4 else \
+                self.lib.omc_price_american_basket_bounds_runnerup
+            _check(self.lib, entry(self.handle, C.byref(params), C.byref(basket), C.byref(cfg), *tail, C.byref(bb)))
             d = {k: getattr(bb.bounds, k) for k, _ in Bounds._fields_}
             d.update(index0=bb.index0, n_assets=bb.n_assets, kind=bb.kind)
         d["betas"] = bo

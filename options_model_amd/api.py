@@ -673,24 +673,30 @@ def price_american_bounds(S0, K, r, sigma, T, n_paths, n_steps, option_type="put
 @dataclass
 class BasketBoundsResult(BoundsResult):
     """price_american_basket_bounds: BoundsResult for the index of a basket, with the index of the initial spots, the number
-    of assets and the kind.  The policy is a function of the index alone, so `lower` is what that policy earns; `upper`
-    bounds the value of the multi-asset game under ANY policy."""
+    of assets and the kind.  With regressors "index" the policy is a function of the index alone, with "index+runner-up" of
+    the index and the second order statistic of the weighted spots (`betas` is then [n_steps+1][8] = c0 .. c5, n, 0);
+    `lower` is what that policy earns, `upper` bounds the value of the multi-asset game under ANY policy."""
     index0: float = 0.0
     n_assets: int = 1
     kind: str = "basket"
+    regressors: str = "index"
 
 
 def price_american_basket_bounds(spots, K, r, sigmas, T, n_paths, n_steps, correlation=None, weights=None,
                                  dividend_yields=None, kind="basket", option_type="put", policy="textbook",
                                  n_lower=1_000_000, n_outer=8192, n_inner=1024, seed=42, stream=0, betas=None, device=None,
-                                 ctx=None) -> BasketBoundsResult:
+                                 ctx=None, regressors="index") -> BasketBoundsResult:
     """Lower and upper bounds on the Bermudan value of an option on an index of 1 .. 8 correlated GBM assets
     (omc_price_american_basket_bounds): price_american_bounds with the assets, kinds and defaults of
     price_american_basket.  The policy (`policy` / `betas` as price_american_bounds takes them) regresses on the index
     alone; the lower-bound, outer and inner paths use Philox streams stream + 1, + 2, + 3.  With one asset and a dividend
     yield these are the bounds of a single stock with a continuous yield.  kind="geometric": the geometric index is itself
     one GBM, so the call is made with ONE asset (G0, sigma_G, q_G) of weight 1 -- n_assets of the result is then 1 and
-    index0 is G0.  One GPU."""
+    index0 is G0.  One GPU.
+    regressors="index+runner-up" (DESIGN.md section 18): for kind "best-of" / "worst-of" on 2 .. 8 assets the policy also
+    sees the runner-up, the second largest (smallest) weighted spot -- on the two-asset max-call benchmark that closes nine
+    tenths of the gap between the index policy's lower bound and the lattice value.  policy is then "textbook" or "given",
+    and `betas` is [n_steps+1][8] = c0, c1, c2 (1, u, u^2 of the index), c3, c4 (w, w^2 of the runner-up), c5 (u w), n, 0."""
     if policy not in _ffi.BOUND_POLICIES:
         raise ValueError(f"policy must be one of {sorted(_ffi.BOUND_POLICIES)}.")
     if (policy == "given") != (betas is not None):
@@ -699,6 +705,7 @@ def price_american_basket_bounds(spots, K, r, sigmas, T, n_paths, n_steps, corre
         if int(v) < 2 or int(v) % 2:
             raise ValueError(f"{name} must be an even integer >= 2 (antithetic pairs).")
     S0, sig, q, w, rho = _basket_args(spots, sigmas, weights, dividend_yields, correlation, kind)
+    _ffi.check_runnerup(regressors, policy, kind, len(S0))
     _validate(S0[0], K, T, r, sig[0], n_paths, n_steps, option_type)
     M = int(n_paths) // 2 * 2
     if M <= 0:
@@ -711,7 +718,7 @@ def price_american_basket_bounds(spots, K, r, sigmas, T, n_paths, n_steps, corre
         b = _ffi.make_basket([G0], [sigma_G], [q_G], [1.0], None, "basket")
     c = ctx or _ffi.default_context(device)
     out = c.price_american_basket_bounds(p, b, policy=policy, n_lower=int(n_lower), n_outer=int(n_outer),
-                                         n_inner=int(n_inner), betas=betas)
+                                         n_inner=int(n_inner), betas=betas, regressors=regressors)
     return BasketBoundsResult(lower=out["lower"], se_lower=out["se_lower"], upper=out["upper"], se_upper=out["se_upper"],
                               ci_lo=out["ci_lo"], ci_hi=out["ci_hi"], n_lower=out["n_lower"], n_outer=out["n_outer"],
                               n_inner=out["n_inner"], n_exercised_lower=out["n_exercised_lower"],
@@ -719,7 +726,7 @@ def price_american_basket_bounds(spots, K, r, sigmas, T, n_paths, n_steps, corre
                               option_type=option_type,
                               timings_ms=dict(fit=out["ms_fit"], lower=out["ms_lower"], upper=out["ms_upper"],
                                               total=out["ms_total"]),
-                              index0=out["index0"], n_assets=out["n_assets"], kind=kind)
+                              index0=out["index0"], n_assets=out["n_assets"], kind=kind, regressors=regressors)
 
 
 _job = {}

@@ -36,7 +36,8 @@ int run_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg, co
     const int64_t M = fitted ? p->n_paths : 2;
     omc::LsmWorkspace w;
     if ((rc = prepare_lsm(c, M, N, p->r, p->T, policy == OMC_SEM_TWO_PASS, true, &w))) return rc;
-    if (!fitted && (rc = upload_fits(c, w, betas, N))) return rc;
+    const bool own = (bool)f.own_policy;  // the flow brings its policy, its walk and its read-back
+    if (!fitted && !own && (rc = upload_fits(c, w, betas, N))) return rc;
     // the workspace: outer paths [N+1][n_outer] f32 | the flow's own room | Q^ [n_outer][N] | samples [n_outer] | tables
     // [N+1][8] u32 | partials [8][kPStride] | sums [16] | inner step count
     const size_t o_extra = up256(sizeof(float) * (size_t)(N + 1) * (size_t)no);
@@ -62,7 +63,12 @@ int run_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg, co
     f.bind(a, b + o_extra);
 
     HIP_TRY(hipEventRecord(c->ev[0], st));
-    if (fitted) {  // omc_lsm_poly's fits on the paths of p
+    if (own) {
+        float* S = nullptr;
+        int64_t ld = 0;
+        if (fitted && (rc = ensure_paths(c, p, Storage::full_only, &S, &ld))) return rc;
+        if ((rc = f.own_policy(w, S, ld))) return rc;
+    } else if (fitted) {  // omc_lsm_poly's fits on the paths of p
         float* S = nullptr;
         int64_t ld = 0;
         if ((rc = ensure_paths(c, p, Storage::full_only, &S, &ld))) return rc;
@@ -71,10 +77,12 @@ int run_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg, co
         if ((rc = enqueue_lsm(c, prob, w, policy, false))) return rc;
     }
     HIP_TRY(hipEventRecord(c->ev[1], st));
-    omc::CritArgs ct;  // the stored-path tables of the policy
-    ct.betas = w.betas; ct.tab = (uint32_t*)a.tab;
-    ct.N = N; ct.is_put = a.is_put; ct.K = p->K; ct.irr_every = c->pass2_irr_every;
-    HIP_TRY(omc::lsm_crit_build(st, ct));
+    if (!own) {
+        omc::CritArgs ct;  // the stored-path tables of the policy
+        ct.betas = w.betas; ct.tab = (uint32_t*)a.tab;
+        ct.N = N; ct.is_put = a.is_put; ct.K = p->K; ct.irr_every = c->pass2_irr_every;
+        HIP_TRY(omc::lsm_crit_build(st, ct));
+    }
     HIP_TRY(f.lower(st, res));
     HIP_TRY(hipEventRecord(c->ev[2], st));
     HIP_TRY(f.outer(st));
@@ -83,13 +91,14 @@ int run_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg, co
     int64_t blk = (int64_t)(kLaunchSteps / (double)f.d / work1);
     blk = blk < 1 ? 1 : (blk > no ? no : blk);
     for (int64_t i0 = 0; i0 < no; i0 += blk) HIP_TRY(f.inner(st, i0, no - i0 < blk ? no - i0 : blk));
-    HIP_TRY(omc::bounds_walk(st, a, res + 8));
+    HIP_TRY(own ? f.walk(st, res + 8) : omc::bounds_walk(st, a, res + 8));
     HIP_TRY(hipEventRecord(c->ev[3], st));
     double h[16];
     unsigned long long steps = 0;
     HIP_TRY(hipMemcpyAsync(h, res, sizeof h, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&steps, a.steps, sizeof steps, hipMemcpyDeviceToHost, st));
-    if (betas_out)
+    if (betas_out && own) HIP_TRY(f.read_policy(st, betas_out));
+    if (betas_out && !own)
         HIP_TRY(hipMemcpyAsync(betas_out, w.betas, sizeof(double) * 4 * (size_t)(N + 1), hipMemcpyDeviceToHost, st));
     if (q_out) HIP_TRY(hipMemcpyAsync(q_out, a.q, sizeof(double) * (size_t)no * (size_t)N, hipMemcpyDeviceToHost, st));
     if (samples_out) HIP_TRY(hipMemcpyAsync(samples_out, a.samples, sizeof(double) * (size_t)no, hipMemcpyDeviceToHost, st));

@@ -169,6 +169,15 @@ struct BoundsFlow {
     std::function<hipError_t(hipStream_t, double* result)> lower;
     std::function<hipError_t(hipStream_t)> outer;  // the outer paths into a.So (and what the caller keeps in `extra`)
     std::function<hipError_t(hipStream_t, int64_t i0, int64_t ni)> inner;
+    // A policy of the flow's own (omc_api_runnerup_bounds.hip: a rule on two regressors), all three set or none.  With them
+    // run_bounds neither uploads nor fits a [N+1][4] table and builds no exercise tables:
+    //   own_policy(w, S, ld)   between the fit events: the caller's table to the device (S == nullptr), or the fit on the
+    //                          p->n_paths paths it writes itself into S [N+1][ld]; w.sx, w.tex, w.D are its to use
+    //   walk                   in the place of bounds_walk
+    //   read_policy            the policy used into the caller's betas_out (enqueued; run_bounds waits for the stream)
+    std::function<int(const omc::LsmWorkspace& w, float* S, int64_t ld)> own_policy;
+    std::function<hipError_t(hipStream_t, double* result)> walk;
+    std::function<hipError_t(hipStream_t, double* betas_out)> read_policy;
 };
 // the cfg checks (-10, -4, -7, -3, -16), the policy, the sweeps, the walk, the read-back and *out
 int run_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg, const double* betas, double* betas_out,
