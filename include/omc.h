@@ -516,6 +516,61 @@ int omc_basket_table(const omc_params* p, const omc_basket* b, double* L_packed,
 int omc_price_american_basket(omc_ctx* ctx, const omc_params* p, const omc_basket* b, omc_basket_result* out,
                               float* S_keep, float* assets_keep, int64_t ld);
 
+/* ---- frozen-policy pathwise Greeks of the multi-asset options ------------------------------ */
+/* omc_price_american_greeks for omc_price_american_basket: per-asset delta, diagonal gamma and vega, and rho and theta of
+ * the option, with the exercise policy FROZEN.  Scope as omc_price_american_basket (its checks run unchanged): GBM assets,
+ * two-pass flow, antithetic pairs, one GPU, full storage, d = 1 .. 8, all four kinds.
+ * Policy: the [1, u, u^2] fits pass 1 makes on the index matrix at p's and b's parameters, or `betas` (host
+ *   [n_steps+1][4] = b0, b1, b2, n; n <= 0: no exercise at that step; an all-zero table gives European Greeks).  With
+ *   `betas` the generator and pass 1 are skipped, no matrix is written and base.base.sum_nitm = 0.  betas_out (NULL or host
+ *   [n_steps+1][4]) receives the policy used.
+ * Paths: ONE sweep regenerates the spots omc_price_american_basket's generator stores, bit for bit (the section above),
+ *   and walks every path forward.  Below, of a path at step t: s_i = (double) of the float32 spot of asset i, X = (double)
+ *   of the float32 index, p_i = (double)(wf_i * s_i), the float32 product the best-of / worst-of index compares.
+ * Exercise step k of a path: pass 2's -- the latest t in 1 .. N-1 at which the payoff phi(X) = K - X (put) / X - K (call)
+ *   is positive and above the fit at u = X / K - 1, else N.  D_k = exp(-r (k-1) dt), cf = D_k max(phi(X), 0) (the pricing's
+ *   cash-flow), phi' = -1{phi > 0} (put) / +1{phi > 0} (call), all at step k.
+ * Partials x_i = dX/ds_i s_i, float64, at step k:
+ *   OMC_BASKET_ARITHMETIC  x_i = (double)wf_i s_i;      OMC_BASKET_GEOMETRIC  x_i = (double)wf_i X;
+ *   OMC_BASKET_BEST_OF / _WORST_OF  x_i = p_i if i is the lowest asset number whose float32 product equals the float32
+ *   index, else 0.
+ * Per asset i:  delta_i = D_k phi'(X) x_i / S0_i;
+ *   vega_i = D_k phi'(X) x_i (ln(s_i / S0_i) - (r - q_i + sigma_i^2 / 2) k dt) / sigma_i  (the correlated Brownian value of
+ *   asset i is a function of its own spot and does not depend on sigma_j).
+ * Of the option:  rho = -(k-1) dt cf + D_k phi'(X) k dt sum_i x_i;
+ *   theta = -[ -r (k-1) dt / T cf + D_k phi'(X) sum_i x_i (ln(s_i / S0_i) + (r - q_i - sigma_i^2 / 2) k dt) / (2 T) ]
+ *   (-dV/dT at fixed n_steps).  With d = 1, w = 1, q = 0 these are omc_price_american_greeks' expressions.
+ * Diagonal gamma (want_gamma != 0), h = bump: scenario i+- scales asset i ALONE by lambda = 1 +- h, forms its own float64
+ *   index at every step, decides with the same fits and keeps its own exercise step k_i+-.  The scenario index:
+ *   arithmetic  X + (+-h (double)wf_i) s_i (one fma);   geometric  X c_i+-, c_i+- = pow(1 +- h, (double)wf_i) (host);
+ *   best-of / worst-of  max / min of lambda p_i and m_i, m_i = (double) of the float32 max / min of the OTHER assets'
+ *   products (none: -inf / +inf).
+ *   delta_i+- = D_k+- phi'(X^i+-) x_i^+- / S0_i with x_i^+- UNSCALED at the scenario's own step: (double)wf_i s_i,
+ *   (double)wf_i X, or p_i where the scaled asset carries the scenario index (lambda p_i >= m_i, worst-of <=; a tie goes
+ *   to the scaled asset), else 0.  gamma_i = (delta_i+ - delta_i-) / (2 h S0_i); price_up[i] / price_down[i] = the means
+ *   of D_k+- max(phi(X^i+-), 0); n_exercised_up / _down[i] count k_i+- < N.  Without want_gamma: gamma, se_gamma, price_up
+ *   and price_down are NaN, the scenario counts 0, and every other field has the bits of the call with want_gamma.
+ * Standard errors: sqrt(max(E[x^2] - E[x]^2, 0) / n_paths), antithetic partners counted as independent paths.  float64
+ *   sums, per-workgroup partials, a finalize in workgroup order: identical calls return identical bits.
+ * base: omc_price_american_basket's result (counts identical, price up to the order of its float64 sum) with
+ *   ms_pass2 = 0: the sweep replaces pass 2.  Entries of the per-asset arrays at or above d are 0.
+ * Out of scope: cross-gammas, correlation and yield sensitivities, Heston or jump assets, the runner-up policy.
+ * Errors (nothing is launched): omc_price_american_basket's own, in its order (-7 null ctx / out / params, -12, -29 .. -32,
+ * the omc_params checks, -24, -11, -33); -4 bump outside (0, 0.5]; -10 a distributed context (one GPU). */
+typedef struct {
+    omc_basket_result base;
+    double delta[8], gamma[8], vega[8];        /* raw units: per unit S0_i / S0_i^2 / sigma_i                         */
+    double se_delta[8], se_gamma[8], se_vega[8];
+    double rho, theta, se_rho, se_theta;       /* per unit r / per year                                               */
+    double bump, price_up[8], price_down[8];   /* the frozen-policy prices at S0_i (1 +- bump)                        */
+    int64_t n_exercised_up[8], n_exercised_down[8];
+    double ms_greeks;                          /* HIP-event time of the Greeks sweep                                  */
+    int32_t gamma_on, reserved;
+} omc_basket_greeks;
+int omc_price_american_basket_greeks(omc_ctx* ctx, const omc_params* p, const omc_basket* b, double bump, int want_gamma,
+                                     const double* betas /* NULL or host [n_steps+1][4] */,
+                                     double* betas_out /* NULL or host [n_steps+1][4] */, omc_basket_greeks* out);
+
 /* ---- Andersen-Broadie price bounds for American options ----------------------------------- */
 /* A lower and an upper bound on the value of the Bermudan put / call on the pricing grid, both from ONE frozen exercise
  * policy: the lower bound applies the policy as a stopping rule on fresh paths, the upper bound is the Andersen-Broadie

@@ -145,6 +145,17 @@ class BasketResult(C.Structure):
                 ("kind", C.c_int32)]
 
 
+class BasketGreeks(C.Structure):
+    """omc_basket_greeks: the base pricing plus the frozen-policy per-asset Greeks (omc_price_american_basket_greeks)."""
+    _fields_ = [("base", BasketResult),
+                ("delta", C.c_double * 8), ("gamma", C.c_double * 8), ("vega", C.c_double * 8),
+                ("se_delta", C.c_double * 8), ("se_gamma", C.c_double * 8), ("se_vega", C.c_double * 8),
+                ("rho", C.c_double), ("theta", C.c_double), ("se_rho", C.c_double), ("se_theta", C.c_double),
+                ("bump", C.c_double), ("price_up", C.c_double * 8), ("price_down", C.c_double * 8),
+                ("n_exercised_up", C.c_int64 * 8), ("n_exercised_down", C.c_int64 * 8),
+                ("ms_greeks", C.c_double), ("gamma_on", C.c_int32), ("reserved", C.c_int32)]
+
+
 class BoundsConfig(C.Structure):
     """omc_bounds_config: policy (BOUND_POLICIES), the three sizes and the three Philox streams."""
     _fields_ = [("policy", C.c_int32), ("reserved", C.c_int32), ("n_lower", C.c_int64), ("n_outer", C.c_int64),
@@ -239,6 +250,8 @@ SIGNATURES = {
     "omc_basket_table": (C.c_int, [C.POINTER(Params), C.POINTER(Basket), _P, _P, _P, C.POINTER(_D), _P]),
     "omc_price_american_basket": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Basket), C.POINTER(BasketResult), _P, _P,
                                             _I64]),
+    "omc_price_american_basket_greeks": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Basket), _D, _I, _P, _P,
+                                                   C.POINTER(BasketGreeks)]),
     "omc_price_american_bounds": (C.c_int, [_P, C.POINTER(Params), C.POINTER(BoundsConfig), _P, _P, _P, _P,
                                             C.POINTER(Bounds)]),
     "omc_price_american_basket_bounds": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Basket), C.POINTER(BoundsConfig), _P,
@@ -856,6 +869,37 @@ class Context:
                                                              S_keep.ptr if S_keep else None,
                                                              assets_keep.ptr if assets_keep else None, ld))
         return _with_base(out)
+
+    def price_american_basket_greeks(self, params: Params, basket: Basket, bump=0.01, gamma=True, betas=None,
+                                     want_betas=False):
+        """Frozen-policy pathwise Greeks of price_american_basket (omc_price_american_basket_greeks) -> dict: the keys
+        of price_american_basket (ms_pass2 = 0) plus delta, gamma, vega, se_delta, se_gamma, se_vega, price_up,
+        price_down, n_exercised_up, n_exercised_down (lists, one entry per asset), rho, theta, se_rho, se_theta, bump,
+        ms_greeks, gamma_on.  gamma=False: no scenario chains (gamma, se_gamma, price_up, price_down are NaN); `betas`
+        [n_steps+1][4] freezes a given policy (no paths are written); want_betas adds the policy used."""
+        N = int(params.n_steps)
+        b = None
+        if betas is not None:
+            b = np.ascontiguousarray(betas, np.float64)
+            if b.shape != (N + 1, 4):
+                raise ValueError(f"betas must have shape ({N + 1}, 4), got {b.shape}.")
+        bo = np.zeros((N + 1, 4)) if want_betas else None
+        g = BasketGreeks()
+        _check(self.lib, self.lib.omc_price_american_basket_greeks(self.handle, C.byref(params), C.byref(basket),
+                                                                    float(bump), int(bool(gamma)),
+                                                                    b.ctypes.data if b is not None else None,
+                                                                    bo.ctypes.data if bo is not None else None,
+                                                                    C.byref(g)))
+        d = _with_base(g.base)
+        n = int(g.base.n_assets)
+        for k, _ in BasketGreeks._fields_:
+            if k in ("base", "reserved"):
+                continue
+            v = getattr(g, k)
+            d[k] = list(v)[:n] if hasattr(v, "__len__") else v
+        if want_betas:
+            d["betas"] = bo
+        return d
 
     def price_american_bounds(self, params: Params, policy="textbook", n_lower=1_000_000, n_outer=8192, n_inner=1024,
                               stream_lower=None, stream_outer=None, stream_inner=None, betas=None, want_q=False,

@@ -614,6 +614,81 @@ def price_american_basket(spots, K, r, sigmas, T, n_paths, n_steps, correlation=
 
 
 @dataclass
+class BasketGreeksResult:
+    """price_american_basket_greeks: the price of price_american_basket and its frozen-policy pathwise Greeks -- delta,
+    gamma (diagonal) and vega per asset, rho and theta of the option -- in raw units (per unit S0_i / S0_i^2 / sigma_i /
+    r / year), with their standard errors.  price_up[i] / price_down[i]: the frozen-policy prices at S0_i (1 +- bump)."""
+    price: float
+    stderr: float
+    delta: list
+    gamma: list
+    vega: list
+    rho: float
+    theta: float
+    se_delta: list
+    se_gamma: list
+    se_vega: list
+    se_rho: float
+    se_theta: float
+    price_up: list
+    price_down: list
+    bump: float
+    n_paths: int
+    n_exercised: int
+    index0: float
+    n_assets: int
+    kind: str
+    option_type: str
+    betas: object = None
+    timings_ms: dict = field(default_factory=dict)
+    info: dict = field(default_factory=dict)  # weights
+
+    def __float__(self):
+        return float(self.price)
+
+
+def price_american_basket_greeks(spots, K, r, sigmas, T, n_paths, n_steps, correlation=None, weights=None,
+                                 dividend_yields=None, kind="basket", option_type="put", bump=0.01, gamma=True, betas=None,
+                                 seed=None, device=None, ctx=None, n_gpus=1) -> BasketGreeksResult:
+    """Per-asset delta, diagonal gamma and vega, and rho and theta, of the price of price_american_basket with the
+    exercise policy pass 1 fits held fixed (omc_price_american_basket_greeks): the assets, kinds and
+    defaults of price_american_basket.  They are exact derivatives of that frozen-policy estimator.  gamma[i] is a central
+    difference of pathwise deltas with asset i alone at S0_i (1 +- bump) on the same normals; gamma=False skips it.
+    betas ([n_steps+1][4] = b0, b1, b2, n): a given policy instead of the fitted one; an all-zero table gives the Greeks
+    of the European option.  Antithetic paths, one GPU."""
+    if int(n_gpus) != 1:
+        raise ValueError("price_american_basket_greeks runs on one GPU (n_gpus=1).")
+    if not (0.0 < float(bump) <= 0.5):
+        raise ValueError("bump must lie in (0, 0.5].")
+    S0, sig, q, w, rho = _basket_args(spots, sigmas, weights, dividend_yields, correlation, kind)
+    d = len(S0)
+    _validate(S0[0], K, T, r, sig[0], n_paths, n_steps, option_type)
+    M = int(n_paths) // 2 * 2
+    if M <= 0:
+        raise ValueError("num_simulations and num_time_steps must be positive integers.")
+    if betas is not None:
+        import numpy as np
+        if np.asarray(betas).shape != (int(n_steps) + 1, 4):
+            raise ValueError(f"betas must have shape ({int(n_steps) + 1}, 4).")
+    p = _ffi.make_params(model="gbm", is_put=(option_type == "put"), semantics="two_pass", antithetic=True, n_paths=M,
+                         n_steps=int(n_steps), S0=S0[0], K=K, r=r, sigma=sig[0], T=T, seed=42 if seed is None else int(seed))
+    b = _ffi.make_basket(S0, sig, q, w, rho, kind)
+    _ffi.basket_table(p, b)  # host only: the library's own checks (the correlation matrix among them)
+    c = ctx or _ffi.default_context(device)
+    out = c.price_american_basket_greeks(p, b, bump=float(bump), gamma=bool(gamma), betas=betas, want_betas=True)
+    var = max(out["sumsq"] / M - out["price"] ** 2, 0.0)
+    return BasketGreeksResult(price=out["price"], stderr=math.sqrt(var / M), delta=out["delta"], gamma=out["gamma"],
+                              vega=out["vega"], rho=out["rho"], theta=out["theta"], se_delta=out["se_delta"],
+                              se_gamma=out["se_gamma"], se_vega=out["se_vega"], se_rho=out["se_rho"],
+                              se_theta=out["se_theta"], price_up=out["price_up"], price_down=out["price_down"],
+                              bump=out["bump"], n_paths=M, n_exercised=out["n_exercised"], index0=out["index0"],
+                              n_assets=d, kind=kind, option_type=option_type, betas=out["betas"],
+                              timings_ms=dict(paths=out["ms_basket_paths"], pass1=out["ms_pass1"], greeks=out["ms_greeks"],
+                                              total=out["ms_total"]),
+                              info=dict(weights=w))
+
+
+@dataclass
 class BoundsResult:
     """price_american_bounds: Andersen-Broadie bounds on the value of the BERMUDAN option with exercise dates t = 1..n_steps
     of the grid dt = T / n_steps, all values discounted to t = 0 (Z_t = exp(-r t dt) max(phi(S_t), 0)) -- the textbook
