@@ -11,7 +11,8 @@
   7. NN pass 2 with random networks, dropout on and off, against the oracle's sticky sweep;
   8. the rows of NN pass 1 (count, order, normalisers, float32 matrix) against the numpy restatement;
   9. curve batches (American and European) == single calls;
- 10. the calibrator's inner Monte-Carlo (one expiry, many strikes) against the C oracle's terminal spots;
+ 10. the calibrator's inner Monte-Carlo (one expiry, many strikes) against the C oracle's terminal spots (prices and
+     stderrs on the device's own spots, to the order of a float64 sum: tests/test_gpu_european_sums.py);
  11. the local-vol simulator with random IV networks against the per-step PyTorch evaluation;
  12. a whole quote surface in one launch set == its per-expiry calls, bit for bit (round 6);
  13. the frozen-policy Greeks sweep against the numpy restatement (tests/helpers/greeks_ref.py) on the matrix the device
