@@ -175,6 +175,16 @@ int omc_heston_paths_f32(omc_ctx* ctx, float* S, int64_t ld, int64_t n_paths, in
                          double S0, double r, double T, double v0, double kappa, double theta,
                          double xi, double rho, uint64_t seed, uint64_t stream,
                          uint64_t pair_offset, int scheme);
+/* omc_heston_paths_f32 with the variance kept: S has the bits of omc_heston_paths_f32 for the same arguments (all three
+ * schemes), and V [n_steps+1][ld] (device float32, the layout of S: column p and its antithetic partner p + n_paths/2)
+ * holds the variance STATE of the same path: row 0 = (float)v0, row t = what the scheme carries into step t + 1 -- scheme
+ * 0 floored at 0, scheme 1 unfloored (it may be negative), scheme 2 floored at 1e-8.  (S_t, V_t) is the Markov state:
+ * omc_heston_paths_from_normals_f32 started at (S[t][j], V[t][j]) with the generator's remaining normals reproduces rows
+ * t+1 .. of that pair bit for bit.  The checks of omc_heston_paths_f32, and -7 for a null V. */
+int omc_heston_paths_sv_f32(omc_ctx* ctx, float* S, float* V, int64_t ld, int64_t n_paths, int n_steps,
+                            double S0, double r, double T, double v0, double kappa, double theta,
+                            double xi, double rho, uint64_t seed, uint64_t stream,
+                            uint64_t pair_offset, int scheme);
 /* injected-normals parity mode: Zhalf is device float32 [n_steps][ldz], row t-1 drives step t
  * (the exact consumption order of options_model_3.py:475-480 / :223-233) */
 int omc_gbm_paths_from_normals_f32(omc_ctx* ctx, float* S, int64_t ld, int64_t n_paths,
@@ -709,6 +719,38 @@ int omc_price_american_basket_bounds_runnerup(omc_ctx* ctx, const omc_params* p,
                                               double* betas_out /* NULL or host [N+1][8] */,
                                               double* q_out /* NULL or host [n_outer][N] */,
                                               double* samples_out /* NULL or host [n_outer] */, omc_basket_bounds* out);
+
+/* ---- Andersen-Broadie price bounds for American options under Heston ---------------------- */
+/* omc_price_american_bounds for p->model = OMC_MODEL_HESTON, scheme OMC_HESTON_REFERENCE_CLAMP or
+ * OMC_HESTON_FULL_TRUNCATION: the same game Z_t = exp(-r t dt) max(phi(S_t), 0), t = 1..N, the same policy table betas
+ * [N+1][4], stopping rule, estimators, outputs, argument list and result struct (the section "price bounds for American
+ * options" above, word for word, with the Heston generator in the place of the GBM one).  One GPU.
+ * What the policy sees: the SPOT alone.  The fitted policies are omc_lsm_poly's fits on the Heston paths of p
+ *   (omc_heston_paths_f32 at p->seed, p->stream, p->pair_offset); the variance is not a regressor.
+ * What the bounds bound: the Bermudan game of the DISCRETISED scheme on the grid -- the Markov chain (S_t, V_t) that
+ *   heston_scheme defines with n_steps steps, exercisable at every step -- not the continuous-time Heston model and not the
+ *   continuously exercisable option.  lower is what the spot-only policy earns in that game; upper bounds the value under
+ *   ANY policy, one that sees the variance included: upper - lower contains what the spot-only policy gives away.
+ * Lower bound: the n_lower paths of omc_heston_paths_f32(n_lower, N, .., seed, stream_lower, pair_offset 0, scheme), bit
+ *   for bit; each partner of a pair stops at the first date the rule fires on its spot.
+ * Outer paths: omc_heston_paths_sv_f32(n_outer, N, .., seed, stream_outer, 0, scheme): S_t[i] and the variance state
+ *   V_t[i].  The martingale needs the conditional expectation given the whole Markov state, so inner pair j of item
+ *   (i, t) starts BOTH partners at (S_t[i], V_t[i]); it is generator pair g = (i (N+1) + t) (n_inner/2) + j of stream
+ *   stream_inner, and inner step k = 1..N-t consumes that pair's Heston step k: rows 2(k-1) and 2(k-1)+1 of
+ *   omc_gbm_normals_f32(.., 2 N, seed, stream_inner, pair_offset g) as (z1, z2), the partner (-z1, -z2).  The inner spots
+ *   are bit for bit omc_heston_paths_from_normals_f32(z1, z2, S0 = S_t[i], v0 = V_t[i], ..) (a float32 is exact in the
+ *   double argument; that entry point takes a negative v0 of scheme 1 as it is).
+ * Q^, L^, M^, the samples, upper, se_*, ci_*, n_exercised_lower, inner_path_steps and ms_* as omc_price_american_bounds.
+ *   A step draws two normals, so the inner simulations run as launches of at most 2^29 worst-case inner path steps.
+ *   Option "pass2_tables_irregular_every" acts as there.  float64 sums in a fixed order: identical calls return identical
+ *   bits.
+ * Errors (nothing is launched): -7 null cfg / out; the omc_params checks; -12 p->model not OMC_MODEL_HESTON, or
+ * heston_scheme OMC_HESTON_CALIBRATOR (its arithmetic Euler step lets the spot cross zero); then -10, -4, -7, -3, -16 as
+ * omc_price_american_bounds, which itself keeps refusing Heston with -12. */
+int omc_price_american_bounds_heston(omc_ctx* ctx, const omc_params* p, const omc_bounds_config* cfg,
+                                     const double* betas /* policy == OMC_POLICY_GIVEN: host [N+1][4] */,
+                                     double* betas_out, double* q_out /* NULL or host [n_outer][N] */,
+                                     double* samples_out /* NULL or host [n_outer] */, omc_bounds* out);
 
 /* ---- calibrator inner loop -------------------------------------- */
 /* replaces HestonPricer.price_options_batch / price_european_option

@@ -217,6 +217,7 @@ SIGNATURES = {
     "omc_set_option": (C.c_int, [_P, C.c_char_p, _I64]),
     "omc_gbm_paths_f32": (C.c_int, [_P, _P, _I64, _I64, _I, _D, _D, _D, _D, _U64, _U64, _U64, _I]),
     "omc_heston_paths_f32": (C.c_int, [_P, _P, _I64, _I64, _I] + [_D] * 8 + [_U64, _U64, _U64, _I]),
+    "omc_heston_paths_sv_f32": (C.c_int, [_P, _P, _P, _I64, _I64, _I] + [_D] * 8 + [_U64, _U64, _U64, _I]),
     "omc_gbm_paths_from_normals_f32": (C.c_int, [_P, _P, _I64, _I64, _I, _D, _D, _D, _D, _P, _I64, _I]),
     "omc_heston_paths_from_normals_f32": (C.c_int, [_P, _P, _I64, _I64, _I] + [_D] * 8 + [_P, _P, _I64, _I]),
     "omc_philox4x32_10": (C.c_int, [_P, _P, _P, _I]),
@@ -259,6 +260,8 @@ SIGNATURES = {
     "omc_price_american_basket_bounds_runnerup": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Basket),
                                                             C.POINTER(BoundsConfig), _P, _P, _P, _P,
                                                             C.POINTER(BasketBounds)]),
+    "omc_price_american_bounds_heston": (C.c_int, [_P, C.POINTER(Params), C.POINTER(BoundsConfig), _P, _P, _P, _P,
+                                                   C.POINTER(Bounds)]),
     "omc_heston_price_strikes": (C.c_int, [_P, _I64, _I] + [_D] * 8 + [_U64, _U64, _I, _P, _I, _I, _P, _P]),
     "omc_heston_price_surface": (C.c_int, [_P, _I64, _I] + [_D] * 7 + [_U64, _I, _P, _P, _I, _P, _P, _I, _I, _P, _P]),
     "omc_price_american_seq": (C.c_int, [_P, C.POINTER(Params), _I, C.POINTER(Result)]),
@@ -599,6 +602,16 @@ class Context:
                                                         seed, stream, pair_offset, scheme))
         return S
 
+    def heston_paths_sv(self, n_paths, n_steps, S0, r, T, v0, kappa, theta, xi, rho, seed, stream=0,
+                        pair_offset=0, scheme=0):
+        """heston_paths with the variance state kept (omc_heston_paths_sv_f32) -> (S, V), both [n_steps+1][n_paths]."""
+        S = self.empty((n_steps + 1, n_paths), np.float32)
+        V = self.empty((n_steps + 1, n_paths), np.float32)
+        _check(self.lib, self.lib.omc_heston_paths_sv_f32(self.handle, S.ptr, V.ptr, S.shape[1], n_paths,
+                                                           n_steps, S0, r, T, v0, kappa, theta, xi, rho,
+                                                           seed, stream, pair_offset, scheme))
+        return S, V
+
     def gbm_paths_from_normals(self, z_half, S0, r, sigma, T, antithetic=True):
         z = self.to_device(z_half, np.float32)
         N, P = z.shape
@@ -911,6 +924,16 @@ class Context:
         return self._bounds(params, None, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner,
                             betas, want_q, want_samples)
 
+    def price_american_bounds_heston(self, params: Params, policy="textbook", n_lower=1_000_000, n_outer=8192,
+                                     n_inner=1024, stream_lower=None, stream_outer=None, stream_inner=None, betas=None,
+                                     want_q=False, want_samples=False):
+        """Andersen-Broadie bounds of the Bermudan game of the discretised Heston scheme on the grid
+        (omc_price_american_bounds_heston; scheme reference or full_truncation) -> the dict of price_american_bounds.  The
+        policy is a function of the spot alone; the inner paths start at the outer (spot, variance) state.  Streams default
+        to params.stream + 1 / 2 / 3."""
+        return self._bounds(params, None, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner,
+                            betas, want_q, want_samples, heston=True)
+
     def price_american_basket_bounds(self, params: Params, basket: Basket, policy="textbook", n_lower=1_000_000,
                                      n_outer=8192, n_inner=1024, stream_lower=None, stream_outer=None, stream_inner=None,
                                      betas=None, want_q=False, want_samples=False, regressors="index"):
@@ -926,7 +949,7 @@ class Context:
                             betas, want_q, want_samples, 8 if regressors == "index+runner-up" else 4)
 
     def _bounds(self, params, basket, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner, betas,
-                want_q, want_samples, cols=4):
+                want_q, want_samples, cols=4, heston=False):
         N = int(params.n_steps)
         cfg = BoundsConfig()
         cfg.policy = BOUND_POLICIES.get(policy, -1) if isinstance(policy, str) else int(policy)
@@ -947,8 +970,8 @@ class Context:
                 smp.ctypes.data if smp is not None else None)
         if basket is None:
             out = Bounds()
-            _check(self.lib, self.lib.omc_price_american_bounds(self.handle, C.byref(params), C.byref(cfg), *tail,
-                                                                C.byref(out)))
+            entry = self.lib.omc_price_american_bounds_heston if heston else self.lib.omc_price_american_bounds
+            _check(self.lib, entry(self.handle, C.byref(params), C.byref(cfg), *tail, C.byref(out)))
             d = {k: getattr(out, k) for k, _ in Bounds._fields_}
         else:
             bb = BasketBounds()

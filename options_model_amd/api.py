@@ -745,6 +745,51 @@ def price_american_bounds(S0, K, r, sigma, T, n_paths, n_steps, option_type="put
                                         total=out["ms_total"]))
 
 
+def price_american_bounds_heston(S0, K, r, T, n_paths, n_steps, heston_params=None, heston_scheme="reference",
+                                 option_type="put", policy="textbook", n_lower=1_000_000, n_outer=8192, n_inner=1024,
+                                 seed=42, stream=0, betas=None, device=None, ctx=None) -> BoundsResult:
+    """Lower and upper bounds on the Bermudan value of a put / call under the Heston model
+    (omc_price_american_bounds_heston): price_american_bounds with Heston paths.  heston_params as
+    price_american_option takes them (v0, kappa, theta, xi, rho; the defaults of heston_defaults at sigma = 0.2);
+    heston_scheme "reference" (= "clamp") or "full_truncation" -- the calibrator's scheme has no bounds.  The policy
+    (`policy` / `betas` as price_american_bounds takes them) regresses on the spot alone; the inner simulations start at the
+    outer paths' (spot, variance) state, so `upper` bounds the value under any policy of the DISCRETISED scheme's game on
+    the grid, one that sees the variance included.  The lower-bound, outer and inner paths use Philox streams stream + 1,
+    + 2, + 3.  One GPU."""
+    if policy not in _ffi.BOUND_POLICIES:
+        raise ValueError(f"policy must be one of {sorted(_ffi.BOUND_POLICIES)}.")
+    if (policy == "given") != (betas is not None):
+        raise ValueError("betas must be given exactly when policy='given'.")
+    for name, v in (("n_lower", n_lower), ("n_outer", n_outer), ("n_inner", n_inner)):
+        if int(v) < 2 or int(v) % 2:
+            raise ValueError(f"{name} must be an even integer >= 2 (antithetic pairs).")
+    if heston_scheme not in _ffi.HESTON_SCHEMES:
+        raise ValueError(f"heston_scheme must be one of {sorted(_ffi.HESTON_SCHEMES)}.")
+    if _ffi.HESTON_SCHEMES[heston_scheme] == _ffi.HESTON_SCHEMES["calibrator"]:
+        raise ValueError("price bounds under Heston take heston_scheme 'reference' or 'full_truncation', not 'calibrator'.")
+    _validate(S0, K, T, r, None, n_paths, n_steps, option_type, need_sigma=False)
+    M = int(n_paths) // 2 * 2
+    if M <= 0:
+        raise ValueError("num_simulations and num_time_steps must be positive integers.")
+    if betas is not None:
+        import numpy as np
+        if np.shape(betas) != (int(n_steps) + 1, 4):
+            raise ValueError(f"betas must have shape ({int(n_steps) + 1}, 4), got {np.shape(betas)}.")
+    p = _ffi.make_params(model="heston", is_put=(option_type == "put"), semantics="two_pass", antithetic=True,
+                         heston_scheme=heston_scheme, n_paths=M, n_steps=int(n_steps), S0=S0, K=K, r=r, sigma=0.0, T=T,
+                         seed=seed, stream=stream, **heston_defaults(None, heston_params))
+    c = ctx or _ffi.default_context(device)
+    out = c.price_american_bounds_heston(p, policy=policy, n_lower=int(n_lower), n_outer=int(n_outer),
+                                         n_inner=int(n_inner), betas=betas)
+    return BoundsResult(lower=out["lower"], se_lower=out["se_lower"], upper=out["upper"], se_upper=out["se_upper"],
+                        ci_lo=out["ci_lo"], ci_hi=out["ci_hi"], n_lower=out["n_lower"], n_outer=out["n_outer"],
+                        n_inner=out["n_inner"], n_exercised_lower=out["n_exercised_lower"],
+                        inner_path_steps=out["inner_path_steps"], policy=policy, betas=out["betas"],
+                        option_type=option_type,
+                        timings_ms=dict(fit=out["ms_fit"], lower=out["ms_lower"], upper=out["ms_upper"],
+                                        total=out["ms_total"]))
+
+
 @dataclass
 class BasketBoundsResult(BoundsResult):
     """price_american_basket_bounds: BoundsResult for the index of a basket, with the index of the initial spots, the number

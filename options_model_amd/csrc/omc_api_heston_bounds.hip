@@ -1,0 +1,60 @@
+// omc_api_heston_bounds.hip -- Andersen-Broadie price bounds of American options under the Heston model and the Heston
+// generator that keeps the variance state (include/omc.h): omc_price_american_bounds' flow
+// (run_bounds, omc_api_bounds.hip) with the Heston generator writing the matrices and the kernels of omc_heston_bounds.hip
+// simulating the fresh paths from the outer (spot, variance) state.
+#include "omc_ctx.h"
+#include "omc_heston_bounds.h"
+
+using namespace omc::abi;
+
+extern "C" int omc_heston_paths_sv_f32(omc_ctx* c, float* S, float* V, int64_t ld, int64_t n_paths, int n_steps, double S0,
+                                       double r, double T, double v0, double kappa, double theta, double xi, double rho,
+                                       uint64_t seed, uint64_t stream, uint64_t pair_offset, int scheme)
+{
+    int rc;
+    if ((rc = bind_in(c))) return rc;
+    if (!(S0 > 0) || !(T > 0)) return fail(-1, "S0, K, T must be positive.");
+    if (!(rho >= -1.0 && rho <= 1.0) || !(v0 >= 0)) return fail(-5, "invalid Heston parameters.");
+    if ((rc = check_sizes(n_paths, n_steps))) return rc;
+    if ((rc = check_matrix(S, ld, n_paths))) return rc;
+    if (!V) return fail(-7, "null variance matrix pointer.");
+    if (n_paths & 1) return fail(-3, "antithetic layout needs an even n_paths.");
+    if (scheme < 0 || scheme > 2) return fail(-4, "unknown Heston scheme.");
+    HIP_TRY(omc::launch_heston_paths_sv(c->stream, S, V, ld, n_paths, n_steps, S0, r, T, v0, kappa, theta, xi, rho, seed,
+                                        (uint32_t)stream, pair_offset, scheme));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int omc_price_american_bounds_heston(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg,
+                                                const double* betas, double* betas_out, double* q_out,
+                                                double* samples_out, omc_bounds* out)
+{
+    int rc;
+    if ((rc = bind(c))) return rc;
+    if (!cfg || !out) return fail(-7, "null bounds config or result pointer.");
+    if ((rc = check_params(p))) return rc;
+    if (p->model != OMC_MODEL_HESTON) return fail(-12, "these price bounds are for the Heston model (GBM: omc_price_american_bounds).");
+    if (p->heston_scheme == OMC_HESTON_CALIBRATOR)
+        return fail(-12, "price bounds under Heston take the reference or the full-truncation scheme, not the calibrator's.");
+    omc::BoundsArgs a{};
+    omc::HestonBoundsLaw h{p->r, p->T, p->v0, p->kappa, p->theta, p->xi, p->rho, p->heston_scheme, nullptr};
+    BoundsFlow f;
+    f.d = 2;  // two normals per step
+    if (cfg->n_outer > 0)  // (sizes are checked in run_bounds, before the room is used)
+        f.extra_bytes = sizeof(float) * (size_t)(p->n_steps + 1) * (size_t)cfg->n_outer;
+    f.fit_paths = [&](float* S, int64_t ld) { return enqueue_paths(c, p, S, ld, false); };
+    f.bind = [&](const omc::BoundsArgs& common, char* extra) {
+        a = common;
+        a.s0 = (float)p->S0;  // the generator's start value, so every spot is the generator's
+        h.Vo = (const float*)extra;
+    };
+    f.lower = [&](hipStream_t st, double* res) { return omc::heston_bounds_lower(st, a, h, res); };
+    f.outer = [&](hipStream_t st) {  // the outer paths: spots and variance state, KEEP
+        return omc::launch_heston_paths_sv(st, (float*)a.So, (float*)h.Vo, a.n_outer, a.n_outer, a.N, p->S0, p->r, p->T, p->v0,
+                                           p->kappa, p->theta, p->xi, p->rho, p->seed, (uint32_t)cfg->stream_outer, 0,
+                                           p->heston_scheme);
+    };
+    f.inner = [&](hipStream_t st, int64_t i0, int64_t ni) { return omc::heston_bounds_inner(st, a, h, i0, ni); };
+    return run_bounds(c, p, cfg, betas, betas_out, q_out, samples_out, out, f);
+}
