@@ -25,6 +25,7 @@ import pytest
 
 from helpers import basket_greeks_case as gc
 from helpers import dividend_ref as dr
+from helpers.call_catalogue import diff, flat
 from helpers.greeks_check import close
 from options_model_amd import _ffi
 from test_gpu_basket import CASE3, CASE8, KINDS, basket_of
@@ -205,6 +206,7 @@ def test_error_codes_and_the_context_still_prices(ctx):
     p = params(M=4096, N=20)
     good, _ = basket_of(CASE3, "basket")
     out = _ffi.BasketGreeks()
+    before = flat(ctx.price_american_basket_greeks(p, good)), flat(ctx.price_american_basket(p, good))
 
     def call(q, b, bump, o, c=ctx):
         return c.lib.omc_price_american_basket_greeks(c.handle, C.byref(q) if q is not None else None,
@@ -234,10 +236,11 @@ def test_error_codes_and_the_context_still_prices(ctx):
         c2.set_allreduce_hook(lambda dptr, count: None)
         assert call(p, good, H, C.byref(out), c2) == -10
         c2.set_allreduce_hook(None)
-        assert c2.price_american_basket_greeks(p, good)["price"] > 0.0
+        assert not diff(flat(c2.price_american_basket_greeks(p, good)), before[0])
     finally:
         c2.close()
-    assert ctx.price_american_basket_greeks(p, good)["price"] > 0.0 and ctx.price_american_basket(p, good)["price"] > 0.0
+    assert not diff(flat(ctx.price_american_basket_greeks(p, good)), before[0])
+    assert not diff(flat(ctx.price_american_basket(p, good)), before[1])
 
 
 # ------------------------------------------------------------------ 10. facade and example

@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 from helpers import dividend_ref as dr
+from helpers.call_catalogue import diff, flat
 from oracle import cpu as orc
 from options_model_amd import _ffi
 
@@ -295,14 +296,15 @@ def test_invalid_arguments_raise(ctx):
 def test_distributed_context_is_refused(ctx):
     c = _ffi.Context(0)
     try:
-        c.set_allreduce_hook(lambda dptr, count: None)
         p = params(M=4096, N=20)
+        before = flat(c.price_american_div(p, 0.0, [(0.5, 1.0)]))
+        c.set_allreduce_hook(lambda dptr, count: None)
         out = _ffi.DivResult()
         import ctypes as C
         assert c.lib.omc_price_american_div(c.handle, C.byref(p), 0.01, None, 0, C.byref(out), None, 0) == -10
         with pytest.raises(ValueError):
             c.price_american_div(p, 0.0, [(0.5, 1.0)])
         c.set_allreduce_hook(None)
-        assert c.price_american_div(p, 0.0, [(0.5, 1.0)])["price"] > 0.0
+        assert not diff(flat(c.price_american_div(p, 0.0, [(0.5, 1.0)])), before)
     finally:
         c.close()
