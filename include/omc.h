@@ -180,7 +180,9 @@ int omc_heston_paths_f32(omc_ctx* ctx, float* S, int64_t ld, int64_t n_paths, in
  * holds the variance STATE of the same path: row 0 = (float)v0, row t = what the scheme carries into step t + 1 -- scheme
  * 0 floored at 0, scheme 1 unfloored (it may be negative), scheme 2 floored at 1e-8.  (S_t, V_t) is the Markov state:
  * omc_heston_paths_from_normals_f32 started at (S[t][j], V[t][j]) with the generator's remaining normals reproduces rows
- * t+1 .. of that pair bit for bit.  The checks of omc_heston_paths_f32, and -7 for a null V. */
+ * t+1 .. of that pair bit for bit.  The checks of omc_heston_paths_f32, and -7 for a null V -- but with scheme 1 a
+ * negative v0 is taken as it is, as omc_heston_paths_from_normals_f32 takes it: a state this generator stores is a state
+ * it starts from (the inner paths of omc_price_american_bounds_heston start there; section 21's tests rebuild them so). */
 int omc_heston_paths_sv_f32(omc_ctx* ctx, float* S, float* V, int64_t ld, int64_t n_paths, int n_steps,
                             double S0, double r, double T, double v0, double kappa, double theta,
                             double xi, double rho, uint64_t seed, uint64_t stream,
@@ -623,7 +625,8 @@ int omc_price_american_basket_greeks(omc_ctx* ctx, const omc_params* p, const om
 enum { OMC_POLICY_GIVEN = 3 };
 typedef struct {
     int32_t policy;    /* OMC_SEM_REFERENCE, OMC_SEM_TEXTBOOK, OMC_SEM_TWO_PASS: fitted here; OMC_POLICY_GIVEN: `betas` */
-    int32_t reserved;
+    int32_t regressors; /* omc_price_american_bounds_heston: OMC_HESTON_REG_SPOT (0) or OMC_HESTON_REG_SPOT_VARIANCE; the
+                          other three bounds entry points do not read it (it was a reserved field: callers zero it) */
     int64_t n_lower, n_outer, n_inner;
     uint64_t stream_lower, stream_outer, stream_inner;
 } omc_bounds_config;
@@ -746,9 +749,43 @@ int omc_price_american_basket_bounds_runnerup(omc_ctx* ctx, const omc_params* p,
  *   bits.
  * Errors (nothing is launched): -7 null cfg / out; the omc_params checks; -12 p->model not OMC_MODEL_HESTON, or
  * heston_scheme OMC_HESTON_CALIBRATOR (its arithmetic Euler step lets the spot cross zero); then -10, -4, -7, -3, -16 as
- * omc_price_american_bounds, which itself keeps refusing Heston with -12. */
+ * omc_price_american_bounds, which itself keeps refusing Heston with -12.
+ *
+ * ---- ... with a policy on the spot and the variance state ----
+ * Selector: cfg->regressors = OMC_HESTON_REG_SPOT (0): everything above, bit for bit.  OMC_HESTON_REG_SPOT_VARIANCE (1): a
+ *   second policy family, a rule on TWO regressors.  Under Heston the variance is half of the Markov state; the spot-only
+ *   rule is the one simplification the lower bound above still carries.  Any other value is refused with -4.  The field is
+ *   omc_bounds_config's former reserved one: no new entry point, the same struct layout, OMC_ABI_VERSION unchanged;
+ *   omc_price_american_bounds, omc_price_american_basket_bounds and omc_price_american_basket_bounds_runnerup ignore it.
+ * Regressors: X = the float32 spot.  Y = the float32 variance state as the scheme's step leaves it -- the value
+ *   omc_heston_paths_sv_f32 stores: scheme OMC_HESTON_REFERENCE_CLAMP floored at 0, OMC_HESTON_FULL_TRUNCATION unfloored,
+ *   negative values included.  u = fma((double)X, 1/K, -1), w = fma((double)Y, 1/vbar, -1) with vbar = max(v0, theta) in
+ *   double.  vbar is a scale for conditioning only, not a model quantity: a caller who builds a `given` table must form w
+ *   with the same vbar.
+ * Policy table: betas [N+1][8] = (c0, c1, c2, c3, c4, c5, n, 0) per date,
+ *     cont = fma(w, fma(w, c4, fma(u, c5, c3)), fma(u, fma(u, c2, c1), c0))     = c0 + c1 u + c2 u^2 + c3 w + c4 w^2 + c5 u w
+ *   At 1 <= t < N a path exercises iff n_t > 0.5, imm = phi(X) > 0 and imm > cont, all in float64; at N it takes its payoff:
+ *   omc_price_american_basket_bounds_runnerup's rule and row layout with the variance in the runner-up's place.  There are
+ *   no float32 exercise tables: option "pass2_tables_irregular_every" has no effect.  With c3 = c4 = c5 = 0 every output has
+ *   the bits of the spot-only call given (c0, c1, c2, n).
+ * cfg->policy = OMC_SEM_TEXTBOOK: fitted here by classic Longstaff-Schwartz on the p->n_paths paths of
+ *   omc_heston_paths_sv_f32 at (p->seed, p->stream, p->pair_offset), spots and variance state kept.  Per-path state
+ *   (x_ex, tex), initialised to (S_N, N).  For t = N-1 .. 1: the regression set is the paths with phi(S_t) > 0, the target
+ *   y = D[tex - t] max(phi(x_ex), 0), the features f = (u, u^2, w, w^2, uw) of (S_t, V_t); the 27 float64 sums in a fixed
+ *   order, the centred 5 x 5 system by LDL' without pivoting and the truncation rule (feature j and every later one get
+ *   coefficient 0 when n < j + 1.5 or the pivot is not above 1e-12 |C_jj| + 1e-300) are those of the runner-up section,
+ *   word for word; n_0 = n_N = 0.  With xi = 0 and v0 = theta exact in float32, w is 0 on every path and the rule gives
+ *   c3 = c4 = c5 = 0 exactly.
+ * cfg->policy = OMC_POLICY_GIVEN: the caller's table `betas`, host [N+1][8].  betas_out: NULL or host [N+1][8].
+ * Everything else is unchanged: the game, the discretised scheme as the model, the Philox coordinates of the lower, outer and
+ *   inner paths, inner pairs started at (S_t[i], V_t[i]), Q^, L^, M^, the samples, the standard errors from pair means,
+ *   inner_path_steps, the launches of at most 2^29 worst-case inner path steps, the refusals -3, -7, -10, -12, -16.
+ * Errors, beside those: -4 a selector other than 0 or 1, or OMC_SEM_REFERENCE / OMC_SEM_TWO_PASS with selector 1; -5
+ *   max(v0, theta) not above 0; -16 more than 512 dates (the kernels keep the policy rows, 64 bytes per date, in LDS).
+ * Memory: the fit additionally keeps the variance state V [N+1][ld] of its fitting paths on the device. */
+enum { OMC_HESTON_REG_SPOT = 0, OMC_HESTON_REG_SPOT_VARIANCE = 1 };
 int omc_price_american_bounds_heston(omc_ctx* ctx, const omc_params* p, const omc_bounds_config* cfg,
-                                     const double* betas /* policy == OMC_POLICY_GIVEN: host [N+1][4] */,
+                                     const double* betas /* policy == OMC_POLICY_GIVEN: host [N+1][4], or [N+1][8] */,
                                      double* betas_out, double* q_out /* NULL or host [n_outer][N] */,
                                      double* samples_out /* NULL or host [n_outer] */, omc_bounds* out);
 

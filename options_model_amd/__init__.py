@@ -21,7 +21,8 @@ def __getattr__(name):
                 "price_barrier_option", "BarrierResult", "price_american_bounds", "BoundsResult", "price_american_chain",
                 "ChainResult", "price_american_dividends", "DividendResult", "price_american_jumps", "JumpResult",
                 "price_american_basket", "BasketResult", "price_american_basket_bounds", "BasketBoundsResult",
-                "price_american_basket_greeks", "BasketGreeksResult", "price_american_bounds_heston"):
+                "price_american_basket_greeks", "BasketGreeksResult", "price_american_bounds_heston",
+                "HestonBoundsResult"):
         from . import api
         return getattr(api, name)
     if name in ("AdvancedOptionPricer", "RNGManager", "BlackScholesGreeks", "welford_batch_update",

@@ -26,6 +26,8 @@ BASKET_KINDS = {"basket": 0, "arithmetic": 0, "geometric": 1, "best-of": 2, "wor
 BASKET_MAX_ASSETS = 8
 BOUND_POLICIES = {"reference": 0, "textbook": 1, "two_pass": 2, "given": 3}
 BOUND_REGRESSORS = ("index", "index+runner-up")  # what the policy of the multi-asset bounds sees
+HESTON_BOUND_REGRESSORS = ("spot", "spot+variance")  # ... of the Heston bounds: the codes of omc_bounds_config.regressors
+HESTON_SV_MAX_STEPS = 512  # dates of a spot+variance policy (its rows live in LDS)
 
 
 def check_runnerup(regressors, policy, kind, n_assets):
@@ -41,6 +43,21 @@ def check_runnerup(regressors, policy, kind, n_assets):
         raise ValueError("regressors='index+runner-up' is for kind 'best-of' or 'worst-of'.")
     if int(n_assets) < 2:
         raise ValueError("regressors='index+runner-up' needs at least two assets.")
+
+
+def check_heston_regressors(regressors, policy, n_steps, v0, theta):
+    """The argument checks of regressors="spot+variance" (omc_price_american_bounds_heston with cfg.regressors = 1), raised
+    as ValueError before anything touches the device."""
+    if regressors not in HESTON_BOUND_REGRESSORS:
+        raise ValueError(f"regressors must be one of {list(HESTON_BOUND_REGRESSORS)}.")
+    if regressors == "spot":
+        return
+    if BOUND_POLICIES.get(policy, policy) not in (BOUND_POLICIES["textbook"], BOUND_POLICIES["given"]):
+        raise ValueError("regressors='spot+variance' takes policy 'textbook' or 'given'.")
+    if int(n_steps) > HESTON_SV_MAX_STEPS:
+        raise ValueError(f"regressors='spot+variance' takes at most {HESTON_SV_MAX_STEPS} steps.")
+    if not max(float(v0), float(theta)) > 0.0:
+        raise ValueError("regressors='spot+variance' scales the variance by max(v0, theta), which must be positive.")
 
 
 class OmcError(RuntimeError):
@@ -158,7 +175,7 @@ class BasketGreeks(C.Structure):
 
 class BoundsConfig(C.Structure):
     """omc_bounds_config: policy (BOUND_POLICIES), the three sizes and the three Philox streams."""
-    _fields_ = [("policy", C.c_int32), ("reserved", C.c_int32), ("n_lower", C.c_int64), ("n_outer", C.c_int64),
+    _fields_ = [("policy", C.c_int32), ("regressors", C.c_int32), ("n_lower", C.c_int64), ("n_outer", C.c_int64),
                 ("n_inner", C.c_int64), ("stream_lower", C.c_uint64), ("stream_outer", C.c_uint64),
                 ("stream_inner", C.c_uint64)]
 
@@ -926,13 +943,21 @@ class Context:
 
     def price_american_bounds_heston(self, params: Params, policy="textbook", n_lower=1_000_000, n_outer=8192,
                                      n_inner=1024, stream_lower=None, stream_outer=None, stream_inner=None, betas=None,
-                                     want_q=False, want_samples=False):
+                                     want_q=False, want_samples=False, regressors="spot"):
         """Andersen-Broadie bounds of the Bermudan game of the discretised Heston scheme on the grid
         (omc_price_american_bounds_heston; scheme reference or full_truncation) -> the dict of price_american_bounds.  The
         policy is a function of the spot alone; the inner paths start at the outer (spot, variance) state.  Streams default
-        to params.stream + 1 / 2 / 3."""
+        to params.stream + 1 / 2 / 3.
+        regressors="spot+variance" (cfg.regressors = 1; policy "textbook" or "given", at most 512 steps): the policy sees the
+        spot and the variance state, w = V / max(v0, theta) - 1, and `betas` (given and returned) is [n_steps+1][8] =
+        c0 .. c5, n, 0.  A key of HESTON_BOUND_REGRESSORS or its code."""
+        if isinstance(regressors, str):
+            if regressors not in HESTON_BOUND_REGRESSORS:
+                raise ValueError(f"regressors must be one of {list(HESTON_BOUND_REGRESSORS)}.")
+            regressors = HESTON_BOUND_REGRESSORS.index(regressors)
         return self._bounds(params, None, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner,
-                            betas, want_q, want_samples, heston=True)
+                            betas, want_q, want_samples, 8 if int(regressors) == 1 else 4, heston=True,
+                            regressors=int(regressors))
 
     def price_american_basket_bounds(self, params: Params, basket: Basket, policy="textbook", n_lower=1_000_000,
                                      n_outer=8192, n_inner=1024, stream_lower=None, stream_outer=None, stream_inner=None,
@@ -949,9 +974,10 @@ class Context:
                             betas, want_q, want_samples, 8 if regressors == "index+runner-up" else 4)
 
     def _bounds(self, params, basket, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner, betas,
-                want_q, want_samples, cols=4, heston=False):
+                want_q, want_samples, cols=4, heston=False, regressors=0):
         N = int(params.n_steps)
         cfg = BoundsConfig()
+        cfg.regressors = regressors  # read by the Heston entry point alone
         cfg.policy = BOUND_POLICIES.get(policy, -1) if isinstance(policy, str) else int(policy)
         cfg.n_lower, cfg.n_outer, cfg.n_inner = int(n_lower), int(n_outer), int(n_inner)
         base = int(params.stream)

@@ -745,9 +745,20 @@ def price_american_bounds(S0, K, r, sigma, T, n_paths, n_steps, option_type="put
                                         total=out["ms_total"]))
 
 
+@dataclass
+class HestonBoundsResult(BoundsResult):
+    """price_american_bounds_heston: BoundsResult with what the policy saw.  With regressors "spot" the policy is a function
+    of the spot alone; with "spot+variance" of the spot and the variance state (`betas` is then [n_steps+1][8] = c0 .. c5,
+    n, 0, and its w is V / variance_scale - 1 with variance_scale = max(v0, theta)).  `lower` is what that policy earns,
+    `upper` bounds the value of the discretised scheme's game under ANY policy."""
+    regressors: str = "spot"
+    variance_scale: float = 0.0
+
+
 def price_american_bounds_heston(S0, K, r, T, n_paths, n_steps, heston_params=None, heston_scheme="reference",
                                  option_type="put", policy="textbook", n_lower=1_000_000, n_outer=8192, n_inner=1024,
-                                 seed=42, stream=0, betas=None, device=None, ctx=None) -> BoundsResult:
+                                 seed=42, stream=0, betas=None, device=None, ctx=None,
+                                 regressors="spot") -> HestonBoundsResult:
     """Lower and upper bounds on the Bermudan value of a put / call under the Heston model
     (omc_price_american_bounds_heston): price_american_bounds with Heston paths.  heston_params as
     price_american_option takes them (v0, kappa, theta, xi, rho; the defaults of heston_defaults at sigma = 0.2);
@@ -755,7 +766,11 @@ def price_american_bounds_heston(S0, K, r, T, n_paths, n_steps, heston_params=No
     (`policy` / `betas` as price_american_bounds takes them) regresses on the spot alone; the inner simulations start at the
     outer paths' (spot, variance) state, so `upper` bounds the value under any policy of the DISCRETISED scheme's game on
     the grid, one that sees the variance included.  The lower-bound, outer and inner paths use Philox streams stream + 1,
-    + 2, + 3.  One GPU."""
+    + 2, + 3.  One GPU.
+    regressors="spot+variance" (DESIGN.md section 21): the policy also sees the variance state, the other half of the Markov
+    state, as w = V / max(v0, theta) - 1 (`variance_scale` of the result: a scale for conditioning only, which a `given`
+    table must share).  policy is then "textbook" or "given", n_steps at most 512, and `betas` is [n_steps+1][8] = c0, c1,
+    c2 (1, u, u^2 of the spot), c3, c4 (w, w^2 of the variance), c5 (u w), n, 0."""
     if policy not in _ffi.BOUND_POLICIES:
         raise ValueError(f"policy must be one of {sorted(_ffi.BOUND_POLICIES)}.")
     if (policy == "given") != (betas is not None):
@@ -771,23 +786,27 @@ def price_american_bounds_heston(S0, K, r, T, n_paths, n_steps, heston_params=No
     M = int(n_paths) // 2 * 2
     if M <= 0:
         raise ValueError("num_simulations and num_time_steps must be positive integers.")
+    hp = heston_defaults(None, heston_params)
+    _ffi.check_heston_regressors(regressors, policy, n_steps, hp["v0"], hp["theta"])
+    cols = 8 if regressors == "spot+variance" else 4
     if betas is not None:
         import numpy as np
-        if np.shape(betas) != (int(n_steps) + 1, 4):
-            raise ValueError(f"betas must have shape ({int(n_steps) + 1}, 4), got {np.shape(betas)}.")
+        if np.shape(betas) != (int(n_steps) + 1, cols):
+            raise ValueError(f"betas must have shape ({int(n_steps) + 1}, {cols}), got {np.shape(betas)}.")
     p = _ffi.make_params(model="heston", is_put=(option_type == "put"), semantics="two_pass", antithetic=True,
                          heston_scheme=heston_scheme, n_paths=M, n_steps=int(n_steps), S0=S0, K=K, r=r, sigma=0.0, T=T,
-                         seed=seed, stream=stream, **heston_defaults(None, heston_params))
+                         seed=seed, stream=stream, **hp)
     c = ctx or _ffi.default_context(device)
     out = c.price_american_bounds_heston(p, policy=policy, n_lower=int(n_lower), n_outer=int(n_outer),
-                                         n_inner=int(n_inner), betas=betas)
-    return BoundsResult(lower=out["lower"], se_lower=out["se_lower"], upper=out["upper"], se_upper=out["se_upper"],
-                        ci_lo=out["ci_lo"], ci_hi=out["ci_hi"], n_lower=out["n_lower"], n_outer=out["n_outer"],
-                        n_inner=out["n_inner"], n_exercised_lower=out["n_exercised_lower"],
-                        inner_path_steps=out["inner_path_steps"], policy=policy, betas=out["betas"],
-                        option_type=option_type,
-                        timings_ms=dict(fit=out["ms_fit"], lower=out["ms_lower"], upper=out["ms_upper"],
-                                        total=out["ms_total"]))
+                                         n_inner=int(n_inner), betas=betas, regressors=regressors)
+    return HestonBoundsResult(lower=out["lower"], se_lower=out["se_lower"], upper=out["upper"], se_upper=out["se_upper"],
+                              ci_lo=out["ci_lo"], ci_hi=out["ci_hi"], n_lower=out["n_lower"], n_outer=out["n_outer"],
+                              n_inner=out["n_inner"], n_exercised_lower=out["n_exercised_lower"],
+                              inner_path_steps=out["inner_path_steps"], policy=policy, betas=out["betas"],
+                              option_type=option_type,
+                              timings_ms=dict(fit=out["ms_fit"], lower=out["ms_lower"], upper=out["ms_upper"],
+                                              total=out["ms_total"]),
+                              regressors=regressors, variance_scale=max(float(hp["v0"]), float(hp["theta"])))
 
 
 @dataclass

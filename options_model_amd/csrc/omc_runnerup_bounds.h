@@ -42,6 +42,9 @@ struct RunnerupFit {
 };
 
 hipError_t runnerup_fit(hipStream_t st, const RunnerupFit& f);
+// the one-workgroup solve of a date on its own, for a fit whose sums kernel is another file's (omc_heston_sv_bounds.hip): the
+// partial sums part [kRunnerupSlots][kRunnerupFitBlocks] of nblk workgroups -> the policy row (c0 .. c5, n, 0)
+hipError_t runnerup_fit_solve(hipStream_t st, const double* part, int nblk, double* row);
 hipError_t runnerup_lower(hipStream_t st, const RunnerupArgs& a, double* result);
 // Q^_t[i] for outer paths [i0, i0 + ni) and t = 0..N-1
 hipError_t runnerup_inner(hipStream_t st, const RunnerupArgs& a, int64_t i0, int64_t ni);

@@ -421,6 +421,13 @@ hipError_t runnerup_fit(hipStream_t st, const RunnerupFit& f)
     return hipGetLastError();
 }
 
+hipError_t runnerup_fit_solve(hipStream_t st, const double* part, int nblk, double* row)
+{
+    if (nblk < 1 || nblk > kRunnerupFitBlocks) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(runnerup_fit_solve_kernel, dim3(1), dim3(kBlock), 0, st, part, nblk, row);
+    return hipGetLastError();
+}
+
 static size_t ru_policy_lds(const RunnerupArgs& a) { return sizeof(double) * kRunnerupCols * (size_t)(a.g.v.N + 1); }
 
 hipError_t runnerup_lower(hipStream_t st, const RunnerupArgs& a, double* result)
