@@ -45,8 +45,28 @@ enum { OMC_MODEL_GBM = 0, OMC_MODEL_HESTON = 1 };
 enum {
     OMC_HESTON_REFERENCE_CLAMP = 0, /* options_model_3.py:230-233                                 */
     OMC_HESTON_FULL_TRUNCATION = 1, /* Lord et al. (named by BASELINE.json)                       */
-    OMC_HESTON_CALIBRATOR = 2       /* heston_calibration.py:242-255: floor 1e-8, arithmetic Euler */
+    OMC_HESTON_CALIBRATOR = 2,      /* heston_calibration.py:242-255: floor 1e-8, arithmetic Euler */
+    OMC_HESTON_QE = 3               /* Andersen (2008) quadratic-exponential; the rule is below    */
 };
+/* OMC_HESTON_QE -- the step of one antithetic pair.  Needs kappa > 0, theta > 0, xi > 0: every entry
+ * point that takes a Heston scheme refuses it otherwise with -36 before anything is launched (-4 stays "unknown scheme").
+ * Taken wherever a scheme is taken except the price bounds (omc_price_american_bounds_heston: -12).  No struct layout and
+ * no OMC_ABI_VERSION change: heston_scheme had the room.
+ *   Constants, formed in double and rounded to float32 once (dt = T / n_steps, E = exp(-kappa dt), L = log2 e):
+ *     c1 = xi^2 E (1 - E) / kappa,  c2 = theta xi^2 (1 - E)^2 / (2 kappa),
+ *     k0 = L (r dt - rho kappa theta dt / xi),  k1 = L (dt (kappa rho / xi - 1/2) / 2 - rho / xi),
+ *     k2 = L (dt (kappa rho / xi - 1/2) / 2 + rho / xi),  k34 = L^2 dt (1 - rho^2) / 2      (gamma1 = gamma2 = 1/2).
+ *   Draws: Zv = z1, Zs = z2 of the pair's Philox block, two steps per block as for the Euler schemes; the partner takes
+ *     (-Zv, -Zs).  No further random words.
+ *   float32 state (s, v), v >= 0, in this order (fma = one rounding; rcp, sqrt, exp2 the hardware's ~1 ulp instructions):
+ *     m = fma(v - theta, E, theta);  s2 = fma(v, c1, c2);  m2 = m m;   psi = s2 / m2 is > 1.5 iff s2 > 1.5f m2
+ *     psi <= 1.5:  t = (m2 + m2) rcp(s2)  [= 2 / psi];  b2 = (t - 1) + sqrt(t (t - 1));  a = m rcp(1 + b2);
+ *                  v' = a (sqrt(b2) + Zv)^2
+ *     psi > 1.5:   q = fma(s2, rcp(m2), 1)  [= psi + 1];  1 - p = 2 / q;  Q = erfcf(Zv / sqrt 2) / 2  (the UPPER tail, 1 - U
+ *                  with U = Phi(Zv), formed directly: the partner's is erfcf(-Zv / sqrt 2) / 2, not a subtraction);
+ *                  v' = max(0, (logf(1 - p) - logf(Q)) (m q / 2))            [1 / beta = m / (1 - p) = m q / 2]
+ *     s' = s exp2(fma(sqrt(fma(k34, v', k34 v)), Zs, fma(k2, v', fma(k1, v, k0))))
+ *   No martingale correction (K0*), no floor in the arithmetic.  omc_heston_paths_sv_f32 stores v' (row t, after step t). */
 
 typedef struct {
     int32_t model;         /* OMC_MODEL_*                                               */
@@ -175,10 +195,10 @@ int omc_heston_paths_f32(omc_ctx* ctx, float* S, int64_t ld, int64_t n_paths, in
                          double S0, double r, double T, double v0, double kappa, double theta,
                          double xi, double rho, uint64_t seed, uint64_t stream,
                          uint64_t pair_offset, int scheme);
-/* omc_heston_paths_f32 with the variance kept: S has the bits of omc_heston_paths_f32 for the same arguments (all three
- * schemes), and V [n_steps+1][ld] (device float32, the layout of S: column p and its antithetic partner p + n_paths/2)
+/* omc_heston_paths_f32 with the variance kept: S has the bits of omc_heston_paths_f32 for the same arguments (every
+ * scheme), and V [n_steps+1][ld] (device float32, the layout of S: column p and its antithetic partner p + n_paths/2)
  * holds the variance STATE of the same path: row 0 = (float)v0, row t = what the scheme carries into step t + 1 -- scheme
- * 0 floored at 0, scheme 1 unfloored (it may be negative), scheme 2 floored at 1e-8.  (S_t, V_t) is the Markov state:
+ * 0 floored at 0, scheme 1 unfloored (it may be negative), scheme 2 floored at 1e-8, scheme 3 the sampled v' >= 0.  (S_t, V_t) is the Markov state:
  * omc_heston_paths_from_normals_f32 started at (S[t][j], V[t][j]) with the generator's remaining normals reproduces rows
  * t+1 .. of that pair bit for bit.  The checks of omc_heston_paths_f32, and -7 for a null V -- but with scheme 1 a
  * negative v0 is taken as it is, as omc_heston_paths_from_normals_f32 takes it: a state this generator stores is a state
@@ -748,7 +768,8 @@ int omc_price_american_basket_bounds_runnerup(omc_ctx* ctx, const omc_params* p,
  *   Option "pass2_tables_irregular_every" acts as there.  float64 sums in a fixed order: identical calls return identical
  *   bits.
  * Errors (nothing is launched): -7 null cfg / out; the omc_params checks; -12 p->model not OMC_MODEL_HESTON, or
- * heston_scheme OMC_HESTON_CALIBRATOR (its arithmetic Euler step lets the spot cross zero); then -10, -4, -7, -3, -16 as
+ * heston_scheme OMC_HESTON_CALIBRATOR (its arithmetic Euler step lets the spot cross zero) or OMC_HESTON_QE (no bounds
+ * kernels are built for it); then -10, -4, -7, -3, -16 as
  * omc_price_american_bounds, which itself keeps refusing Heston with -12.
  *
  * ---- ... with a policy on the spot and the variance state ----

@@ -16,7 +16,7 @@ ABI_VERSION = 14
 
 SEMANTICS = {"reference": 0, "textbook": 1, "two_pass": 2}
 MODELS = {"gbm": 0, "heston": 1}
-HESTON_SCHEMES = {"reference": 0, "clamp": 0, "full_truncation": 1, "calibrator": 2}
+HESTON_SCHEMES = {"reference": 0, "clamp": 0, "full_truncation": 1, "calibrator": 2, "qe": 3}
 BARRIER_KINDS = {"down-and-out": 0, "up-and-out": 1, "down-and-in": 2, "up-and-in": 3}
 MONITORING = {"discrete": 0, "continuous": 1}
 DIVIDEND_KINDS = {"proportional": 0, "cash": 1}

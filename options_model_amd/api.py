@@ -81,6 +81,20 @@ def _validate(S0, K, T, r, sigma, n_paths, n_steps, option_type, need_sigma=True
                          if sigma is None else "S0, K, T, and sigma must be positive.")
 
 
+def _validate_scheme(model_l, heston_scheme, sigma, heston_params):
+    """heston_scheme by name or number; "qe" (Andersen's quadratic-exponential rule) needs kappa, theta and xi positive:
+    its constants divide by kappa and xi, and the long-run mean is the floor of the next variance's mean."""
+    if model_l != "heston":
+        return
+    if isinstance(heston_scheme, str) and heston_scheme not in _ffi.HESTON_SCHEMES:
+        raise ValueError(f"heston_scheme must be one of {sorted(_ffi.HESTON_SCHEMES)}.")
+    code = _ffi.HESTON_SCHEMES[heston_scheme] if isinstance(heston_scheme, str) else int(heston_scheme)
+    if code == _ffi.HESTON_SCHEMES["qe"]:
+        hp = heston_defaults(sigma, heston_params)
+        if not (hp["kappa"] > 0 and hp["xi"] > 0 and hp["theta"] > 0):
+            raise ValueError("heston_scheme 'qe' needs kappa, theta and xi positive.")
+
+
 def heston_defaults(sigma, heston_params=None):
     """kappa=2, xi=0.3, rho=-0.7, v0=theta=sigma^2: the reference's hard-coded defaults
     (options_model_3.py:948-950,995-996; options_model_2_ui.py:74-80)."""
@@ -97,7 +111,9 @@ def price_american_option(S0, K, r, sigma, T, n_paths, n_steps, model="GBM", opt
     """regressor: "poly" (OLS on [1, u, u^2] per time step: the flows of `semantics`), "nn" (the reference's network, two-pass
     flow), "ols7" (one least-squares fit on the reference's 7 features, two-pass flow).
     nn_options (regressor="nn" only): dict with any of nn_hidden, nn_layers, nn_dropout, nn_epochs, nn_lr, nn_batch,
-    inference_dropout, torch_seed -- the network named by BASELINE config 5 (2 x 64) by default."""
+    inference_dropout, torch_seed -- the network named by BASELINE config 5 (2 x 64) by default.
+    heston_scheme (model="Heston"): "reference" (= "clamp"), "full_truncation", "calibrator", or "qe" -- Andersen's (2008)
+    quadratic-exponential rule, which needs kappa > 0, theta > 0 and xi > 0 (ValueError otherwise)."""
     model_l = str(model).lower()
     n_gpus = int(n_gpus)
     if n_gpus < 1:
@@ -115,6 +131,7 @@ def price_american_option(S0, K, r, sigma, T, n_paths, n_steps, model="GBM", opt
         if ctx is not None:
             raise ValueError("n_gpus > 1 uses one context per rank process; do not pass ctx.")
         _validate(S0, K, T, r, sigma, n_paths, n_steps, option_type, need_sigma=(model_l == "gbm"))
+        _validate_scheme(model_l, heston_scheme, sigma, heston_params)
         from . import launcher
         if isinstance(device, int) and not os.environ.get("OMC_RCCL_LIB"):
             # (real RCCL refuses two ranks on one card; only the shared-memory stand-in of the tests runs that way)
@@ -137,6 +154,7 @@ def price_american_option(S0, K, r, sigma, T, n_paths, n_steps, model="GBM", opt
         # (omc_price_american_ols7): the linear regressor between the per-step polynomial and the network.  Across GPUs the
         # paths shard by antithetic pair and the ranks' co-moments are merged by two small all-reduces: the fit is the job's.
         _validate(S0, K, T, r, sigma, n_paths, n_steps, option_type, need_sigma=(model_l == "gbm"))
+        _validate_scheme(model_l, heston_scheme, sigma, heston_params)
         M = int(n_paths) // 2 * 2 if antithetic else int(n_paths)
         if M <= 0:
             raise ValueError("num_simulations and num_time_steps must be positive integers.")
@@ -170,6 +188,7 @@ def price_american_option(S0, K, r, sigma, T, n_paths, n_steps, model="GBM", opt
             S0, K, r, sigma, T, n_paths, n_steps, model=model, option_type=option_type,
             heston_params=heston_params, seed=seed, stream=stream, device=device, **(nn_options or {}))
     _validate(S0, K, T, r, sigma, n_paths, n_steps, option_type, need_sigma=(model_l == "gbm"))
+    _validate_scheme(model_l, heston_scheme, sigma, heston_params)
     M = int(n_paths) // 2 * 2 if antithetic else int(n_paths)  # options_model_3.py:458
     if M <= 0:
         raise ValueError("num_simulations and num_time_steps must be positive integers.")
@@ -221,7 +240,9 @@ def price_american_chain(S0, strikes, r, sigma, T, n_paths, n_steps, option_type
                          heston_scheme="reference", seed=42, stream=0, device=None, ctx=None) -> ChainResult:
     """Every quote of one expiry -- `strikes`, each a put or a call (`option_types`: one string for all, or one per
     strike) -- from ONE set of paths (omc_price_american_chain): two-pass flow, polynomial regressor, antithetic pairs,
-    one GPU.  entries[i] equals price_american_option(S0, strikes[i], ..., option_type=option_types[i]) bit for bit."""
+    one GPU.  entries[i] equals price_american_option(S0, strikes[i], ..., option_type=option_types[i]) bit for bit.
+    heston_scheme (model="Heston"): "reference" (= "clamp"), "full_truncation", "calibrator", or "qe" -- Andersen's (2008)
+    quadratic-exponential rule, which needs kappa > 0, theta > 0 and xi > 0 (ValueError otherwise)."""
     model_l = str(model).lower()
     if model_l not in ("gbm", "heston"):
         raise ValueError("model must be 'GBM' or 'Heston'.")
@@ -240,6 +261,7 @@ def price_american_chain(S0, strikes, r, sigma, T, n_paths, n_steps, option_type
         if not (math.isfinite(k) and k > 0):
             raise ValueError("S0, K, T must be positive.")
         _validate(S0, k, T, r, sigma, n_paths, n_steps, ot, need_sigma=(model_l == "gbm"))
+        _validate_scheme(model_l, heston_scheme, sigma, heston_params)
     M = int(n_paths) // 2 * 2
     if M <= 0:
         raise ValueError("num_simulations and num_time_steps must be positive integers.")
@@ -300,7 +322,10 @@ def price_american_greeks(S0, K, r, sigma, T, n_paths, n_steps, model="GBM", opt
     """Delta, gamma, vega, rho and theta of the American price of price_american_option(regressor="poly",
     semantics="two_pass") with the exercise policy pass 1 fits held fixed (omc_price_american_greeks).  They are exact
     derivatives of that frozen-policy estimator; they differ from the true American Greeks only through the policy's
-    suboptimality.  gamma is a central difference of pathwise deltas at S0 (1 +- bump) on the same paths.  One GPU."""
+    suboptimality.  gamma is a central difference of pathwise deltas at S0 (1 +- bump) on the same paths.  One GPU.
+    heston_scheme (model="Heston"): "reference" (= "clamp"), "full_truncation", "calibrator", or "qe" -- Andersen's (2008)
+    quadratic-exponential rule, which needs kappa > 0, theta > 0 and xi > 0 (ValueError otherwise).  The spot of every
+    scheme is linear in S0, so the Heston delta and gamma need nothing of the scheme."""
     model_l = str(model).lower()
     if int(n_gpus) != 1:
         raise ValueError("price_american_greeks runs on one GPU (n_gpus=1).")
@@ -309,6 +334,7 @@ def price_american_greeks(S0, K, r, sigma, T, n_paths, n_steps, model="GBM", opt
     if not (0.0 < float(bump) <= 0.5):
         raise ValueError("bump must lie in (0, 0.5].")
     _validate(S0, K, T, r, sigma, n_paths, n_steps, option_type, need_sigma=(model_l == "gbm"))
+    _validate_scheme(model_l, heston_scheme, sigma, heston_params)
     M = int(n_paths) // 2 * 2 if antithetic else int(n_paths)
     if M <= 0:
         raise ValueError("num_simulations and num_time_steps must be positive integers.")
@@ -359,7 +385,9 @@ def price_barrier_option(S0, K, r, sigma, T, n_paths, n_steps, barrier, barrier_
     """Knock-in / knock-out barrier option (omc_price_barrier).  style "american": the two-pass poly
     LSM (price_american_option(semantics="two_pass")) on the path matrix with the spots where the option is not live
     replaced by a dead spot; "european": the discounted terminal payoff, no matrix.  monitoring "discrete" (grid steps
-    1..n_steps) or "continuous" (GBM: Brownian-bridge crossing test between grid points).  Antithetic paths, one GPU."""
+    1..n_steps) or "continuous" (GBM: Brownian-bridge crossing test between grid points).  Antithetic paths, one GPU.
+    heston_scheme (model="Heston"): "reference" (= "clamp"), "full_truncation", "calibrator", or "qe" -- Andersen's (2008)
+    quadratic-exponential rule, which needs kappa > 0, theta > 0 and xi > 0 (ValueError otherwise)."""
     model_l = str(model).lower()
     if model_l not in ("gbm", "heston"):
         raise ValueError("model must be 'GBM' or 'Heston'.")
@@ -374,6 +402,7 @@ def price_barrier_option(S0, K, r, sigma, T, n_paths, n_steps, barrier, barrier_
     if not (math.isfinite(float(barrier)) and float(barrier) > 0):
         raise ValueError("barrier H must be finite and positive.")
     _validate(S0, K, T, r, sigma, n_paths, n_steps, option_type, need_sigma=(model_l == "gbm"))
+    _validate_scheme(model_l, heston_scheme, sigma, heston_params)
     M = int(n_paths) // 2 * 2
     if M <= 0:
         raise ValueError("num_simulations and num_time_steps must be positive integers.")
@@ -417,11 +446,14 @@ class DividendResult:
 
 
 def price_american_dividends(S0, K, r, sigma, T, n_paths, n_steps, dividend_yield=0.0, dividends=(), model="GBM",
-                             option_type="put", heston_params=None, seed=42, device=None) -> DividendResult:
+                             option_type="put", heston_params=None, seed=42, device=None,
+                             heston_scheme="reference") -> DividendResult:
     """American option on a stock that pays dividends (omc_price_american_div): the two-pass poly
     LSM of price_american_option on paths that drift at r - dividend_yield and drop by every discrete dividend on its
     ex-dividend step.  dividends: items (t, amount) -- a cash dividend -- or (t, amount, "cash" | "proportional"), with
-    0 < t <= T; a proportional amount is the fraction of the spot paid out, in [0, 1).  Antithetic paths, one GPU."""
+    0 < t <= T; a proportional amount is the fraction of the spot paid out, in [0, 1).  Antithetic paths, one GPU.
+    heston_scheme (model="Heston"): "reference" (= "clamp"), "full_truncation", "calibrator", or "qe" -- Andersen's (2008)
+    quadratic-exponential rule, which needs kappa > 0, theta > 0 and xi > 0 (ValueError otherwise)."""
     model_l = str(model).lower()
     if model_l not in ("gbm", "heston"):
         raise ValueError("model must be 'GBM' or 'Heston'.")
@@ -438,13 +470,14 @@ def price_american_dividends(S0, K, r, sigma, T, n_paths, n_steps, dividend_yiel
             raise ValueError("a dividend's kind must be 'cash' or 'proportional'.")
         divs.append((float(d[0]), float(d[1]), kind))
     _validate(S0, K, T, r, sigma, n_paths, n_steps, option_type, need_sigma=(model_l == "gbm"))
+    _validate_scheme(model_l, heston_scheme, sigma, heston_params)
     M = int(n_paths) // 2 * 2
     if M <= 0:
         raise ValueError("num_simulations and num_time_steps must be positive integers.")
     c = _ffi.default_context(device)
     p = _ffi.make_params(model=model_l, is_put=(option_type == "put"), semantics="two_pass", antithetic=True,
                          n_paths=M, n_steps=int(n_steps), S0=S0, K=K, r=r, sigma=sigma or 0.0, T=T, seed=seed,
-                         **heston_defaults(sigma, heston_params))
+                         heston_scheme=heston_scheme, **heston_defaults(sigma, heston_params))
     out = c.price_american_div(p, q, divs)
     var = max(out["sumsq"] / M - out["price"] ** 2, 0.0)
     return DividendResult(price=out["price"], stderr=math.sqrt(var / M), std=out["std"], zero_prob=out["zero_prob"],
@@ -485,12 +518,15 @@ class JumpResult:
 
 def price_american_jumps(S0, K, r, sigma, T, n_paths, n_steps, jump_intensity, jump_mean=0.0, jump_vol=0.0,
                          dividend_yield=0.0, model="GBM", option_type="put", heston_params=None, seed=42,
-                         device=None) -> JumpResult:
+                         device=None, heston_scheme="reference") -> JumpResult:
     """American option under jump-diffusion (omc_price_american_jump): the two-pass poly LSM of
     price_american_option on paths that carry compound-Poisson jumps -- jump_intensity jumps per year, each multiplying
     the spot by exp(J), J ~ N(jump_mean, jump_vol^2) -- and drift at r - dividend_yield - jump_intensity (E[e^J] - 1).
     model "GBM" is Merton's jump-diffusion, "Heston" is Bates's model.  jump_intensity * T / n_steps may not exceed 1.
-    Antithetic paths, one GPU."""
+    Antithetic paths, one GPU.
+    heston_scheme (model="Heston"): "reference" (= "clamp"), "full_truncation", "calibrator", or "qe" -- Andersen's (2008)
+    quadratic-exponential rule, which needs kappa > 0, theta > 0 and xi > 0 (ValueError otherwise).  With "qe" the jump multiplies the
+    spot after the QE step (Bates on QE)."""
     model_l = str(model).lower()
     if model_l not in ("gbm", "heston"):
         raise ValueError("model must be 'GBM' or 'Heston'.")
@@ -504,6 +540,7 @@ def price_american_jumps(S0, K, r, sigma, T, n_paths, n_steps, jump_intensity, j
     if not math.isfinite(q):
         raise ValueError("dividend_yield must be finite.")
     _validate(S0, K, T, r, sigma, n_paths, n_steps, option_type, need_sigma=(model_l == "gbm"))
+    _validate_scheme(model_l, heston_scheme, sigma, heston_params)
     if lam * float(T) / int(n_steps) > 1.0:
         raise ValueError("jump_intensity * T / n_steps must not exceed 1: use more time steps.")
     M = int(n_paths) // 2 * 2
@@ -512,7 +549,7 @@ def price_american_jumps(S0, K, r, sigma, T, n_paths, n_steps, jump_intensity, j
     c = _ffi.default_context(device)
     p = _ffi.make_params(model=model_l, is_put=(option_type == "put"), semantics="two_pass", antithetic=True,
                          n_paths=M, n_steps=int(n_steps), S0=S0, K=K, r=r, sigma=sigma or 0.0, T=T, seed=seed,
-                         **heston_defaults(sigma, heston_params))
+                         heston_scheme=heston_scheme, **heston_defaults(sigma, heston_params))
     out = c.price_american_jump(p, (lam, mu, sj), q)
     var = max(out["sumsq"] / M - out["price"] ** 2, 0.0)
     return JumpResult(price=out["price"], stderr=math.sqrt(var / M), std=out["std"], zero_prob=out["zero_prob"],
@@ -762,7 +799,7 @@ def price_american_bounds_heston(S0, K, r, T, n_paths, n_steps, heston_params=No
     """Lower and upper bounds on the Bermudan value of a put / call under the Heston model
     (omc_price_american_bounds_heston): price_american_bounds with Heston paths.  heston_params as
     price_american_option takes them (v0, kappa, theta, xi, rho; the defaults of heston_defaults at sigma = 0.2);
-    heston_scheme "reference" (= "clamp") or "full_truncation" -- the calibrator's scheme has no bounds.  The policy
+    heston_scheme "reference" (= "clamp") or "full_truncation" -- the calibrator's scheme and "qe" have no bounds.  The policy
     (`policy` / `betas` as price_american_bounds takes them) regresses on the spot alone; the inner simulations start at the
     outer paths' (spot, variance) state, so `upper` bounds the value under any policy of the DISCRETISED scheme's game on
     the grid, one that sees the variance included.  The lower-bound, outer and inner paths use Philox streams stream + 1,
@@ -782,6 +819,8 @@ def price_american_bounds_heston(S0, K, r, T, n_paths, n_steps, heston_params=No
         raise ValueError(f"heston_scheme must be one of {sorted(_ffi.HESTON_SCHEMES)}.")
     if _ffi.HESTON_SCHEMES[heston_scheme] == _ffi.HESTON_SCHEMES["calibrator"]:
         raise ValueError("price bounds under Heston take heston_scheme 'reference' or 'full_truncation', not 'calibrator'.")
+    if _ffi.HESTON_SCHEMES[heston_scheme] == _ffi.HESTON_SCHEMES["qe"]:
+        raise ValueError("price bounds under Heston take heston_scheme 'reference' or 'full_truncation', not 'qe'.")
     _validate(S0, K, T, r, None, n_paths, n_steps, option_type, need_sigma=False)
     M = int(n_paths) // 2 * 2
     if M <= 0:
@@ -915,6 +954,7 @@ def price_european_option(S0, K, r, sigma, T, n_paths, n_steps=1, model="GBM", o
     """Discounted terminal payoff mean; no path matrix is stored (options_model_3.py:382-437)."""
     model_l = str(model).lower()
     _validate(S0, K, T, r, sigma, n_paths, n_steps, option_type, need_sigma=(model_l == "gbm"))
+    _validate_scheme(model_l, heston_scheme, sigma, heston_params)
     M = int(n_paths) // 2 * 2 if antithetic else int(n_paths)
     hp = heston_defaults(sigma, heston_params)
     c = ctx or _ffi.default_context(device)

@@ -416,6 +416,14 @@ int upload_fits(omc_ctx* c, const omc::LsmWorkspace& w, const double* betas, int
     return 0;
 }
 
+int check_heston_scheme(int scheme, double kappa, double theta, double xi)
+{
+    if (scheme < 0 || scheme > OMC_HESTON_QE) return fail(-4, "unknown Heston scheme.");
+    if (scheme == OMC_HESTON_QE && (!(kappa > 0) || !(xi > 0) || !(theta > 0)))
+        return fail(-36, "the QE scheme needs kappa, theta and xi positive.");
+    return 0;
+}
+
 int check_params(const omc_params* p)
 {
     int rc;
@@ -426,7 +434,7 @@ int check_params(const omc_params* p)
         if (!(p->sigma > 0)) return fail(-5, "S0, K, T, and sigma must be positive.");
     } else if (p->model == OMC_MODEL_HESTON) {
         if (!(p->rho >= -1.0 && p->rho <= 1.0) || !(p->v0 >= 0)) return fail(-5, "invalid Heston parameters.");
-        if (p->heston_scheme < 0 || p->heston_scheme > 2) return fail(-4, "unknown Heston scheme.");
+        if ((rc = check_heston_scheme(p->heston_scheme, p->kappa, p->theta, p->xi))) return rc;
         if (!p->antithetic) return fail(-4, "Heston paths are always antithetic.");
     } else {
         return fail(-4, "unknown model.");

@@ -26,7 +26,7 @@ static int check_batch(const omc_params* p, int n)
 static int generator_id(const omc_params* p)
 {
     if (p->model == OMC_MODEL_GBM) return p->antithetic ? 0 : 1;
-    return 2 + p->heston_scheme;  // 2 reference clamp, 3 full truncation, 4 calibrator scheme
+    return 2 + p->heston_scheme;  // 2 reference clamp, 3 full truncation, 4 calibrator scheme, 5 QE
 }
 
 // (behind run_batch's checks)

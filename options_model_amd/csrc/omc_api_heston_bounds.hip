@@ -23,7 +23,7 @@ extern "C" int omc_heston_paths_sv_f32(omc_ctx* c, float* S, float* V, int64_t l
     if ((rc = check_matrix(S, ld, n_paths))) return rc;
     if (!V) return fail(-7, "null variance matrix pointer.");
     if (n_paths & 1) return fail(-3, "antithetic layout needs an even n_paths.");
-    if (scheme < 0 || scheme > 2) return fail(-4, "unknown Heston scheme.");
+    if ((rc = check_heston_scheme(scheme, kappa, theta, xi))) return rc;
     HIP_TRY(omc::launch_heston_paths_sv(c->stream, S, V, ld, n_paths, n_steps, S0, r, T, v0, kappa, theta, xi, rho, seed,
                                         (uint32_t)stream, pair_offset, scheme));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -106,8 +106,8 @@ extern "C" int omc_price_american_bounds_heston(omc_ctx* c, const omc_params* p,
     if (!cfg || !out) return fail(-7, "null bounds config or result pointer.");
     if ((rc = check_params(p))) return rc;
     if (p->model != OMC_MODEL_HESTON) return fail(-12, "these price bounds are for the Heston model (GBM: omc_price_american_bounds).");
-    if (p->heston_scheme == OMC_HESTON_CALIBRATOR)
-        return fail(-12, "price bounds under Heston take the reference or the full-truncation scheme, not the calibrator's.");
+    if (p->heston_scheme != OMC_HESTON_REFERENCE_CLAMP && p->heston_scheme != OMC_HESTON_FULL_TRUNCATION)
+        return fail(-12, "price bounds under Heston take the reference or the full-truncation scheme, not the calibrator's or QE.");
     if (cfg->regressors == OMC_HESTON_REG_SPOT_VARIANCE)
         return heston_sv_bounds(c, p, cfg, betas, betas_out, q_out, samples_out, out);
     if (cfg->regressors != OMC_HESTON_REG_SPOT) return fail(-4, "unknown regressors (spot or spot + variance).");

@@ -39,7 +39,7 @@ int omc_heston_paths_f32(omc_ctx* c, float* S, int64_t ld, int64_t n_paths, int 
     if ((rc = check_sizes(n_paths, n_steps))) return rc;
     if ((rc = check_matrix(S, ld, n_paths))) return rc;
     if (n_paths & 1) return fail(-3, "antithetic layout needs an even n_paths.");
-    if (scheme < 0 || scheme > 2) return fail(-4, "unknown Heston scheme.");
+    if ((rc = check_heston_scheme(scheme, kappa, theta, xi))) return rc;
     HIP_TRY(omc::launch_heston_paths(c->stream, S, ld, n_paths, n_steps, S0, r, T, v0, kappa, theta,
                                      xi, rho, seed, (uint32_t)stream, pair_offset, scheme,
                                      c->heston_vec));
@@ -78,7 +78,7 @@ int omc_heston_paths_from_normals_f32(omc_ctx* c, float* S, int64_t ld, int64_t 
     if (!Z1 || !Z2) return fail(-7, "null normals pointer.");
     if (n_paths & 1) return fail(-3, "antithetic layout needs an even n_paths.");
     if (ldz < n_paths / 2) return fail(-6, "ldz too small.");
-    if (scheme < 0 || scheme > 2) return fail(-4, "unknown Heston scheme.");
+    if ((rc = check_heston_scheme(scheme, kappa, theta, xi))) return rc;
     HIP_TRY(omc::launch_heston_from_normals(c->stream, S, ld, n_paths, n_steps, S0, r, T, v0, kappa,
                                             theta, xi, rho, Z1, Z2, ldz, scheme));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -422,7 +422,7 @@ int omc_heston_price_strikes(omc_ctx* c, int64_t n_paths, int n_steps, double S0
     if (!(S0 > 0) || !(T > 0)) return fail(-1, "S0, K, T must be positive.");
     if ((rc = check_sizes(n_paths, n_steps))) return rc;
     if (n_paths & 1) return fail(-3, "antithetic layout needs an even n_paths.");
-    if (scheme < 0 || scheme > 2) return fail(-4, "unknown Heston scheme.");
+    if ((rc = check_heston_scheme(scheme, kappa, theta, xi))) return rc;
     if (!(rho >= -1.0 && rho <= 1.0) || !(v0 >= 0)) return fail(-5, "invalid Heston parameters.");
     if (!strikes || !prices || n_strikes <= 0) return fail(-7, "bad strike arguments.");
     if (n_paths > (int64_t)65535 * 4096) return fail(-3, "at most 268,431,360 paths per expiry.");
@@ -465,7 +465,7 @@ int omc_heston_price_surface(omc_ctx* c, int64_t n_paths, int n_steps, double S0
     if (!(S0 > 0)) return fail(-1, "S0, K, T must be positive.");
     if ((rc = check_sizes(n_paths, n_steps))) return rc;
     if (n_paths & 1) return fail(-3, "antithetic layout needs an even n_paths.");
-    if (scheme < 0 || scheme > 2) return fail(-4, "unknown Heston scheme.");
+    if ((rc = check_heston_scheme(scheme, kappa, theta, xi))) return rc;
     if (!(rho >= -1.0 && rho <= 1.0) || !(v0 >= 0)) return fail(-5, "invalid Heston parameters.");
     if (!expiries || !streams || n_expiries <= 0 || n_expiries > 65535) return fail(-7, "bad expiry arguments (1 .. 65535 expiries).");
     if (!strikes || !expiry_of || !prices || n_quotes <= 0) return fail(-7, "bad strike arguments.");

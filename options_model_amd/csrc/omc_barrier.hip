@@ -53,7 +53,7 @@ __device__ __forceinline__ void put_row(float* p, const float (&v)[VEC])
     }
 }
 
-// MODEL 0 GBM, 1/2/3 Heston scheme 0/1/2; MON 0 discrete, 1 continuous (GBM only); VSTORE: VEC-wide stores
+// MODEL 0 GBM, 1/2/3/4 Heston scheme 0/1/2/3; MON 0 discrete, 1 continuous (GBM only); VSTORE: VEC-wide stores
 template <int MODEL, bool STORE, int MON, int VEC, bool VSTORE>
 __device__ __forceinline__ void barrier_paths_body(const BarArgs& A)
 {

@@ -32,7 +32,7 @@ struct BatchProb {
 };
 
 // ------------------------------------------------------------------ batched entry points
-template <int VEC, int GEN>  // GEN 0 GBM antithetic, 1 GBM plain, 2 Heston clamp, 3 full truncation, 4 calibrator
+template <int VEC, int GEN>  // GEN 0 GBM antithetic, 1 GBM plain, 2 Heston clamp, 3 full truncation, 4 calibrator, 5 QE
 __global__ __launch_bounds__(kBlock) void paths_batch_kernel(const BatchProb* __restrict__ pr)
 {
     const PathArgs g = pr[blockIdx.y].path;
@@ -40,7 +40,8 @@ __global__ __launch_bounds__(kBlock) void paths_batch_kernel(const BatchProb* __
     else if constexpr (GEN == 1) gbm_paths_body<VEC, false>(g);
     else if constexpr (GEN == 2) heston_paths_body<VEC, 0>(g);
     else if constexpr (GEN == 3) heston_paths_body<VEC, 1>(g);
-    else heston_paths_body<VEC, 2>(g);
+    else if constexpr (GEN == 4) heston_paths_body<VEC, 2>(g);
+    else heston_paths_body<VEC, 3>(g);
 }
 
 template <int GEN>
@@ -51,7 +52,8 @@ __global__ __launch_bounds__(kBlock) void terminal_batch_kernel(const BatchProb*
     else if constexpr (GEN == 1) terminal_body<0, false>(a);
     else if constexpr (GEN == 2) terminal_body<1, true>(a);
     else if constexpr (GEN == 3) terminal_body<2, true>(a);
-    else terminal_body<3, true>(a);
+    else if constexpr (GEN == 4) terminal_body<3, true>(a);
+    else terminal_body<4, true>(a);
 }
 
 template <int SEM, int VEC, int BLOCK>
@@ -345,7 +347,7 @@ hipError_t batch_paths(hipStream_t st, const void* table_dev, int n, const Batch
     const int vec = e.vec4 ? 4 : 1;
     const dim3 grid((unsigned)((e.path_blocks + vec - 1) / vec), (unsigned)n), block(kBlock);
     for_vec4(e.vec4 != 0, [&](auto v) {
-        for_int<0, 1, 2, 3, 4>(gen, [&](auto g) {
+        for_int<0, 1, 2, 3, 4, 5>(gen, [&](auto g) {
             hipLaunchKernelGGL((paths_batch_kernel<decltype(v)::value, decltype(g)::value>), grid, block, 0, st, pr);
         });
     });
@@ -402,7 +404,7 @@ hipError_t batch_terminal(hipStream_t st, const void* table_dev, int n, const Ba
 {
     const BatchProb* pr = (const BatchProb*)table_dev;
     const dim3 grid((unsigned)e.term_blocks, 1, (unsigned)n);
-    for_int<0, 1, 2, 3, 4>(gen, [&](auto g) {
+    for_int<0, 1, 2, 3, 4, 5>(gen, [&](auto g) {
         hipLaunchKernelGGL((terminal_batch_kernel<decltype(g)::value>), grid, dim3(kBlock), 0, st, pr);
     });
     hipLaunchKernelGGL(lsm_finalize_batch_kernel, dim3(1, 1, (unsigned)n), dim3(kBlock), 0, st, pr, 0);

@@ -89,6 +89,9 @@ int check_sizes(int64_t n_paths, int n_steps);
 int check_matrix(const void* S, int64_t ld, int64_t n_paths);
 int check_lsm_args(const void* S, int64_t ld, int64_t n_paths, int n_steps, double K, double r, double T);
 int check_params(const omc_params* p);
+// a Heston scheme (0 .. 3, else -4) and what it needs of the law: OMC_HESTON_QE divides by kappa and xi and needs a positive
+// long-run mean (-36)
+int check_heston_scheme(int scheme, double kappa, double theta, double xi);
 int check_contnet(omc_ctx* c, int hidden, int epochs, double lr);
 
 // streams, workspace, collectives

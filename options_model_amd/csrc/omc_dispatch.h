@@ -44,11 +44,19 @@ inline auto for_vec4(bool v4, F&& f)
     return for_int<4, 1>(v4 ? 4 : 1, f);
 }
 
-// the path model: 0 GBM, 1 / 2 / 3 Heston scheme 0 / 1 / 2
+// the path model: 0 GBM, 1 / 2 / 3 / 4 Heston scheme 0 / 1 / 2 / 3 (the entry points refuse every other scheme before a launcher
+// is reached)
 template <class F>
 inline auto for_model(int model, int scheme, F&& f)
 {
-    return for_int<0, 1, 2, 3>(model == 0 ? 0 : scheme == 0 ? 1 : scheme == 1 ? 2 : 3, f);
+    return for_int<0, 1, 2, 3, 4>(model == 0 ? 0 : scheme == 0 ? 1 : scheme == 1 ? 2 : scheme == 2 ? 3 : 4, f);
+}
+
+// a Heston scheme alone: 0 .. 3
+template <class F>
+inline auto for_scheme(int scheme, F&& f)
+{
+    return for_int<0, 1, 2, 3>(scheme, f);
 }
 
 }  // namespace omc

@@ -17,7 +17,7 @@
 
 namespace omc {
 
-// MODEL 0 GBM, 1/2/3 Heston scheme 0/1/2.  VEC-wide stores: the launcher picks a VEC every row start is aligned to.
+// MODEL 0 GBM, 1/2/3/4 Heston scheme 0/1/2/3.  VEC-wide stores: the launcher picks a VEC every row start is aligned to.
 template <int MODEL, int VEC>
 __global__ __launch_bounds__(kBlock) void dividend_paths_kernel(PathArgs g, const DivEntry* __restrict__ tab)
 {

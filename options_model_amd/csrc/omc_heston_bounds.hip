@@ -122,10 +122,10 @@ hipError_t launch_heston_paths_sv(hipStream_t st, float* S, float* V, int64_t ld
     if (P <= 0) return hipSuccess;
     const PathArgs g = make_path_args(s, P);
     const dim3 grid((unsigned)((P + kBlock - 1) / kBlock)), block(kBlock);
-    if (scheme == 0) hipLaunchKernelGGL((heston_paths_sv_kernel<0>), grid, block, 0, st, g, V);
-    else if (scheme == 1) hipLaunchKernelGGL((heston_paths_sv_kernel<1>), grid, block, 0, st, g, V);
-    else if (scheme == 2) hipLaunchKernelGGL((heston_paths_sv_kernel<2>), grid, block, 0, st, g, V);
-    else return hipErrorInvalidValue;
+    if (scheme < 0 || scheme > 3) return hipErrorInvalidValue;
+    for_scheme(scheme, [&](auto sc) {
+        hipLaunchKernelGGL((heston_paths_sv_kernel<decltype(sc)::value>), grid, block, 0, st, g, V);
+    });
     return hipGetLastError();
 }
 

@@ -35,7 +35,7 @@ __device__ __forceinline__ float jump_log2(const JumpLaw& j, uint32_t w, uint64_
     return __builtin_fmaf(sqrtf(fn) * j.sj2, zc, fn * j.mj2);
 }
 
-// MODEL 0 GBM, 1/2/3 Heston scheme 0/1/2.  VEC-wide stores: the launcher picks a VEC every row start is aligned to.
+// MODEL 0 GBM, 1/2/3/4 Heston scheme 0/1/2/3.  VEC-wide stores: the launcher picks a VEC every row start is aligned to.
 template <int MODEL, int VEC>
 __global__ __launch_bounds__(kBlock) void jump_paths_kernel(PathArgs g, JumpLaw j)
 {

@@ -97,7 +97,7 @@ HestonC make_heston(double r, double T, int n_steps, double kappa, double theta,
                                   double xi, double rho)
 {
     const double dt = T / n_steps, L2E = 1.4426950408889634074;
-    HestonC c;
+    HestonC c{};
     c.dtf = (float)dt;
     c.kdt = (float)(kappa * dt);
     c.theta = (float)theta;
@@ -111,6 +111,16 @@ HestonC make_heston(double r, double T, int n_steps, double kappa, double theta,
     c.rdt = (float)(r * dt);
     c.xi_sqdt = (float)(xi * sqrt(dt));
     c.l2e_sqdt = (float)(L2E * sqrt(dt));
+    if (kappa > 0 && xi > 0) {  // scheme 3 (the entry points refuse it otherwise); 1 - E without its cancellation
+        const double E = exp(-kappa * dt), ome = -expm1(-kappa * dt), ro = rho / xi, kk = 0.5 * dt * (kappa * ro - 0.5);
+        c.qe_e = (float)E;
+        c.qe_c1 = (float)(xi * xi * E * ome / kappa);
+        c.qe_c2 = (float)(theta * xi * xi * ome * ome / (2.0 * kappa));
+        c.qe_k0 = (float)(L2E * (r * dt - ro * kappa * theta * dt));
+        c.qe_k1 = (float)(L2E * (kk - ro));
+        c.qe_k2 = (float)(L2E * (kk + ro));
+        c.qe_k34 = (float)(L2E * L2E * 0.5 * dt * (1.0 - rho * rho));
+    }
     return c;
 }
 
@@ -198,15 +208,10 @@ hipError_t launch_heston_from_normals(hipStream_t st, float* S, int64_t ld, int6
     const HestonC c = make_heston(r, T, n_steps, kappa, theta, xi, rho);
     const int64_t P = n_paths / 2;
     if (P <= 0) return hipSuccess;
-    if (scheme == 0)
-        hipLaunchKernelGGL((heston_from_normals_kernel<0>), dim3(grid_for(P)), dim3(kBlock), 0, st,
+    for_scheme(scheme, [&](auto sc) {
+        hipLaunchKernelGGL((heston_from_normals_kernel<decltype(sc)::value>), dim3(grid_for(P)), dim3(kBlock), 0, st,
                            S, ld, P, n_steps, (float)S0, (float)v0, c, Z1, Z2, ldz);
-    else if (scheme == 1)
-        hipLaunchKernelGGL((heston_from_normals_kernel<1>), dim3(grid_for(P)), dim3(kBlock), 0, st,
-                           S, ld, P, n_steps, (float)S0, (float)v0, c, Z1, Z2, ldz);
-    else
-        hipLaunchKernelGGL((heston_from_normals_kernel<2>), dim3(grid_for(P)), dim3(kBlock), 0, st,
-                           S, ld, P, n_steps, (float)S0, (float)v0, c, Z1, Z2, ldz);
+    });
     return hipGetLastError();
 }
 
@@ -247,9 +252,9 @@ __global__ __launch_bounds__(kBlock) void heston_terminal_store_kernel(float* __
 // per QUOTE reduces its strike over its expiry's row, in payoff_means_kernel's order.
 struct SurfaceExpiry {
     HestonC hc;
-    uint32_t stream, pad[2];
+    uint32_t stream, pad[3];
 };
-static_assert(sizeof(SurfaceExpiry) == 64, "omc::heston_surface_table_bytes");
+static_assert(sizeof(SurfaceExpiry) == 96, "omc::heston_surface_table_bytes");
 
 template <int SCHEME>
 __global__ __launch_bounds__(kBlock) void heston_terminal_surface_kernel(float* __restrict__ ST, int64_t ldst, PathArgs g,
@@ -338,9 +343,9 @@ hipError_t launch_heston_terminal_store(hipStream_t st, float* ST, int64_t n_pat
     g.k0 = (uint32_t)seed; g.k1 = (uint32_t)(seed >> 32); g.stream = stream; g.pair_offset = pair_offset;
     if (g.P <= 0) return hipSuccess;
     const dim3 grid(grid_for(g.P)), block(kBlock);
-    if (scheme == 0) hipLaunchKernelGGL((heston_terminal_store_kernel<0>), grid, block, 0, st, ST, g);
-    else if (scheme == 1) hipLaunchKernelGGL((heston_terminal_store_kernel<1>), grid, block, 0, st, ST, g);
-    else hipLaunchKernelGGL((heston_terminal_store_kernel<2>), grid, block, 0, st, ST, g);
+    for_scheme(scheme, [&](auto sc) {
+        hipLaunchKernelGGL((heston_terminal_store_kernel<decltype(sc)::value>), grid, block, 0, st, ST, g);
+    });
     return hipGetLastError();
 }
 
@@ -369,9 +374,9 @@ hipError_t launch_heston_terminal_surface(hipStream_t st, float* ST, int64_t lds
     if (g.P <= 0 || n_expiries <= 0) return hipSuccess;
     const dim3 grid(grid_for(g.P), (unsigned)n_expiries), block(kBlock);
     const SurfaceExpiry* tab = (const SurfaceExpiry*)tab_dev;
-    if (scheme == 0) hipLaunchKernelGGL((heston_terminal_surface_kernel<0>), grid, block, 0, st, ST, ldst, g, tab);
-    else if (scheme == 1) hipLaunchKernelGGL((heston_terminal_surface_kernel<1>), grid, block, 0, st, ST, ldst, g, tab);
-    else hipLaunchKernelGGL((heston_terminal_surface_kernel<2>), grid, block, 0, st, ST, ldst, g, tab);
+    for_scheme(scheme, [&](auto sc) {
+        hipLaunchKernelGGL((heston_terminal_surface_kernel<decltype(sc)::value>), grid, block, 0, st, ST, ldst, g, tab);
+    });
     return hipGetLastError();
 }
 
@@ -427,12 +432,10 @@ hipError_t launch_terminal(hipStream_t st, double* part, int* nblk_out, int mode
     if (model == 0) {
         if (antithetic) hipLaunchKernelGGL((terminal_kernel<0, true>), grid, block, 0, st, a);
         else hipLaunchKernelGGL((terminal_kernel<0, false>), grid, block, 0, st, a);
-    } else if (scheme == 0) {
-        hipLaunchKernelGGL((terminal_kernel<1, true>), grid, block, 0, st, a);
-    } else if (scheme == 1) {
-        hipLaunchKernelGGL((terminal_kernel<2, true>), grid, block, 0, st, a);
     } else {
-        hipLaunchKernelGGL((terminal_kernel<3, true>), grid, block, 0, st, a);
+        for_scheme(scheme, [&](auto sc) {
+            hipLaunchKernelGGL((terminal_kernel<decltype(sc)::value + 1, true>), grid, block, 0, st, a);
+        });
     }
     return hipGetLastError();
 }

@@ -28,6 +28,11 @@ struct HestonC {
     float dtf, kdt, theta, xi, rho, rho2, rdt_l2, hdt_l2, l2e;
     float sqdt, rdt, xi_sqdt;  // sqrt(dt), r*dt, xi*sqrt(dt)
     float l2e_sqdt;            // log2(e)*sqrt(dt)
+    // scheme 3 (Andersen's QE), formed in double and rounded once (make_heston); all 0 where kappa or xi is not positive
+    float qe_e;                // E = exp(-kappa dt)
+    float qe_c1, qe_c2;        // s2 = v c1 + c2: c1 = xi^2 E (1 - E) / kappa, c2 = theta xi^2 (1 - E)^2 / (2 kappa)
+    float qe_k0, qe_k1, qe_k2; // log2(e) (r dt + K0), log2(e) K1, log2(e) K2
+    float qe_k34;              // log2(e)^2 K3 (= K4): sqrt(K3 v + K4 v') log2(e) as one square root
 };
 
 // one argument block for both generators (Heston ignores a/b, GBM ignores v_init/hc)
@@ -115,11 +120,66 @@ __device__ __forceinline__ void heston_path_step(const HestonC& c, float tw, flo
     v = SCHEME ? vn : floor_at(vn, 0.0f);
 }
 
+// ---- scheme 3: Andersen's quadratic-exponential step (the operation order is include/omc.h's)
+// Every fused multiply-add of the rule is written as one; the compiler forms no others here (fp contract off): left to
+// it, a product feeding a sum (t - 1 below, say) may be fused in one kernel and not in another, and the kernels that share
+// this step must give the same bits: with contraction on, the from-normals kernel's spots were one ulp off the generator's.
+// the next variance of a lane whose psi = s2 / m^2 is at most 1.5: a (b + Zv)^2 with t = 2 / psi,
+// b^2 = t - 1 + sqrt(t (t - 1)), a = m / (1 + b^2) -- two reciprocals and two square roots, psi itself never formed
+__device__ __forceinline__ float qe_quadratic(float m, float s2, float m2, float zv)
+{
+#pragma clang fp contract(off)
+    const float t = (m2 + m2) * __builtin_amdgcn_rcpf(s2);
+    const float tm = t - 1.0f;
+    const float b2 = tm + __builtin_amdgcn_sqrtf(t * tm);
+    const float a = m * __builtin_amdgcn_rcpf(1.0f + b2);
+    const float bz = __builtin_amdgcn_sqrtf(b2) + zv;
+    return a * (bz * bz);
+}
+
+// ... and of a lane with psi > 1.5: max(0, (ln(1 - p) - ln Q) / beta) with 1 - p = 2 / (psi + 1), 1 / beta = m (psi + 1) / 2
+// and Q = erfc(Zv / sqrt 2) / 2 the UPPER tail of the variance normal (1 - U, formed directly)
+__device__ __forceinline__ float qe_exponential(float m, float s2, float m2, float zv)
+{
+#pragma clang fp contract(off)
+    const float psi1 = __builtin_fmaf(s2, __builtin_amdgcn_rcpf(m2), 1.0f);
+    const float q1 = 2.0f / psi1;
+    const float Q = 0.5f * erfcf(zv * 0.70710678118654752f);
+    return floor_at((logf(q1) - logf(Q)) * (0.5f * m * psi1), 0.0f);
+}
+
+// ln s' = ln s + r dt + K0 + K1 v + K2 v' + sqrt(K3 v + K4 v') Zs, in log2 units
+__device__ __forceinline__ void qe_spot(const HestonC& c, float v, float vn, float zs, float& s)
+{
+#pragma clang fp contract(off)
+    const float sq = __builtin_amdgcn_sqrtf(__builtin_fmaf(c.qe_k34, vn, c.qe_k34 * v));
+    s = s * fast_exp2(__builtin_fmaf(sq, zs, __builtin_fmaf(c.qe_k2, vn, __builtin_fmaf(c.qe_k1, v, c.qe_k0))));
+}
+
 template <int SCHEME>
 __device__ __forceinline__ void heston_pair_step(const HestonC& c, float z1, float z2, float& s, float& v,
                                                  float& sa, float& vb)
 {
-    if constexpr (SCHEME == 2) {
+    if constexpr (SCHEME == 3) {
+        // Zv = z1, Zs = z2; the partner takes (-z1, -z2).  A wave with no exponential lane (the usual one: Feller
+        // satisfied, v near theta) pays the compare and one scalar branch for the erfc / log code (as the jump generator
+        // does for its rare lanes)
+#pragma clang fp contract(off)
+        const float ma = __builtin_fmaf(v - c.theta, c.qe_e, c.theta), mb = __builtin_fmaf(vb - c.theta, c.qe_e, c.theta);
+        const float s2a = __builtin_fmaf(v, c.qe_c1, c.qe_c2), s2b = __builtin_fmaf(vb, c.qe_c1, c.qe_c2);
+        const float m2a = ma * ma, m2b = mb * mb;
+        const bool ea = s2a > 1.5f * m2a, eb = s2b > 1.5f * m2b;
+        float vna = qe_quadratic(ma, s2a, m2a, z1), vnb = qe_quadratic(mb, s2b, m2b, -z1);
+        if (__builtin_amdgcn_ballot_w64(ea || eb) != 0) {
+            if (ea) vna = qe_exponential(ma, s2a, m2a, z1);
+            if (eb) vnb = qe_exponential(mb, s2b, m2b, -z1);
+        }
+        qe_spot(c, v, vna, z2, s);
+        qe_spot(c, vb, vnb, -z2, sa);
+        v = vna;
+        vb = vnb;
+        return;
+    } else if constexpr (SCHEME == 2) {
         // The calibrator's own scheme (heston_calibration.py:242-255): variance floored at 1e-8
         // before use and at store, ARITHMETIC Euler for S (S may cross zero; so be it).
         const float w2 = __builtin_fmaf(c.rho, z1, c.rho2 * z2);
@@ -149,7 +209,7 @@ __device__ __forceinline__ void heston_pair_step(const HestonC& c, float z1, flo
 
 // ---- what the exotic generators (dividend, jump, barrier) share with the bodies here
 // The vanilla step of one antithetic pair from its Philox block z: MODEL 0 GBM, step i = 0 .. 3 of the block (gbm_paths_body's
-// operations); MODEL 1/2/3 Heston scheme 0/1/2, step i = 0, 1 of the block (heston_paths_body's)
+// operations); MODEL 1/2/3/4 Heston scheme 0/1/2/3, step i = 0, 1 of the block (heston_paths_body's)
 template <int MODEL>
 __device__ __forceinline__ void pair_step(const PathArgs& g, const float (&z)[4], int i, float& s, float& v, float& sa,
                                           float& vb)
@@ -230,7 +290,7 @@ __device__ __forceinline__ void add_payoff(double (&acc)[8], float s, double K, 
     acc[3] += (p == 0.0) ? 1.0 : 0.0;
 }
 
-// MODEL 0 GBM (ANTI selectable), MODEL 1/2/3 Heston scheme 0/1/2 (always antithetic)
+// MODEL 0 GBM (ANTI selectable), MODEL 1/2/3/4 Heston scheme 0/1/2/3 (always antithetic)
 template <int MODEL, bool ANTI>
 __device__ __forceinline__ void terminal_body(const TermArgs& a)
 {

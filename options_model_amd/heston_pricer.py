@@ -10,7 +10,8 @@ this module only reads attributes (`params.kappa/theta/sigma/rho/v0`, `config.n_
 seed`) and re-declares neither schema.  Any object with those attributes works (a SimpleNamespace, a
 dataclass of your own, a dict through `as_params` / `as_config`).
 
-Scheme = the calibrator's own (NOT the pricer's one in options_model_3.py): variance floored at
+Scheme (default; `HestonPricer(scheme=...)` takes any other, "qe" included) = the calibrator's own (NOT the pricer's one in
+options_model_3.py): variance floored at
 1e-8 before use and at store, arithmetic Euler for S, rho-mix before the antithetic stacking
 (:223-255).  On the GPU the terminal spots go to a 4-byte-per-path buffer and every strike is one
 workgroup's reduction over it; no [path][step] matrix is ever built.
@@ -53,9 +54,16 @@ def as_config(obj=None, **kw):
 
 
 class HestonPricer:
-    def __init__(self, config=None, device: int = 0):
+    def __init__(self, config=None, device: int = 0, scheme="calibrator"):
+        """scheme: the discretisation of the inner Monte-Carlo, by name (_ffi.HESTON_SCHEMES) or number.  "calibrator" (the
+        default) is the reference calibrator's own; "qe" is Andersen's (2008) quadratic-exponential rule, far less biased at
+        coarse grids when sigma^2 >> 2 kappa theta -- it needs kappa > 0, theta > 0 and sigma (the vol of vol) > 0, and a
+        parameter set without that prices as nan with the reference's warning, as every failed pricing does."""
         self.config = as_config(config)
         self.device = device
+        if isinstance(scheme, str) and scheme not in _ffi.HESTON_SCHEMES:
+            raise ValueError(f"scheme must be one of {sorted(_ffi.HESTON_SCHEMES)}.")
+        self.scheme = _ffi.HESTON_SCHEMES[scheme] if isinstance(scheme, str) else int(scheme)
         self._stream = 0  # next Philox sub-stream (plays the role of the advancing self.rng)
 
     def _strikes(self, params, S0, strikes, T, r, is_put):
@@ -67,7 +75,7 @@ class HestonPricer:
             n_paths, int(getattr(cfg, "n_time_steps", 100)), float(S0), float(r), float(T), float(params.v0),
             float(params.kappa), float(params.theta), float(params.sigma), float(params.rho), strikes,
             is_put=is_put, seed=int(getattr(cfg, "seed", 42)), stream=self._stream,
-            scheme=_ffi.HESTON_SCHEMES["calibrator"])
+            scheme=self.scheme)
         return prices, errs
 
     def price_european_option(self, params, S0: float, K: float, T: float,
@@ -110,7 +118,7 @@ class HestonPricer:
                 got, _ = _ffi.default_context(self.device).heston_price_surface(
                     n_paths, int(getattr(cfg, "n_time_steps", 100)), float(S0), float(r), float(prm.v0), float(prm.kappa),
                     float(prm.theta), float(prm.sigma), float(prm.rho), uniq, streams, K_array, expiry_of, is_put=False,
-                    seed=int(getattr(cfg, "seed", 42)), scheme=_ffi.HESTON_SCHEMES["calibrator"])
+                    seed=int(getattr(cfg, "seed", 42)), scheme=self.scheme)
                 self._stream += len(uniq)
                 return got
             except Exception as e:  # noqa: BLE001  (the reference prints and returns nan for what failed, :308-310)
