@@ -202,7 +202,10 @@ int omc_heston_paths_f32(omc_ctx* ctx, float* S, int64_t ld, int64_t n_paths, in
  * omc_heston_paths_from_normals_f32 started at (S[t][j], V[t][j]) with the generator's remaining normals reproduces rows
  * t+1 .. of that pair bit for bit.  The checks of omc_heston_paths_f32, and -7 for a null V -- but with scheme 1 a
  * negative v0 is taken as it is, as omc_heston_paths_from_normals_f32 takes it: a state this generator stores is a state
- * it starts from (the inner paths of omc_price_american_bounds_heston start there; section 21's tests rebuild them so). */
+ * it starts from (the inner paths of omc_price_american_bounds_heston start there; section 21's tests rebuild them so).
+ * omc_heston_paths_from_normals_f32 takes a negative v0 with schemes 0, 1 and 2 (0 and 2 floor it before use); it returns
+ * -5 for a rho outside [-1, 1] or NaN at every scheme, and for scheme 3 with a v0 that is not >= 0 (NaN included): the
+ * moments of QE's next variance need a state >= 0, which is all scheme 3 ever stores.  Nothing is launched then. */
 int omc_heston_paths_sv_f32(omc_ctx* ctx, float* S, float* V, int64_t ld, int64_t n_paths, int n_steps,
                             double S0, double r, double T, double v0, double kappa, double theta,
                             double xi, double rho, uint64_t seed, uint64_t stream,

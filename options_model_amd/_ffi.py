@@ -645,11 +645,16 @@ class Context:
         z2 = self.to_device(z2_half, np.float32)
         N, P = z1.shape
         S = self.empty((N + 1, 2 * P), np.float32)
-        _check(self.lib, self.lib.omc_heston_paths_from_normals_f32(
-            self.handle, S.ptr, 2 * P, 2 * P, N, S0, r, T, v0, kappa, theta, xi, rho, z1.ptr, z2.ptr,
-            P, scheme))
-        z1.free()
-        z2.free()
+        try:
+            rc = self.lib.omc_heston_paths_from_normals_f32(
+                self.handle, S.ptr, 2 * P, 2 * P, N, S0, r, T, v0, kappa, theta, xi, rho, z1.ptr, z2.ptr,
+                P, scheme)
+        finally:
+            z1.free()
+            z2.free()
+        if rc != 0:
+            S.free()
+        _check(self.lib, rc)  # ValueError for a refusal (-5: rho outside [-1, 1]; scheme 3 with v0 < 0)
         return S
 
     # -- backward induction on a device path matrix

@@ -73,6 +73,9 @@ int omc_heston_paths_from_normals_f32(omc_ctx* c, float* S, int64_t ld, int64_t 
     int rc;
     if ((rc = bind_in(c))) return rc;
     if (!(S0 > 0) || !(T > 0)) return fail(-1, "S0, K, T must be positive.");
+    // (a stored variance state is a start state, so schemes 0, 1 and 2 take a negative v0 as it is; QE's moments of the next
+    // variance need v0 >= 0: the float comparisons let NaN fail)
+    if (!(rho >= -1.0 && rho <= 1.0) || (scheme == 3 && !(v0 >= 0))) return fail(-5, "invalid Heston parameters.");
     if ((rc = check_sizes(n_paths, n_steps))) return rc;
     if ((rc = check_matrix(S, ld, n_paths))) return rc;
     if (!Z1 || !Z2) return fail(-7, "null normals pointer.");

@@ -61,10 +61,11 @@ STRIKE_COUNTS = [1, 3, 61]
 SURFACE_M = 4098                 # padded_ld(4098) = 4160: a chunk must stop at M, not at the row's stride
 
 
-def _params(model, scheme, is_put, M, N, stream, antithetic=True, pair_offset=OFFSET, seed=SEED):
+def _params(model, scheme, is_put, M, N, stream, antithetic=True, pair_offset=OFFSET, seed=SEED, law=None):
+    """(law: a Heston law in place of HES -- tests/test_gpu_heston_qe_consumers.py passes the laws of the QE scheme)"""
     return _ffi.make_params(model=model, heston_scheme=scheme, is_put=is_put, semantics="two_pass", antithetic=antithetic,
                             n_paths=M, n_steps=N, S0=S0, K=K, r=R, sigma=SIG, T=T, seed=seed, stream=stream,
-                            pair_offset=pair_offset, **HES)
+                            pair_offset=pair_offset, **(law or HES))
 
 
 def _matrix(ctx, p):
@@ -176,16 +177,16 @@ def _check_barrier(ctx, p, V, kind, H, monitoring, ref, what):
     return eu
 
 
-def _barrier_shape(ctx, model, scheme, monitoring, M, N, stream=13):
+def _barrier_shape(ctx, model, scheme, monitoring, M, N, stream=13, law=None, levels=(H_DOWN, H_UP)):
     df = math.exp(-R * T)
-    V = _matrix(ctx, _params(model, scheme, True, M, N, stream))
+    V = _matrix(ctx, _params(model, scheme, True, M, N, stream, law=law))
     seen = []
-    for direction, H in (("down", H_DOWN), ("up", H_UP)):
-        hit = _hit_set(ctx, _params(model, scheme, True, M, N, stream), V, direction, H, monitoring)
+    for direction, H in (("down", levels[0]), ("up", levels[1])):
+        hit = _hit_set(ctx, _params(model, scheme, True, M, N, stream, law=law), V, direction, H, monitoring)
         seen.append(int(hit.sum()))
         for is_put in (True, False):
             ref = er.barrier_sums(V[-1], hit, K, df, is_put)
-            p = _params(model, scheme, is_put, M, N, stream)
+            p = _params(model, scheme, is_put, M, N, stream, law=law)
             for kind in (direction + "-and-out", direction + "-and-in"):
                 _check_barrier(ctx, p, V, kind, H, monitoring, ref, (model, scheme, monitoring, M, N, kind, is_put))
     return seen
@@ -286,8 +287,9 @@ def _check_quotes(prices, errs, strikes, row, df, is_put, what):
     return True
 
 
-def _row(ctx, M, N, Texp, scheme, stream, seed=SEED):
-    S = ctx.heston_paths(M, N, S0, R, Texp, HES["v0"], HES["kappa"], HES["theta"], HES["xi"], HES["rho"], seed, stream, 0,
+def _row(ctx, M, N, Texp, scheme, stream, seed=SEED, law=None):
+    h = law or HES
+    S = ctx.heston_paths(M, N, S0, R, Texp, h["v0"], h["kappa"], h["theta"], h["xi"], h["rho"], seed, stream, 0,
                          scheme=scheme)
     out = S.to_host()[-1].copy()
     S.free()

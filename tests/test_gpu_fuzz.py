@@ -26,6 +26,7 @@ paths they are there for whatever the seed, asserted at import and, without a GP
 OMC_FUZZ_SCALE multiplies every sweep's case count and OMC_FUZZ_SEED shifts its seed: soak runs (profiles/r05_fuzz_soak.txt:
 what they found -- exact ties, ill-conditioned fits, units on their ReLU kink, an ill-conditioned recurrence -- and how
 the tests tell such an undecidable comparison from a failure)."""
+import math
 import os
 
 import numpy as np
@@ -614,6 +615,64 @@ def test_quote_surface_equals_its_per_expiry_calls(ctx, case):
         assert np.array_equal(got[m], one) and np.array_equal(err[m], one_err), e
 
 
+# The QE scheme (heston_scheme 3) has lists of its own, appended: widening rng.integers(0, 3) above would redraw every
+# existing case.  The C oracle's heston_step knows no scheme 3, so the strike prices are compared with the device's STORED
+# generator's last row (same stream; the register-only kernel runs the same step on the same normals) under
+# european_ref's bounds, which leave room for the order of a float64 sum only.
+def _qe_cases(n, seed):
+    from helpers import heston_qe_cases as qc
+    return qc.fuzz_laws(n, seed)
+
+
+def _qe_id(c):
+    return f"qe-{c['M']}x{c['N']}-{'feller' if 2.0 * c['kappa'] * c['theta'] >= c['xi'] ** 2 else 'beyond'}"
+
+
+def _qe_law(c):
+    return (c["v0"], c["kappa"], c["theta"], c["xi"], c["rho"])
+
+
+@pytest.mark.parametrize("case", _qe_cases(6 * _SCALE, 20270101 + _SHIFT), ids=_qe_id)
+def test_qe_strike_prices_are_the_payoff_means_of_the_stored_last_row(ctx, case):
+    from fractions import Fraction
+
+    from helpers import european_ref as er
+    c = case
+    M, N, df = c["M"], c["N"], math.exp(-c["r"] * c["T"])
+    Sd = ctx.heston_paths(M, N, c["S0"], c["r"], c["T"], *_qe_law(c), c["seed"], c["stream"], 0, scheme=3)
+    row = Sd.to_host()[-1].copy()
+    Sd.free()
+    assert np.isfinite(row).all() and row.min() > 0.0
+    K = np.sort(np.random.default_rng(c["seed"]).uniform(0.5 * c["S0"], 1.5 * c["S0"], c["nk"]))
+    K[0] = float(row[row.size // 3])  # a payoff of exactly 0 on the p > 0 edge
+    prices, errs = ctx.heston_price_strikes(M, N, c["S0"], c["r"], c["T"], *_qe_law(c), K, is_put=c["is_put"], seed=c["seed"],
+                                            stream=c["stream"], scheme=3)
+    for k, price, err in zip(K, prices, errs):
+        ref = er.sums(row, float(k), df, c["is_put"], False)
+        er.sums_close(Fraction(float(price)) / Fraction(df), Fraction(ref["sum"]) / M, Fraction(ref["sum_abs"]) / M, M)
+        er.se_close(float(err), ref["sum"], ref["sumsq"], M, scale=df)
+
+
+@pytest.mark.parametrize("case", _qe_cases(6 * _SCALE, 20270202 + _SHIFT), ids=_qe_id)
+def test_qe_quote_surface_equals_its_per_expiry_calls(ctx, case):
+    c = case
+    rng = np.random.default_rng(c["seed"])
+    T = np.sort(rng.uniform(0.05, 2.0, c["n_exp"]))
+    quotes = [(e, k) for e in range(c["n_exp"]) for k in rng.uniform(0.5 * c["S0"], 1.5 * c["S0"], rng.integers(1, c["nk"] + 1))]
+    order = rng.permutation(len(quotes))
+    eo = np.array([quotes[i][0] for i in order], np.int32)
+    K = np.array([quotes[i][1] for i in order])
+    M, streams = c["M"], c["stream"] + np.arange(c["n_exp"])
+    got, err = ctx.heston_price_surface(M, c["N"], c["S0"], c["r"], *_qe_law(c), T, streams, K, eo, is_put=c["is_put"],
+                                        seed=c["seed"], scheme=3)
+    assert np.isfinite(got).all() and np.isfinite(err).all() and got.max() > 0.0
+    for e in range(c["n_exp"]):
+        m = eo == e
+        one, one_err = ctx.heston_price_strikes(M, c["N"], c["S0"], c["r"], float(T[e]), *_qe_law(c), K[m], is_put=c["is_put"],
+                                                seed=c["seed"], stream=int(streams[e]), scheme=3)
+        assert np.array_equal(got[m], one) and np.array_equal(err[m], one_err), e
+
+
 def _localvol_cases(n, seed):
     rng = np.random.default_rng(seed)
     out = []
@@ -803,6 +862,37 @@ def test_greeks_sweep_excused_few_cases():
     """The tie rule must not hide failures: at most one case in eight may go without its value comparison."""
     print(f"greeks sweep: {len(_GREEKS_EXCUSED)} of {len(_GREEKS_CASES)} cases excused by ties: {_GREEKS_EXCUSED}")
     assert 8 * len(_GREEKS_EXCUSED) <= len(_GREEKS_CASES), _GREEKS_EXCUSED
+
+
+_QE_GREEKS_CASES = _qe_cases(6 * _SCALE, 20270303 + _SHIFT)
+_QE_GREEKS_EXCUSED = []
+
+
+@pytest.mark.parametrize("case", _QE_GREEKS_CASES, ids=lambda c: _qe_id(dict(c, M=c["M_greeks"])))
+def test_qe_greeks_match_the_numpy_restatement(ctx, case):
+    """the sweep above at heston_scheme 3, on a list of its own: random QE laws (every third beyond Feller's condition)
+    against greeks_ref on the matrix the device stores"""
+    from helpers import greeks_check as gc
+    from helpers import greeks_ref as gr
+    from options_model_amd import _ffi
+    c = case
+    v0, kappa, theta, xi, rho = _qe_law(c)
+    p = _ffi.make_params(model="heston", heston_scheme=3, semantics="two_pass", is_put=c["is_put"], n_paths=c["M_greeks"],
+                         n_steps=c["N"], S0=c["S0"], K=c["K"], r=c["r"], sigma=0.0, T=c["T"], seed=c["seed"], stream=c["stream"],
+                         pair_offset=c["pair_offset"], v0=v0, kappa=kappa, theta=theta, xi=xi, rho=rho)
+    d = ctx.price_american_greeks(p, bump=c["bump"], want_betas=True)
+    Sd = gc.stored(ctx, p)
+    S = Sd.to_host()
+    Sd.free()
+    assert d["folded"] == 0 and d["n_paths"] == c["M_greeks"]
+    ref = gr.greeks(S, p.K, p.r, p.T, c["is_put"], d["betas"], p.S0, 0.0, h=c["bump"], gbm=False)
+    print(f"greeks {_qe_id(c)}: ties {ref['ties']} counts {d['n_exercised']}/{d['n_exercised_up']}/{d['n_exercised_down']}")
+    if not gc.agrees(d, ref, p):
+        _QE_GREEKS_EXCUSED.append(_qe_id(c))
+
+
+def test_qe_greeks_sweep_excused_few_cases():
+    assert 8 * len(_QE_GREEKS_EXCUSED) <= len(_QE_GREEKS_CASES), _QE_GREEKS_EXCUSED
 
 
 # ---------------------------------------------------------------------------------------------- 14: the bounds sweep

@@ -15,6 +15,7 @@ empty -- and 9 steps, which end inside a Philox block for GBM (4 steps per block
 import numpy as np
 import pytest
 
+from helpers.heston_qe_ref import SET_B
 from options_model_amd import _ffi
 from test_gpu_dividends import KEYS, at_steps, bits, params
 
@@ -26,8 +27,8 @@ JUMP = (4.0, -0.1, 0.15)
 EURO = ("euro_out", "euro_out_se", "euro_in", "euro_in_se", "hit_prob")
 
 
-def _params(model="gbm", scheme=0):
-    return params(model, scheme, M=M, N=N, seed=11, stream=5, pair_offset=321)
+def _params(model="gbm", scheme=0, **law):
+    return params(model, scheme, M=M, N=N, seed=11, stream=5, pair_offset=321, **law)
 
 
 def _dividends(ctx, p, keep, akeep):
@@ -50,19 +51,22 @@ def _barrier(ctx, p, keep, akeep):
     return ctx.price_barrier(p, "down-and-out", 80.0, monitoring="discrete", american=True, keep_paths=keep)
 
 
-# name -> (the call, model, Heston scheme, the width option, asset matrices kept)
+# name -> (the call, model, Heston scheme, the width option, asset matrices kept[, a Heston law of its own])
 CASES = {"dividends-gbm": (_dividends, "gbm", 0, "gbm_vec", 0),
          "dividends-heston2": (_dividends, "heston", 2, "heston_vec", 0),
          "jumps-gbm": (_jumps, "gbm", 0, "gbm_vec", 0),
          "jumps-heston0": (_jumps, "heston", 0, "heston_vec", 0),
          "basket": (_basket, "gbm", 0, "gbm_vec", 2),
-         "barrier": (_barrier, "gbm", 0, "gbm_vec", 0)}
+         "barrier": (_barrier, "gbm", 0, "gbm_vec", 0),
+         # the QE scheme at the law whose waves mix its two branches (tests/helpers/heston_qe_ref.py, set B)
+         "dividends-heston3": (_dividends, "heston", 3, "heston_vec", 0, SET_B),
+         "jumps-heston3": (_jumps, "heston", 3, "heston_vec", 0, SET_B)}
 
 
 def run(ctx, name, pad=0):
     """-> (result dict, the matrices as the call left them, padding columns included: [index or spot matrix, assets])"""
-    call, model, scheme, _, d = CASES[name]
-    p = _params(model, scheme)
+    call, model, scheme, _, d, *law = CASES[name]
+    p = _params(model, scheme, **(law[0] if law else {}))
     keep = ctx.to_device(np.full((N + 1, M + pad), SENTINEL, np.float32))
     akeep = ctx.to_device(np.full((d, N + 1, M + pad), SENTINEL, np.float32)) if d else None
     try:
@@ -97,7 +101,8 @@ def same_pricing(out, ref_out, what):
     assert out["price"] == pytest.approx(ref_out["price"], rel=1e-12, abs=0.0), what
 
 
-@pytest.mark.parametrize("name", ["dividends-gbm", "dividends-heston2", "jumps-gbm", "jumps-heston0", "basket"])
+@pytest.mark.parametrize("name", ["dividends-gbm", "dividends-heston2", "jumps-gbm", "jumps-heston0", "basket",
+                                  "dividends-heston3", "jumps-heston3"])
 def test_width_hint_selects_nothing_but_speed(ctx, name):
     ref_out, ref = aligned(ctx, name)
     option = CASES[name][3]
@@ -113,7 +118,7 @@ def test_width_hint_selects_nothing_but_speed(ctx, name):
 
 
 @pytest.mark.parametrize("pad", [2, 1])
-@pytest.mark.parametrize("name", ["dividends-gbm", "jumps-gbm", "basket"])
+@pytest.mark.parametrize("name", ["dividends-gbm", "jumps-gbm", "basket", "dividends-heston3", "jumps-heston3"])
 def test_padded_leading_dimension_gives_the_aligned_columns(ctx, name, pad):
     ref_out, ref = aligned(ctx, name)
     out, mats = run(ctx, name, pad=pad)

@@ -11,6 +11,7 @@ What is compared, and how tightly:
   * barrier / dividend / jump          an untouched barrier, a zero dividend, zero jumps: the vanilla matrix bit for bit
   * the American price, the Greeks     the C oracle's two-pass flow on the device's matrix: counts equal, price 1e-9
   * known answers                      Andersen's Case I at quarter-year steps against the semi-analytic price
+The consumers with work to do (a barrier that is met, real dividends and jumps): tests/test_gpu_heston_qe_consumers.py.
 """
 import ctypes as C
 import math
