@@ -517,6 +517,14 @@ int omc_price_american_jump(omc_ctx* ctx, const omc_params* p, const omc_jump* j
  *   OMC_BASKET_GEOMETRIC   a state of its own: g_0 = (float)prod_i S0[i]^w[i] (float64 product, i ascending), and per step
  *                          g *= exp2(E), E = wf_0 e_0, then E = fmaf(wf_k, e_k, E) (the partner from its own e'_k).
  *   Row 0 holds the index of the initial spots by the same rule (geometric: g_0).
+ *   OMC_BASKET_ASIAN_ARITHMETIC / _GEOMETRIC: the running average of the BASKET VALUE over the grid
+ *     dates 1 .. t (S_0 is not in it) -- a fixed-strike average-price option with early exercise; with d = 1 and w = 1 the
+ *     basket value is the spot, the plain Asian option.  B_t = the value of step t by OMC_BASKET_ARITHMETIC's rule exactly
+ *     (wf_0 s_0, then fmaf(wf_k, s_k, B), k ascending); inv_t = 1.0f / (float)t, an IEEE correctly rounded float32 division.
+ *       _ARITHMETIC  c_0 = 0, c_t = c_{t-1} + B_t (ONE float32 add, not contracted with the product of B), X_t = c_t * inv_t;
+ *       _GEOMETRIC   l_0 = 0, l_t = l_{t-1} + log2(B_t) (the hardware log2, v_log_f32), X_t = exp2(l_t * inv_t) (v_exp_f32);
+ *     X_0 = B_0 for both.  The partner of a pair keeps its own c or l.  The arithmetic rule can be restated bit for bit in
+ *     float32 from the asset matrices; the geometric one is compared by tolerance (4.5e-6 relative at 252 dates).
  * Storage: the index goes to the context's full-storage matrix or to S_keep ([n_steps+1][ld], ld >= n_paths); with
  *   assets_keep the per-asset matrices go to that buffer, [d][n_steps+1][ld] (the same ld; without S_keep, ld as passed).
  *   Columns p and p + n_paths / 2 are the partners, as everywhere else.
@@ -528,12 +536,14 @@ int omc_price_american_jump(omc_ctx* ctx, const omc_params* p, const omc_jump* j
  *   (DESIGN.md section 12): these prices are not comparable with literature tables of textbook LSM.
  * omc_basket_table: host only (no context, no device work): the argument checks of omc_price_american_basket and the
  *   constants -- L_packed [d (d+1) / 2] (row i at i (i+1) / 2, float64), a, b [d], x0 (the index of the initial spots in
- *   float64: sum w_i S0_i, max / min of w_i S0_i, or G_0), geo [3] = G_0, sigma_G, q_G; any output may be NULL.
+ *   float64: sum w_i S0_i, max / min of w_i S0_i, or G_0; the Asian kinds: sum w_i S0_i), geo [3] = G_0, sigma_G, q_G (for
+ *   every kind those of OMC_BASKET_GEOMETRIC); any output may be NULL.
  * Errors (nothing is launched): -7 null ctx / params / out; -12 p->model not GBM; -29 basket NULL or n_assets outside
  * 1 .. 8; -30 a bad per-asset field; -32 unknown kind; -31 rho refused; then the omc_params checks as omc_price_american
  * (on the copy); -24 p->antithetic = 0; -11 p->semantics != OMC_SEM_TWO_PASS; -33 pair_offset + n_paths / 2 > 2^40;
  * -10 a distributed context (one GPU); -6 ld < n_paths (S_keep or assets_keep given). */
-enum { OMC_BASKET_ARITHMETIC = 0, OMC_BASKET_GEOMETRIC = 1, OMC_BASKET_BEST_OF = 2, OMC_BASKET_WORST_OF = 3 };
+enum { OMC_BASKET_ARITHMETIC = 0, OMC_BASKET_GEOMETRIC = 1, OMC_BASKET_BEST_OF = 2, OMC_BASKET_WORST_OF = 3,
+       OMC_BASKET_ASIAN_ARITHMETIC = 5, OMC_BASKET_ASIAN_GEOMETRIC = 6 }; /* 4 is not a kind: it stays refused (-32) */
 #define OMC_BASKET_MAX_ASSETS 8
 typedef struct {
     int32_t n_assets, kind;                 /* d in 1 .. 8; OMC_BASKET_*                                       */
@@ -554,7 +564,8 @@ int omc_price_american_basket(omc_ctx* ctx, const omc_params* p, const omc_baske
 /* ---- frozen-policy pathwise Greeks of the multi-asset options ------------------------------ */
 /* omc_price_american_greeks for omc_price_american_basket: per-asset delta, diagonal gamma and vega, and rho and theta of
  * the option, with the exercise policy FROZEN.  Scope as omc_price_american_basket (its checks run unchanged): GBM assets,
- * two-pass flow, antithetic pairs, one GPU, full storage, d = 1 .. 8, all four kinds.
+ * two-pass flow, antithetic pairs, one GPU, full storage, d = 1 .. 8, kinds 0 .. 3.  The Asian kinds are refused: the
+ * sweep regenerates the asset spots and would need the running state beside them.
  * Policy: the [1, u, u^2] fits pass 1 makes on the index matrix at p's and b's parameters, or `betas` (host
  *   [n_steps+1][4] = b0, b1, b2, n; n <= 0: no exercise at that step; an all-zero table gives European Greeks).  With
  *   `betas` the generator and pass 1 are skipped, no matrix is written and base.base.sum_nitm = 0.  betas_out (NULL or host
@@ -591,7 +602,8 @@ int omc_price_american_basket(omc_ctx* ctx, const omc_params* p, const omc_baske
  *   ms_pass2 = 0: the sweep replaces pass 2.  Entries of the per-asset arrays at or above d are 0.
  * Out of scope: cross-gammas, correlation and yield sensitivities, Heston or jump assets, the runner-up policy.
  * Errors (nothing is launched): omc_price_american_basket's own, in its order (-7 null ctx / out / params, -12, -29 .. -32,
- * the omc_params checks, -24, -11, -33); -4 bump outside (0, 0.5]; -10 a distributed context (one GPU). */
+ * the omc_params checks, -24, -11, -33); then -32 kind OMC_BASKET_ASIAN_ARITHMETIC / _GEOMETRIC; -4 bump outside (0, 0.5];
+ * -10 a distributed context (one GPU). */
 typedef struct {
     omc_basket_result base;
     double delta[8], gamma[8], vega[8];        /* raw units: per unit S0_i / S0_i^2 / sigma_i                         */
@@ -695,6 +707,12 @@ int omc_price_american_bounds(omc_ctx* ctx, const omc_params* p, const omc_bound
  *   omc_price_american_bounds for (S0[0], sigma[0]); with d = 1 and a yield q[0] these are the bounds of a single asset
  *   with a continuous dividend yield.  A geometric index is one GBM: price it with d = 1 from (G0, sigma_G, q_G) of
  *   omc_basket_table and w = 1 (kind OMC_BASKET_GEOMETRIC is refused here).
+ * The Asian kinds: X is the running average, and the Markov state of a path is its asset spots AND
+ *   its running state c_t (l_t).  The outer generator stores that state in a matrix of its own, [N+1][n_outer] beside the
+ *   outer asset matrices (row 0 = 0); the inner pairs of item (i, t) start at (A_k[t][i], c_t[i]) and inner step n forms
+ *   X_{t+n} by the rule of step t + n: c += B, X = c * (1.0f / (float)(t + n)).  The state is the stored one, never X_t t.
+ *   The inner index spots of the arithmetic kind are bit for bit the rule continued in float32 from c_t[i] over the basket
+ *   values of the restart call above (kind OMC_BASKET_ARITHMETIC at S0[k] = A_k[t][i]).  The policy sees the average alone.
  * Errors (nothing is launched): -7 null cfg / out; omc_price_american_basket's own (-7, -12, -29 .. -33, the omc_params
  * checks, -24, -11); -34 kind OMC_BASKET_GEOMETRIC; -10 a distributed context; then -4, -7 (betas NULL with
  * OMC_POLICY_GIVEN), -3 and -16 as omc_price_american_bounds. */
@@ -737,6 +755,11 @@ int omc_price_american_basket_bounds(omc_ctx* ctx, const omc_params* p, const om
  * Errors (nothing is launched): omc_price_american_basket_bounds' own, and -35 kind OMC_BASKET_ARITHMETIC or one asset
  * (OMC_BASKET_GEOMETRIC keeps -34); -4 also for OMC_SEM_REFERENCE and OMC_SEM_TWO_PASS; -16 also for more than 512 dates
  * (the kernels keep the policy rows, 64 bytes per date, in LDS; omc_price_american_basket_bounds has no such cap).
+ * The Asian kinds, any d in 1 .. 8: the second regressor is the current basket value, Y = B_t, where
+ *   best-of and worst-of use the runner-up: the Markov state of the option is (average, spot), and the average alone leaves
+ *   the lower bound percent short.  The same table, the same rule on (u, w) with w = fma((double)B, 1/K, -1), the same fit,
+ *   solve, truncation rule and 512-date cap; paths, running state and inner starts as omc_price_american_basket_bounds has
+ *   them for these kinds.  -35 does not apply to them.
  * Memory: the fit keeps the asset matrices of its paths, n_assets (N+1) n_paths floats on the device; a request the card
  * cannot hold fails as a HIP allocation error (a positive code), as for every workspace of the library. */
 int omc_price_american_basket_bounds_runnerup(omc_ctx* ctx, const omc_params* p, const omc_basket* b,

@@ -22,7 +22,7 @@ def __getattr__(name):
                 "ChainResult", "price_american_dividends", "DividendResult", "price_american_jumps", "JumpResult",
                 "price_american_basket", "BasketResult", "price_american_basket_bounds", "BasketBoundsResult",
                 "price_american_basket_greeks", "BasketGreeksResult", "price_american_bounds_heston",
-                "HestonBoundsResult"):
+                "HestonBoundsResult", "price_asian_option"):
         from . import api
         return getattr(api, name)
     if name in ("AdvancedOptionPricer", "RNGManager", "BlackScholesGreeks", "welford_batch_update",

@@ -22,10 +22,12 @@ MONITORING = {"discrete": 0, "continuous": 1}
 DIVIDEND_KINDS = {"proportional": 0, "cash": 1}
 # argument errors of the dividend entry points (include/omc.h): raised as DividendError
 DIVIDEND_ERRORS = range(-24, -16)
-BASKET_KINDS = {"basket": 0, "arithmetic": 0, "geometric": 1, "best-of": 2, "worst-of": 3}
+BASKET_KINDS = {"basket": 0, "arithmetic": 0, "geometric": 1, "best-of": 2, "worst-of": 3, "asian": 5,
+                "asian-geometric": 6}
 BASKET_MAX_ASSETS = 8
 BOUND_POLICIES = {"reference": 0, "textbook": 1, "two_pass": 2, "given": 3}
-BOUND_REGRESSORS = ("index", "index+runner-up")  # what the policy of the multi-asset bounds sees
+BOUND_REGRESSORS = ("index", "index+runner-up", "index+spot")  # what the policy of the multi-asset bounds sees
+ASIAN_KINDS = (5, 6)  # the running-average kinds: "index+spot" is theirs, "index+runner-up" best-of's and worst-of's
 HESTON_BOUND_REGRESSORS = ("spot", "spot+variance")  # ... of the Heston bounds: the codes of omc_bounds_config.regressors
 HESTON_SV_MAX_STEPS = 512  # dates of a spot+variance policy (its rows live in LDS)
 
@@ -38,7 +40,11 @@ def check_runnerup(regressors, policy, kind, n_assets):
     if regressors == "index":
         return
     if BOUND_POLICIES.get(policy, policy) not in (BOUND_POLICIES["textbook"], BOUND_POLICIES["given"]):
-        raise ValueError("regressors='index+runner-up' takes policy 'textbook' or 'given'.")
+        raise ValueError(f"regressors='{regressors}' takes policy 'textbook' or 'given'.")
+    if regressors == "index+spot":  # the average and the current basket value
+        if BASKET_KINDS.get(kind, kind) not in ASIAN_KINDS:
+            raise ValueError("regressors='index+spot' is for kind 'asian' or 'asian-geometric'.")
+        return
     if BASKET_KINDS.get(kind, kind) not in (BASKET_KINDS["best-of"], BASKET_KINDS["worst-of"]):
         raise ValueError("regressors='index+runner-up' is for kind 'best-of' or 'worst-of'.")
     if int(n_assets) < 2:
@@ -973,10 +979,11 @@ class Context:
         index alone.  Streams default to params.stream + 1 / 2 / 3.
         regressors="index+runner-up" (omc_price_american_basket_bounds_runnerup; best-of and worst-of on 2 .. 8 assets,
         policy "textbook" or "given"): the policy sees the index and the second order statistic of the weighted spots, and
-        `betas` (given and returned) is [n_steps+1][8] = c0 .. c5, n, 0."""
+        `betas` (given and returned) is [n_steps+1][8] = c0 .. c5, n, 0.  regressors="index+spot": the same entry point for
+        the Asian kinds, whose second regressor is the current basket value."""
         check_runnerup(regressors, policy, int(basket.kind), int(basket.n_assets))
         return self._bounds(params, basket, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner,
-                            betas, want_q, want_samples, 8 if regressors == "index+runner-up" else 4)
+                            betas, want_q, want_samples, 4 if regressors == "index" else 8)
 
     def _bounds(self, params, basket, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner, betas,
                 want_q, want_samples, cols=4, heston=False, regressors=0):

@@ -583,7 +583,7 @@ class BasketResult:
         return float(self.price)
 
 
-_BASKET_KINDS = ("basket", "geometric", "best-of", "worst-of")
+_BASKET_KINDS = ("basket", "geometric", "best-of", "worst-of", "asian", "asian-geometric")
 
 
 def _basket_args(spots, sigmas, weights, dividend_yields, correlation, kind):
@@ -600,7 +600,7 @@ def _basket_args(spots, sigmas, weights, dividend_yields, correlation, kind):
         raise ValueError(f"a basket has 1 .. {_ffi.BASKET_MAX_ASSETS} assets.")
     if len(sig) != d:
         raise ValueError("sigmas must have one entry per asset.")
-    w = [1.0 / d if kind in ("basket", "geometric") else 1.0] * d if weights is None else [float(x) for x in weights]
+    w = [1.0 / d if kind in ("basket", "geometric", "asian", "asian-geometric") else 1.0] * d if weights is None else [float(x) for x in weights]
     q = [0.0] * d if dividend_yields is None else [float(x) for x in dividend_yields]
     if len(w) != d or len(q) != d:
         raise ValueError("weights and dividend_yields must have one entry per asset.")
@@ -627,6 +627,9 @@ def price_american_basket(spots, K, r, sigmas, T, n_paths, n_steps, correlation=
     regression is on the index, so the exercise policy is a function of the index alone: the usual dominant regressor for
     baskets, a deliberately simple policy for best-of / worst-of.  correlation: [d][d], default identity; weights: default
     1 / d for "basket" and "geometric", 1 for "best-of" and "worst-of"; dividend_yields: default 0; seed: default 42.
+    kind "asian" / "asian-geometric" (DESIGN.md section 23): the index is the running arithmetic / geometric average over
+    the grid dates 1 .. t of the basket value sum w_i S_i -- a fixed-strike average-price option with early exercise; with
+    one asset of weight 1 the plain Asian option (price_asian_option).
     The flow is the reference's two-pass rule: not comparable with tables of textbook LSM.
     Antithetic paths, one GPU."""
     S0, sig, q, w, rho = _basket_args(spots, sigmas, weights, dividend_yields, correlation, kind)
@@ -874,7 +877,11 @@ def price_american_basket_bounds(spots, K, r, sigmas, T, n_paths, n_steps, corre
     regressors="index+runner-up" (DESIGN.md section 18): for kind "best-of" / "worst-of" on 2 .. 8 assets the policy also
     sees the runner-up, the second largest (smallest) weighted spot -- on the two-asset max-call benchmark that closes nine
     tenths of the gap between the index policy's lower bound and the lattice value.  policy is then "textbook" or "given",
-    and `betas` is [n_steps+1][8] = c0, c1, c2 (1, u, u^2 of the index), c3, c4 (w, w^2 of the runner-up), c5 (u w), n, 0."""
+    and `betas` is [n_steps+1][8] = c0, c1, c2 (1, u, u^2 of the index), c3, c4 (w, w^2 of the runner-up), c5 (u w), n, 0.
+    kind "asian" / "asian-geometric" (DESIGN.md section 23): the index is the running average; the inner paths start at the
+    outer path's asset spots and running sum.  regressors="index+spot" is theirs alone: the policy also sees the current
+    basket value, the other half of the Markov state (average, spot), with the table and the policies of
+    "index+runner-up"; at most 512 steps."""
     if policy not in _ffi.BOUND_POLICIES:
         raise ValueError(f"policy must be one of {sorted(_ffi.BOUND_POLICIES)}.")
     if (policy == "given") != (betas is not None):
@@ -884,6 +891,8 @@ def price_american_basket_bounds(spots, K, r, sigmas, T, n_paths, n_steps, corre
             raise ValueError(f"{name} must be an even integer >= 2 (antithetic pairs).")
     S0, sig, q, w, rho = _basket_args(spots, sigmas, weights, dividend_yields, correlation, kind)
     _ffi.check_runnerup(regressors, policy, kind, len(S0))
+    if regressors == "index+spot" and int(n_steps) > _ffi.HESTON_SV_MAX_STEPS:
+        raise ValueError(f"regressors='index+spot' takes at most {_ffi.HESTON_SV_MAX_STEPS} steps.")
     _validate(S0[0], K, T, r, sig[0], n_paths, n_steps, option_type)
     M = int(n_paths) // 2 * 2
     if M <= 0:
@@ -905,6 +914,28 @@ def price_american_basket_bounds(spots, K, r, sigmas, T, n_paths, n_steps, corre
                               timings_ms=dict(fit=out["ms_fit"], lower=out["ms_lower"], upper=out["ms_upper"],
                                               total=out["ms_total"]),
                               index0=out["index0"], n_assets=out["n_assets"], kind=kind, regressors=regressors)
+
+
+_ASIAN_AVERAGING = {"arithmetic": "asian", "geometric": "asian-geometric"}
+
+
+def price_asian_option(S0, K, r, sigma, T, n_paths, n_steps, option_type="put", averaging="arithmetic", dividend_yield=0.0,
+                       bounds=False, seed=None, device=None, **bounds_args):
+    """Fixed-strike average-price (Asian) option with early exercise on one GBM stock: the one-asset
+    call of price_american_basket with kind "asian" (averaging="arithmetic") or "asian-geometric" ("geometric") and weight
+    1.  The average runs over the grid dates 1 .. t; S0 is not in it.  bounds=False -> BasketResult, the two-pass price.
+    bounds=True -> BasketBoundsResult of price_american_basket_bounds, which takes the further keywords (policy, n_lower,
+    n_outer, n_inner, stream, betas, ctx, regressors="index" | "index+spot")."""
+    if averaging not in _ASIAN_AVERAGING:
+        raise ValueError(f"averaging must be one of {list(_ASIAN_AVERAGING)}.")
+    kind = _ASIAN_AVERAGING[averaging]
+    common = dict(weights=[1.0], dividend_yields=[float(dividend_yield)], kind=kind, option_type=option_type, device=device)
+    if not bounds:
+        if bounds_args:
+            raise ValueError(f"{sorted(bounds_args)} are arguments of the bounds (bounds=True).")
+        return price_american_basket([S0], K, r, [sigma], T, n_paths, n_steps, seed=seed, **common)
+    return price_american_basket_bounds([S0], K, r, [sigma], T, n_paths, n_steps, seed=42 if seed is None else seed,
+                                        **common, **bounds_args)
 
 
 _job = {}

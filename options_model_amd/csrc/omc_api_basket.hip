@@ -1,5 +1,6 @@
 // omc_api_basket.hip -- American options on several correlated GBM assets (include/omc.h):
-// arithmetic and geometric baskets, best-of and worst-of.  The basket generator (omc_basket.hip) simulates the assets in
+// arithmetic and geometric baskets, best-of and worst-of, and the running averages of the basket value (the Asian kinds,
+// section 23).  The basket generator (omc_basket.hip) simulates the assets in
 // registers and writes the full-storage matrix of the INDEX; the unchanged two-pass flow (enqueue_lsm) prices it, so the
 // exercise policy is a function of the index alone.
 #include <algorithm>
@@ -26,7 +27,10 @@ int compose_basket(const omc_params* p, const omc_basket* k, BasketTable* t)
         if (!std::isfinite(k->q[i])) return fail(-30, "every asset's dividend yield must be finite.");
         if (!(std::isfinite(k->w[i]) && k->w[i] > 0.0)) return fail(-30, "every asset's weight must be finite and positive.");
     }
-    if (k->kind < OMC_BASKET_ARITHMETIC || k->kind > OMC_BASKET_WORST_OF) return fail(-32, "unknown basket kind.");
+    // (the value 4 between the two families was never a kind and callers were promised -32 for it: it stays refused)
+    if (k->kind < OMC_BASKET_ARITHMETIC || k->kind > OMC_BASKET_ASIAN_GEOMETRIC ||
+        (k->kind > OMC_BASKET_WORST_OF && !omc::basket_kind_is_asian(k->kind)))
+        return fail(-32, "unknown basket kind.");
     const double* rho = k->rho;
     for (int i = 0; i < d; ++i) {
         for (int j = 0; j < d; ++j) {
@@ -64,7 +68,9 @@ int compose_basket(const omc_params* p, const omc_basket* k, BasketTable* t)
     t->G0 = G0;
     t->sigma_G = std::sqrt(var);
     t->q_G = p->r - drift - var / 2.0;
-    t->x0 = k->kind == OMC_BASKET_ARITHMETIC ? arith : k->kind == OMC_BASKET_GEOMETRIC ? G0 : k->kind == OMC_BASKET_BEST_OF ? best : worst;
+    // (the running averages start at the basket value: X_0 = B_0)
+    t->x0 = k->kind == OMC_BASKET_ARITHMETIC || omc::basket_kind_is_asian(k->kind) ? arith
+            : k->kind == OMC_BASKET_GEOMETRIC ? G0 : k->kind == OMC_BASKET_BEST_OF ? best : worst;
     if (!(std::isfinite(t->x0) && t->x0 > 0.0 && (float)t->x0 > 0.0f && std::isfinite((float)t->x0)))
         return fail(-30, "the index of the initial spots must be a positive float32.");
     omc_params c = *p;  // the omc_params checks, with the index in the place of the single stock

@@ -19,6 +19,8 @@ extern "C" int omc_price_american_basket_greeks(omc_ctx* c, const omc_params* p,
     if (!out) return fail(-7, "null result pointer.");
     BasketTable t;
     if ((rc = compose_basket(p, bk, &t))) return rc;
+    if (omc::basket_kind_is_asian(bk->kind))  // the regenerated-asset sweep carries no running state
+        return fail(-32, "the multi-asset Greeks take no running-average (Asian) kind.");
     if (!(bump > 0.0 && bump <= 0.5)) return fail(-4, "bump must lie in (0, 0.5].");
     if (c->distributed()) return fail(-10, "the multi-asset Greeks sweep runs on one GPU.");
     const int64_t M = p->n_paths;

@@ -9,6 +9,8 @@
 #include "omc_dispatch.h"
 #include "omc_kernels.h"
 
+#include "../../include/omc.h"
+
 namespace omc {
 
 constexpr int kBasketMax = 8;                                  // assets at most
@@ -43,7 +45,12 @@ struct BasketGen {
     BasketLaw law;
     float* assets;      // device, or null: the asset matrices [d][N+1][ld_assets]
     int64_t ld_assets;
+    float* state;       // device, or null (read with `assets` only): the running state c_t / l_t of the Asian kinds,
+                        // [N+1][ld_assets], row 0 = 0 -- what an inner path of the bounds starts from
 };
+
+// the running-average kinds: an index rule with a state of its own beside the asset spots
+constexpr bool basket_kind_is_asian(int kind) { return kind == OMC_BASKET_ASIAN_ARITHMETIC || kind == OMC_BASKET_ASIAN_GEOMETRIC; }
 
 // pairs per thread an instantiation for d assets holds at most (so that none spills: DESIGN.md 16.3)
 constexpr int basket_vec_cap(int d) { return d <= 2 ? 4 : d <= 4 ? 2 : 1; }

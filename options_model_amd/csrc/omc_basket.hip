@@ -1,5 +1,5 @@
 // omc_basket.hip -- path generator of the multi-asset options: basket (arithmetic / geometric), best-of and worst-of,
-// DESIGN.md section 16.
+// DESIGN.md section 16; and the running averages of the basket value, the Asian kinds of section 23.
 //
 // basket_paths_kernel<D, VEC, KEEP> writes the full-storage matrix of the INDEX X_t of D correlated GBM assets, which the
 // unchanged two-pass LSM sweeps then price.  A lane owns VEC antithetic pairs for all steps and holds the 2 D VEC asset
@@ -14,6 +14,11 @@
 // registers, no table in memory.  D is a template parameter so that every loop over assets unrolls and every index of
 // the constants is a compile-time one; the kind is wave-uniform and switched on where the index is formed.  No
 // grid-stride loop, no LDS; every write is a VEC-wide vector store.
+//
+// The Asian kinds (include/omc.h) form the index from a running state per partner -- c += B_t, X_t = c * (1.0f / t), or
+// l += log2(B_t), X_t = exp2(l * (1.0f / t)) -- with B_t the arithmetic basket value of the step: one more register per
+// partner, no more memory traffic, the same launch shape.  The bound kernels' inner paths start from that state, so a
+// caller inside the library may have it stored beside the asset rows (BasketGen::state).
 #include "omc_basket.h"
 #include "omc_basket_dev.h"
 #include "omc_paths_dev.h"
@@ -23,13 +28,17 @@ namespace omc {
 struct BasketArgs {
     float* S;       // index matrix [N+1][ld]
     float* A;       // asset matrices [D][N+1][lda] (KEEP only)
+    float* C;       // running state of the Asian kinds [N+1][lda], or null (KEEP only)
     int64_t ld, lda, P;
     int n_steps;
     uint32_t k0, k1, stream;
     uint64_t pair_offset;
 };
 
-template <int D, int VEC, bool KEEP>
+// ASIAN: the two running-average kinds (OMC_BASKET_ASIAN_*), an instantiation of their own so that the kernels of kinds
+// 0 .. 3 keep their instruction streams.  The running state -- c_t, the float32 sum of the basket values B_1 .. B_t, or
+// l_t, the sum of their log2 -- is one more register per partner; with g.C it is stored beside the asset rows.
+template <int D, int VEC, bool KEEP, bool ASIAN = false>
 __global__ __launch_bounds__(kBlock) void basket_paths_kernel(BasketArgs g, BasketLaw c)
 {
     const int64_t P = g.P, ld = g.ld;
@@ -47,10 +56,46 @@ __global__ __launch_bounds__(kBlock) void basket_paths_kernel(BasketArgs g, Bask
     float* row = g.S + p0;
     float* arow = KEEP ? g.A + p0 : nullptr;
     const int64_t astride = KEEP ? (int64_t)(g.n_steps + 1) * g.lda : 0;  // one asset's matrix
+    [[maybe_unused]] float cs[VEC], ca[VEC];  // ASIAN: the running state of either partner
+    [[maybe_unused]] float* crow = nullptr;
+    [[maybe_unused]] int t = 0;
+    if constexpr (ASIAN) {
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) cs[v] = ca[v] = 0.0f;
+        if constexpr (KEEP) crow = g.C ? g.C + p0 : nullptr;
+    }
 
     auto store_rows = [&]() {
         float x[VEC], xa[VEC];
-        if (geo) {
+        if constexpr (ASIAN) {
+            // B_t by the arithmetic rule; row 0 is B_0 and leaves the state at 0.  inv_t is wave-uniform
+            const float inv_t = __fdiv_rn(1.0f, (float)(t > 0 ? t : 1));
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) {
+                const float B = basket_index<OMC_BASKET_ARITHMETIC, D>(c, s[v]);
+                const float Ba = basket_index<OMC_BASKET_ARITHMETIC, D>(c, sa[v]);
+                if (t == 0) {
+                    x[v] = B;
+                    xa[v] = Ba;
+                } else if (kind == OMC_BASKET_ASIAN_ARITHMETIC) {
+                    cs[v] = asian_add(cs[v], B);
+                    ca[v] = asian_add(ca[v], Ba);
+                    x[v] = cs[v] * inv_t;
+                    xa[v] = ca[v] * inv_t;
+                } else {
+                    cs[v] = cs[v] + __builtin_amdgcn_logf(B);
+                    ca[v] = ca[v] + __builtin_amdgcn_logf(Ba);
+                    x[v] = fast_exp2(cs[v] * inv_t);
+                    xa[v] = fast_exp2(ca[v] * inv_t);
+                }
+            }
+            if constexpr (KEEP) {
+                if (crow) {
+                    store_vec<VEC>(crow, cs);
+                    store_vec<VEC>(crow + P, ca);
+                }
+            }
+        } else if (geo) {
 #pragma unroll
             for (int v = 0; v < VEC; ++v) {
                 x[v] = gs[v];
@@ -95,7 +140,6 @@ __global__ __launch_bounds__(kBlock) void basket_paths_kernel(BasketArgs g, Bask
 
     const int n_steps = g.n_steps;
     const int nblk = (n_steps + 3) >> 2;
-    int t = 0;
     for (int blk = 0; blk < nblk; ++blk) {
         float y[VEC][D][4];  // the correlated normals of the block's four steps
 #pragma unroll
@@ -112,6 +156,7 @@ __global__ __launch_bounds__(kBlock) void basket_paths_kernel(BasketArgs g, Bask
             if (++t > n_steps) break;
             row += ld;
             if constexpr (KEEP) arow += g.lda;
+            if constexpr (ASIAN && KEEP) crow = crow ? crow + g.lda : nullptr;
             if (geo) {
 #pragma unroll
                 for (int v = 0; v < VEC; ++v) {
@@ -149,6 +194,11 @@ template <int D, int VEC>
 static void launch_basket(hipStream_t st, const BasketArgs& g, const BasketLaw& law, bool keep)
 {
     const dim3 block(kBlock), grid((unsigned)((g.P / VEC + kBlock - 1) / kBlock));
+    if (basket_kind_is_asian(law.kind)) {
+        if (keep) hipLaunchKernelGGL((basket_paths_kernel<D, VEC, true, true>), grid, block, 0, st, g, law);
+        else hipLaunchKernelGGL((basket_paths_kernel<D, VEC, false, true>), grid, block, 0, st, g, law);
+        return;
+    }
     if (keep) hipLaunchKernelGGL((basket_paths_kernel<D, VEC, true>), grid, block, 0, st, g, law);
     else hipLaunchKernelGGL((basket_paths_kernel<D, VEC, false>), grid, block, 0, st, g, law);
 }
@@ -177,8 +227,9 @@ hipError_t launch_basket_paths(hipStream_t st, const BasketGen& a)
     // VEC-wide stores in both buffers (asset k's matrix starts k (N + 1) ld_assets floats in: aligned where its rows are)
     vec = store_vec_width(vec, P, s.S, s.ld);
     if (a.assets) vec = store_vec_width(vec, P, a.assets, a.ld_assets);
+    if (a.assets && a.state) vec = store_vec_width(vec, P, a.state, a.ld_assets);
     BasketArgs g{};
-    g.S = s.S; g.A = a.assets; g.ld = s.ld; g.lda = a.ld_assets; g.P = P; g.n_steps = s.n_steps;
+    g.S = s.S; g.A = a.assets; g.C = a.assets ? a.state : nullptr; g.ld = s.ld; g.lda = a.ld_assets; g.P = P; g.n_steps = s.n_steps;
     g.k0 = (uint32_t)s.seed; g.k1 = (uint32_t)(s.seed >> 32); g.stream = s.stream; g.pair_offset = s.pair_offset;
     const bool keep = a.assets != nullptr;
     for_assets(a.d, [&](auto d) { launch_basket_d<d()>(st, g, a.law, keep, vec); });

@@ -14,6 +14,7 @@ struct BasketBoundsArgs {
     BasketLaw law;     // by value: wave-uniform scalars, as in the generator
     int d;             // assets, 1 .. kBasketMax
     const float* Ao;   // [d][N+1][n_outer] outer asset matrices (launch_basket_paths with `assets`, ld_assets = n_outer)
+    const float* Co;   // the Asian kinds: [N+1][n_outer] outer running state (... with `state`); else not read
 };
 
 hipError_t basket_bounds_lower(hipStream_t st, const BasketBoundsArgs& a, double* result);

@@ -15,6 +15,8 @@
 // time (no scratch: section 17.3).
 // With D = 1 and w = 1 both kernels perform the vanilla kernels' operations in the vanilla order: the same bits.
 // The outer walk, the exercise tables and the finalize are omc_bounds.hip's / omc_lsm.hip's, on the index matrix.
+// The Asian kinds (section 23) run the same two bodies with the path law of omc_asian_dev.h.
+#include "omc_asian_dev.h"
 #include "omc_basket_bounds.h"
 #include "omc_basket_dev.h"
 #include "omc_bounds_dev.h"
@@ -152,11 +154,35 @@ __global__ __launch_bounds__(kBlock) void basket_bounds_inner_kernel<1>(BasketBo
     if (lane == 0 && steps) atomicAdd(a.steps, steps);
 }
 
+// ------------------------------------------------------------------ the running-average (Asian) kinds, section 23
+// the same two bodies with the path law of omc_asian_dev.h: the running state beside the spots, the step counter in Spots
+template <int D>
+__global__ __launch_bounds__(kBlock) void asian_bounds_lower_kernel(BasketBoundsArgs g, int nblk)
+{
+    extern __shared__ uint4 sh_bt[];
+    __shared__ double red[kNQ * kRedStride];
+    bounds_lower_body(g.v, AsianModel<D>{g}, nblk, sh_bt, red);
+}
+
+template <int D>
+__global__ __launch_bounds__(kBlock) void asian_bounds_inner_kernel(BasketBoundsArgs g, int64_t i0, int64_t ni)
+{
+    extern __shared__ uint4 sh_bt[];
+    bounds_inner_body(g.v, AsianModel<D>{g}, i0, ni, sh_bt);
+}
+
 // ------------------------------------------------------------------ launchers
 hipError_t basket_bounds_lower(hipStream_t st, const BasketBoundsArgs& a, double* result)
 {
     if (a.d < 1 || a.d > kBasketMax) return hipErrorInvalidValue;
     const int nblk = (int)bounds_lower_blocks(a.v);  // the vanilla sweep's grid
+    if (basket_kind_is_asian(a.law.kind)) {
+        for_assets(a.d, [&](auto d) {
+            hipLaunchKernelGGL((asian_bounds_lower_kernel<d()>), dim3(nblk), dim3(kBlock), sizeof(uint4) * (size_t)(a.v.N + 1),
+                               st, a, nblk);
+        });
+        return lsm_finalize(st, a.v.part, nullptr, result, nblk, 0);
+    }
     for_assets(a.d, [&](auto d) {
         hipLaunchKernelGGL((basket_bounds_lower_kernel<d()>), dim3(nblk), dim3(kBlock), sizeof(uint4) * (size_t)(a.v.N + 1), st,
                            a, nblk);
@@ -170,6 +196,14 @@ hipError_t basket_bounds_inner(hipStream_t st, const BasketBoundsArgs& a, int64_
     const int64_t items = ni * a.v.N;
     int64_t g = (items + 3) / 4;
     if (g > 2048) g = 2048;
+    if (basket_kind_is_asian(a.law.kind)) {
+        if (!a.Co) return hipErrorInvalidValue;
+        for_assets(a.d, [&](auto d) {
+            hipLaunchKernelGGL((asian_bounds_inner_kernel<d()>), dim3((unsigned)g), dim3(kBlock),
+                               sizeof(uint4) * (size_t)(a.v.N + 1), st, a, i0, ni);
+        });
+        return hipGetLastError();
+    }
     for_assets(a.d, [&](auto d) {
         hipLaunchKernelGGL((basket_bounds_inner_kernel<d()>), dim3((unsigned)g), dim3(kBlock),
                            sizeof(uint4) * (size_t)(a.v.N + 1), st, a, i0, ni);

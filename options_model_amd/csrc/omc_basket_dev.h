@@ -65,6 +65,14 @@ __device__ __forceinline__ float basket_index(const BasketLaw& c, const float (&
     return x;
 }
 
+// the running sum of the Asian kinds (section 23): ONE float32 add.  With one asset B is a bare product, which the compiler
+// would otherwise contract into the sum -- and the documented rule, restated in numpy by the tests, has two roundings
+__device__ __forceinline__ float asian_add(float c, float B)
+{
+#pragma clang fp contract(off)
+    return c + B;
+}
+
 // ... of the law's own kind (wave-uniform: a scalar branch)
 template <int D>
 __device__ __forceinline__ float basket_law_index(const BasketLaw& c, const float (&s)[D])
