@@ -1108,19 +1108,34 @@ int omc_seq_group_width(omc_ctx* ctx, const omc_params* p, int n);
  * entry's sums in the tile, block and slot geometry of the single kernels; UNFUSED (Heston, full storage,
  * "pass2_tables" = 0, and the default, "chain_fused" = 0): the single-strike sweeps per entry on the shared matrix.  Either way the
  * pass-1 reductions, table builds and finalizes of up to 16 entries share one launch each.
+ * EXERCISE SCHEDULES: e[i].exercise_every = k is the entry's schedule on the grid of n_steps = N dates.
+ *   k = 0 or 1   every date: the American quote, THE CONTRACT above.
+ *   k >= 2       a Bermudan quote: early exercise only at the dates t in 1 .. N-1 with (N - t) % k == 0 -- the schedule
+ *                is anchored at expiry, which takes the payoff as ever; k >= N leaves no early date (the European value
+ *                of the flow).  res[i] is the two-pass flow with every other date skipped in BOTH passes: rows of slice
+ *                i of betas_out at scheduled dates carry the bits of the American entry's fits of the same (K, is_put),
+ *                every other row is zero, sum_nitm sums the scheduled dates, pass 2 is the sticky backward rule over
+ *                them, valued as the flow values, exp(-r dt (t - 1)).  The entry's sweeps read its scheduled rows (and
+ *                the expiry's) only -- but for pass 1 on full storage when n_paths is a multiple of 4, which walks
+ *                all rows to keep the fits' bits.  It changes what no other entry returns; a chain that holds one takes the unfused
+ *                route as a whole (info->fused = 0), on which the American entries carry the same bits.
+ *   k < 0        refused, -37.
  * Timings: res[i].ms_* repeat the chain's whole-call times, res[i].timed is 1 for i = 0 only; info (may be NULL): the
  * route taken, the number of sweep launches per pass, and the phases -- ms_paths the generator, ms_pass1 the pass-1
  * sweeps + reductions, ms_pass2 the table builds + pass-2 sweeps + finalizes, ms_total from the first launch to the
  * last completion (it also holds the entries' fold tables, which every call builds anew in front of the generator).
  * Errors: those of omc_price_american for p (nothing is launched); -7 null e / res; -3 n < 1 or n > 256; -4 an entry
  * whose K is not finite and positive or whose is_put is not 0 / 1, or p->semantics != 2; -15 p->antithetic == 0;
- * -10 a context with a communicator or an all-reduce hook.
+ * -37 an entry whose exercise_every is negative; -10 a context with a communicator or an all-reduce hook.  They are
+ * checked in this order -- p's own, the -4 of every entry, then -37, then -10 -- before anything is launched: res is untouched.
  * Options: "chain_fused" (0 = default: unfused -- 8 quotes at 1M paths x 252 steps in 1.99 ms against 3.08 ms as a
  * sequence; 1 = fused: measured 0.3 - 5.5 % slower than unfused at the sizes of DESIGN.md 13.4, kept as an option), "chain_k" (entries per fused launch at most: -1 = default, 1 .. 16;
  * it can only lower omc_chain_width). */
 typedef struct {
     double K;
-    int32_t is_put, reserved;
+    int32_t is_put;
+    int32_t exercise_every; /* 0 or 1: every date (American); k >= 2: every k-th date counted back from expiry (it was
+                               a reserved field that nothing read: callers that zero it keep their results) */
 } omc_chain_entry;
 typedef struct {
     int32_t folded, fused, n_launch_groups, reserved;

@@ -19,7 +19,7 @@ def __getattr__(name):
     # lazy: keep `import options_model_amd` cheap and free of side effects
     if name in ("price_american_option", "PriceResult", "price_european_option", "price_american_greeks", "GreeksResult",
                 "price_barrier_option", "BarrierResult", "price_american_bounds", "BoundsResult", "price_american_chain",
-                "ChainResult", "price_american_dividends", "DividendResult", "price_american_jumps", "JumpResult",
+                "ChainResult", "price_bermudan_option", "exercise_dates", "price_american_dividends", "DividendResult", "price_american_jumps", "JumpResult",
                 "price_american_basket", "BasketResult", "price_american_basket_bounds", "BasketBoundsResult",
                 "price_american_basket_greeks", "BasketGreeksResult", "price_american_bounds_heston",
                 "HestonBoundsResult", "price_asian_option"):

@@ -201,8 +201,9 @@ class BasketBounds(C.Structure):
 
 
 class ChainEntry(C.Structure):
-    """omc_chain_entry: strike and side of one quote of a chain (omc_price_american_chain)."""
-    _fields_ = [("K", C.c_double), ("is_put", C.c_int32), ("reserved", C.c_int32)]
+    """omc_chain_entry: strike, side and exercise schedule of one quote of a chain (omc_price_american_chain);
+    exercise_every 0 or 1 = every date (American), k >= 2 = every k-th date counted back from expiry (Bermudan)."""
+    _fields_ = [("K", C.c_double), ("is_put", C.c_int32), ("exercise_every", C.c_int32)]
 
 
 class ChainInfo(C.Structure):
@@ -1225,19 +1226,23 @@ class Context:
         arr = (Params * len(plist))(*plist)
         return int(self.lib.omc_seq_group_width(self.handle, arr, len(plist)))
 
-    def price_american_chain(self, params: Params, strikes, is_put=True, want_betas=False):
+    def price_american_chain(self, params: Params, strikes, is_put=True, want_betas=False, exercise_every=0):
         """A whole chain of one expiry from one set of paths (omc_price_american_chain) -> (list of result dicts, info dict).
         strikes: the entries' strikes; is_put: one flag for all or one per strike; params.K / params.is_put are ignored.
         Entry i carries the bits of price_american(params with strikes[i], is_put[i]); want_betas adds its fits
-        [n_steps+1][4] as "betas"."""
+        [n_steps+1][4] as "betas".  exercise_every: one schedule for all or one per strike (ChainEntry); an entry with k >= 2 is
+        the Bermudan quote, its fits zero at every unscheduled date."""
         ks = [float(k) for k in strikes]
         n = len(ks)
+        every = [int(exercise_every)] * n if isinstance(exercise_every, (int, np.integer)) else [int(k) for k in exercise_every]
+        if len(every) != n:
+            raise ValueError("one exercise_every per strike.")
         sides = [int(bool(is_put))] * n if isinstance(is_put, (bool, int, np.integer)) else [int(bool(s)) for s in is_put]
         if len(sides) != n:
             raise ValueError("one side per strike.")
         ent = (ChainEntry * max(n, 1))()
         for i in range(n):
-            ent[i].K, ent[i].is_put = ks[i], sides[i]
+            ent[i].K, ent[i].is_put, ent[i].exercise_every = ks[i], sides[i], every[i]
         res = (Result * max(n, 1))()
         info = ChainInfo()
         N = int(params.n_steps)

@@ -220,12 +220,48 @@ def price_american_option(S0, K, r, sigma, T, n_paths, n_steps, model="GBM", opt
                        timings_ms=dict(paths=out["ms_paths"], lsm=out["ms_lsm"], total=out["ms_total"]))
 
 
+def exercise_dates(n_steps, exercise_every):
+    """The early-exercise dates of a schedule on a grid of n_steps dates (omc_chain_entry::exercise_every): every date
+    1 .. n_steps-1 for 0 or 1, else the dates t with (n_steps - t) % exercise_every == 0 -- every k-th date counted back
+    from expiry, which is no early date itself."""
+    N, k = int(n_steps), int(exercise_every)
+    if k < 0:
+        raise ValueError("exercise_every must be a non-negative integer.")
+    return [t for t in range(1, N) if k < 2 or (N - t) % k == 0]
+
+
+def _schedules(exercise_every, n):
+    """exercise_every of price_american_chain -> one non-negative int per strike (ValueError otherwise)."""
+    def one(k):
+        if isinstance(k, bool) or not isinstance(k, (int, float)) and not hasattr(k, "__index__"):
+            raise ValueError("exercise_every must be a non-negative integer.")
+        if isinstance(k, float) and not (math.isfinite(k) and k == int(k)):
+            raise ValueError("exercise_every must be a non-negative integer.")
+        k = int(k)
+        if k < 0 or k > 2 ** 31 - 1:
+            raise ValueError("exercise_every must be a non-negative integer.")
+        return k
+    if exercise_every is None:
+        return [0] * n
+    if isinstance(exercise_every, (str, bytes)):
+        raise ValueError("exercise_every must be a non-negative integer.")
+    try:
+        ks = list(exercise_every)
+    except TypeError:
+        return [one(exercise_every)] * n
+    if len(ks) != n:
+        raise ValueError("exercise_every must be one integer or one per strike.")
+    return [one(k) for k in ks]
+
+
 @dataclass
 class ChainResult:
-    """price_american_chain: one PriceResult per quote, filled as price_american_option fills it."""
+    """price_american_chain: one PriceResult per quote, filled as price_american_option fills it; its info carries the
+    quote's schedule (exercise_every, n_early_dates)."""
     entries: list
     strikes: list
     option_types: list
+    exercise_every: list = field(default_factory=list)  # per quote: 0 = every date
     timings_ms: dict = field(default_factory=dict)  # whole chain: paths, pass1, pass2, total
     info: dict = field(default_factory=dict)        # folded, fused, n_launch_groups
 
@@ -237,15 +273,21 @@ class ChainResult:
 
 
 def price_american_chain(S0, strikes, r, sigma, T, n_paths, n_steps, option_types="put", model="GBM", heston_params=None,
-                         heston_scheme="reference", seed=42, stream=0, device=None, ctx=None) -> ChainResult:
+                         heston_scheme="reference", seed=42, stream=0, device=None, ctx=None, exercise_every=None,
+                         n_gpus=1) -> ChainResult:
     """Every quote of one expiry -- `strikes`, each a put or a call (`option_types`: one string for all, or one per
     strike) -- from ONE set of paths (omc_price_american_chain): two-pass flow, polynomial regressor, antithetic pairs,
     one GPU.  entries[i] equals price_american_option(S0, strikes[i], ..., option_type=option_types[i]) bit for bit.
+    exercise_every: None (every quote American), one int for all quotes or one per strike -- 0 or 1 every date, k >= 2 a
+    Bermudan quote that may exercise early only at every k-th date counted back from expiry (exercise_dates); the
+    American, Bermudan and European (k >= n_steps) values of a strike then come from the same paths.
     heston_scheme (model="Heston"): "reference" (= "clamp"), "full_truncation", "calibrator", or "qe" -- Andersen's (2008)
     quadratic-exponential rule, which needs kappa > 0, theta > 0 and xi > 0 (ValueError otherwise)."""
     model_l = str(model).lower()
     if model_l not in ("gbm", "heston"):
         raise ValueError("model must be 'GBM' or 'Heston'.")
+    if isinstance(n_gpus, bool) or n_gpus != 1:
+        raise ValueError("a chain is priced on one GPU (n_gpus = 1).")
     try:
         ks = [float(k) for k in strikes]
     except TypeError:
@@ -257,6 +299,7 @@ def price_american_chain(S0, strikes, r, sigma, T, n_paths, n_steps, option_type
     types = [option_types] * len(ks) if isinstance(option_types, str) else list(option_types)
     if len(types) != len(ks):
         raise ValueError("option_types must be one string or one per strike.")
+    every = _schedules(exercise_every, len(ks))
     for k, ot in zip(ks, types):
         if not (math.isfinite(k) and k > 0):
             raise ValueError("S0, K, T must be positive.")
@@ -269,19 +312,37 @@ def price_american_chain(S0, strikes, r, sigma, T, n_paths, n_steps, option_type
     p = _ffi.make_params(model=model_l, is_put=True, semantics="two_pass", antithetic=True, heston_scheme=heston_scheme,
                          n_paths=M, n_steps=int(n_steps), S0=S0, K=ks[0], r=r, sigma=sigma or 0.0, T=T, seed=seed,
                          stream=stream, **heston_defaults(sigma, heston_params))
-    outs, info = c.price_american_chain(p, ks, [ot == "put" for ot in types])
+    outs, info = c.price_american_chain(p, ks, [ot == "put" for ot in types], exercise_every=every)
     entries = []
-    for out, ot in zip(outs, types):
+    for out, ot, k in zip(outs, types, every):
         var = max(out["sumsq"] / M - out["price"] ** 2, 0.0)
         entries.append(PriceResult(price=out["price"], stderr=math.sqrt(var / M), std=out["std"],
                                    zero_prob=out["zero_prob"], n_paths=M, n_exercised=out["n_exercised"],
                                    sum_nitm=out["sum_nitm"], model=model_l, semantics="two_pass", option_type=ot,
-                                   timings_ms=dict(paths=out["ms_paths"], lsm=out["ms_lsm"], total=out["ms_total"])))
-    return ChainResult(entries=entries, strikes=ks, option_types=types,
+                                   timings_ms=dict(paths=out["ms_paths"], lsm=out["ms_lsm"], total=out["ms_total"]),
+                                   info=dict(exercise_every=k, n_early_dates=len(exercise_dates(n_steps, k)))))
+    return ChainResult(entries=entries, strikes=ks, option_types=types, exercise_every=every,
                        timings_ms=dict(paths=info["ms_paths"], pass1=info["ms_pass1"], pass2=info["ms_pass2"],
                                        total=info["ms_total"]),
                        info=dict(folded=bool(info["folded"]), fused=bool(info["fused"]),
                                  n_launch_groups=info["n_launch_groups"]))
+
+
+def price_bermudan_option(S0, K, r, sigma, T, n_paths, n_steps, exercise_every, model="GBM", option_type="put",
+                          heston_params=None, heston_scheme="reference", seed=42, stream=0, device=None,
+                          ctx=None) -> PriceResult:
+    """A Bermudan option on a grid of n_steps dates that may be exercised early at every exercise_every-th date counted
+    back from expiry (exercise_dates): the one-entry chain (price_american_chain), two-pass flow, polynomial regressor,
+    antithetic pairs, one GPU.  0 or 1 is the American option, exercise_every >= n_steps the European value of the flow.
+    The result is price_american_option's; info carries exercise_every, n_early_dates and the storage."""
+    if exercise_every is None or isinstance(exercise_every, (list, tuple)):
+        raise ValueError("exercise_every must be a non-negative integer.")
+    chain = price_american_chain(S0, [K], r, sigma, T, n_paths, n_steps, option_types=option_type, model=model,
+                                 heston_params=heston_params, heston_scheme=heston_scheme, seed=seed, stream=stream,
+                                 device=device, ctx=ctx, exercise_every=exercise_every)
+    out = chain.entries[0]
+    out.info = dict(out.info, folded=chain.info["folded"])
+    return out
 
 
 @dataclass

@@ -4,6 +4,8 @@
 // No kernel code here.
 #include <sched.h>
 
+#include <algorithm>
+
 #include "omc_ctx.h"
 
 namespace omc::abi {
@@ -354,7 +356,7 @@ void TwoPassGroup::add(const omc::LsmProblem& p, double* result)
     wk.result = result;
     prob[k] = p;
     g.slot[k] = omc::lsm_group_slot(p, wk);
-    g.N = p.N;
+    g.N = std::max(g.N, p.N);  // (members of one length, but for a chain's Bermudan entries: shorter)
 }
 
 // after a wait: did a direct exchange give up (its bounded poll ran out) -- on this rank (its sticky error word; the

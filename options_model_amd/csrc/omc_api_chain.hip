@@ -7,6 +7,9 @@
 //         ONE launch: the table builds   gmom[j] -> betas[j], crit[j]        (folded storage with "pass2_tables")
 //         pass-2 sweeps -> part[j]       fused / per entry, as above
 //         ONE launch: the finalizes      part[j], gmom[j] -> result slot of the entry
+// A Bermudan entry (exercise_every >= 2) is the same flow on the view of S that holds its scheduled rows (omc_chain.h,
+// DESIGN.md section 24): one more launch in front of the generator gathers its tables, its sweeps are the single
+// pricing's on that view, its slot of the shared launches carries the view's length.  A chain that holds one runs unfused.
 // A group is a TwoPassGroup (omc_ctx.h), as in the grouped sequences: it carves the entries' buffers from the context's
 // group state and issues the three shared launches, every slot carrying its entry's own fold table.
 // The unfused sweeps ARE the single pricing's launches (lsm_pass1_sweep, lsm_pass2_sweep), the three shared launches run the
@@ -53,6 +56,8 @@ int check_chain(const omc_ctx* c, const omc_params* p, const omc_chain_entry* e,
         if (!(std::isfinite(e[i].K) && e[i].K > 0.0)) return fail(-4, "an entry's strike must be finite and positive.");
         if (e[i].is_put != 0 && e[i].is_put != 1) return fail(-4, "an entry's is_put must be 0 or 1.");
     }
+    for (int i = 0; e && i < n; ++i)
+        if (e[i].exercise_every < 0) return fail(-37, "an entry's exercise_every must not be negative (0 or 1: every date).");
     if (c->distributed()) return fail(-10, "a chain is priced on one GPU.");
     return 0;
 }
@@ -98,7 +103,17 @@ int omc_price_american_chain(omc_ctx* c, const omc_params* p, const omc_chain_en
     const int64_t ld = folded ? padded_ld(M / 2) : padded_ld(M);
     if ((rc = c->S.ensure(sizeof(float) * (size_t)ld * n1))) return rc;
     float* S = (float*)c->S.p;
-    const int width = fused_width(c, p, ld, folded);
+    // the schedules: k cut to 2 .. N (k >= N leaves no early date, as k = N does), 0 where every date is one
+    static_assert(omc::kChainMax == OMC_CHAIN_MAX, "ChainSchedules holds one word per entry");
+    omc::ChainSchedules sch;
+    memset(&sch, 0, sizeof sch);
+    bool bermudan = false;
+    for (int i = 0; i < n; ++i) {
+        const int k = std::min(e[i].exercise_every, N);
+        sch.every[i] = k >= 2 ? k : 0;
+        bermudan = bermudan || k >= 2;
+    }
+    const int width = bermudan ? 0 : fused_width(c, p, ld, folded);
     const bool fused = width > 0;
     const bool tables = folded && c->pass2_tables;  // lsm_pass2_tables of every entry
     const int G = std::min(n, omc::kChainGroupMax);
@@ -135,10 +150,18 @@ int omc_price_american_chain(omc_ctx* c, const omc_params* p, const omc_chain_en
         HIP_TRY(hipMemcpyAsync(c0_dev, c0, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(omc::chain_fold_tables(c->stream, fold, fstride, c0_dev, n, N, g));
     }
+    double* sched = nullptr;  // entry i: [d1 | d2 | cv] at sched + 3 fstride i
+    if (bermudan) {
+        if ((rc = c->chain_sched.ensure(sizeof(double) * 3 * fstride * (size_t)n))) return rc;
+        sched = (double*)c->chain_sched.p;
+        HIP_TRY(omc::chain_schedule_tables(c->stream, sched, fstride, w0.D, fold, fstride, sch, n, N));
+    }
     HIP_TRY(hipEventRecord(c->ev[3], c->stream));
     if ((rc = enqueue_paths(c, &q0, S, ld, folded))) return rc;
     HIP_TRY(hipEventRecord(c->ev[1], c->stream));
     int launches = 0;
+    std::vector<double> hview;  // the fits of the Bermudan entries on their views' rows, n1 x 4 doubles each
+    if (betas_out && bermudan) hview.resize(4 * n1 * (size_t)n);
     for (int gi = 0; gi < ngroups; ++gi) {
         const int i0 = gi * G, Kb = std::min(G, n - i0);
         TwoPassGroup grp(L, c->gstate.p, w0, c->pass2_tables != 0);
@@ -147,6 +170,13 @@ int omc_price_american_chain(omc_ctx* c, const omc_params* p, const omc_chain_en
             const omc_chain_entry& ek = e[i0 + k];
             omc::LsmProblem q{S, ld, M, N, ek.is_put, ek.K, p->r, p->T};
             q.fold_cK = folded ? fold + fstride * (size_t)(i0 + k) : nullptr;
+            if (const int every = sch.every[i0 + k]) {  // the view of the scheduled rows; its row 0 is never read
+                const int Nv = omc::chain_view_steps(N, every);
+                q.S = S + (int64_t)(N - every * Nv) * ld;
+                q.ld = ld * every;
+                q.N = Nv;
+                if (folded) q.fold_cK = sched + fstride * (3 * (size_t)(i0 + k) + 2);
+            }
             grp.add(q, dres + 8 * (size_t)(i0 + k));
             // rows 0 and N of the fits are only ever copied out (prepare_lsm's clear_tables)
             if (betas_out) HIP_TRY(hipMemsetAsync(w[k].betas, 0, sizeof(double) * 4 * n1, c->stream));
@@ -179,14 +209,51 @@ int omc_price_american_chain(omc_ctx* c, const omc_params* p, const omc_chain_en
             }
             return a;
         };
+        // the sweeps of member k: a Bermudan entry's read its own discounts (d1 in pass 1, d2 in pass 2)
+        auto swept = [&](int k, int pass) {
+            omc::LsmWorkspace wk = w[k];
+            if (sch.every[i0 + k]) wk.D = sched + fstride * (3 * (size_t)(i0 + k) + (size_t)pass - 1);
+            return wk;
+        };
+        // pass 1 on full storage with 16-byte loads walks all rows for a Bermudan entry too (omc_chain.h: its row slots
+        // do not round alike); the scheduled rows of its moments are gathered after the reduction
+        omc::ChainGatherArgs ga;
+        memset(&ga, 0, sizeof ga);
+        ga.N = N;
+        bool gather = false;
+        for (int k = 0; k < Kb; ++k) {
+            const int every = sch.every[i0 + k];
+            if (every && !folded && prob[k].N >= 2 && omc::rows_aligned(4, M, S, ld)) {
+                ga.gmom[k] = w[k].gmom;
+                ga.every[k] = every;
+                gather = true;
+            }
+        }
         // ---- pass 1
         if (fused) {
             for (const Piece& pc : pieces)
                 HIP_TRY(omc::chain_pass1_sweep(c->stream, sweep_args(pc), prob[0], &grp.g.ntiles));
         } else {
-            for (int k = 0; k < Kb; ++k) HIP_TRY(omc::lsm_pass1_sweep(c->stream, prob[k], w[k], &grp.g.ntiles));
+            for (int k = 0; k < Kb; ++k) {  // (tiles depend on the columns alone; a view of one row has no pass 1: 0)
+                int64_t nt = 0;
+                if (ga.every[k]) {
+                    omc::LsmProblem all = prob[k];
+                    all.S = S; all.ld = ld; all.N = N;
+                    HIP_TRY(omc::lsm_pass1_sweep(c->stream, all, w[k], &nt));
+                    grp.g.slot[k].N = N;  // (for the reduction: all rows of this member, hence of the grid)
+                    grp.g.N = N;
+                } else {
+                    HIP_TRY(omc::lsm_pass1_sweep(c->stream, prob[k], swept(k, 1), &nt));
+                }
+                if (nt) grp.g.ntiles = nt;
+            }
         }
         HIP_TRY(grp.reduce_pass1(c->stream));
+        if (gather) {
+            HIP_TRY(omc::chain_gather_moments(c->stream, ga, Kb));
+            for (int k = 0; k < Kb; ++k)
+                if (ga.every[k]) grp.g.slot[k].N = prob[k].N;
+        }
         HIP_TRY(hipEventRecord(c->ev_pool[2 * (size_t)gi], c->stream));
         // ---- pass 2
         if (tables) HIP_TRY(grp.build_tables(c->stream));
@@ -195,19 +262,31 @@ int omc_price_american_chain(omc_ctx* c, const omc_params* p, const omc_chain_en
                 HIP_TRY(omc::chain_pass2_sweep(c->stream, sweep_args(pc), prob[0], &grp.g.nblk));
         } else {
             for (int k = 0; k < Kb; ++k)
-                HIP_TRY(omc::lsm_pass2_sweep(c->stream, prob[k], w[k], false, true, &grp.g.nblk));
+                HIP_TRY(omc::lsm_pass2_sweep(c->stream, prob[k], swept(k, 2), false, true, &grp.g.nblk));
         }
         HIP_TRY(grp.finalize(c->stream));
         HIP_TRY(hipEventRecord(c->ev_pool[2 * (size_t)gi + 1], c->stream));
         launches += fused ? (int)pieces.size() : Kb;
         if (betas_out)
-            for (int k = 0; k < Kb; ++k)
-                HIP_TRY(hipMemcpyAsync(betas_out + 4 * n1 * (size_t)(i0 + k), w[k].betas, sizeof(double) * 4 * n1,
+            for (int k = 0; k < Kb; ++k) {
+                double* to = sch.every[i0 + k] ? hview.data() : betas_out;
+                HIP_TRY(hipMemcpyAsync(to + 4 * n1 * (size_t)(i0 + k), w[k].betas, sizeof(double) * 4 * n1,
                                        hipMemcpyDeviceToHost, c->stream));
+            }
     }
     std::vector<double> h(8 * (size_t)n);
     HIP_TRY(hipMemcpyAsync(h.data(), dres, sizeof(double) * 8 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     if ((rc = wait_stream(c))) return rc;
+    // a Bermudan entry's fits from its view's rows to the dates they belong to; every other row is zero
+    for (int i = 0; betas_out && i < n; ++i) {
+        const int every = sch.every[i];
+        if (!every) continue;
+        const int Nv = omc::chain_view_steps(N, every);
+        double* out = betas_out + 4 * n1 * (size_t)i;
+        const double* in = hview.data() + 4 * n1 * (size_t)i;
+        memset(out, 0, sizeof(double) * 4 * n1);
+        for (int j = 1; j < Nv; ++j) memcpy(out + 4 * (size_t)(N - every * (Nv - j)), in + 4 * (size_t)j, sizeof(double) * 4);
+    }
     omc_chain_info inf;
     memset(&inf, 0, sizeof inf);
     inf.folded = folded ? 1 : 0;

@@ -13,6 +13,40 @@ constexpr int kChainWidthMax = 4;   // entries of one side per fused sweep launc
 // (fold_table_fill; c0: device, n doubles)
 hipError_t chain_fold_tables(hipStream_t st, double* cK, size_t stride, const double* c0, int n, int N, double g);
 
+// ---- Bermudan entries (omc_chain_entry::exercise_every = k >= 2)
+// The scheduled dates of an N-step grid are t = N - k m >= 1, m = 1, 2, ...: n_e = (N - 1) / k of them.  Together with
+// the expiry they are the rows 1 .. Nv = n_e + 1 of a VIEW of the path matrix with leading dimension k ld whose row j
+// is the matrix's row N - k (Nv - j) (row 0 of the view lies above the matrix when k does not divide N: no sweep reads a
+// row 0).  The two-pass flow with every unscheduled date skipped in both passes is the two-pass flow of that view -- the
+// single pricing's own sweeps, which then touch the scheduled rows and no others -- once the three tables the sweeps
+// index by row are restated on the view's rows:
+//     pass 1 discounts a row's targets from expiry by D[N - t]              ->  d1[Nv - j] = D[k (Nv - j)]
+//     pass 2 values an exercise at row t by D[t - 1]                        ->  d2[j - 1]  = D[N - k (Nv - j) - 1]
+//     the fold table of the entry                                           ->  cv[j]      = cK[N - k (Nv - j)]
+// gathered (copied, so they carry the bits of the tables every other entry reads) by one launch for the whole chain.
+constexpr int kChainMax = 256;  // OMC_CHAIN_MAX
+struct ChainSchedules {
+    int every[kChainMax];  // per entry: k, already cut to 2 .. N; below 2 = every date (no tables)
+};
+__host__ __device__ inline int chain_view_steps(int N, int k) { return (N - 1) / k + 1; }  // Nv
+// tables of entry i at out + 3 stride i: d1, d2, cv, each of `stride` >= N + 1 doubles (cv only when cK is given: the
+// entries' fold tables, table i at cK + cstride i)
+hipError_t chain_schedule_tables(hipStream_t st, double* out, size_t stride, const double* D, const double* cK,
+                                 size_t cstride, const ChainSchedules& s, int n, int N);
+
+// The one sweep that cannot take the view: pass 1 on FULL storage with 16-byte loads (lsm_pass1_kernel<4, ..>).  Its three
+// unrolled row slots do not round alike -- the first forms the u^2 sum of its first two columns as fma(u0, u0, rnd(u1^2)),
+// the other two as fma(u1, u1, rnd(u0^2)) -- so a date's moments depend on its position in its chunk, which the view
+// changes: the fits would leave the American entry's in the last bits (seen at 1 date in ~20).  Such an entry's pass 1 is
+// the American entry's own, over all rows, and this launch then moves the scheduled rows of its reduced moments to the
+// view's rows: gmom[j] = gmom[N - k (Nv - j)], j = 1 .. Nv - 1, in place (ascending j: a source row is never below j).
+struct ChainGatherArgs {
+    double* gmom[kChainGroupMax];  // [N+1][8]
+    int every[kChainGroupMax];     // 0: nothing to do for this member
+    int N, pad_;
+};
+hipError_t chain_gather_moments(hipStream_t st, const ChainGatherArgs& a, int K);
+
 // One fused launch: KE entries of ONE side on the folded matrix S ([N+1][ld], P stored columns).  Entry e reads its strike,
 // its fold table and -- pass 2 -- its exercise tables and fits, and leaves its partial sums in its own slabs, in the
 // geometry of the single kernels: part1[e] as lsm_pass1_sweep leaves w.part1, part[e] as lsm_pass2_sweep leaves w.part.

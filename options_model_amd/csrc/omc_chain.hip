@@ -36,6 +36,55 @@ hipError_t chain_fold_tables(hipStream_t st, double* cK, size_t stride, const do
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------ Bermudan entries: the tables on the scheduled rows
+// One workgroup per entry, one thread per row j = 0 .. Nv of its view (omc_chain.h).  Indices that fall outside a table
+// (d1 at j = Nv and d2 at j = Nv when k > 1, the view's row 0 above the matrix) are slots no sweep reads: they are
+// clamped into the table, not skipped, so every slot holds a finite number.
+__global__ __launch_bounds__(64) void chain_schedule_tables_kernel(double* __restrict__ out, size_t stride,
+                                                                    const double* __restrict__ D,
+                                                                    const double* __restrict__ cK, size_t cstride,
+                                                                    ChainSchedules s, int N)
+{
+    const int i = (int)blockIdx.x, k = s.every[i];
+    if (k < 2 || k > N) return;
+    const int Nv = chain_view_steps(N, k);
+    double* d1 = out + 3 * stride * (size_t)i;
+    double* d2 = d1 + stride;
+    double* cv = d2 + stride;
+    const double* ci = cK ? cK + cstride * (size_t)i : nullptr;
+    for (int j = (int)threadIdx.x; j <= Nv; j += 64) {
+        const int row = N - k * (Nv - j);  // >= 1 for j >= 1, == N for j == Nv
+        d1[j] = D[min(k * j, N)];
+        d2[j] = D[min(row + k - 1, N)];
+        if (ci) cv[j] = ci[max(row, 0)];
+    }
+}
+
+hipError_t chain_schedule_tables(hipStream_t st, double* out, size_t stride, const double* D, const double* cK,
+                                 size_t cstride, const ChainSchedules& s, int n, int N)
+{
+    if (n < 1 || n > kChainMax || stride < (size_t)N + 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(chain_schedule_tables_kernel, dim3((unsigned)n), dim3(64), 0, st, out, stride, D, cK, cstride, s, N);
+    return hipGetLastError();
+}
+
+// one workgroup per member of the group, one thread per quantity: the rows of a column are moved one after the other
+__global__ __launch_bounds__(64) void chain_gather_moments_kernel(ChainGatherArgs a)
+{
+    const int m = (int)blockIdx.x, k = a.every[m], q = (int)threadIdx.x;
+    if (k < 2 || k > a.N || q >= 8) return;
+    const int Nv = chain_view_steps(a.N, k);
+    double* g = a.gmom[m];
+    for (int j = 1; j < Nv; ++j) g[(size_t)j * 8 + q] = g[(size_t)(a.N - k * (Nv - j)) * 8 + q];
+}
+
+hipError_t chain_gather_moments(hipStream_t st, const ChainGatherArgs& a, int K)
+{
+    if (K < 1 || K > kChainGroupMax) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(chain_gather_moments_kernel, dim3((unsigned)K), dim3(64), 0, st, a);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------ pass 1, KE entries of one side per launch
 // lsm_pass1_fold_body with an entry loop inside every step.  Per spot, once: the conversion and the reciprocal (fold_rcp);
 // per entry: both moneynesses (fold_u_rcp keeps the partner's the fma(cK, rcp, -1) of fold_u), the two in-the-money tests,

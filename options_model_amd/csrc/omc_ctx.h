@@ -291,6 +291,7 @@ struct omc_ctx {
     DevBuf div_tab;            // omc_price_american_div: the dividend steps of the call (omc::DivEntry)
     DevBuf bnd;                // omc_price_american_bounds: outer paths, Q^ table, samples, tables, partials, sums
     DevBuf chain_fold;         // omc_price_american_chain: the entries' fold tables + c0 (their small buffers: gstate)
+    DevBuf chain_sched;        // ... and its Bermudan entries' tables on their scheduled dates (omc::chain_schedule_tables)
     int chain_fused = 0;       // option "chain_fused": 0 = default, the single-strike sweeps per entry; 1 = the fused sweeps
     int chain_k = -1;          // option "chain_k": entries per fused launch at most (-1: what omc_chain.hip allows)
     struct FoldKey { int N = -1; double c0 = 0, g = 0; } fold_key[2];

@@ -250,12 +250,13 @@ struct SeqGroupSlot {
     double* result;       // [8]
     const double* cK;     // the pricing's fold table (LsmProblem::fold_cK); null = full storage: no table build
     double K, invK;
-    int is_put, pad_;
+    int is_put;
+    int N;                // the pricing's own steps, at most the group's (a Bermudan chain entry is a shorter problem)
 };
 struct SeqGroupArgs {
     SeqGroupSlot slot[kSeqGroupMax];
     int64_t ntiles;    // lsm_pass1_sweep
-    int N, nblk;       // nblk: lsm_pass2_sweep
+    int N, nblk;       // N: the longest member's steps (the launches' grids); nblk: lsm_pass2_sweep
     int irr_every, pad_;
 };
 static_assert(sizeof(SeqGroupSlot) == 80 && sizeof(SeqGroupArgs) == 80 * kSeqGroupMax + 24 && sizeof(SeqGroupArgs) <= 4096,

@@ -154,22 +154,23 @@ __global__ __launch_bounds__(kBlock) void lsm_finalize_multi_kernel(const SweepA
 __global__ __launch_bounds__(kBlock) void lsm_reduce_pass1_group_kernel(SeqGroupArgs g)
 {
     const SeqGroupSlot& s = g.slot[blockIdx.y];
-    lsm_reduce_pass1_body(s.part1, s.gmom, g.ntiles, g.N);
+    lsm_reduce_pass1_body(s.part1, s.gmom, g.ntiles, s.N);
 }
 
 __global__ __launch_bounds__(128) void lsm_crit_build_group_kernel(SeqGroupArgs g)
 {
     const SeqGroupSlot& s = g.slot[blockIdx.y];
+    if ((int)blockIdx.x > s.N) return;  // (the grid is sized for the longest member)
     CritArgs a;
     a.gmom = s.gmom; a.betas = s.betas; a.betas_out = s.betas; a.cK = s.cK; a.tab = s.crit;
-    a.N = g.N; a.is_put = s.is_put; a.K = s.K; a.invK = s.invK; a.irr_every = g.irr_every;
+    a.N = s.N; a.is_put = s.is_put; a.K = s.K; a.invK = s.invK; a.irr_every = g.irr_every;
     lsm_crit_build_body(a);
 }
 
 __global__ __launch_bounds__(kBlock) void lsm_finalize_group_kernel(SeqGroupArgs g)
 {
     const SeqGroupSlot& s = g.slot[blockIdx.y];
-    lsm_finalize_body(s.part, s.gmom, s.result, g.nblk, g.N, kPStride);
+    lsm_finalize_body(s.part, s.gmom, s.result, g.nblk, s.N, kPStride);
 }
 
 // ------------------------------------------------------------------ host launchers
@@ -534,7 +535,7 @@ SeqGroupSlot lsm_group_slot(const LsmProblem& p, const LsmWorkspace& w)
     SeqGroupSlot s;
     s.part1 = w.part1; s.gmom = w.gmom; s.betas = w.betas; s.crit = w.crit; s.part = w.part; s.result = w.result;
     s.cK = p.fold_cK;
-    s.K = p.K; s.invK = 1.0 / p.K; s.is_put = p.is_put; s.pad_ = 0;
+    s.K = p.K; s.invK = 1.0 / p.K; s.is_put = p.is_put; s.N = p.N;
     return s;
 }
 
