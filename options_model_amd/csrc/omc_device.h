@@ -17,8 +17,23 @@ constexpr int kNQ = 8;             // quantities reduced together
 // ------------------------------------------------------------------ Philox4x32-10
 // Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3" (SC'11).
 // Round keys are wave-uniform, so they stay in SGPRs; each round is two 32x32->64
-// multiplies (v_mad_u64_u32 / v_mul_hi_u32) plus three XORs per lane.
+// multiplies (v_mad_u64_u32 / v_mul_hi_u32) plus two three-input XORs per lane.
 struct U4 { uint32_t x, y, z, w; };
+
+// a ^ b ^ c in one instruction: v_bitop3_b32 with truth table 0x96 (the compiler does not form it from a ^ b ^ c)
+#ifdef __has_builtin
+#if __has_builtin(__builtin_amdgcn_bitop3_b32)
+#define OMC_HAS_BITOP3 1
+#endif
+#endif
+__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c)
+{
+#ifdef OMC_HAS_BITOP3
+    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
+#else
+    return a ^ b ^ c;  // host-side or older-compiler builds
+#endif
+}
 
 __device__ __forceinline__ U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
                                             uint32_t k0, uint32_t k1)
@@ -27,8 +42,8 @@ __device__ __forceinline__ U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c
     for (int r = 0; r < 10; ++r) {
         const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
         const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        const uint32_t n0 = xor3((uint32_t)(p1 >> 32), c1, k0);
+        const uint32_t n2 = xor3((uint32_t)(p0 >> 32), c3, k1);
         c1 = (uint32_t)p1;
         c3 = (uint32_t)p0;
         c0 = n0;

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Instruction mix of a kernel's hot loop from the gfx950 ISA (hipcc -save-temps), priced with the issue
-intervals measured by tools/ubench.hip (profiles/r02c_ubench.txt).  usage: isa_mix.py <source.hip> <mangled-name-substring> <outputs per loop body>"""
+intervals measured by tools/ubench.hip (profiles/r02c_ubench.txt, profiles/r09_ubench_xor3.txt).  usage: isa_mix.py <source.hip> <mangled-name-substring> <outputs per loop body>"""
 import collections
 import os
 import re
@@ -16,7 +16,24 @@ COST = collections.OrderedDict([
 ])
 
 
+# the Philox round's XORs (profiles/r09_ubench_xor3.txt): the interval depends on whether an operand is an SGPR (the
+# wave-uniform round key).  Such an instruction is counted under "<op> [sgpr]".
+COST_SGPR = {"v_bitop3_b32": (2.5, 4.3), "v_xor_b32": (2.7, 4.2)}  # (VGPR operands only, one SGPR operand)
+SGPR_OPERAND = re.compile(r"[ ,]s(\d+|\[)")
+
+
+def classify(ln):
+    op = ln.split()[0]
+    for k in COST_SGPR:
+        if op.startswith(k) and SGPR_OPERAND.search(ln):
+            return op + " [sgpr]"
+    return op
+
+
 def cost(op):
+    for k, (v, s) in COST_SGPR.items():
+        if op.startswith(k):
+            return s if op.endswith("[sgpr]") else v
     for k, v in COST.items():
         if k in op:
             return v
@@ -38,7 +55,7 @@ def main():
     for ln in loop.split("\n"):
         ln = ln.strip()
         if ln and not ln.startswith((".", ";", "/")) and not ln.endswith(":"):
-            c[ln.split()[0]] += 1
+            c[classify(ln)] += 1
     tot = sum(c.values())
     cyc = sum(cost(k) * v for k, v in c.items())
     print(f"{m.group(1)}\nkernel body: {tot} instructions, {outputs:.0f} outputs per pass -> {tot / outputs:.1f} instructions, "

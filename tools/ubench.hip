@@ -137,6 +137,32 @@ __global__ __launch_bounds__(256) void rate_kernel(float* out, float seed, unsig
         float s = 0;
         for (int i = 0; i < 8; ++i) s += a[i];
         out[tid] = s;
+    } else if constexpr (MODE >= 10 && MODE <= 14) {
+        // the Philox round's three-input XOR, two VGPRs and a wave-uniform key in an SGPR: one v_bitop3_b32 with truth
+        // table 0x96 (MODE 10) against the two v_xor_b32 the compiler makes of a ^ b ^ k (MODE 11).  The empty asm
+        // keeps both vector operands opaque, so b ^ k is not hoisted and no XOR cancels against the next iteration's.
+        // MODE 12: the same v_bitop3_b32 with three VGPR operands; MODE 13 / 14: one v_xor_b32 with a VGPR / the SGPR.
+        uint32_t a[8], b[8];
+        const uint32_t k = blockIdx.x * 0x9E3779B9u + 1u;
+        for (int i = 0; i < 8; ++i) a[i] = (uint32_t)seed + 0x01000193u * i + tid, b[i] = ~a[i] * 0x85EBCA6Bu;
+        for (int it = 0; it < ITER; ++it)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                if constexpr (MODE == 10)
+                    a[i] = __builtin_amdgcn_bitop3_b32(a[i], b[i], k, 0x96);
+                else if constexpr (MODE == 11)
+                    a[i] = a[i] ^ b[i] ^ k;
+                else if constexpr (MODE == 12)
+                    a[i] = __builtin_amdgcn_bitop3_b32(a[i], b[i], b[(i + 1) & 7], 0x96);
+                else if constexpr (MODE == 13)
+                    a[i] = a[i] ^ b[i];
+                else
+                    a[i] = a[i] ^ k;
+                asm volatile("" : "+v"(a[i]), "+v"(b[i]));
+            }
+        uint32_t s = 0;
+        for (int i = 0; i < 8; ++i) s += a[i];
+        out[tid] = (float)s;
     }
 }
 
@@ -184,5 +210,10 @@ int main()
     run<7>("v_pk_fma_f32", 8);
     run<8>("f64 cmp+mul+2 cndmask", 32);
     run<9>("sqrt/log/sin/cos f32 (+add)", 16);
+    run<10>("v_bitop3_b32 0x96 (a^b^k)", 8);
+    run<11>("2 v_xor_b32 (a^b^k)", 16);
+    run<12>("v_bitop3_b32 0x96 (a^b^c)", 8);
+    run<13>("v_xor_b32 (a^b)", 8);
+    run<14>("v_xor_b32 (a^k)", 8);
     return 0;
 }
