@@ -37,6 +37,7 @@ def lib():
         f32p, i64, i32, u64, u32, dbl = (C.c_void_p, C.c_int64, C.c_int, C.c_uint64, C.c_uint32,
                                           C.c_double)
         _lib.orc_philox4x32_10.argtypes = [C.c_void_p] * 3
+        _lib.orc_philox_words.argtypes = [C.c_void_p, i64, u64, u32, u32, u64]
         _lib.orc_gbm_normals_f32.argtypes = [f32p, i64, i64, i32, u64, u32, u64]
         _lib.orc_gbm_paths_f32.argtypes = [f32p, i64, i64, i32, dbl, dbl, dbl, dbl, u64, u32, u64, i32]
         _lib.orc_gbm_paths_from_normals_f32.argtypes = [f32p, i64, i64, i32, dbl, dbl, dbl, dbl,
@@ -75,6 +76,14 @@ def philox4x32_10(ctr, key):
     o = np.zeros(4, np.uint32)
     lib().orc_philox4x32_10(_p(c), _p(k), _p(o))
     return o
+
+
+def philox_words(n_pairs, pair0, c2, stream, seed):
+    """uint32 [n_pairs][4]: the Philox block of counter (pair lo, pair hi, c2, stream low 32 bits), key (seed lo, seed hi),
+    for pairs pair0 .. pair0 + n_pairs - 1"""
+    W = np.empty((n_pairs, 4), np.uint32)
+    lib().orc_philox_words(_p(W), n_pairs, pair0, c2 & 0xFFFFFFFF, stream & 0xFFFFFFFF, seed)
+    return W
 
 
 def gbm_normals(n_pairs, n_steps, seed, stream=0, pair_offset=0):

@@ -76,6 +76,19 @@ void orc_normals4(uint64_t seed, uint64_t pair, uint32_t block, uint32_t stream,
     box_muller(o[2], o[3], &z[2], &z[3]);
 }
 
+/* the four raw words of pairs pair0 .. pair0+n-1 at one third counter word (a normals block index, or a tagged block of
+ * the jump-count 0x40000000, bridge 0x80000000 or jump-size 0xC0000000 domain): W[p][4] */
+void orc_philox_words(uint32_t *W, int64_t n, uint64_t pair0, uint32_t c2, uint32_t stream, uint64_t seed)
+{
+    const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+#pragma omp parallel for schedule(static) if (n >= 65536)
+    for (int64_t p = 0; p < n; ++p) {
+        const uint64_t pair = pair0 + (uint64_t)p;
+        const uint32_t ctr[4] = {(uint32_t)pair, (uint32_t)(pair >> 32), c2, stream};
+        orc_philox4x32_10(ctr, key, W + 4 * p);
+    }
+}
+
 /* dump normals as the GBM generator consumes them: Z[t-1][p], t=1..n_steps (4 steps/block) */
 void orc_gbm_normals_f32(float *Z, int64_t ldz, int64_t n_pairs, int n_steps, uint64_t seed,
                          uint32_t stream, uint64_t pair_offset)

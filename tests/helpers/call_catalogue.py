@@ -112,6 +112,41 @@ def options(ctx, **opts):
             ctx.set_option(k, OPTION_DEFAULTS[k])
 
 
+# ------------------------------------------------------------------ where an entry draws
+class Draw(NamedTuple):
+    seed: int
+    stream: int
+    pair_offset: int
+
+
+_DRAW = None  # set by `drawing`: tests/test_gpu_rng_keys.py runs the entries at keys and counters of its choice
+
+
+@contextlib.contextmanager
+def drawing(seed, stream, pair_offset):
+    """the entries called inside draw at this seed and pair offset and at stream + their own (small) stream, not at
+    their defaults"""
+    global _DRAW
+    before, _DRAW = _DRAW, Draw(int(seed), int(stream), int(pair_offset))
+    try:
+        yield
+    finally:
+        _DRAW = before
+
+
+def draw(seed, stream=0, pair_offset=0):
+    """(seed, stream, pair_offset) of an entry: its own, unless `drawing` says otherwise"""
+    if _DRAW is None:
+        return seed, stream, pair_offset
+    return _DRAW.seed, _DRAW.stream + stream, _DRAW.pair_offset
+
+
+def run_at(name, ctx, seed, stream, pair_offset):
+    """the flat result of entry `name` drawn at (seed, stream, pair_offset)"""
+    with drawing(seed, stream, pair_offset):
+        return flat(BY_NAME[name].call(ctx))
+
+
 # ------------------------------------------------------------------ seeded host data
 def P(cls, **kw):
     M, N = SIZES[cls]
@@ -122,6 +157,7 @@ def P(cls, **kw):
     kw.setdefault("K", K0)
     kw.setdefault("r", R0)
     kw.setdefault("T", T0)
+    kw["seed"], kw["stream"], kw["pair_offset"] = draw(kw["seed"], kw.get("stream", 0), kw.get("pair_offset", 0))
     return _ffi.make_params(**kw)
 
 
@@ -543,7 +579,7 @@ def build_rows(ctx, S_host, K, count_first=True, between=None, S_dev=None, K_cou
 @entry("gbm_paths", "antithetic", "SML")
 def _(ctx, cls):
     M, N = SIZES[cls]
-    S = ctx.gbm_paths(M, N, 100.0, R0, 0.25, T0, 11, 2, 64)
+    S = ctx.gbm_paths(M, N, 100.0, R0, 0.25, T0, *draw(11, 2, 64))
     try:
         return {"S": S.to_host()}
     finally:
@@ -553,7 +589,8 @@ def _(ctx, cls):
 @entry("heston_paths", "scheme1", "SM")
 def _(ctx, cls):
     M, N = SIZES[cls]
-    S = ctx.heston_paths(M, N, 100.0, R0, T0, seed=12, scheme=1, **HES)
+    seed, stream, off = draw(12)
+    S = ctx.heston_paths(M, N, 100.0, R0, T0, seed=seed, stream=stream, pair_offset=off, scheme=1, **HES)
     try:
         return {"S": S.to_host()}
     finally:
@@ -563,7 +600,8 @@ def _(ctx, cls):
 @entry("heston_paths", "scheme3", "SM")
 def _(ctx, cls):
     M, N = SIZES[cls]
-    S = ctx.heston_paths(M, N, 100.0, R0, T0, seed=12, scheme=3, **HES_QE)
+    seed, stream, off = draw(12)
+    S = ctx.heston_paths(M, N, 100.0, R0, T0, seed=seed, stream=stream, pair_offset=off, scheme=3, **HES_QE)
     try:
         return {"S": S.to_host()}
     finally:
@@ -573,7 +611,8 @@ def _(ctx, cls):
 @entry("heston_paths_sv", "scheme0", "SM")
 def _(ctx, cls):
     M, N = SIZES[cls]
-    S, V = ctx.heston_paths_sv(M, N, 100.0, R0, T0, seed=13, scheme=0, **HES)
+    seed, stream, off = draw(13)
+    S, V = ctx.heston_paths_sv(M, N, 100.0, R0, T0, seed=seed, stream=stream, pair_offset=off, scheme=0, **HES)
     try:
         return {"S": S.to_host(), "V": V.to_host()}
     finally:
@@ -602,7 +641,7 @@ def _(ctx, cls):
 @entry("gbm_normals", "tap", "SM")
 def _(ctx, cls):
     M, N = SIZES[cls]
-    Z = ctx.gbm_normals(M // 2, N, 17, 1, 32)
+    Z = ctx.gbm_normals(M // 2, N, *draw(17, 1, 32))
     try:
         return {"Z": Z.to_host()}
     finally:
@@ -634,15 +673,17 @@ def _(ctx, cls):
 @entry("heston_price_strikes", "calibrator", "SM")
 def _(ctx, cls):
     M, N = SIZES[cls]
-    p, e = ctx.heston_price_strikes(M, N, 100.0, R0, T0, strikes=[85.0, 100.0, 110.0, 125.0], seed=21, stream=2, **HES)
+    seed, stream, _ = draw(21, 2)
+    p, e = ctx.heston_price_strikes(M, N, 100.0, R0, T0, strikes=[85.0, 100.0, 110.0, 125.0], seed=seed, stream=stream, **HES)
     return {"prices": p, "stderrs": e}
 
 
 @entry("heston_price_surface", "calibrator", "SM")
 def _(ctx, cls):
     M, N = SIZES[cls]
-    p, e = ctx.heston_price_surface(M, N, 100.0, R0, expiries=[0.25, 1.0, 2.0], streams=[1, 2, 3],
-                                    strikes=[90.0, 100.0, 110.0, 95.0, 105.0], expiry_of=[0, 0, 1, 2, 2], is_put=True, seed=22, **HES)
+    seed, stream, _ = draw(22)
+    p, e = ctx.heston_price_surface(M, N, 100.0, R0, expiries=[0.25, 1.0, 2.0], streams=[stream + 1, stream + 2, stream + 3],
+                                    strikes=[90.0, 100.0, 110.0, 95.0, 105.0], expiry_of=[0, 0, 1, 2, 2], is_put=True, seed=seed, **HES)
     return {"prices": p, "stderrs": e}
 
 
@@ -735,7 +776,7 @@ def _(ctx, cls):
 
 @entry("contnet_init_params", "h32", "SM")
 def _(ctx, cls):
-    d = ctx.contnet_init_params(32 if cls == "S" else 100, SIZES[cls][1] - 1, 9)
+    d = ctx.contnet_init_params(32 if cls == "S" else 100, SIZES[cls][1] - 1, draw(9)[0])
     return {"flat": d["flat"]}
 
 

@@ -13,6 +13,7 @@ typedef struct {
 } orc_lsm_result;
 
 void orc_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
+void orc_philox_words(uint32_t *W, int64_t n, uint64_t pair0, uint32_t c2, uint32_t stream, uint64_t seed);
 void orc_gbm_normals_f32(float *Z, int64_t ldz, int64_t n_pairs, int n_steps, uint64_t seed, uint32_t stream,
                          uint64_t pair_offset);
 void orc_gbm_paths_f32(float *S, int64_t ld, int64_t n_paths, int n_steps, double S0, double r, double sigma,
@@ -43,6 +44,23 @@ int main(void)
     uint32_t ctr[4] = {0, 0, 0, 0}, key[2] = {0, 0}, out[4];
     orc_philox4x32_10(ctr, key, out);
     REQUIRE(out[0] == 0x6627e8d5u && out[3] == 0x9b00dbd8u);
+
+    /* bulk words on an exactly-sized buffer: one pair, an odd count across the 2^32 carry of the pair counter, and a count
+     * above the OpenMP threshold; row p is the scalar function at pair0 + p */
+    const int64_t wn[] = {1, 7, 70001};
+    for (unsigned a = 0; a < sizeof wn / sizeof *wn; ++a) {
+        const uint64_t pair0 = 0xFFFFFFFDull, seed = 0x9E3779B97F4A7C15ull;
+        uint32_t *W = malloc(sizeof(uint32_t) * 4 * (size_t)wn[a]);
+        orc_philox_words(W, wn[a], pair0, 0x80000003u, 0xDEADBEEFu, seed);
+        for (int64_t p = 0; p < wn[a]; p += (wn[a] > 100 ? 997 : 1)) {
+            const uint64_t g = pair0 + (uint64_t)p;
+            uint32_t c[4] = {(uint32_t)g, (uint32_t)(g >> 32), 0x80000003u, 0xDEADBEEFu};
+            uint32_t k[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+            orc_philox4x32_10(c, k, out);
+            REQUIRE(memcmp(out, W + 4 * p, sizeof out) == 0);
+        }
+        free(W);
+    }
 
     const int64_t sizes[] = {2, 6, 10, 1000, 1002, 4096};
     const int steps[] = {1, 2, 7, 50};
