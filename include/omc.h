@@ -157,6 +157,11 @@ int omc_memcpy_d2h(omc_ctx* ctx, void* dst, const void* src, size_t bytes);
  * of the two-pass flow; see omc_seq_step_width and omc_seq_group_width),
  * "chain_fused" / "chain_k" (omc_price_american_chain: 1 / 0 (default) = the fused chain sweeps or the single-strike sweeps per
  * entry; entries per fused launch, -1 = default, 1 .. 16; see omc_chain_width),
+ * "bounds_exercise_every" (omc_price_american_bounds and omc_price_american_bounds_heston with a policy on the spot: 0 =
+ * default or 1 = the game with exercise at every date of the grid; k >= 2 = the game with exercise at every k-th date
+ * counted back from expiry, and at expiry, on paths of the whole grid -- it changes the GAME whose value is bounded, not
+ * the route by which the same numbers are computed; see "an exercise schedule" in the price bounds section.  k < 0 or
+ * k > 2^31 - 1 is refused with -4 and the stored value stays; the other three bounds calls refuse k >= 2 with -38),
  * "alloc_limit" (PER PROCESS, bytes; 0 = none: no single buffer of the library -- path matrix, workspace, row scratch --
  * may grow beyond it; a larger request fails like a hipMalloc that found no room, code 2 = hipErrorOutOfMemory.  A
  * budget for a card shared with other tenants; on a distributed context such a rank-local failure is reported on
@@ -656,7 +661,40 @@ int omc_price_american_basket_greeks(omc_ctx* ctx, const omc_params* p, const om
  * Errors (nothing is launched): omc_params checks as omc_price_american; -12 a model other than GBM; -10 a context with
  * a communicator or all-reduce hook; -4 policy not one of the four; -3 n_lower, n_outer or n_inner odd or < 2;
  * -16 n_outer (N+1) n_inner above 2^32 or n_outer n_inner N (N+1) / 2 (the inner steps of a policy that never
- * exercises) above 2^39; -7 null cfg / out, or betas NULL with OMC_POLICY_GIVEN. */
+ * exercises) above 2^39; -7 null cfg / out, or betas NULL with OMC_POLICY_GIVEN.
+ *
+ * ---- ... with an exercise schedule ----
+ * Option "bounds_exercise_every" = k (omc_set_option; a context option because omc_bounds_config has no free field and the
+ * entry points are frozen: no new symbol, the same struct layout, OMC_ABI_VERSION unchanged).  k = 0 (default) or 1:
+ * everything above, bit for bit.  k >= 2 changes the GAME, not a route: the option whose value is bounded may be exercised at
+ *     tau_j = N - (J - j) k,  j = 1 .. J,  J = (N - 1) / k + 1      (the dates t in 1..N with (N - t) % k == 0; tau_0 = 0)
+ * -- every k-th date counted back from expiry, omc_chain_entry::exercise_every's anchoring, and the expiry itself; k >= N
+ * leaves the expiry alone (J = 1, the European option).  Z_t = D[t] max(phi(S_t), 0) at the scheduled t, the same discount.
+ * Paths: the fine grid's in every sweep.  The lower, outer and inner paths keep their Philox coordinates exactly; inner pair
+ *   j' of item (i, t) is still generator pair (i (N+1) + t) (n_inner/2) + j' of stream_inner, its blocks counted from the
+ *   item's start, so an inner path of a scheduled item is bit for bit the inner path the all-dates call simulates at (i, t).
+ * Policy: the table stays betas [N+1][4].  Rows off the schedule count as n = 0 whatever they hold and come back as zero
+ *   rows in betas_out (row 0 and row N included: no rule is read there).  OMC_POLICY_GIVEN: the caller's scheduled rows.
+ *   Fitted: rows 0, tau_1 .. tau_J of the p->n_paths fitting paths are gathered into a matrix [J+1][ld] and omc_lsm_poly's
+ *   fit of that semantics runs on it with J steps and horizon T_v = T when J k == N, else T (double)(J k) / (double)N (a
+ *   short first gap counts as a whole one); fit row j becomes row tau_j.  The scheduled rows of betas_out carry the bits
+ *   omc_lsm_poly returns for that matrix, (J, T_v) and the same K, r, is_put.
+ * Lower bound: the sweep above on the tables of that policy; a zero row never stops a path.
+ * Upper bound: inner simulations at the dates tau_0 .. tau_{J-1} only,
+ *     Q^_j[i] = mean of Z at the first scheduled date > tau_j where the rule fires (else N), over n_inner inner paths started
+ *               at the outer state at tau_j
+ *     M_0 = 0,  M_j = M_{j-1} + L_j - Q^_{j-1},  L_j = Z_{tau_j} if the policy exercises at tau_j or j = J, else Q^_j
+ *     sample_i = max_{j=1..J} (Z_{tau_j} - M_j)
+ * q_out keeps its shape [n_outer][N]: column tau_j holds Q^_j, every other column 0.0.  inner_path_steps counts steps of
+ *   the fine grid, as above; at most n_outer n_inner sum_{j<J} (N - tau_j).  The -16 limits stay the all-dates formulas
+ *   above, which is conservative: a scheduled call does less work than they allow for.  Option
+ *   "pass2_tables_irregular_every" acts as above.  Identical calls return identical bits.
+ * With the policy P of an all-dates call masked to the schedule (rows off it zeroed) and given to an all-dates call, that
+ *   call's lower, se_lower, n_exercised_lower and its Q^ at the columns tau_j equal the scheduled call's bit for bit.
+ * Taken by omc_price_american_bounds and by omc_price_american_bounds_heston with cfg->regressors = OMC_HESTON_REG_SPOT.
+ * Error -38 (k >= 2 only; after the call's own argument checks, nothing is launched, the outputs are untouched): the
+ *   spot + variance policy of omc_price_american_bounds_heston, omc_price_american_basket_bounds (the Asian kinds included)
+ *   and omc_price_american_basket_bounds_runnerup take no schedule.  Entry points that compute no bounds ignore the option. */
 enum { OMC_POLICY_GIVEN = 3 };
 typedef struct {
     int32_t policy;    /* OMC_SEM_REFERENCE, OMC_SEM_TEXTBOOK, OMC_SEM_TWO_PASS: fitted here; OMC_POLICY_GIVEN: `betas` */
@@ -715,7 +753,8 @@ int omc_price_american_bounds(omc_ctx* ctx, const omc_params* p, const omc_bound
  *   values of the restart call above (kind OMC_BASKET_ARITHMETIC at S0[k] = A_k[t][i]).  The policy sees the average alone.
  * Errors (nothing is launched): -7 null cfg / out; omc_price_american_basket's own (-7, -12, -29 .. -33, the omc_params
  * checks, -24, -11); -34 kind OMC_BASKET_GEOMETRIC; -10 a distributed context; then -4, -7 (betas NULL with
- * OMC_POLICY_GIVEN), -3 and -16 as omc_price_american_bounds. */
+ * OMC_POLICY_GIVEN), -3 and -16 as omc_price_american_bounds; then -38 while option "bounds_exercise_every" holds k >= 2 (no
+ * exercise schedule for the index of several assets, the Asian kinds included; with the option back at 0 the call is as above). */
 typedef struct {
     omc_bounds bounds;
     double index0;          /* the index of the initial spots, float64 (x0 of omc_basket_table) */
@@ -754,7 +793,8 @@ int omc_price_american_basket_bounds(omc_ctx* ctx, const omc_params* p, const om
  * cfg->policy = OMC_POLICY_GIVEN: the caller's table `betas`, host [N+1][8].  betas_out: NULL or host [N+1][8].
  * Errors (nothing is launched): omc_price_american_basket_bounds' own, and -35 kind OMC_BASKET_ARITHMETIC or one asset
  * (OMC_BASKET_GEOMETRIC keeps -34); -4 also for OMC_SEM_REFERENCE and OMC_SEM_TWO_PASS; -16 also for more than 512 dates
- * (the kernels keep the policy rows, 64 bytes per date, in LDS; omc_price_american_basket_bounds has no such cap).
+ * (the kernels keep the policy rows, 64 bytes per date, in LDS; omc_price_american_basket_bounds has no such cap); -38, after
+ * all of these, while option "bounds_exercise_every" holds k >= 2.
  * The Asian kinds, any d in 1 .. 8: the second regressor is the current basket value, Y = B_t, where
  *   best-of and worst-of use the runner-up: the Markov state of the option is (average, spot), and the average alone leaves
  *   the lower bound percent short.  The same table, the same rule on (u, w) with w = fma((double)B, 1/K, -1), the same fit,
@@ -797,6 +837,10 @@ int omc_price_american_basket_bounds_runnerup(omc_ctx* ctx, const omc_params* p,
  * heston_scheme OMC_HESTON_CALIBRATOR (its arithmetic Euler step lets the spot cross zero) or OMC_HESTON_QE (no bounds
  * kernels are built for it); then -10, -4, -7, -3, -16 as
  * omc_price_american_bounds, which itself keeps refusing Heston with -12.
+ * Option "bounds_exercise_every" = k >= 2 (an exercise schedule; "... with an exercise schedule" above, word for word, with the
+ *   inner pairs started at the outer (S, V) state at tau_j and the fit on the gathered Heston paths): taken with
+ *   cfg->regressors = OMC_HESTON_REG_SPOT, schemes 0 and 1; it changes the game, not a route.  On a fine grid it bounds the
+ *   option exercisable at the scheduled dates of the discretised scheme without inner simulations at every step.
  *
  * ---- ... with a policy on the spot and the variance state ----
  * Selector: cfg->regressors = OMC_HESTON_REG_SPOT (0): everything above, bit for bit.  OMC_HESTON_REG_SPOT_VARIANCE (1): a
@@ -828,7 +872,8 @@ int omc_price_american_basket_bounds_runnerup(omc_ctx* ctx, const omc_params* p,
  *   inner paths, inner pairs started at (S_t[i], V_t[i]), Q^, L^, M^, the samples, the standard errors from pair means,
  *   inner_path_steps, the launches of at most 2^29 worst-case inner path steps, the refusals -3, -7, -10, -12, -16.
  * Errors, beside those: -4 a selector other than 0 or 1, or OMC_SEM_REFERENCE / OMC_SEM_TWO_PASS with selector 1; -5
- *   max(v0, theta) not above 0; -16 more than 512 dates (the kernels keep the policy rows, 64 bytes per date, in LDS).
+ *   max(v0, theta) not above 0; -16 more than 512 dates (the kernels keep the policy rows, 64 bytes per date, in LDS);
+ *   -38, after all of these, while option "bounds_exercise_every" holds k >= 2 (selector 1 takes no exercise schedule).
  * Memory: the fit additionally keeps the variance state V [N+1][ld] of its fitting paths on the device. */
 enum { OMC_HESTON_REG_SPOT = 0, OMC_HESTON_REG_SPOT_VARIANCE = 1 };
 int omc_price_american_bounds_heston(omc_ctx* ctx, const omc_params* p, const omc_bounds_config* cfg,

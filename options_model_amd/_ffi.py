@@ -4,6 +4,7 @@ loudly -- there is no CPU fallback in the product path.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import threading
@@ -539,6 +540,8 @@ class DeviceArray:
 class Context:
     """One per (process, device).  Calls on a context are serialised by the caller."""
 
+    _bounds_every = 0  # option "bounds_exercise_every" as last set through this object (the ABI has no getter)
+
     def __init__(self, device: int = 0, stream: int | None = None):
         self.lib = load_library()
         h = C.c_void_p()
@@ -575,6 +578,8 @@ class Context:
 
     def set_option(self, key: str, value: int):
         _check(self.lib, self.lib.omc_set_option(self.handle, key.encode(), int(value)))
+        if key == "bounds_exercise_every":
+            self._bounds_every = int(value)
 
     def set_allreduce_hook(self, fn):
         """fn(dptr:int, count:int) -> None must sum-all-reduce `count` device doubles in place."""
@@ -945,31 +950,50 @@ class Context:
 
     def price_american_bounds(self, params: Params, policy="textbook", n_lower=1_000_000, n_outer=8192, n_inner=1024,
                               stream_lower=None, stream_outer=None, stream_inner=None, betas=None, want_q=False,
-                              want_samples=False):
+                              want_samples=False, exercise_every=0):
         """Andersen-Broadie bounds of the Bermudan game on the grid (omc_price_american_bounds) -> dict with the fields of
         omc_bounds plus `betas` (the policy used, [n_steps+1][4]) and, when asked, `q` ([n_outer][n_steps]: Q^_t) and
         `samples` ([n_outer]).  policy: a key of BOUND_POLICIES or its code; betas: the table of policy "given".  Streams
-        default to params.stream + 1 / 2 / 3."""
+        default to params.stream + 1 / 2 / 3.
+        exercise_every = k >= 2: the game with exercise at every k-th date counted back from expiry (option
+        "bounds_exercise_every", set for this call and put back after it); `betas` has zero rows off the schedule and `q` is
+        zero in the columns that are no scheduled date."""
         return self._bounds(params, None, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner,
-                            betas, want_q, want_samples)
+                            betas, want_q, want_samples, exercise_every=exercise_every)
+
+    @contextlib.contextmanager
+    def _bounds_schedule(self, exercise_every):
+        """option "bounds_exercise_every" = exercise_every for the calls inside, the previous value after them (None: the
+        option stays as the context holds it)"""
+        if exercise_every is None:
+            yield
+            return
+        before = self._bounds_every
+        self.set_option("bounds_exercise_every", int(exercise_every))
+        try:
+            yield
+        finally:
+            self.set_option("bounds_exercise_every", before)
 
     def price_american_bounds_heston(self, params: Params, policy="textbook", n_lower=1_000_000, n_outer=8192,
                                      n_inner=1024, stream_lower=None, stream_outer=None, stream_inner=None, betas=None,
-                                     want_q=False, want_samples=False, regressors="spot"):
+                                     want_q=False, want_samples=False, regressors="spot", exercise_every=0):
         """Andersen-Broadie bounds of the Bermudan game of the discretised Heston scheme on the grid
         (omc_price_american_bounds_heston; scheme reference or full_truncation) -> the dict of price_american_bounds.  The
         policy is a function of the spot alone; the inner paths start at the outer (spot, variance) state.  Streams default
         to params.stream + 1 / 2 / 3.
         regressors="spot+variance" (cfg.regressors = 1; policy "textbook" or "given", at most 512 steps): the policy sees the
         spot and the variance state, w = V / max(v0, theta) - 1, and `betas` (given and returned) is [n_steps+1][8] =
-        c0 .. c5, n, 0.  A key of HESTON_BOUND_REGRESSORS or its code."""
+        c0 .. c5, n, 0.  A key of HESTON_BOUND_REGRESSORS or its code.
+        exercise_every: as price_american_bounds takes it, with regressors "spot" (the spot + variance policy refuses a
+        schedule with -38)."""
         if isinstance(regressors, str):
             if regressors not in HESTON_BOUND_REGRESSORS:
                 raise ValueError(f"regressors must be one of {list(HESTON_BOUND_REGRESSORS)}.")
             regressors = HESTON_BOUND_REGRESSORS.index(regressors)
         return self._bounds(params, None, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner,
                             betas, want_q, want_samples, 8 if int(regressors) == 1 else 4, heston=True,
-                            regressors=int(regressors))
+                            regressors=int(regressors), exercise_every=exercise_every)
 
     def price_american_basket_bounds(self, params: Params, basket: Basket, policy="textbook", n_lower=1_000_000,
                                      n_outer=8192, n_inner=1024, stream_lower=None, stream_outer=None, stream_inner=None,
@@ -987,7 +1011,7 @@ class Context:
                             betas, want_q, want_samples, 4 if regressors == "index" else 8)
 
     def _bounds(self, params, basket, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner, betas,
-                want_q, want_samples, cols=4, heston=False, regressors=0):
+                want_q, want_samples, cols=4, heston=False, regressors=0, exercise_every=None):
         N = int(params.n_steps)
         cfg = BoundsConfig()
         cfg.regressors = regressors  # read by the Heston entry point alone
@@ -1010,7 +1034,8 @@ class Context:
         if basket is None:
             out = Bounds()
             entry = self.lib.omc_price_american_bounds_heston if heston else self.lib.omc_price_american_bounds
-            _check(self.lib, entry(self.handle, C.byref(params), C.byref(cfg), *tail, C.byref(out)))
+            with self._bounds_schedule(exercise_every):  # (the multi-asset calls below leave the option as it is)
+                _check(self.lib, entry(self.handle, C.byref(params), C.byref(cfg), *tail, C.byref(out)))
             d = {k: getattr(out, k) for k, _ in Bounds._fields_}
         else:
             bb = BasketBounds()

@@ -230,17 +230,29 @@ def exercise_dates(n_steps, exercise_every):
     return [t for t in range(1, N) if k < 2 or (N - t) % k == 0]
 
 
+def _one_schedule(k):
+    """one exercise_every -> a non-negative int (ValueError otherwise)"""
+    if isinstance(k, bool) or not isinstance(k, (int, float)) and not hasattr(k, "__index__"):
+        raise ValueError("exercise_every must be a non-negative integer.")
+    if isinstance(k, float) and not (math.isfinite(k) and k == int(k)):
+        raise ValueError("exercise_every must be a non-negative integer.")
+    k = int(k)
+    if k < 0 or k > 2 ** 31 - 1:
+        raise ValueError("exercise_every must be a non-negative integer.")
+    return k
+
+
+def bounds_exercise_dates(n_steps, exercise_every):
+    """The exercise dates of the price bounds' game on a grid of n_steps dates (option "bounds_exercise_every"): every date
+    1 .. n_steps for 0 or 1, else the dates of exercise_dates -- every k-th date counted back from expiry -- and the expiry
+    itself: (n_steps - 1) // k + 1 dates."""
+    N, k = int(n_steps), _one_schedule(exercise_every)
+    return [t for t in range(1, N + 1) if k < 2 or (N - t) % k == 0]
+
+
 def _schedules(exercise_every, n):
     """exercise_every of price_american_chain -> one non-negative int per strike (ValueError otherwise)."""
-    def one(k):
-        if isinstance(k, bool) or not isinstance(k, (int, float)) and not hasattr(k, "__index__"):
-            raise ValueError("exercise_every must be a non-negative integer.")
-        if isinstance(k, float) and not (math.isfinite(k) and k == int(k)):
-            raise ValueError("exercise_every must be a non-negative integer.")
-        k = int(k)
-        if k < 0 or k > 2 ** 31 - 1:
-            raise ValueError("exercise_every must be a non-negative integer.")
-        return k
+    one = _one_schedule
     if exercise_every is None:
         return [0] * n
     if isinstance(exercise_every, (str, bytes)):
@@ -812,15 +824,22 @@ class BoundsResult:
     betas: object
     option_type: str
     timings_ms: dict = field(default_factory=dict)
+    exercise_every: int = 0  # 0 = every date of the grid; k >= 2: every k-th date counted back from expiry (section 25)
+    n_exercise_dates: int = 0  # the dates of the game, the expiry included (0: not recorded)
 
 
 def price_american_bounds(S0, K, r, sigma, T, n_paths, n_steps, option_type="put", policy="textbook", n_lower=1_000_000,
                           n_outer=8192, n_inner=1024, seed=42, stream=0, betas=None, device=None,
-                          ctx=None) -> BoundsResult:
+                          ctx=None, exercise_every=0) -> BoundsResult:
     """Lower and upper bounds on the Bermudan value of a GBM put / call (omc_price_american_bounds).
     policy: "textbook" (classic Longstaff-Schwartz fits, the best of the library's policies), "two_pass" or "reference"
     (the fits of the headline flows), each fitted on n_paths paths at (seed, stream); or "given" with `betas`
-    [n_steps+1][4].  The lower-bound, outer and inner paths use Philox streams stream + 1, + 2, + 3.  One GPU."""
+    [n_steps+1][4].  The lower-bound, outer and inner paths use Philox streams stream + 1, + 2, + 3.  One GPU.
+    exercise_every = k >= 2: the bounds of the game with exercise at every k-th date counted back
+    from expiry, and at expiry, on paths of the whole grid; `betas` then has zero rows off the schedule."""
+    if exercise_every is None or isinstance(exercise_every, (list, tuple)):
+        raise ValueError("exercise_every must be a non-negative integer.")
+    every = _one_schedule(exercise_every)
     if policy not in _ffi.BOUND_POLICIES:
         raise ValueError(f"policy must be one of {sorted(_ffi.BOUND_POLICIES)}.")
     if (policy == "given") != (betas is not None):
@@ -836,14 +855,15 @@ def price_american_bounds(S0, K, r, sigma, T, n_paths, n_steps, option_type="put
     p = _ffi.make_params(is_put=(option_type == "put"), semantics="two_pass", n_paths=M, n_steps=int(n_steps), S0=S0, K=K,
                          r=r, sigma=sigma, T=T, seed=seed, stream=stream)
     out = c.price_american_bounds(p, policy=policy, n_lower=int(n_lower), n_outer=int(n_outer), n_inner=int(n_inner),
-                                  betas=betas)
+                                  betas=betas, exercise_every=every)
     return BoundsResult(lower=out["lower"], se_lower=out["se_lower"], upper=out["upper"], se_upper=out["se_upper"],
                         ci_lo=out["ci_lo"], ci_hi=out["ci_hi"], n_lower=out["n_lower"], n_outer=out["n_outer"],
                         n_inner=out["n_inner"], n_exercised_lower=out["n_exercised_lower"],
                         inner_path_steps=out["inner_path_steps"], policy=policy, betas=out["betas"],
                         option_type=option_type,
                         timings_ms=dict(fit=out["ms_fit"], lower=out["ms_lower"], upper=out["ms_upper"],
-                                        total=out["ms_total"]))
+                                        total=out["ms_total"]),
+                        exercise_every=every, n_exercise_dates=len(bounds_exercise_dates(n_steps, every)))
 
 
 @dataclass
@@ -859,7 +879,7 @@ class HestonBoundsResult(BoundsResult):
 def price_american_bounds_heston(S0, K, r, T, n_paths, n_steps, heston_params=None, heston_scheme="reference",
                                  option_type="put", policy="textbook", n_lower=1_000_000, n_outer=8192, n_inner=1024,
                                  seed=42, stream=0, betas=None, device=None, ctx=None,
-                                 regressors="spot") -> HestonBoundsResult:
+                                 regressors="spot", exercise_every=0) -> HestonBoundsResult:
     """Lower and upper bounds on the Bermudan value of a put / call under the Heston model
     (omc_price_american_bounds_heston): price_american_bounds with Heston paths.  heston_params as
     price_american_option takes them (v0, kappa, theta, xi, rho; the defaults of heston_defaults at sigma = 0.2);
@@ -871,7 +891,13 @@ def price_american_bounds_heston(S0, K, r, T, n_paths, n_steps, heston_params=No
     regressors="spot+variance" (DESIGN.md section 21): the policy also sees the variance state, the other half of the Markov
     state, as w = V / max(v0, theta) - 1 (`variance_scale` of the result: a scale for conditioning only, which a `given`
     table must share).  policy is then "textbook" or "given", n_steps at most 512, and `betas` is [n_steps+1][8] = c0, c1,
-    c2 (1, u, u^2 of the spot), c3, c4 (w, w^2 of the variance), c5 (u w), n, 0."""
+    c2 (1, u, u^2 of the spot), c3, c4 (w, w^2 of the variance), c5 (u w), n, 0.
+    exercise_every = k >= 2: as price_american_bounds takes it, with regressors "spot" only."""
+    if exercise_every is None or isinstance(exercise_every, (list, tuple)):
+        raise ValueError("exercise_every must be a non-negative integer.")
+    every = _one_schedule(exercise_every)
+    if every >= 2 and regressors == "spot+variance":
+        raise ValueError("the spot + variance policy takes no exercise schedule (exercise_every must be 0 or 1).")
     if policy not in _ffi.BOUND_POLICIES:
         raise ValueError(f"policy must be one of {sorted(_ffi.BOUND_POLICIES)}.")
     if (policy == "given") != (betas is not None):
@@ -901,7 +927,7 @@ def price_american_bounds_heston(S0, K, r, T, n_paths, n_steps, heston_params=No
                          seed=seed, stream=stream, **hp)
     c = ctx or _ffi.default_context(device)
     out = c.price_american_bounds_heston(p, policy=policy, n_lower=int(n_lower), n_outer=int(n_outer),
-                                         n_inner=int(n_inner), betas=betas, regressors=regressors)
+                                         n_inner=int(n_inner), betas=betas, regressors=regressors, exercise_every=every)
     return HestonBoundsResult(lower=out["lower"], se_lower=out["se_lower"], upper=out["upper"], se_upper=out["se_upper"],
                               ci_lo=out["ci_lo"], ci_hi=out["ci_hi"], n_lower=out["n_lower"], n_outer=out["n_outer"],
                               n_inner=out["n_inner"], n_exercised_lower=out["n_exercised_lower"],
@@ -909,7 +935,31 @@ def price_american_bounds_heston(S0, K, r, T, n_paths, n_steps, heston_params=No
                               option_type=option_type,
                               timings_ms=dict(fit=out["ms_fit"], lower=out["ms_lower"], upper=out["ms_upper"],
                                               total=out["ms_total"]),
-                              regressors=regressors, variance_scale=max(float(hp["v0"]), float(hp["theta"])))
+                              regressors=regressors, variance_scale=max(float(hp["v0"]), float(hp["theta"])),
+                              exercise_every=every, n_exercise_dates=len(bounds_exercise_dates(n_steps, every)))
+
+
+def price_bermudan_bounds(S0, K, r, sigma, T, n_paths, n_steps, exercise_every, model="GBM", option_type="put",
+                          policy="textbook", n_lower=1_000_000, n_outer=8192, n_inner=1024, heston_params=None,
+                          heston_scheme="reference", seed=42, stream=0, betas=None, device=None, ctx=None) -> BoundsResult:
+    """Lower and upper bounds on the value of a Bermudan option that may be exercised at every exercise_every-th date of a
+    grid of n_steps dates, counted back from expiry, and at expiry: price_american_bounds (model
+    "GBM") or price_american_bounds_heston (model "Heston", a policy on the spot; sigma only sets the defaults of
+    heston_defaults) with that schedule.  0 or 1 is the game on every date, exercise_every >= n_steps the European option.
+    The bracket for the quote of price_bermudan_option, which is a two-pass-flow value and lies above `upper`."""
+    if exercise_every is None or isinstance(exercise_every, (list, tuple)):
+        raise ValueError("exercise_every must be a non-negative integer.")
+    model_l = str(model).lower()
+    if model_l == "gbm":
+        return price_american_bounds(S0, K, r, sigma, T, n_paths, n_steps, option_type=option_type, policy=policy,
+                                     n_lower=n_lower, n_outer=n_outer, n_inner=n_inner, seed=seed, stream=stream, betas=betas,
+                                     device=device, ctx=ctx, exercise_every=exercise_every)
+    if model_l == "heston":
+        return price_american_bounds_heston(S0, K, r, T, n_paths, n_steps, heston_params=heston_defaults(sigma, heston_params),
+                                            heston_scheme=heston_scheme, option_type=option_type, policy=policy,
+                                            n_lower=n_lower, n_outer=n_outer, n_inner=n_inner, seed=seed, stream=stream,
+                                            betas=betas, device=device, ctx=ctx, exercise_every=exercise_every)
+    raise ValueError("model must be 'GBM' or 'Heston'.")
 
 
 @dataclass

@@ -819,6 +819,10 @@ int omc_set_option(omc_ctx* c, const char* key, int64_t value)
     else if (!strcmp(key, "seq_event_stride")) c->seq_event_stride = value > 0 ? (int)value : 0;
     else if (!strcmp(key, "seq_step_k")) c->seq_step_k = value < 0 ? -1 : (int)(value > 32 ? 32 : value);
     else if (!strcmp(key, "seq_two_pass_k")) c->seq_two_pass_k = value < 0 ? -1 : (int)(value > 32 ? 32 : value);
+    else if (!strcmp(key, "bounds_exercise_every")) {
+        if (value < 0 || value > 2147483647) return fail(-4, "bounds_exercise_every must be in 0 .. 2^31 - 1.");
+        c->bounds_every = value;
+    }
     else if (!strcmp(key, "chain_fused")) c->chain_fused = value ? 1 : 0;
     else if (!strcmp(key, "chain_k")) c->chain_k = value < 1 ? -1 : (int)(value > 16 ? 16 : value);
     else if (!strcmp(key, "seq_step_wgs")) c->seq_step_wgs = value > 0 ? (int)value : 0;

@@ -31,6 +31,12 @@ int run_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg, co
     if ((double)no * (double)(N + 1) * (double)ni > kMaxItemPairs || (double)no * work1 > kMaxInnerSteps)
         return fail(-16, "bounds request too large: n_outer (N+1) n_inner must be <= 2^32 and n_outer n_inner N (N+1) / 2 "
                          "<= 2^39.");
+    // an exercise schedule (option "bounds_exercise_every" = k >= 2): the flows that bring the scheduled inner sweep take it
+    if (c->bounds_every >= 2 && !f.inner_sched)
+        return fail(-38, "option bounds_exercise_every: these bounds take no exercise schedule (one asset, a policy on the "
+                         "spot: omc_price_american_bounds, omc_price_american_bounds_heston with regressors spot).");
+    const bool sched = c->bounds_every >= 2;
+    const omc::BoundsSched sc = sched ? omc::bounds_schedule(N, c->bounds_every) : omc::BoundsSched{};
     hipStream_t st = c->stream;
     const bool fitted = policy != OMC_POLICY_GIVEN;
     const int64_t M = fitted ? p->n_paths : 2;
@@ -38,8 +44,10 @@ int run_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg, co
     if ((rc = prepare_lsm(c, M, N, p->r, p->T, policy == OMC_SEM_TWO_PASS, true, &w))) return rc;
     const bool own = (bool)f.own_policy;  // the flow brings its policy, its walk and its read-back
     if (!fitted && !own && (rc = upload_fits(c, w, betas, N))) return rc;
+    if (!fitted && sched) HIP_TRY(omc::bounds_sched_policy(st, w.betas, w.betas, N, sc, false));  // zero rows off the schedule
     // the workspace: outer paths [N+1][n_outer] f32 | the flow's own room | Q^ [n_outer][N] | samples [n_outer] | tables
-    // [N+1][8] u32 | partials [8][kPStride] | sums [16] | inner step count
+    // [N+1][8] u32 | partials [8][kPStride] | sums [16] | inner step count | with a schedule: the fit's discounts [J+1] | its
+    // fits [J+1][4]
     const size_t o_extra = up256(sizeof(float) * (size_t)(N + 1) * (size_t)no);
     const size_t o_q = o_extra + up256(f.extra_bytes);
     const size_t o_smp = o_q + up256(sizeof(double) * (size_t)no * (size_t)N);
@@ -47,7 +55,9 @@ int run_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg, co
     const size_t o_part = o_tab + up256(sizeof(uint32_t) * 8 * (size_t)(N + 1));
     const size_t o_res = o_part + up256(sizeof(double) * 8 * omc::kMaxLsmBlocks);
     const size_t o_steps = o_res + up256(sizeof(double) * 16);
-    if ((rc = c->bnd.ensure(o_steps + 256))) return rc;
+    const size_t o_fD = o_steps + 256;
+    const size_t o_fb = o_fD + (sched ? up256(sizeof(double) * (size_t)(sc.J + 1)) : 0);
+    if ((rc = c->bnd.ensure(o_fb + (sched ? sizeof(double) * 4 * (size_t)(sc.J + 1) : 0)))) return rc;
     char* b = (char*)c->bnd.p;
     double* res = (double*)(b + o_res);
 
@@ -61,6 +71,22 @@ int run_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg, co
     a.steps = (unsigned long long*)(b + o_steps);
     a.part = (double*)(b + o_part);
     f.bind(a, b + o_extra);
+    // With a schedule the fit is omc_lsm_poly's on the J scheduled dates: its horizon T_v = T (J k) / N counts a short first
+    // gap as a whole one, and its discount table is ensure_discounts' for (J, r, T_v)
+    omc::LsmWorkspace wf = w;
+    double Tv = p->T;
+    if (sched && fitted) {
+        const int64_t Jk = (int64_t)sc.J * c->bounds_every;
+        if (Jk != N) Tv = p->T * (double)Jk / (double)N;
+        std::vector<double> hD((size_t)sc.J + 1);
+        const double dt = Tv / sc.J;
+        for (int k = 0; k <= sc.J; ++k) hD[(size_t)k] = std::exp(-p->r * dt * (double)k);
+        wf.D = (double*)(b + o_fD);
+        wf.betas = (double*)(b + o_fb);
+        HIP_TRY(hipMemcpyAsync(wf.D, hD.data(), sizeof(double) * hD.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));  // hD is pageable host memory
+        HIP_TRY(hipMemsetAsync(wf.betas, 0, sizeof(double) * 4 * (size_t)(sc.J + 1), st));
+    }
 
     HIP_TRY(hipEventRecord(c->ev[0], st));
     if (own) {
@@ -73,8 +99,15 @@ int run_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg, co
         int64_t ld = 0;
         if ((rc = ensure_paths(c, p, Storage::full_only, &S, &ld))) return rc;
         if ((rc = f.fit_paths(S, ld))) return rc;
-        omc::LsmProblem prob{S, ld, M, N, a.is_put, p->K, p->r, p->T};
-        if ((rc = enqueue_lsm(c, prob, w, policy, false))) return rc;
+        if (sched) {  // rows 0, tau_1 .. tau_J of the fitting paths, J steps; fit row j is the policy's row tau_j
+            HIP_TRY(omc::bounds_sched_gather(st, S, ld, sc));
+            omc::LsmProblem prob{S, ld, M, sc.J, a.is_put, p->K, p->r, Tv};
+            if ((rc = enqueue_lsm(c, prob, wf, policy, false))) return rc;
+            HIP_TRY(omc::bounds_sched_policy(st, wf.betas, w.betas, N, sc, true));
+        } else {
+            omc::LsmProblem prob{S, ld, M, N, a.is_put, p->K, p->r, p->T};
+            if ((rc = enqueue_lsm(c, prob, w, policy, false))) return rc;
+        }
     }
     HIP_TRY(hipEventRecord(c->ev[1], st));
     if (!own) {
@@ -88,10 +121,22 @@ int run_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg, co
     HIP_TRY(f.outer(st));
     HIP_TRY(hipMemsetAsync(a.steps, 0, sizeof(unsigned long long), st));
     // launches over blocks of outer paths, each at most kLaunchSteps / d inner path steps even if the policy never exercises
-    int64_t blk = (int64_t)(kLaunchSteps / (double)f.d / work1);
+    // (a schedule: the scheduled worst case n_inner sum_j (N - tau_j), j = 0 .. J-1)
+    double launch_work = work1;
+    if (sched) {
+        launch_work = (double)ni * (double)N;
+        for (int j = 1; j < sc.J; ++j) launch_work += (double)ni * (double)(N - (sc.tau1 + (j - 1) * sc.k));
+        // Q^ keeps its shape [n_outer][N]; the sweep writes the scheduled columns, the others read 0
+        HIP_TRY(hipMemsetAsync(a.q, 0, sizeof(double) * (size_t)no * (size_t)N, st));
+    }
+    int64_t blk = (int64_t)(kLaunchSteps / (double)f.d / launch_work);
     blk = blk < 1 ? 1 : (blk > no ? no : blk);
-    for (int64_t i0 = 0; i0 < no; i0 += blk) HIP_TRY(f.inner(st, i0, no - i0 < blk ? no - i0 : blk));
-    HIP_TRY(own ? f.walk(st, res + 8) : omc::bounds_walk(st, a, res + 8));
+    for (int64_t i0 = 0; i0 < no; i0 += blk) {
+        const int64_t n = no - i0 < blk ? no - i0 : blk;
+        HIP_TRY(sched ? f.inner_sched(st, sc, i0, n) : f.inner(st, i0, n));
+    }
+    if (sched) HIP_TRY(omc::bounds_sched_walk(st, a, sc, res + 8));
+    else HIP_TRY(own ? f.walk(st, res + 8) : omc::bounds_walk(st, a, res + 8));
     HIP_TRY(hipEventRecord(c->ev[3], st));
     double h[16];
     unsigned long long steps = 0;
@@ -148,5 +193,8 @@ extern "C" int omc_price_american_bounds(omc_ctx* c, const omc_params* p, const 
                                      (uint32_t)cfg->stream_outer, 0, 1, c->gbm_vec);
     };
     f.inner = [&](hipStream_t st, int64_t i0, int64_t ni) { return omc::bounds_inner(st, a, i0, ni); };
+    f.inner_sched = [&](hipStream_t st, const omc::BoundsSched& sc, int64_t i0, int64_t ni) {
+        return omc::bounds_sched_inner(st, a, sc, i0, ni);
+    };
     return run_bounds(c, p, cfg, betas, betas_out, q_out, samples_out, out, f);
 }

@@ -37,4 +37,21 @@ hipError_t bounds_inner(hipStream_t st, const BoundsArgs& a, int64_t i0, int64_t
 int64_t bounds_walk_blocks(const BoundsArgs& a);
 hipError_t bounds_walk(hipStream_t st, const BoundsArgs& a, double* result);
 
+// An exercise schedule on the grid of N steps (option "bounds_exercise_every" = k >= 2): the dates
+// tau_j = tau1 + (j - 1) k, j = 1 .. J, with tau_J = N, and tau_0 = 0.  bounds_schedule(N, k) builds it; the launchers below
+// refuse (hipErrorInvalidValue) one that does not end at N, on which the inner sweep's termination rests.
+struct BoundsSched {
+    int k, J, tau1;
+};
+BoundsSched bounds_schedule(int N, int64_t every);  // every >= 2; k = min(every, N), J = (N - 1) / k + 1
+bool bounds_schedule_ok(const BoundsSched& sc, int N);
+// Q^ at the dates tau_0 .. tau_{J-1} for outer paths [i0, i0 + ni): column tau_j of a.q (the other columns are not written)
+hipError_t bounds_sched_inner(hipStream_t st, const BoundsArgs& a, const BoundsSched& sc, int64_t i0, int64_t ni);
+hipError_t bounds_sched_walk(hipStream_t st, const BoundsArgs& a, const BoundsSched& sc, double* result);
+// rows 0, tau_1 .. tau_J of S [N+1][ld] to its rows 0 .. J, in place
+hipError_t bounds_sched_gather(hipStream_t st, float* S, int64_t ld, const BoundsSched& sc);
+// dst [N+1][4] <- the scheduled rows of src (gathered: src is [J+1][4], row j for date tau_j; else src is [N+1][4] and may be
+// dst), zero rows elsewhere
+hipError_t bounds_sched_policy(hipStream_t st, const double* src, double* dst, int N, const BoundsSched& sc, bool gathered);
+
 }  // namespace omc

@@ -17,6 +17,7 @@
 // The lower and the inner sweep are bounds_lower_body / bounds_inner_body (omc_bounds_dev.h), which the multi-asset
 // kernels share; this file supplies their path law, one GBM asset, and the walk.
 #include "omc_bounds_dev.h"
+#include "omc_bounds_sched_dev.h"
 
 namespace omc {
 
@@ -132,6 +133,80 @@ hipError_t bounds_walk(hipStream_t st, const BoundsArgs& a, double* result)
     const int nblk = (int)bounds_walk_blocks(a);
     hipLaunchKernelGGL(bounds_walk_kernel, dim3(nblk), dim3(kBlock), 0, st, a, nblk);
     return lsm_finalize(st, a.part, nullptr, result, nblk, 0);
+}
+
+// ------------------------------------------------------------------ an exercise schedule
+// the sweeps of omc_bounds_sched_dev.h with the GBM path law, and what is the same under every law that decides on the spot:
+// the walk over the scheduled dates, the gather of the fit's rows, the scatter of the policy
+BoundsSched bounds_schedule(int N, int64_t every)
+{
+    BoundsSched sc;
+    sc.k = every >= N ? N : (int)every;  // beyond N every schedule is the expiry alone
+    sc.J = (N - 1) / sc.k + 1;
+    sc.tau1 = N - (sc.J - 1) * sc.k;
+    return sc;
+}
+
+bool bounds_schedule_ok(const BoundsSched& sc, int N)
+{
+    return sc.k >= 1 && sc.J >= 1 && sc.tau1 >= 1 && sc.tau1 <= sc.k && (int64_t)sc.tau1 + (int64_t)(sc.J - 1) * sc.k == N;
+}
+
+__global__ __launch_bounds__(kBlock) void bounds_sched_inner_kernel(BoundsArgs a, BoundsSched sc, int64_t i0, int64_t ni)
+{
+    extern __shared__ uint4 sh_bt[];
+    bounds_sched_inner_body(a, sc, GbmBoundsModel{a}, i0, ni, sh_bt);
+}
+
+hipError_t bounds_sched_inner(hipStream_t st, const BoundsArgs& a, const BoundsSched& sc, int64_t i0, int64_t ni)
+{
+    if (!bounds_schedule_ok(sc, a.N)) return hipErrorInvalidValue;
+    const int64_t items = ni * sc.J;
+    int64_t g = (items + 3) / 4;
+    if (g > 2048) g = 2048;
+    hipLaunchKernelGGL(bounds_sched_inner_kernel, dim3((unsigned)g), dim3(kBlock), sizeof(uint4) * (size_t)(a.N + 1), st, a,
+                       sc, i0, ni);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(kBlock) void bounds_sched_walk_kernel(BoundsArgs a, BoundsSched sc, int nblk)
+{
+    __shared__ double red[kNQ * kRedStride];
+    bounds_sched_walk_body(a, sc, nblk, red);
+}
+
+hipError_t bounds_sched_walk(hipStream_t st, const BoundsArgs& a, const BoundsSched& sc, double* result)
+{
+    if (!bounds_schedule_ok(sc, a.N)) return hipErrorInvalidValue;
+    const int nblk = (int)bounds_walk_blocks(a);
+    hipLaunchKernelGGL(bounds_sched_walk_kernel, dim3(nblk), dim3(kBlock), 0, st, a, sc, nblk);
+    return lsm_finalize(st, a.part, nullptr, result, nblk, 0);
+}
+
+__global__ __launch_bounds__(kBlock) void bounds_sched_gather_kernel(float* S, int64_t ld, BoundsSched sc)
+{
+    bounds_sched_gather_body(S, ld, sc);
+}
+
+hipError_t bounds_sched_gather(hipStream_t st, float* S, int64_t ld, const BoundsSched& sc)
+{
+    if (ld <= 0) return hipSuccess;
+    hipLaunchKernelGGL(bounds_sched_gather_kernel, dim3((unsigned)((ld + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, S, ld, sc);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(kBlock) void bounds_sched_policy_kernel(const double* src, double* dst, int N, BoundsSched sc,
+                                                                     int gathered)
+{
+    bounds_sched_policy_body(src, dst, N, sc, gathered);
+}
+
+hipError_t bounds_sched_policy(hipStream_t st, const double* src, double* dst, int N, const BoundsSched& sc, bool gathered)
+{
+    if (!bounds_schedule_ok(sc, N)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(bounds_sched_policy_kernel, dim3((unsigned)((N + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, src,
+                       dst, N, sc, gathered ? 1 : 0);
+    return hipGetLastError();
 }
 
 }  // namespace omc

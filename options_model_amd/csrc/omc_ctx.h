@@ -172,6 +172,10 @@ struct BoundsFlow {
     std::function<hipError_t(hipStream_t, double* result)> lower;
     std::function<hipError_t(hipStream_t)> outer;  // the outer paths into a.So (and what the caller keeps in `extra`)
     std::function<hipError_t(hipStream_t, int64_t i0, int64_t ni)> inner;
+    // The schedule (option "bounds_exercise_every" = k >= 2; default: none).  A flow that sets it takes
+    // the context's schedule -- Q^ at the scheduled dates only, with run_bounds' own fit on the gathered rows and walk over
+    // the scheduled dates -- and one that leaves it empty is refused (-38) while the option holds a schedule.
+    std::function<hipError_t(hipStream_t, const omc::BoundsSched& sc, int64_t i0, int64_t ni)> inner_sched;
     // A policy of the flow's own (omc_api_runnerup_bounds.hip: a rule on two regressors), all three set or none.  With them
     // run_bounds neither uploads nor fits a [N+1][4] table and builds no exercise tables:
     //   own_policy(w, S, ld)   between the fit events: the caller's table to the device (S == nullptr), or the fit on the
@@ -289,6 +293,7 @@ struct omc_ctx {
     DevBuf gk_part, gk_res;  // omc_price_american_greeks: per-workgroup partials, reduced sums
     DevBuf bar_part, bar_res;  // omc_price_barrier: the generator's per-workgroup partials, reduced sums
     DevBuf div_tab;            // omc_price_american_div: the dividend steps of the call (omc::DivEntry)
+    int64_t bounds_every = 0;  // option "bounds_exercise_every": 0 / 1 every date, k >= 2 the bounds of the scheduled game
     DevBuf bnd;                // omc_price_american_bounds: outer paths, Q^ table, samples, tables, partials, sums
     DevBuf chain_fold;         // omc_price_american_chain: the entries' fold tables + c0 (their small buffers: gstate)
     DevBuf chain_sched;        // ... and its Bermudan entries' tables on their scheduled dates (omc::chain_schedule_tables)

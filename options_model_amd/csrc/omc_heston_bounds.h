@@ -22,5 +22,8 @@ hipError_t launch_heston_paths_sv(hipStream_t st, float* S, float* V, int64_t ld
 // bounds_lower / bounds_inner (omc_bounds.h) under the Heston path law; scheme 0 or 1, anything else is hipErrorInvalidValue
 hipError_t heston_bounds_lower(hipStream_t st, const BoundsArgs& a, const HestonBoundsLaw& h, double* result);
 hipError_t heston_bounds_inner(hipStream_t st, const BoundsArgs& a, const HestonBoundsLaw& h, int64_t i0, int64_t ni);
+// bounds_sched_inner (omc_bounds.h) under the Heston path law: Q^ at the scheduled dates only
+hipError_t heston_bounds_sched_inner(hipStream_t st, const BoundsArgs& a, const HestonBoundsLaw& h, const BoundsSched& sc,
+                                     int64_t i0, int64_t ni);
 
 }  // namespace omc

@@ -13,6 +13,7 @@
 #include "omc_heston_bounds.h"
 
 #include "omc_bounds_dev.h"
+#include "omc_bounds_sched_dev.h"
 #include "omc_paths_dev.h"
 
 namespace omc {
@@ -74,6 +75,15 @@ __global__ __launch_bounds__(kBlock) void heston_bounds_inner_kernel(HestonBound
 {
     extern __shared__ uint4 sh_bt[];
     bounds_inner_body(g.v, HestonBoundsModel<SCHEME>{g}, i0, ni, sh_bt);
+}
+
+// the inner sweep of an exercise schedule (omc_bounds_sched_dev.h) under the Heston law
+template <int SCHEME>
+__global__ __launch_bounds__(kBlock) void heston_bounds_sched_inner_kernel(HestonBoundsArgs g, BoundsSched sc, int64_t i0,
+                                                                           int64_t ni)
+{
+    extern __shared__ uint4 sh_bt[];
+    bounds_sched_inner_body(g.v, sc, HestonBoundsModel<SCHEME>{g}, i0, ni, sh_bt);
 }
 
 // ------------------------------------------------------------------ the generator that keeps the variance
@@ -162,6 +172,22 @@ hipError_t heston_bounds_inner(hipStream_t st, const BoundsArgs& a, const Heston
         hipLaunchKernelGGL((heston_bounds_inner_kernel<0>), dim3((unsigned)nb), dim3(kBlock), lds, st, g, i0, ni);
     else
         hipLaunchKernelGGL((heston_bounds_inner_kernel<1>), dim3((unsigned)nb), dim3(kBlock), lds, st, g, i0, ni);
+    return hipGetLastError();
+}
+
+hipError_t heston_bounds_sched_inner(hipStream_t st, const BoundsArgs& a, const HestonBoundsLaw& h, const BoundsSched& sc,
+                                     int64_t i0, int64_t ni)
+{
+    if ((h.scheme != 0 && h.scheme != 1) || !bounds_schedule_ok(sc, a.N)) return hipErrorInvalidValue;
+    const HestonBoundsArgs g = heston_bounds_args(a, h);
+    const int64_t items = ni * sc.J;
+    int64_t nb = (items + 3) / 4;
+    if (nb > 2048) nb = 2048;
+    const size_t lds = sizeof(uint4) * (size_t)(a.N + 1);
+    if (h.scheme == 0)
+        hipLaunchKernelGGL((heston_bounds_sched_inner_kernel<0>), dim3((unsigned)nb), dim3(kBlock), lds, st, g, sc, i0, ni);
+    else
+        hipLaunchKernelGGL((heston_bounds_sched_inner_kernel<1>), dim3((unsigned)nb), dim3(kBlock), lds, st, g, sc, i0, ni);
     return hipGetLastError();
 }
 
