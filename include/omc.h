@@ -162,6 +162,10 @@ int omc_memcpy_d2h(omc_ctx* ctx, void* dst, const void* src, size_t bytes);
  * counted back from expiry, and at expiry, on paths of the whole grid -- it changes the GAME whose value is bounded, not
  * the route by which the same numbers are computed; see "an exercise schedule" in the price bounds section.  k < 0 or
  * k > 2^31 - 1 is refused with -4 and the stored value stays; the other three bounds calls refuse k >= 2 with -38),
+ * "bounds_control_variate" (omc_price_american_bounds: 0 = default, 1 = the discounted Black-Scholes value of the European
+ * option as a control variate in the lower bound and in every inner mean -- the same paths and stops, far smaller standard
+ * errors; see "the Black-Scholes control variate" in the price bounds section.  Another value is refused with -4 and the
+ * stored value stays; the other bounds calls refuse 1 with -39),
  * "alloc_limit" (PER PROCESS, bytes; 0 = none: no single buffer of the library -- path matrix, workspace, row scratch --
  * may grow beyond it; a larger request fails like a hipMalloc that found no room, code 2 = hipErrorOutOfMemory.  A
  * budget for a card shared with other tenants; on a distributed context such a rank-local failure is reported on
@@ -694,7 +698,42 @@ int omc_price_american_basket_greeks(omc_ctx* ctx, const omc_params* p, const om
  * Taken by omc_price_american_bounds and by omc_price_american_bounds_heston with cfg->regressors = OMC_HESTON_REG_SPOT.
  * Error -38 (k >= 2 only; after the call's own argument checks, nothing is launched, the outputs are untouched): the
  *   spot + variance policy of omc_price_american_bounds_heston, omc_price_american_basket_bounds (the Asian kinds included)
- *   and omc_price_american_basket_bounds_runnerup take no schedule.  Entry points that compute no bounds ignore the option. */
+ *   and omc_price_american_basket_bounds_runnerup take no schedule.  Entry points that compute no bounds ignore the option.
+ *
+ * ---- ... with the Black-Scholes control variate ----
+ * Option "bounds_control_variate" = v (omc_set_option; a context option for the reasons above: no new symbol, the same struct
+ * layout, OMC_ABI_VERSION unchanged).  v = 0 (default): everything above, bit for bit, and the same launches.  v = 1: the
+ * controlled estimators below.  Any other value is refused with -4 and the stored value stays.
+ * Inputs: dt = T / N in double, D[t] the discount table above, x = (double)s for a float32 spot s.  E(x, d) is the
+ *   Black-Scholes value (no dividend yield) of the European put / call at spot x, strike K, rate r, volatility sigma and time
+ *   to expiry (N - d) dt, in float64 with Phi(y) = erfc(-y / sqrt 2) / 2:
+ *     d1 = (log(x / K) + (r + sigma^2 / 2) tau) / (sigma sqrt tau),  d2 = d1 - sigma sqrt tau,  tau = (N - d) dt
+ *     put: K exp(-r tau) Phi(-d2) - x Phi(-d1)        call: x Phi(d1) - K exp(-r tau) Phi(d2)
+ *   D_t E(S_t, t) is a martingale on the grid, so D_tau E(S_tau, tau) - D_t E(S_t, t) has conditional mean zero for every
+ *   stopping time tau of the policy (the inner control variate of Andersen-Broadie 2004, section 5).
+ * Paths, stopping rule, Philox coordinates, policy, exercise tables, walk and Z are unchanged; only what is averaged changes.
+ *   Controlled term: a partner stopped at index x and date d contributes c = Z - D[d] E(x, d) when d < N, and exactly 0.0,
+ *     with nothing evaluated, when d = N.
+ *   Inner items: Q^_t[i] = D[t] E(S_t[i], t) + (1 / n_inner) sum of c over the item's inner paths.  q_out holds these values;
+ *     the walk is the one above, scheduled or not, reading them.
+ *   Lower bound: the device sums the centred pair means (c_a + c_b) / 2 and their squares; lower = E0 + their mean with
+ *     E0 = D[0] E((double)(float)S0, 0) formed on the host in double, and se_lower comes from the centred pair means alone.
+ *     n_exercised_lower is unchanged.
+ *   With the same arguments betas_out, n_exercised_lower and inner_path_steps equal the plain call's exactly: the same
+ *     paths, the same stops.
+ *   Validity: the inner estimate stays conditionally unbiased, so `upper` is still biased upward only.  (The control's mean
+ *     is zero up to the float32 rounding of the generator's step constants, of the order of 1e-7 relative: five orders below
+ *     any standard error the call can reach.)
+ *   float64 sums in a fixed order: identical calls return identical bits.  The inner sweep gives an item a group of G = 8,
+ *     16, 32 or 64 lanes (the smallest G >= n_inner / 2, at most 64); an inner pair's Philox coordinates do not depend on G.
+ * Taken by omc_price_american_bounds: all four policies, the all-dates game and a schedule ("bounds_exercise_every" >= 2).
+ * Error -39 (v = 1 only; after the call's own argument checks, behind -16 and -38; nothing is launched, the outputs are
+ *   untouched): omc_price_american_bounds_heston (both regressor sets), omc_price_american_basket_bounds (the Asian kinds
+ *   included) and omc_price_american_basket_bounds_runnerup have no control variate.  With the option back at 0 they return
+ *   their old bits.  Entry points that compute no bounds ignore the option.
+ * Option "bounds_cv_form" (for the library's tests and timing tool only: unsupported, and it may vanish without an ABI bump;
+ *   0 = default, the lane groups above): 1 = one item per wave, G = 64 whatever n_inner.  The same Q^ up to the order of the
+ *   float64 sums.  Another value is refused with -4. */
 enum { OMC_POLICY_GIVEN = 3 };
 typedef struct {
     int32_t policy;    /* OMC_SEM_REFERENCE, OMC_SEM_TEXTBOOK, OMC_SEM_TWO_PASS: fitted here; OMC_POLICY_GIVEN: `betas` */

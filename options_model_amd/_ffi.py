@@ -541,6 +541,7 @@ class Context:
     """One per (process, device).  Calls on a context are serialised by the caller."""
 
     _bounds_every = 0  # option "bounds_exercise_every" as last set through this object (the ABI has no getter)
+    _bounds_cv = 0     # option "bounds_control_variate", likewise
 
     def __init__(self, device: int = 0, stream: int | None = None):
         self.lib = load_library()
@@ -580,6 +581,8 @@ class Context:
         _check(self.lib, self.lib.omc_set_option(self.handle, key.encode(), int(value)))
         if key == "bounds_exercise_every":
             self._bounds_every = int(value)
+        if key == "bounds_control_variate":
+            self._bounds_cv = int(value)
 
     def set_allreduce_hook(self, fn):
         """fn(dptr:int, count:int) -> None must sum-all-reduce `count` device doubles in place."""
@@ -950,16 +953,34 @@ class Context:
 
     def price_american_bounds(self, params: Params, policy="textbook", n_lower=1_000_000, n_outer=8192, n_inner=1024,
                               stream_lower=None, stream_outer=None, stream_inner=None, betas=None, want_q=False,
-                              want_samples=False, exercise_every=0):
+                              want_samples=False, exercise_every=0, control_variate=False):
         """Andersen-Broadie bounds of the Bermudan game on the grid (omc_price_american_bounds) -> dict with the fields of
         omc_bounds plus `betas` (the policy used, [n_steps+1][4]) and, when asked, `q` ([n_outer][n_steps]: Q^_t) and
         `samples` ([n_outer]).  policy: a key of BOUND_POLICIES or its code; betas: the table of policy "given".  Streams
         default to params.stream + 1 / 2 / 3.
         exercise_every = k >= 2: the game with exercise at every k-th date counted back from expiry (option
         "bounds_exercise_every", set for this call and put back after it); `betas` has zero rows off the schedule and `q` is
-        zero in the columns that are no scheduled date."""
-        return self._bounds(params, None, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner,
-                            betas, want_q, want_samples, exercise_every=exercise_every)
+        zero in the columns that are no scheduled date.
+        control_variate=True: the Black-Scholes control variate of DESIGN.md section 26 (option "bounds_control_variate",
+        set for this call and put back after it; None: the option as the context holds it): the same paths and stops,
+        `lower` and `q` estimated with the discounted European value as the control."""
+        with self._bounds_control(control_variate):
+            return self._bounds(params, None, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner,
+                                betas, want_q, want_samples, exercise_every=exercise_every)
+
+    @contextlib.contextmanager
+    def _bounds_control(self, control_variate):
+        """option "bounds_control_variate" = control_variate for the calls inside, the previous value after them (None: the
+        option stays as the context holds it)"""
+        if control_variate is None:
+            yield
+            return
+        before = self._bounds_cv
+        self.set_option("bounds_control_variate", 1 if control_variate else 0)
+        try:
+            yield
+        finally:
+            self.set_option("bounds_control_variate", before)
 
     @contextlib.contextmanager
     def _bounds_schedule(self, exercise_every):

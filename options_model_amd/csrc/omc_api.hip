@@ -823,6 +823,14 @@ int omc_set_option(omc_ctx* c, const char* key, int64_t value)
         if (value < 0 || value > 2147483647) return fail(-4, "bounds_exercise_every must be in 0 .. 2^31 - 1.");
         c->bounds_every = value;
     }
+    else if (!strcmp(key, "bounds_control_variate")) {
+        if (value != 0 && value != 1) return fail(-4, "bounds_control_variate must be 0 or 1.");
+        c->bounds_cv = (int)value;
+    }
+    else if (!strcmp(key, "bounds_cv_form")) {
+        if (value != 0 && value != 1) return fail(-4, "bounds_cv_form must be 0 or 1.");
+        c->bounds_cv_form = (int)value;
+    }
     else if (!strcmp(key, "chain_fused")) c->chain_fused = value ? 1 : 0;
     else if (!strcmp(key, "chain_k")) c->chain_k = value < 1 ? -1 : (int)(value > 16 ? 16 : value);
     else if (!strcmp(key, "seq_step_wgs")) c->seq_step_wgs = value > 0 ? (int)value : 0;

@@ -35,6 +35,11 @@ int run_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg, co
     if (c->bounds_every >= 2 && !f.inner_sched)
         return fail(-38, "option bounds_exercise_every: these bounds take no exercise schedule (one asset, a policy on the "
                          "spot: omc_price_american_bounds, omc_price_american_bounds_heston with regressors spot).");
+    // the control variate (option "bounds_control_variate" = 1): the flows that bring the controlled sweeps take it
+    const bool cv = c->bounds_cv != 0;
+    if (cv && !(f.lower_cv && f.inner_cv && (c->bounds_every < 2 || f.inner_sched_cv)))
+        return fail(-39, "option bounds_control_variate: these bounds have no control variate (one GBM asset: "
+                         "omc_price_american_bounds).");
     const bool sched = c->bounds_every >= 2;
     const omc::BoundsSched sc = sched ? omc::bounds_schedule(N, c->bounds_every) : omc::BoundsSched{};
     hipStream_t st = c->stream;
@@ -116,7 +121,7 @@ int run_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg, co
         ct.N = N; ct.is_put = a.is_put; ct.K = p->K; ct.irr_every = c->pass2_irr_every;
         HIP_TRY(omc::lsm_crit_build(st, ct));
     }
-    HIP_TRY(f.lower(st, res));
+    HIP_TRY(cv ? f.lower_cv(st, res) : f.lower(st, res));
     HIP_TRY(hipEventRecord(c->ev[2], st));
     HIP_TRY(f.outer(st));
     HIP_TRY(hipMemsetAsync(a.steps, 0, sizeof(unsigned long long), st));
@@ -133,7 +138,8 @@ int run_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg, co
     blk = blk < 1 ? 1 : (blk > no ? no : blk);
     for (int64_t i0 = 0; i0 < no; i0 += blk) {
         const int64_t n = no - i0 < blk ? no - i0 : blk;
-        HIP_TRY(sched ? f.inner_sched(st, sc, i0, n) : f.inner(st, i0, n));
+        if (cv) HIP_TRY(sched ? f.inner_sched_cv(st, sc, i0, n) : f.inner_cv(st, i0, n));
+        else HIP_TRY(sched ? f.inner_sched(st, sc, i0, n) : f.inner(st, i0, n));
     }
     if (sched) HIP_TRY(omc::bounds_sched_walk(st, a, sc, res + 8));
     else HIP_TRY(own ? f.walk(st, res + 8) : omc::bounds_walk(st, a, res + 8));
@@ -150,6 +156,7 @@ int run_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg, co
     if ((rc = wait_stream(c))) return rc;
     memset(out, 0, sizeof *out);
     mean_and_se(h[0], h[1], (double)(nl / 2), &out->lower, &out->se_lower);  // pair means are the samples
+    if (cv) out->lower += f.cv_e0;  // the sums are those of the centred pair means
     mean_and_se(h[8], h[9], (double)(no / 2), &out->upper, &out->se_upper);
     out->ci_lo = out->lower - 1.96 * out->se_lower;
     out->ci_hi = out->upper + 1.96 * out->se_upper;
@@ -179,13 +186,19 @@ extern "C" int omc_price_american_bounds(omc_ctx* c, const omc_params* p, const 
     if (!cfg || !out) return fail(-7, "null bounds config or result pointer.");
     if ((rc = check_params(p))) return rc;
     if (p->model != OMC_MODEL_GBM) return fail(-12, "price bounds are available for GBM only.");
-    omc::BoundsArgs a{};
+    omc::BoundsCvArgs cva{};  // (cva.b == a once bound; read by the controlled sweeps alone)
+    omc::BoundsArgs& a = cva.b;
     BoundsFlow f;
+    const bool cv = c->bounds_cv != 0;
+    const int form = c->bounds_cv_form;
+    if (cv) f.extra_bytes = sizeof(double) * 4 * ((size_t)p->n_steps + 1);  // the table of E's per-date constants
     f.fit_paths = [&](float* S, int64_t ld) { return enqueue_paths(c, p, S, ld, false); };
-    f.bind = [&](const omc::BoundsArgs& common, char*) {
+    f.bind = [&](const omc::BoundsArgs& common, char* extra) {
         a = common;
         a.s0 = (float)p->S0;  // the generator's start value and step constants, so every spot is the generator's
         omc::gbm_step_constants(p->r, p->sigma, p->T, p->n_steps, &a.a, &a.b);
+        cva.r = p->r; cva.sigma = p->sigma; cva.dt = p->T / (double)p->n_steps;
+        cva.cv = (double*)extra;
     };
     f.lower = [&](hipStream_t st, double* res) { return omc::bounds_lower(st, a, res); };
     f.outer = [&](hipStream_t st) {
@@ -196,5 +209,17 @@ extern "C" int omc_price_american_bounds(omc_ctx* c, const omc_params* p, const 
     f.inner_sched = [&](hipStream_t st, const omc::BoundsSched& sc, int64_t i0, int64_t ni) {
         return omc::bounds_sched_inner(st, a, sc, i0, ni);
     };
+    // the control variate (option "bounds_control_variate"): the table, then the controlled sweeps
+    f.lower_cv = [&](hipStream_t st, double* res) {
+        const hipError_t e = omc::bounds_cv_table(st, cva);
+        return e != hipSuccess ? e : omc::bounds_lower_cv(st, cva, res);
+    };
+    f.inner_cv = [&](hipStream_t st, int64_t i0, int64_t ni) { return omc::bounds_inner_cv(st, cva, form, i0, ni); };
+    f.inner_sched_cv = [&](hipStream_t st, const omc::BoundsSched& sc, int64_t i0, int64_t ni) {
+        return omc::bounds_sched_inner_cv(st, cva, sc, form, i0, ni);
+    };
+    if (cv)  // D[0] = 1; the spot is the generator's float32 start value
+        f.cv_e0 = omc::bounds_cv_euro_host((double)(float)p->S0, p->K, p->r, p->sigma,
+                                           (double)p->n_steps * (p->T / (double)p->n_steps), p->is_put != 0);
     return run_bounds(c, p, cfg, betas, betas_out, q_out, samples_out, out, f);
 }

@@ -54,4 +54,21 @@ hipError_t bounds_sched_gather(hipStream_t st, float* S, int64_t ld, const Bound
 // dst), zero rows elsewhere
 hipError_t bounds_sched_policy(hipStream_t st, const double* src, double* dst, int N, const BoundsSched& sc, bool gathered);
 
+// The Black-Scholes control variate of the GBM bounds (option "bounds_control_variate" = 1; DESIGN.md section 26,
+// omc_bounds_cv_dev.h): BoundsArgs, the law's parameters in double and the table of E's per-date constants.
+struct BoundsCvArgs {
+    BoundsArgs b;
+    double r, sigma, dt;  // dt = T / N
+    double* cv;           // [N+1][4] (r + sigma^2 / 2) tau, sigma sqrt(tau), K exp(-r tau), tau = (N - d) dt
+};
+// how the controlled inner sweep is run (option "bounds_cv_form", for tests and measurement only; both forms compute the same
+// Q^ up to the order of their sums)
+enum { kCvFormDefault = 0, kCvFormWave = 1 };  // lane groups by n_inner; one item per wave (G = 64) whatever n_inner
+int bounds_cv_group(int64_t half_inner, int form);  // G: the smallest of 8, 16, 32, 64 that is >= half_inner, at most 64
+hipError_t bounds_cv_table(hipStream_t st, const BoundsCvArgs& c);
+double bounds_cv_euro_host(double x, double K, double r, double sigma, double tau, bool is_put);  // E, on the host in double
+hipError_t bounds_lower_cv(hipStream_t st, const BoundsCvArgs& c, double* result);
+hipError_t bounds_inner_cv(hipStream_t st, const BoundsCvArgs& c, int form, int64_t i0, int64_t ni);
+hipError_t bounds_sched_inner_cv(hipStream_t st, const BoundsCvArgs& c, const BoundsSched& sc, int form, int64_t i0, int64_t ni);
+
 }  // namespace omc

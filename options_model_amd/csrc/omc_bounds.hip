@@ -15,7 +15,12 @@
 // Sums: float64, per lane in a fixed order, per wave / workgroup in a fixed tree, then lsm_finalize: identical calls
 // return identical bits (the inner step count is an integer atomic sum, exact in any order).
 // The lower and the inner sweep are bounds_lower_body / bounds_inner_body (omc_bounds_dev.h), which the multi-asset
-// kernels share; this file supplies their path law, one GBM asset, and the walk.
+// kernels share; this file supplies their path law, one GBM asset, and the walk.  It also instantiates the sweeps of an
+// exercise schedule (omc_bounds_sched_dev.h, section 25) and those with the Black-Scholes control variate
+// (omc_bounds_cv_dev.h, section 26).
+#include <cmath>
+
+#include "omc_bounds_cv_dev.h"
 #include "omc_bounds_dev.h"
 #include "omc_bounds_sched_dev.h"
 
@@ -207,6 +212,101 @@ hipError_t bounds_sched_policy(hipStream_t st, const double* src, double* dst, i
     hipLaunchKernelGGL(bounds_sched_policy_kernel, dim3((unsigned)((N + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, src,
                        dst, N, sc, gathered ? 1 : 0);
     return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ the Black-Scholes control variate
+// the bodies of omc_bounds_cv_dev.h with the GBM path law; no kernel above is touched
+__global__ __launch_bounds__(kBlock) void bounds_cv_table_kernel(BoundsCvArgs c) { bounds_cv_table_body(c); }
+
+hipError_t bounds_cv_table(hipStream_t st, const BoundsCvArgs& c)
+{
+    hipLaunchKernelGGL(bounds_cv_table_kernel, dim3((unsigned)((c.b.N + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, c);
+    return hipGetLastError();
+}
+
+double bounds_cv_euro_host(double x, double K, double r, double sigma, double tau, bool is_put)
+{
+    const double sq = sigma * std::sqrt(tau);
+    const double d1 = (std::log(x / K) + (r + 0.5 * sigma * sigma) * tau) / sq;
+    const double d2 = d1 - sq;
+    const double sg = is_put ? -1.0 : 1.0;
+    const auto phi = [](double y) { return 0.5 * std::erfc(-y / 1.4142135623730951); };
+    return sg * (x * phi(sg * d1) - K * std::exp(-r * tau) * phi(sg * d2));
+}
+
+__global__ __launch_bounds__(kBlock) void bounds_lower_cv_kernel(BoundsCvArgs c, int nblk)
+{
+    extern __shared__ uint4 sh_bt[];
+    __shared__ double red[kNQ * kRedStride];
+    bounds_lower_cv_body(c, GbmBoundsModel{c.b}, nblk, sh_bt, red);
+}
+
+hipError_t bounds_lower_cv(hipStream_t st, const BoundsCvArgs& c, double* result)
+{
+    const int nblk = (int)bounds_lower_blocks(c.b);
+    hipLaunchKernelGGL(bounds_lower_cv_kernel, dim3(nblk), dim3(kBlock), sizeof(uint4) * (size_t)(c.b.N + 1), st, c, nblk);
+    return lsm_finalize(st, c.b.part, nullptr, result, nblk, 0);
+}
+
+template <int G, bool Sched, int Park>
+__global__ __launch_bounds__(kBlock) void bounds_inner_cv_kernel(BoundsCvArgs c, BoundsSched sc, int64_t i0, int64_t ni)
+{
+    extern __shared__ uint4 sh_bt[];
+    bounds_inner_cv_body<G, Sched, Park>(c, sc, GbmBoundsModel{c.b}, i0, ni, sh_bt);
+}
+
+// Park: n > 0 = a finished pair waits until n lanes of its wave wait; 0 = it is evaluated in the iteration it ends, the form
+// that lost and is not instantiated (measured on the default call at n_inner 1024: 8 lanes 16.9 ms, 16 15.1, 32 14.2, 48 14.0,
+// at the stop 21.5; DESIGN.md sections 6.4 and 26.4)
+constexpr int kCvPark = 32;
+
+int bounds_cv_group(int64_t half_inner, int form)
+{
+    if (form == kCvFormWave) return 64;  // tests and measurement: bounds_inner_body's shape whatever n_inner
+    return half_inner <= 8 ? 8 : (half_inner <= 16 ? 16 : (half_inner <= 32 ? 32 : 64));
+}
+
+namespace {
+template <int G, bool Sched, int Park>
+hipError_t launch_inner_cv(hipStream_t st, const BoundsCvArgs& c, const BoundsSched& sc, int64_t i0, int64_t ni)
+{
+    const int64_t items = ni * (Sched ? sc.J : c.b.N);
+    const int64_t per_block = (kBlock / 64) * (64 / G);
+    int64_t g = (items + per_block - 1) / per_block;
+    if (g > 2048) g = 2048;
+    hipLaunchKernelGGL((bounds_inner_cv_kernel<G, Sched, Park>), dim3((unsigned)g), dim3(kBlock),
+                       sizeof(uint4) * (size_t)(c.b.N + 1), st, c, sc, i0, ni);
+    return hipGetLastError();
+}
+
+template <bool Sched, int Park>
+hipError_t launch_inner_cv_g(hipStream_t st, const BoundsCvArgs& c, const BoundsSched& sc, int G, int64_t i0, int64_t ni)
+{
+    switch (G) {
+    case 8: return launch_inner_cv<8, Sched, Park>(st, c, sc, i0, ni);
+    case 16: return launch_inner_cv<16, Sched, Park>(st, c, sc, i0, ni);
+    case 32: return launch_inner_cv<32, Sched, Park>(st, c, sc, i0, ni);
+    default: return launch_inner_cv<64, Sched, Park>(st, c, sc, i0, ni);
+    }
+}
+
+template <bool Sched>
+hipError_t launch_inner_cv_form(hipStream_t st, const BoundsCvArgs& c, const BoundsSched& sc, int form, int64_t i0, int64_t ni)
+{
+    const int G = bounds_cv_group(c.b.half_inner, form);
+    return launch_inner_cv_g<Sched, kCvPark>(st, c, sc, G, i0, ni);
+}
+}  // namespace
+
+hipError_t bounds_inner_cv(hipStream_t st, const BoundsCvArgs& c, int form, int64_t i0, int64_t ni)
+{
+    return launch_inner_cv_form<false>(st, c, BoundsSched{}, form, i0, ni);
+}
+
+hipError_t bounds_sched_inner_cv(hipStream_t st, const BoundsCvArgs& c, const BoundsSched& sc, int form, int64_t i0, int64_t ni)
+{
+    if (!bounds_schedule_ok(sc, c.b.N)) return hipErrorInvalidValue;
+    return launch_inner_cv_form<true>(st, c, sc, form, i0, ni);
 }
 
 }  // namespace omc

@@ -176,6 +176,14 @@ struct BoundsFlow {
     // the context's schedule -- Q^ at the scheduled dates only, with run_bounds' own fit on the gathered rows and walk over
     // the scheduled dates -- and one that leaves it empty is refused (-38) while the option holds a schedule.
     std::function<hipError_t(hipStream_t, const omc::BoundsSched& sc, int64_t i0, int64_t ni)> inner_sched;
+    // The control variate (option "bounds_control_variate" = 1; default: none).  A flow that sets
+    // lower_cv, inner_cv and (to take a schedule too) inner_sched_cv is run with them in the place of lower, inner and
+    // inner_sched while the option is on: lower_cv leaves the sums of the CENTRED pair means, to whose mean run_bounds adds
+    // cv_e0, and inner_cv writes the controlled Q^.  One that leaves them empty is refused (-39) while the option is on.
+    std::function<hipError_t(hipStream_t, double* result)> lower_cv;
+    std::function<hipError_t(hipStream_t, int64_t i0, int64_t ni)> inner_cv;
+    std::function<hipError_t(hipStream_t, const omc::BoundsSched& sc, int64_t i0, int64_t ni)> inner_sched_cv;
+    double cv_e0 = 0.0;  // E0 = D[0] E(S0, 0), float64 on the host
     // A policy of the flow's own (omc_api_runnerup_bounds.hip: a rule on two regressors), all three set or none.  With them
     // run_bounds neither uploads nor fits a [N+1][4] table and builds no exercise tables:
     //   own_policy(w, S, ld)   between the fit events: the caller's table to the device (S == nullptr), or the fit on the
@@ -294,6 +302,8 @@ struct omc_ctx {
     DevBuf bar_part, bar_res;  // omc_price_barrier: the generator's per-workgroup partials, reduced sums
     DevBuf div_tab;            // omc_price_american_div: the dividend steps of the call (omc::DivEntry)
     int64_t bounds_every = 0;  // option "bounds_exercise_every": 0 / 1 every date, k >= 2 the bounds of the scheduled game
+    int bounds_cv = 0;         // option "bounds_control_variate": 1 = the GBM bounds' Black-Scholes control variate (section 26)
+    int bounds_cv_form = 0;    // option "bounds_cv_form" (tests, measurement): omc::kCvFormDefault / kCvFormWave
     DevBuf bnd;                // omc_price_american_bounds: outer paths, Q^ table, samples, tables, partials, sums
     DevBuf chain_fold;         // omc_price_american_chain: the entries' fold tables + c0 (their small buffers: gstate)
     DevBuf chain_sched;        // ... and its Bermudan entries' tables on their scheduled dates (omc::chain_schedule_tables)
