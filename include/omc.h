@@ -166,6 +166,12 @@ int omc_memcpy_d2h(omc_ctx* ctx, void* dst, const void* src, size_t bytes);
  * option as a control variate in the lower bound and in every inner mean -- the same paths and stops, far smaller standard
  * errors; see "the Black-Scholes control variate" in the price bounds section.  Another value is refused with -4 and the
  * stored value stays; the other bounds calls refuse 1 with -39),
+ * "bounds_suboptimality" (the price bounds on one float32 index -- omc_price_american_bounds, omc_price_american_basket_bounds
+ * with the policy on the index, omc_price_american_bounds_heston with regressors spot: 0 = default, 1 = "payoff", 2 =
+ * "European", omc_price_american_bounds only: Broadie-Cao's sub-optimality checking -- inner simulations only at the (outer
+ * path, date) items at which exercise is not known to be sub-optimal, the same lower bound, an upper bound that can only
+ * fall and stays one; see "sub-optimality checking" in the price bounds section.  Another value is refused with -4 and the
+ * stored value stays; a bounds call that does not take the value is refused with -40),
  * "alloc_limit" (PER PROCESS, bytes; 0 = none: no single buffer of the library -- path matrix, workspace, row scratch --
  * may grow beyond it; a larger request fails like a hipMalloc that found no room, code 2 = hipErrorOutOfMemory.  A
  * budget for a card shared with other tenants; on a distributed context such a rank-local failure is reported on
@@ -733,7 +739,42 @@ int omc_price_american_basket_greeks(omc_ctx* ctx, const omc_params* p, const om
  *   their old bits.  Entry points that compute no bounds ignore the option.
  * Option "bounds_cv_form" (for the library's tests and timing tool only: unsupported, and it may vanish without an ABI bump;
  *   0 = default, the lane groups above): 1 = one item per wave, G = 64 whatever n_inner.  The same Q^ up to the order of the
- *   float64 sums.  Another value is refused with -4. */
+ *   float64 sums.  Another value is refused with -4.
+ *
+ * ---- ... with sub-optimality checking (Broadie-Cao 2008) ----
+ * Option "bounds_suboptimality" = m (omc_set_option; a context option for the reasons above: no new symbol, the same struct
+ * layout, OMC_ABI_VERSION unchanged).  m = 0 (default, "off"): everything above, bit for bit, and the same launches.  m = 1
+ * ("payoff") and m = 2 ("European"): the rule below.  Any other value is refused with -4 and the stored value stays.
+ * Symbols: s = So[t][i], the float32 index of outer path i at date t; x = (double)s; phi(x) = K - x for a put and x - K for a
+ *   call; stop(s, t) the decision of the frozen policy (the exercise tables, the float64 rule on irregular dates).
+ * Which items are kept: item (i, t), 0 <= t < N, is KEPT iff one of
+ *     t == 0;    stop(s, t);    m == 1 and phi(x) > 0;
+ *     m == 2 and phi(x) > E(x, t), E the Black-Scholes value of the control variate's section, formed in float64 from its
+ *                table of per-date constants (built for this purpose alone when the control variate is off) and evaluated as
+ *                not (phi(x) <= E(x, t)), so that a NaN keeps the item.
+ *   The expiry t = N is always a date of the walk.  The stop rule requires a positive payoff, so in mode 1 a skipped item
+ *   is never one at which the policy stops; in mode 2 an item at which the policy stops is kept whatever E says.  There is no
+ *   "local policy fixing": the policy, the exercise tables and the lower bound stay exactly as they are.
+ * Inner simulations run for kept items only, with the item's Philox coordinates (gbase = (i (N+1) + t) n_inner / 2 on
+ *   stream_inner), lane assignment and fixed-order sum: Q^_t[i] of a kept item has the BITS of the unchecked call's value,
+ *   for the plain estimator and for the controlled one (the same lane group G).  q_out keeps its shape [n_outer][N]; a
+ *   skipped item's entry is 0.0.  inner_path_steps counts the kept items' steps only.
+ * Walk, per outer path: M = 0, lq = Q^_0; for t = 1 .. N, only at kept dates and at t = N:
+ *     L = stop ? Z_t : Q^_t  (Q^_N = 0);    M = M + L - lq;    candidate Z_t - M;    lq = Q^_t.
+ *   The sample is the maximum of the candidates.  Between two kept dates the policy continues, so the dense walk's
+ *   increments sum to L_k - Q^_l exactly: the kept-date M is the dense M up to rounding, and when every item is kept the
+ *   checked walk returns the dense walk's bits.
+ * Still an upper bound: at a skipped date Z_t <= D_t E_t <= the continuation value (mode 1: Z_t = 0), so the game without
+ *   those exercise rights has the same value, the dual bound holds for that game with any martingale, and the inner noise
+ *   still biases upward only.  Each sample is at most the unchecked one up to the walk's rounding.
+ * Taken by the all-dates game of omc_price_american_bounds (plain and with "bounds_control_variate" = 1, all four policies;
+ *   m = 1 and m = 2), omc_price_american_basket_bounds (the Asian kinds included; m = 1) and omc_price_american_bounds_heston
+ *   with regressors OMC_HESTON_REG_SPOT (m = 1).
+ * Error -40 (after the call's own argument checks, behind -16, -38 and -39; nothing is launched, the outputs are untouched):
+ *   m >= 1 while "bounds_exercise_every" >= 2; m >= 1 on a flow with a policy of its own (omc_price_american_bounds_heston
+ *   with the spot + variance policy, omc_price_american_basket_bounds_runnerup for the runner-up and for the Asian index +
+ *   spot); m = 2 on any entry point other than omc_price_american_bounds.  With the option back at 0 they return their old
+ *   bits.  Entry points that compute no bounds ignore the option. */
 enum { OMC_POLICY_GIVEN = 3 };
 typedef struct {
     int32_t policy;    /* OMC_SEM_REFERENCE, OMC_SEM_TEXTBOOK, OMC_SEM_TWO_PASS: fitted here; OMC_POLICY_GIVEN: `betas` */

@@ -22,7 +22,8 @@ def __getattr__(name):
                 "ChainResult", "price_bermudan_option", "exercise_dates", "price_american_dividends", "DividendResult", "price_american_jumps", "JumpResult",
                 "price_american_basket", "BasketResult", "price_american_basket_bounds", "BasketBoundsResult",
                 "price_american_basket_greeks", "BasketGreeksResult", "price_american_bounds_heston",
-                "HestonBoundsResult", "price_asian_option", "price_bermudan_bounds", "bounds_exercise_dates"):
+                "HestonBoundsResult", "price_asian_option", "price_bermudan_bounds", "bounds_exercise_dates",
+                "price_american_bounds_checked"):
         from . import api
         return getattr(api, name)
     if name in ("AdvancedOptionPricer", "RNGManager", "BlackScholesGreeks", "welford_batch_update",

@@ -31,6 +31,7 @@ BOUND_REGRESSORS = ("index", "index+runner-up", "index+spot")  # what the policy
 ASIAN_KINDS = (5, 6)  # the running-average kinds: "index+spot" is theirs, "index+runner-up" best-of's and worst-of's
 HESTON_BOUND_REGRESSORS = ("spot", "spot+variance")  # ... of the Heston bounds: the codes of omc_bounds_config.regressors
 HESTON_SV_MAX_STEPS = 512  # dates of a spot+variance policy (its rows live in LDS)
+BOUND_CHECKS = ("off", "payoff", "european")  # sub-optimality checking: the codes of option "bounds_suboptimality"
 
 
 def check_runnerup(regressors, policy, kind, n_assets):
@@ -542,6 +543,7 @@ class Context:
 
     _bounds_every = 0  # option "bounds_exercise_every" as last set through this object (the ABI has no getter)
     _bounds_cv = 0     # option "bounds_control_variate", likewise
+    _bounds_check = 0  # option "bounds_suboptimality", likewise
 
     def __init__(self, device: int = 0, stream: int | None = None):
         self.lib = load_library()
@@ -583,6 +585,8 @@ class Context:
             self._bounds_every = int(value)
         if key == "bounds_control_variate":
             self._bounds_cv = int(value)
+        if key == "bounds_suboptimality":
+            self._bounds_check = int(value)
 
     def set_allreduce_hook(self, fn):
         """fn(dptr:int, count:int) -> None must sum-all-reduce `count` device doubles in place."""
@@ -953,7 +957,7 @@ class Context:
 
     def price_american_bounds(self, params: Params, policy="textbook", n_lower=1_000_000, n_outer=8192, n_inner=1024,
                               stream_lower=None, stream_outer=None, stream_inner=None, betas=None, want_q=False,
-                              want_samples=False, exercise_every=0, control_variate=False):
+                              want_samples=False, exercise_every=0, control_variate=False, suboptimality_check=None):
         """Andersen-Broadie bounds of the Bermudan game on the grid (omc_price_american_bounds) -> dict with the fields of
         omc_bounds plus `betas` (the policy used, [n_steps+1][4]) and, when asked, `q` ([n_outer][n_steps]: Q^_t) and
         `samples` ([n_outer]).  policy: a key of BOUND_POLICIES or its code; betas: the table of policy "given".  Streams
@@ -963,8 +967,12 @@ class Context:
         zero in the columns that are no scheduled date.
         control_variate=True: the Black-Scholes control variate of DESIGN.md section 26 (option "bounds_control_variate",
         set for this call and put back after it; None: the option as the context holds it): the same paths and stops,
-        `lower` and `q` estimated with the discounted European value as the control."""
-        with self._bounds_control(control_variate):
+        `lower` and `q` estimated with the discounted European value as the control.
+        suboptimality_check: "off", "payoff" or "european" (a key of BOUND_CHECKS; DESIGN.md section 27, option
+        "bounds_suboptimality", set for this call and put back after it; None: the option as the context holds it): inner
+        simulations only where exercise is not known to be sub-optimal; `q` is zero at the skipped items, `lower` is the
+        unchecked call's and `upper` is at most its value up to rounding."""
+        with self._bounds_control(control_variate), self._bounds_checking(suboptimality_check):
             return self._bounds(params, None, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner,
                                 betas, want_q, want_samples, exercise_every=exercise_every)
 
@@ -983,6 +991,22 @@ class Context:
             self.set_option("bounds_control_variate", before)
 
     @contextlib.contextmanager
+    def _bounds_checking(self, suboptimality_check):
+        """option "bounds_suboptimality" = the code of suboptimality_check for the calls inside, the previous value after
+        them (None: the option stays as the context holds it)"""
+        if suboptimality_check is None:
+            yield
+            return
+        if suboptimality_check not in BOUND_CHECKS:
+            raise ValueError(f"suboptimality_check must be one of {list(BOUND_CHECKS)} or None.")
+        before = self._bounds_check
+        self.set_option("bounds_suboptimality", BOUND_CHECKS.index(suboptimality_check))
+        try:
+            yield
+        finally:
+            self.set_option("bounds_suboptimality", before)
+
+    @contextlib.contextmanager
     def _bounds_schedule(self, exercise_every):
         """option "bounds_exercise_every" = exercise_every for the calls inside, the previous value after them (None: the
         option stays as the context holds it)"""
@@ -998,7 +1022,8 @@ class Context:
 
     def price_american_bounds_heston(self, params: Params, policy="textbook", n_lower=1_000_000, n_outer=8192,
                                      n_inner=1024, stream_lower=None, stream_outer=None, stream_inner=None, betas=None,
-                                     want_q=False, want_samples=False, regressors="spot", exercise_every=0):
+                                     want_q=False, want_samples=False, regressors="spot", exercise_every=0,
+                                     suboptimality_check=None):
         """Andersen-Broadie bounds of the Bermudan game of the discretised Heston scheme on the grid
         (omc_price_american_bounds_heston; scheme reference or full_truncation) -> the dict of price_american_bounds.  The
         policy is a function of the spot alone; the inner paths start at the outer (spot, variance) state.  Streams default
@@ -1007,18 +1032,22 @@ class Context:
         spot and the variance state, w = V / max(v0, theta) - 1, and `betas` (given and returned) is [n_steps+1][8] =
         c0 .. c5, n, 0.  A key of HESTON_BOUND_REGRESSORS or its code.
         exercise_every: as price_american_bounds takes it, with regressors "spot" (the spot + variance policy refuses a
-        schedule with -38)."""
+        schedule with -38).
+        suboptimality_check: as price_american_bounds takes it, "off" or "payoff" with regressors "spot" (anything else is
+        refused with -40)."""
         if isinstance(regressors, str):
             if regressors not in HESTON_BOUND_REGRESSORS:
                 raise ValueError(f"regressors must be one of {list(HESTON_BOUND_REGRESSORS)}.")
             regressors = HESTON_BOUND_REGRESSORS.index(regressors)
-        return self._bounds(params, None, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner,
-                            betas, want_q, want_samples, 8 if int(regressors) == 1 else 4, heston=True,
-                            regressors=int(regressors), exercise_every=exercise_every)
+        with self._bounds_checking(suboptimality_check):
+            return self._bounds(params, None, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner,
+                                betas, want_q, want_samples, 8 if int(regressors) == 1 else 4, heston=True,
+                                regressors=int(regressors), exercise_every=exercise_every)
 
     def price_american_basket_bounds(self, params: Params, basket: Basket, policy="textbook", n_lower=1_000_000,
                                      n_outer=8192, n_inner=1024, stream_lower=None, stream_outer=None, stream_inner=None,
-                                     betas=None, want_q=False, want_samples=False, regressors="index"):
+                                     betas=None, want_q=False, want_samples=False, regressors="index",
+                                     suboptimality_check=None):
         """Andersen-Broadie bounds of the Bermudan game on the INDEX of 1 .. 8 correlated GBM assets
         (omc_price_american_basket_bounds; arithmetic basket, best-of, worst-of) -> the dict of price_american_bounds plus
         index0, n_assets, kind.  params and basket as price_american_basket takes them; the policy is a function of the
@@ -1026,10 +1055,13 @@ class Context:
         regressors="index+runner-up" (omc_price_american_basket_bounds_runnerup; best-of and worst-of on 2 .. 8 assets,
         policy "textbook" or "given"): the policy sees the index and the second order statistic of the weighted spots, and
         `betas` (given and returned) is [n_steps+1][8] = c0 .. c5, n, 0.  regressors="index+spot": the same entry point for
-        the Asian kinds, whose second regressor is the current basket value."""
+        the Asian kinds, whose second regressor is the current basket value.
+        suboptimality_check: as price_american_bounds takes it, "off" or "payoff" with regressors "index" (anything else is
+        refused with -40)."""
         check_runnerup(regressors, policy, int(basket.kind), int(basket.n_assets))
-        return self._bounds(params, basket, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner,
-                            betas, want_q, want_samples, 4 if regressors == "index" else 8)
+        with self._bounds_checking(suboptimality_check):
+            return self._bounds(params, basket, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer,
+                                stream_inner, betas, want_q, want_samples, 4 if regressors == "index" else 8)
 
     def _bounds(self, params, basket, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner, betas,
                 want_q, want_samples, cols=4, heston=False, regressors=0, exercise_every=None):

@@ -827,6 +827,7 @@ class BoundsResult:
     exercise_every: int = 0  # 0 = every date of the grid; k >= 2: every k-th date counted back from expiry (section 25)
     n_exercise_dates: int = 0  # the dates of the game, the expiry included (0: not recorded)
     control_variate: bool = False  # the Black-Scholes control variate of the GBM bounds (section 26)
+    suboptimality_check: str = "off"  # "payoff" / "european": inner simulations at the kept items only (section 27)
 
 
 def price_american_bounds(S0, K, r, sigma, T, n_paths, n_steps, option_type="put", policy="textbook", n_lower=1_000_000,
@@ -976,6 +977,50 @@ def price_bermudan_bounds(S0, K, r, sigma, T, n_paths, n_steps, exercise_every, 
     raise ValueError("model must be 'GBM' or 'Heston'.")
 
 
+def price_american_bounds_checked(S0, K, r, sigma, T, n_paths, n_steps, check="european", model="GBM", option_type="put",
+                                  policy="textbook", n_lower=1_000_000, n_outer=8192, n_inner=1024, heston_params=None,
+                                  heston_scheme="reference", seed=42, stream=0, betas=None, device=None, ctx=None,
+                                  control_variate=False, exercise_every=0) -> BoundsResult:
+    """price_american_bounds (model "GBM") or price_american_bounds_heston (model "Heston", a policy on the spot; sigma only
+    sets the defaults of heston_defaults) with Broadie-Cao's sub-optimality checking: the inner
+    simulations run only at the (outer path, date) items at which exercise is not known to be sub-optimal, and the walk
+    visits only those dates.  check="payoff" keeps an item when the option is in the money there, "european" (GBM only) when
+    the payoff exceeds the Black-Scholes value of the European option; date 0 and every date at which the policy stops are
+    always kept, "off" keeps everything.  The paths, the stops, the policy and `lower` are the unchecked call's; `upper`
+    stays an upper bound and is at most the unchecked one up to rounding; `inner_path_steps` counts the work that was done.
+    control_variate=True: as price_american_bounds takes it, model "GBM" only.  The game is the one on every date:
+    exercise_every must be 0 or 1."""
+    if check not in _ffi.BOUND_CHECKS:
+        raise ValueError(f"check must be one of {list(_ffi.BOUND_CHECKS)}.")
+    if exercise_every is None or isinstance(exercise_every, (list, tuple)):
+        raise ValueError("exercise_every must be a non-negative integer.")
+    if _one_schedule(exercise_every) >= 2:
+        raise ValueError("sub-optimality checking is for the game on every date (exercise_every must be 0 or 1).")
+    model_l = str(model).lower()
+    if model_l not in ("gbm", "heston"):
+        raise ValueError("model must be 'GBM' or 'Heston'.")
+    if not isinstance(control_variate, (bool, int)) or control_variate not in (0, 1):
+        raise ValueError("control_variate must be True or False.")
+    if model_l == "heston" and control_variate:
+        raise ValueError("control_variate: the Black-Scholes control variate is for model 'GBM' only.")
+    if model_l == "heston" and check == "european":
+        raise ValueError("check='european' is for model 'GBM' only (model 'Heston' takes 'payoff' or 'off').")
+    c = ctx or _ffi.default_context(device)
+    with c._bounds_checking(check):
+        if model_l == "gbm":
+            res = price_american_bounds(S0, K, r, sigma, T, n_paths, n_steps, option_type=option_type, policy=policy,
+                                        n_lower=n_lower, n_outer=n_outer, n_inner=n_inner, seed=seed, stream=stream,
+                                        betas=betas, ctx=c, control_variate=control_variate, exercise_every=0)
+        else:
+            res = price_american_bounds_heston(S0, K, r, T, n_paths, n_steps,
+                                               heston_params=heston_defaults(sigma, heston_params),
+                                               heston_scheme=heston_scheme, option_type=option_type, policy=policy,
+                                               n_lower=n_lower, n_outer=n_outer, n_inner=n_inner, seed=seed, stream=stream,
+                                               betas=betas, ctx=c, exercise_every=0)
+    res.suboptimality_check = check
+    return res
+
+
 @dataclass
 class BasketBoundsResult(BoundsResult):
     """price_american_basket_bounds: BoundsResult for the index of a basket, with the index of the initial spots, the number
@@ -991,7 +1036,7 @@ class BasketBoundsResult(BoundsResult):
 def price_american_basket_bounds(spots, K, r, sigmas, T, n_paths, n_steps, correlation=None, weights=None,
                                  dividend_yields=None, kind="basket", option_type="put", policy="textbook",
                                  n_lower=1_000_000, n_outer=8192, n_inner=1024, seed=42, stream=0, betas=None, device=None,
-                                 ctx=None, regressors="index") -> BasketBoundsResult:
+                                 ctx=None, regressors="index", suboptimality_check=None) -> BasketBoundsResult:
     """Lower and upper bounds on the Bermudan value of an option on an index of 1 .. 8 correlated GBM assets
     (omc_price_american_basket_bounds): price_american_bounds with the assets, kinds and defaults of
     price_american_basket.  The policy (`policy` / `betas` as price_american_bounds takes them) regresses on the index
@@ -1006,7 +1051,15 @@ def price_american_basket_bounds(spots, K, r, sigmas, T, n_paths, n_steps, corre
     kind "asian" / "asian-geometric" (DESIGN.md section 23): the index is the running average; the inner paths start at the
     outer path's asset spots and running sum.  regressors="index+spot" is theirs alone: the policy also sees the current
     basket value, the other half of the Markov state (average, spot), with the table and the policies of
-    "index+runner-up"; at most 512 steps."""
+    "index+runner-up"; at most 512 steps.
+    suboptimality_check="payoff" (regressors "index" only): inner simulations only at the items at
+    which the index is in the money or the policy stops, and at date 0; "off" or None: every item."""
+    if suboptimality_check is not None and suboptimality_check not in _ffi.BOUND_CHECKS:
+        raise ValueError(f"suboptimality_check must be one of {list(_ffi.BOUND_CHECKS)} or None.")
+    if suboptimality_check == "european":
+        raise ValueError("suboptimality_check='european' is for one GBM asset (price_american_bounds_checked).")
+    if suboptimality_check == "payoff" and regressors != "index":
+        raise ValueError("suboptimality_check='payoff' is for regressors='index'.")
     if policy not in _ffi.BOUND_POLICIES:
         raise ValueError(f"policy must be one of {sorted(_ffi.BOUND_POLICIES)}.")
     if (policy == "given") != (betas is not None):
@@ -1030,7 +1083,8 @@ def price_american_basket_bounds(spots, K, r, sigmas, T, n_paths, n_steps, corre
         b = _ffi.make_basket([G0], [sigma_G], [q_G], [1.0], None, "basket")
     c = ctx or _ffi.default_context(device)
     out = c.price_american_basket_bounds(p, b, policy=policy, n_lower=int(n_lower), n_outer=int(n_outer),
-                                         n_inner=int(n_inner), betas=betas, regressors=regressors)
+                                         n_inner=int(n_inner), betas=betas, regressors=regressors,
+                                         suboptimality_check=suboptimality_check)
     return BasketBoundsResult(lower=out["lower"], se_lower=out["se_lower"], upper=out["upper"], se_upper=out["se_upper"],
                               ci_lo=out["ci_lo"], ci_hi=out["ci_hi"], n_lower=out["n_lower"], n_outer=out["n_outer"],
                               n_inner=out["n_inner"], n_exercised_lower=out["n_exercised_lower"],
@@ -1038,7 +1092,8 @@ def price_american_basket_bounds(spots, K, r, sigmas, T, n_paths, n_steps, corre
                               option_type=option_type,
                               timings_ms=dict(fit=out["ms_fit"], lower=out["ms_lower"], upper=out["ms_upper"],
                                               total=out["ms_total"]),
-                              index0=out["index0"], n_assets=out["n_assets"], kind=kind, regressors=regressors)
+                              index0=out["index0"], n_assets=out["n_assets"], kind=kind, regressors=regressors,
+                              suboptimality_check=suboptimality_check or "off")
 
 
 _ASIAN_AVERAGING = {"arithmetic": "asian", "geometric": "asian-geometric"}

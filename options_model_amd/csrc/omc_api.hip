@@ -831,6 +831,10 @@ int omc_set_option(omc_ctx* c, const char* key, int64_t value)
         if (value != 0 && value != 1) return fail(-4, "bounds_cv_form must be 0 or 1.");
         c->bounds_cv_form = (int)value;
     }
+    else if (!strcmp(key, "bounds_suboptimality")) {
+        if (value < 0 || value > 2) return fail(-4, "bounds_suboptimality must be 0 (off), 1 (payoff) or 2 (European).");
+        c->bounds_subopt = (int)value;
+    }
     else if (!strcmp(key, "chain_fused")) c->chain_fused = value ? 1 : 0;
     else if (!strcmp(key, "chain_k")) c->chain_k = value < 1 ? -1 : (int)(value > 16 ? 16 : value);
     else if (!strcmp(key, "seq_step_wgs")) c->seq_step_wgs = value > 0 ? (int)value : 0;

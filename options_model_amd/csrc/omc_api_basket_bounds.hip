@@ -49,6 +49,9 @@ extern "C" int omc_price_american_basket_bounds(omc_ctx* c, const omc_params* p,
         return omc::launch_basket_paths(st, gen);
     };
     f.inner = [&](hipStream_t st, int64_t i0, int64_t ni) { return omc::basket_bounds_inner(st, g, i0, ni); };
+    f.inner_check = [&](hipStream_t st, const omc::BoundsCheck& k, int64_t i0, int64_t ni) {  // section 27: the payoff check
+        return omc::basket_bounds_check_inner(st, g, k, i0, ni);
+    };
     omc_bounds bounds;
     if ((rc = run_bounds(c, p, cfg, betas, betas_out, q_out, samples_out, &bounds, f))) return rc;
     memset(out, 0, sizeof *out);

@@ -40,6 +40,13 @@ int run_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg, co
     if (cv && !(f.lower_cv && f.inner_cv && (c->bounds_every < 2 || f.inner_sched_cv)))
         return fail(-39, "option bounds_control_variate: these bounds have no control variate (one GBM asset: "
                          "omc_price_american_bounds).");
+    // sub-optimality checking (option "bounds_suboptimality" = m >= 1): the all-dates game of the flows that run the shared
+    // sweeps and walk; the European check needs the flow's table of E
+    const int chk = c->bounds_subopt;
+    if (chk >= 1 && (c->bounds_every >= 2 || f.own_policy || !f.inner_check || (cv && !f.inner_check_cv) ||
+                     (chk == 2 && !f.euro_table)))
+        return fail(-40, "option bounds_suboptimality: these bounds take no sub-optimality check (the all-dates game with a "
+                         "policy on the spot or the index; the European check: omc_price_american_bounds).");
     const bool sched = c->bounds_every >= 2;
     const omc::BoundsSched sc = sched ? omc::bounds_schedule(N, c->bounds_every) : omc::BoundsSched{};
     hipStream_t st = c->stream;
@@ -52,7 +59,8 @@ int run_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg, co
     if (!fitted && sched) HIP_TRY(omc::bounds_sched_policy(st, w.betas, w.betas, N, sc, false));  // zero rows off the schedule
     // the workspace: outer paths [N+1][n_outer] f32 | the flow's own room | Q^ [n_outer][N] | samples [n_outer] | tables
     // [N+1][8] u32 | partials [8][kPStride] | sums [16] | inner step count | with a schedule: the fit's discounts [J+1] | its
-    // fits [J+1][4]
+    // fits [J+1][4] | with sub-optimality checking: the keep mask [N][n_outer] u8 | the kept items of one inner launch
+    // [blk N] u32 | their count | the kept items per (inner launch, date) u32
     const size_t o_extra = up256(sizeof(float) * (size_t)(N + 1) * (size_t)no);
     const size_t o_q = o_extra + up256(f.extra_bytes);
     const size_t o_smp = o_q + up256(sizeof(double) * (size_t)no * (size_t)N);
@@ -62,7 +70,15 @@ int run_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg, co
     const size_t o_steps = o_res + up256(sizeof(double) * 16);
     const size_t o_fD = o_steps + 256;
     const size_t o_fb = o_fD + (sched ? up256(sizeof(double) * (size_t)(sc.J + 1)) : 0);
-    if ((rc = c->bnd.ensure(o_fb + (sched ? sizeof(double) * 4 * (size_t)(sc.J + 1) : 0)))) return rc;
+    // launches over blocks of outer paths, each at most kLaunchSteps / d inner path steps even if the policy never exercises
+    int64_t blk = (int64_t)(kLaunchSteps / (double)f.d / work1);
+    blk = blk < 1 ? 1 : (blk > no ? no : blk);
+    const size_t o_keep = o_fb + (sched ? sizeof(double) * 4 * (size_t)(sc.J + 1) : 0);
+    const size_t o_list = o_keep + (chk ? up256((size_t)N * (size_t)no) : 0);
+    const size_t o_cnt = o_list + (chk ? up256(sizeof(uint32_t) * (size_t)blk * (size_t)N) : 0);
+    const size_t o_pd = o_cnt + (chk ? 256 : 0);
+    const size_t pd_bytes = chk ? sizeof(uint32_t) * (size_t)((no + blk - 1) / blk) * (size_t)N : 0;
+    if ((rc = c->bnd.ensure(o_pd + pd_bytes))) return rc;
     char* b = (char*)c->bnd.p;
     double* res = (double*)(b + o_res);
 
@@ -76,6 +92,8 @@ int run_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg, co
     a.steps = (unsigned long long*)(b + o_steps);
     a.part = (double*)(b + o_part);
     f.bind(a, b + o_extra);
+    const omc::BoundsCheck ck{chk, (unsigned char*)(b + o_keep), (uint32_t*)(b + o_list), (uint32_t*)(b + o_cnt),
+                              (uint32_t*)(b + o_pd), blk};
     // With a schedule the fit is omc_lsm_poly's on the J scheduled dates: its horizon T_v = T (J k) / N counts a short first
     // gap as a whole one, and its discount table is ensure_discounts' for (J, r, T_v)
     omc::LsmWorkspace wf = w;
@@ -125,23 +143,32 @@ int run_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg, co
     HIP_TRY(hipEventRecord(c->ev[2], st));
     HIP_TRY(f.outer(st));
     HIP_TRY(hipMemsetAsync(a.steps, 0, sizeof(unsigned long long), st));
-    // launches over blocks of outer paths, each at most kLaunchSteps / d inner path steps even if the policy never exercises
-    // (a schedule: the scheduled worst case n_inner sum_j (N - tau_j), j = 0 .. J-1)
-    double launch_work = work1;
-    if (sched) {
-        launch_work = (double)ni * (double)N;
+    if (chk) {  // the keep mask of every item; Q^ keeps its shape [n_outer][N], a skipped item's entry reads 0
+        const double* cvt = nullptr;
+        if (chk == 2) HIP_TRY(f.euro_table(st, &cvt));
+        HIP_TRY(hipMemsetAsync(ck.per_date, 0, pd_bytes, st));
+        HIP_TRY(omc::bounds_check_mark(st, a, ck, cvt));
+        HIP_TRY(hipMemsetAsync(a.q, 0, sizeof(double) * (size_t)no * (size_t)N, st));
+    }
+    if (sched) {  // the scheduled worst case n_inner sum_j (N - tau_j), j = 0 .. J-1
+        double launch_work = (double)ni * (double)N;
         for (int j = 1; j < sc.J; ++j) launch_work += (double)ni * (double)(N - (sc.tau1 + (j - 1) * sc.k));
         // Q^ keeps its shape [n_outer][N]; the sweep writes the scheduled columns, the others read 0
         HIP_TRY(hipMemsetAsync(a.q, 0, sizeof(double) * (size_t)no * (size_t)N, st));
+        blk = (int64_t)(kLaunchSteps / (double)f.d / launch_work);
+        blk = blk < 1 ? 1 : (blk > no ? no : blk);
     }
-    int64_t blk = (int64_t)(kLaunchSteps / (double)f.d / launch_work);
-    blk = blk < 1 ? 1 : (blk > no ? no : blk);
     for (int64_t i0 = 0; i0 < no; i0 += blk) {
         const int64_t n = no - i0 < blk ? no - i0 : blk;
-        if (cv) HIP_TRY(sched ? f.inner_sched_cv(st, sc, i0, n) : f.inner_cv(st, i0, n));
+        if (chk) {  // the block's kept items, then the sweep over them: the count stays on the device
+            HIP_TRY(omc::bounds_check_compact(st, a, ck, i0, n));
+            HIP_TRY(cv ? f.inner_check_cv(st, ck, i0, n) : f.inner_check(st, ck, i0, n));
+        }
+        else if (cv) HIP_TRY(sched ? f.inner_sched_cv(st, sc, i0, n) : f.inner_cv(st, i0, n));
         else HIP_TRY(sched ? f.inner_sched(st, sc, i0, n) : f.inner(st, i0, n));
     }
-    if (sched) HIP_TRY(omc::bounds_sched_walk(st, a, sc, res + 8));
+    if (chk) HIP_TRY(omc::bounds_check_walk(st, a, ck, res + 8));
+    else if (sched) HIP_TRY(omc::bounds_sched_walk(st, a, sc, res + 8));
     else HIP_TRY(own ? f.walk(st, res + 8) : omc::bounds_walk(st, a, res + 8));
     HIP_TRY(hipEventRecord(c->ev[3], st));
     double h[16];
@@ -191,7 +218,8 @@ extern "C" int omc_price_american_bounds(omc_ctx* c, const omc_params* p, const 
     BoundsFlow f;
     const bool cv = c->bounds_cv != 0;
     const int form = c->bounds_cv_form;
-    if (cv) f.extra_bytes = sizeof(double) * 4 * ((size_t)p->n_steps + 1);  // the table of E's per-date constants
+    // the table of E's per-date constants: the control variate's, and the European sub-optimality check's
+    if (cv || c->bounds_subopt == 2) f.extra_bytes = sizeof(double) * 4 * ((size_t)p->n_steps + 1);
     f.fit_paths = [&](float* S, int64_t ld) { return enqueue_paths(c, p, S, ld, false); };
     f.bind = [&](const omc::BoundsArgs& common, char* extra) {
         a = common;
@@ -217,6 +245,18 @@ extern "C" int omc_price_american_bounds(omc_ctx* c, const omc_params* p, const 
     f.inner_cv = [&](hipStream_t st, int64_t i0, int64_t ni) { return omc::bounds_inner_cv(st, cva, form, i0, ni); };
     f.inner_sched_cv = [&](hipStream_t st, const omc::BoundsSched& sc, int64_t i0, int64_t ni) {
         return omc::bounds_sched_inner_cv(st, cva, sc, form, i0, ni);
+    };
+    // sub-optimality checking (option "bounds_suboptimality"): the list-driven sweeps; the European
+    // check reads the control variate's table, built here when the control variate has not built it
+    f.inner_check = [&](hipStream_t st, const omc::BoundsCheck& k, int64_t i0, int64_t ni) {
+        return omc::bounds_check_inner(st, a, k, i0, ni);
+    };
+    f.inner_check_cv = [&](hipStream_t st, const omc::BoundsCheck& k, int64_t i0, int64_t ni) {
+        return omc::bounds_check_inner_cv(st, cva, k, form, i0, ni);
+    };
+    f.euro_table = [&](hipStream_t st, const double** table) {
+        *table = cva.cv;
+        return cv ? hipSuccess : omc::bounds_cv_table(st, cva);
     };
     if (cv)  // D[0] = 1; the spot is the generator's float32 start value
         f.cv_e0 = omc::bounds_cv_euro_host((double)(float)p->S0, p->K, p->r, p->sigma,

@@ -130,6 +130,9 @@ extern "C" int omc_price_american_bounds_heston(omc_ctx* c, const omc_params* p,
                                            p->heston_scheme);
     };
     f.inner = [&](hipStream_t st, int64_t i0, int64_t ni) { return omc::heston_bounds_inner(st, a, h, i0, ni); };
+    f.inner_check = [&](hipStream_t st, const omc::BoundsCheck& k, int64_t i0, int64_t ni) {  // section 27: the payoff check
+        return omc::heston_bounds_check_inner(st, a, h, k, i0, ni);
+    };
     f.inner_sched = [&](hipStream_t st, const omc::BoundsSched& sc, int64_t i0, int64_t ni) {
         return omc::heston_bounds_sched_inner(st, a, h, sc, i0, ni);
     };

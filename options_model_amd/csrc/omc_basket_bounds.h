@@ -20,5 +20,7 @@ struct BasketBoundsArgs {
 hipError_t basket_bounds_lower(hipStream_t st, const BasketBoundsArgs& a, double* result);
 // Q^_t[i] for outer paths [i0, i0 + ni) and t = 0..N-1
 hipError_t basket_bounds_inner(hipStream_t st, const BasketBoundsArgs& a, int64_t i0, int64_t ni);
+// bounds_check_inner (omc_bounds.h) with d assets: Q^ at the listed items only
+hipError_t basket_bounds_check_inner(hipStream_t st, const BasketBoundsArgs& a, const BoundsCheck& k, int64_t i0, int64_t ni);
 
 }  // namespace omc

@@ -19,6 +19,7 @@
 #include "omc_asian_dev.h"
 #include "omc_basket_bounds.h"
 #include "omc_basket_dev.h"
+#include "omc_bounds_check_dev.h"
 #include "omc_bounds_dev.h"
 
 namespace omc {
@@ -171,6 +172,24 @@ __global__ __launch_bounds__(kBlock) void asian_bounds_inner_kernel(BasketBounds
     bounds_inner_body(g.v, AsianModel<D>{g}, i0, ni, sh_bt);
 }
 
+// ------------------------------------------------------------------ sub-optimality checking, section 27
+// the list-driven sweep of omc_bounds_check_dev.h with both path laws (D = 1 too: bounds_inner_body's sums, the same bits)
+template <int D>
+__global__ __launch_bounds__(kBlock) void basket_bounds_check_inner_kernel(BasketBoundsArgs g, BoundsCheck k, int64_t i0,
+                                                                           int64_t ni)
+{
+    extern __shared__ uint4 sh_bt[];
+    bounds_check_inner_body(g.v, k, BasketBoundsModel<D>{g}, i0, ni, sh_bt);
+}
+
+template <int D>
+__global__ __launch_bounds__(kBlock) void asian_bounds_check_inner_kernel(BasketBoundsArgs g, BoundsCheck k, int64_t i0,
+                                                                          int64_t ni)
+{
+    extern __shared__ uint4 sh_bt[];
+    bounds_check_inner_body(g.v, k, AsianModel<D>{g}, i0, ni, sh_bt);
+}
+
 // ------------------------------------------------------------------ launchers
 hipError_t basket_bounds_lower(hipStream_t st, const BasketBoundsArgs& a, double* result)
 {
@@ -207,6 +226,27 @@ hipError_t basket_bounds_inner(hipStream_t st, const BasketBoundsArgs& a, int64_
     for_assets(a.d, [&](auto d) {
         hipLaunchKernelGGL((basket_bounds_inner_kernel<d()>), dim3((unsigned)g), dim3(kBlock),
                            sizeof(uint4) * (size_t)(a.v.N + 1), st, a, i0, ni);
+    });
+    return hipGetLastError();
+}
+
+hipError_t basket_bounds_check_inner(hipStream_t st, const BasketBoundsArgs& a, const BoundsCheck& k, int64_t i0, int64_t ni)
+{
+    if (a.d < 1 || a.d > kBasketMax) return hipErrorInvalidValue;
+    const int64_t items = ni * a.v.N;  // the dense sweep's grid: the kept items are a subset
+    int64_t g = (items + 3) / 4;
+    if (g > 2048) g = 2048;
+    if (basket_kind_is_asian(a.law.kind)) {
+        if (!a.Co) return hipErrorInvalidValue;
+        for_assets(a.d, [&](auto d) {
+            hipLaunchKernelGGL((asian_bounds_check_inner_kernel<d()>), dim3((unsigned)g), dim3(kBlock),
+                               sizeof(uint4) * (size_t)(a.v.N + 1), st, a, k, i0, ni);
+        });
+        return hipGetLastError();
+    }
+    for_assets(a.d, [&](auto d) {
+        hipLaunchKernelGGL((basket_bounds_check_inner_kernel<d()>), dim3((unsigned)g), dim3(kBlock),
+                           sizeof(uint4) * (size_t)(a.v.N + 1), st, a, k, i0, ni);
     });
     return hipGetLastError();
 }

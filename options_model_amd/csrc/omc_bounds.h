@@ -71,4 +71,22 @@ hipError_t bounds_lower_cv(hipStream_t st, const BoundsCvArgs& c, double* result
 hipError_t bounds_inner_cv(hipStream_t st, const BoundsCvArgs& c, int form, int64_t i0, int64_t ni);
 hipError_t bounds_sched_inner_cv(hipStream_t st, const BoundsCvArgs& c, const BoundsSched& sc, int form, int64_t i0, int64_t ni);
 
+// Sub-optimality checking (option "bounds_suboptimality" = m >= 1; DESIGN.md section 27, omc_bounds_check_dev.h): inner
+// simulations at the kept items only, the walk over the kept dates.
+struct BoundsCheck {
+    int mode;             // 1: kept where phi > 0, 2: kept where phi > E; t = 0 and the policy's stops are kept in both
+    unsigned char* keep;  // [N][n_outer] the keep mask, date-major as So
+    uint32_t* list;       // [ni N] of one inner launch: the kept item numbers t ni + (i - i0), ascending
+    uint32_t* count;      // how many
+    uint32_t* per_date;   // [ceil(n_outer / blk)][N] kept items of a date among the outer paths of an inner launch (zero
+    int64_t blk;          // before the mark); blk: outer paths per inner launch, the launches start at its multiples
+};
+// the mask of every item; cv: BoundsCvArgs::cv, read in mode 2 alone
+hipError_t bounds_check_mark(hipStream_t st, const BoundsArgs& a, const BoundsCheck& k, const double* cv);
+hipError_t bounds_check_compact(hipStream_t st, const BoundsArgs& a, const BoundsCheck& k, int64_t i0, int64_t ni);
+// Q^ at the listed items of outer paths [i0, i0 + ni); the other entries of a.q are not written
+hipError_t bounds_check_inner(hipStream_t st, const BoundsArgs& a, const BoundsCheck& k, int64_t i0, int64_t ni);
+hipError_t bounds_check_inner_cv(hipStream_t st, const BoundsCvArgs& c, const BoundsCheck& k, int form, int64_t i0, int64_t ni);
+hipError_t bounds_check_walk(hipStream_t st, const BoundsArgs& a, const BoundsCheck& k, double* result);
+
 }  // namespace omc

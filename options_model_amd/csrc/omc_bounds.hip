@@ -17,9 +17,10 @@
 // The lower and the inner sweep are bounds_lower_body / bounds_inner_body (omc_bounds_dev.h), which the multi-asset
 // kernels share; this file supplies their path law, one GBM asset, and the walk.  It also instantiates the sweeps of an
 // exercise schedule (omc_bounds_sched_dev.h, section 25) and those with the Black-Scholes control variate
-// (omc_bounds_cv_dev.h, section 26).
+// (omc_bounds_cv_dev.h, section 26), and the kernels of sub-optimality checking (omc_bounds_check_dev.h, section 27).
 #include <cmath>
 
+#include "omc_bounds_check_dev.h"
 #include "omc_bounds_cv_dev.h"
 #include "omc_bounds_dev.h"
 #include "omc_bounds_sched_dev.h"
@@ -307,6 +308,99 @@ hipError_t bounds_sched_inner_cv(hipStream_t st, const BoundsCvArgs& c, const Bo
 {
     if (!bounds_schedule_ok(sc, c.b.N)) return hipErrorInvalidValue;
     return launch_inner_cv_form<true>(st, c, sc, form, i0, ni);
+}
+
+// ------------------------------------------------------------------ sub-optimality checking
+// the bodies of omc_bounds_check_dev.h: the mark, the compaction and the walk of every law that decides on one float32 index,
+// and the list-driven sweeps with the GBM path law; no kernel above is touched
+__global__ __launch_bounds__(kBlock) void bounds_check_mark_kernel(BoundsArgs a, BoundsCheck k, const double* cv)
+{
+    bounds_check_mark_body(a, k, cv);
+}
+
+hipError_t bounds_check_mark(hipStream_t st, const BoundsArgs& a, const BoundsCheck& k, const double* cv)
+{
+    if ((k.mode != 1 && k.mode != 2) || (k.mode == 2 && !cv) || k.blk < 1) return hipErrorInvalidValue;
+    int64_t g = ((int64_t)a.N * a.n_outer + kBlock - 1) / kBlock;
+    if (g > 4096) g = 4096;
+    hipLaunchKernelGGL(bounds_check_mark_kernel, dim3((unsigned)g), dim3(kBlock), 0, st, a, k, cv);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(kCheckBlock) void bounds_check_compact_kernel(BoundsArgs a, BoundsCheck k, int64_t i0, int64_t ni)
+{
+    __shared__ uint32_t sh_w[kCheckBlock / 64];
+    bounds_check_compact_body(a, k, i0, ni, sh_w);
+}
+
+hipError_t bounds_check_compact(hipStream_t st, const BoundsArgs& a, const BoundsCheck& k, int64_t i0, int64_t ni)
+{
+    if (i0 < 0 || ni < 1 || i0 + ni > a.n_outer || (double)ni * (double)a.N >= 4294967296.0 || k.blk < 1 || i0 % k.blk != 0 ||
+        ni > k.blk)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(bounds_check_compact_kernel, dim3((unsigned)a.N), dim3(kCheckBlock), 0, st, a, k, i0, ni);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(kBlock) void bounds_check_inner_kernel(BoundsArgs a, BoundsCheck k, int64_t i0, int64_t ni)
+{
+    extern __shared__ uint4 sh_bt[];
+    bounds_check_inner_body(a, k, GbmBoundsModel{a}, i0, ni, sh_bt);
+}
+
+// (the grids are the dense sweeps': the kept items are a subset, how many is known on the device alone)
+hipError_t bounds_check_inner(hipStream_t st, const BoundsArgs& a, const BoundsCheck& k, int64_t i0, int64_t ni)
+{
+    const int64_t items = ni * a.N;
+    int64_t g = (items + 3) / 4;
+    if (g > 2048) g = 2048;
+    hipLaunchKernelGGL(bounds_check_inner_kernel, dim3((unsigned)g), dim3(kBlock), sizeof(uint4) * (size_t)(a.N + 1), st, a, k,
+                       i0, ni);
+    return hipGetLastError();
+}
+
+template <int G, int Park>
+__global__ __launch_bounds__(kBlock) void bounds_check_inner_cv_kernel(BoundsCvArgs c, BoundsCheck k, int64_t i0, int64_t ni)
+{
+    extern __shared__ uint4 sh_bt[];
+    bounds_check_inner_cv_body<G, Park>(c, k, GbmBoundsModel{c.b}, i0, ni, sh_bt);
+}
+
+namespace {
+template <int G>
+hipError_t launch_check_inner_cv(hipStream_t st, const BoundsCvArgs& c, const BoundsCheck& k, int64_t i0, int64_t ni)
+{
+    const int64_t items = ni * c.b.N;
+    const int64_t per_block = (kBlock / 64) * (64 / G);
+    int64_t g = (items + per_block - 1) / per_block;
+    if (g > 2048) g = 2048;
+    hipLaunchKernelGGL((bounds_check_inner_cv_kernel<G, kCvPark>), dim3((unsigned)g), dim3(kBlock),
+                       sizeof(uint4) * (size_t)(c.b.N + 1), st, c, k, i0, ni);
+    return hipGetLastError();
+}
+}  // namespace
+
+hipError_t bounds_check_inner_cv(hipStream_t st, const BoundsCvArgs& c, const BoundsCheck& k, int form, int64_t i0, int64_t ni)
+{
+    switch (bounds_cv_group(c.b.half_inner, form)) {  // G as the dense controlled sweep chooses it
+    case 8: return launch_check_inner_cv<8>(st, c, k, i0, ni);
+    case 16: return launch_check_inner_cv<16>(st, c, k, i0, ni);
+    case 32: return launch_check_inner_cv<32>(st, c, k, i0, ni);
+    default: return launch_check_inner_cv<64>(st, c, k, i0, ni);
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void bounds_check_walk_kernel(BoundsArgs a, BoundsCheck k, int nblk)
+{
+    __shared__ double red[kNQ * kRedStride];
+    bounds_check_walk_body(a, k, nblk, red);
+}
+
+hipError_t bounds_check_walk(hipStream_t st, const BoundsArgs& a, const BoundsCheck& k, double* result)
+{
+    const int nblk = (int)bounds_walk_blocks(a);
+    hipLaunchKernelGGL(bounds_check_walk_kernel, dim3(nblk), dim3(kBlock), 0, st, a, k, nblk);
+    return lsm_finalize(st, a.part, nullptr, result, nblk, 0);
 }
 
 }  // namespace omc

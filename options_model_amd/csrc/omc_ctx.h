@@ -184,6 +184,14 @@ struct BoundsFlow {
     std::function<hipError_t(hipStream_t, int64_t i0, int64_t ni)> inner_cv;
     std::function<hipError_t(hipStream_t, const omc::BoundsSched& sc, int64_t i0, int64_t ni)> inner_sched_cv;
     double cv_e0 = 0.0;  // E0 = D[0] E(S0, 0), float64 on the host
+    // Sub-optimality checking (option "bounds_suboptimality" = m >= 1; default: off).  A flow that sets
+    // inner_check is run with it in the place of inner -- Q^ at the items of run_bounds' kept list only -- and, with the
+    // control variate on, with inner_check_cv in the place of inner_cv.  euro_table (mode 2) leaves the table of E's
+    // per-date constants on the device, built if the call has not built it yet, and returns it.  A flow that leaves what the
+    // option asks for empty is refused (-40), as is every flow with a policy of its own.
+    std::function<hipError_t(hipStream_t, const omc::BoundsCheck& k, int64_t i0, int64_t ni)> inner_check;
+    std::function<hipError_t(hipStream_t, const omc::BoundsCheck& k, int64_t i0, int64_t ni)> inner_check_cv;
+    std::function<hipError_t(hipStream_t, const double** cv)> euro_table;
     // A policy of the flow's own (omc_api_runnerup_bounds.hip: a rule on two regressors), all three set or none.  With them
     // run_bounds neither uploads nor fits a [N+1][4] table and builds no exercise tables:
     //   own_policy(w, S, ld)   between the fit events: the caller's table to the device (S == nullptr), or the fit on the
@@ -304,6 +312,7 @@ struct omc_ctx {
     int64_t bounds_every = 0;  // option "bounds_exercise_every": 0 / 1 every date, k >= 2 the bounds of the scheduled game
     int bounds_cv = 0;         // option "bounds_control_variate": 1 = the GBM bounds' Black-Scholes control variate (section 26)
     int bounds_cv_form = 0;    // option "bounds_cv_form" (tests, measurement): omc::kCvFormDefault / kCvFormWave
+    int bounds_subopt = 0;     // option "bounds_suboptimality": 0 off, 1 payoff, 2 European (sub-optimality checking, section 27)
     DevBuf bnd;                // omc_price_american_bounds: outer paths, Q^ table, samples, tables, partials, sums
     DevBuf chain_fold;         // omc_price_american_chain: the entries' fold tables + c0 (their small buffers: gstate)
     DevBuf chain_sched;        // ... and its Bermudan entries' tables on their scheduled dates (omc::chain_schedule_tables)

@@ -25,5 +25,8 @@ hipError_t heston_bounds_inner(hipStream_t st, const BoundsArgs& a, const Heston
 // bounds_sched_inner (omc_bounds.h) under the Heston path law: Q^ at the scheduled dates only
 hipError_t heston_bounds_sched_inner(hipStream_t st, const BoundsArgs& a, const HestonBoundsLaw& h, const BoundsSched& sc,
                                      int64_t i0, int64_t ni);
+// bounds_check_inner (omc_bounds.h) under the Heston path law: Q^ at the listed items only
+hipError_t heston_bounds_check_inner(hipStream_t st, const BoundsArgs& a, const HestonBoundsLaw& h, const BoundsCheck& k,
+                                     int64_t i0, int64_t ni);
 
 }  // namespace omc

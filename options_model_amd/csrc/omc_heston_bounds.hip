@@ -12,6 +12,7 @@
 // the finalize are omc_bounds.hip's / omc_lsm.hip's.
 #include "omc_heston_bounds.h"
 
+#include "omc_bounds_check_dev.h"
 #include "omc_bounds_dev.h"
 #include "omc_bounds_sched_dev.h"
 #include "omc_paths_dev.h"
@@ -84,6 +85,15 @@ __global__ __launch_bounds__(kBlock) void heston_bounds_sched_inner_kernel(Hesto
 {
     extern __shared__ uint4 sh_bt[];
     bounds_sched_inner_body(g.v, sc, HestonBoundsModel<SCHEME>{g}, i0, ni, sh_bt);
+}
+
+// the list-driven inner sweep of sub-optimality checking (omc_bounds_check_dev.h) under the Heston law
+template <int SCHEME>
+__global__ __launch_bounds__(kBlock) void heston_bounds_check_inner_kernel(HestonBoundsArgs g, BoundsCheck k, int64_t i0,
+                                                                           int64_t ni)
+{
+    extern __shared__ uint4 sh_bt[];
+    bounds_check_inner_body(g.v, k, HestonBoundsModel<SCHEME>{g}, i0, ni, sh_bt);
 }
 
 // ------------------------------------------------------------------ the generator that keeps the variance
@@ -188,6 +198,22 @@ hipError_t heston_bounds_sched_inner(hipStream_t st, const BoundsArgs& a, const 
         hipLaunchKernelGGL((heston_bounds_sched_inner_kernel<0>), dim3((unsigned)nb), dim3(kBlock), lds, st, g, sc, i0, ni);
     else
         hipLaunchKernelGGL((heston_bounds_sched_inner_kernel<1>), dim3((unsigned)nb), dim3(kBlock), lds, st, g, sc, i0, ni);
+    return hipGetLastError();
+}
+
+hipError_t heston_bounds_check_inner(hipStream_t st, const BoundsArgs& a, const HestonBoundsLaw& h, const BoundsCheck& k,
+                                     int64_t i0, int64_t ni)
+{
+    if (h.scheme != 0 && h.scheme != 1) return hipErrorInvalidValue;
+    const HestonBoundsArgs g = heston_bounds_args(a, h);
+    const int64_t items = ni * a.N;  // the dense sweep's grid: the kept items are a subset
+    int64_t nb = (items + 3) / 4;
+    if (nb > 2048) nb = 2048;
+    const size_t lds = sizeof(uint4) * (size_t)(a.N + 1);
+    if (h.scheme == 0)
+        hipLaunchKernelGGL((heston_bounds_check_inner_kernel<0>), dim3((unsigned)nb), dim3(kBlock), lds, st, g, k, i0, ni);
+    else
+        hipLaunchKernelGGL((heston_bounds_check_inner_kernel<1>), dim3((unsigned)nb), dim3(kBlock), lds, st, g, k, i0, ni);
     return hipGetLastError();
 }
 
