@@ -961,6 +961,10 @@ int omc_price_american_bounds_heston(omc_ctx* ctx, const omc_params* p, const om
                                      double* betas_out, double* q_out /* NULL or host [n_outer][N] */,
                                      double* samples_out /* NULL or host [n_outer] */, omc_bounds* out);
 
+/* ---- Andersen-Broadie price bounds under jump-diffusion: Merton and Bates ------------------ */
+/* The jump generator as an entry point and the price bounds with the jump law are declared, with their contract, in
+ * include/omc_jump_bounds.h, which includes this header: this file's set of entry points is unchanged. */
+
 /* ---- calibrator inner loop -------------------------------------- */
 /* replaces HestonPricer.price_options_batch / price_european_option
  * (options_model_3/heston_calibration.py:259-312) for ONE expiry: simulate n_paths antithetic

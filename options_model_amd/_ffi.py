@@ -326,6 +326,14 @@ SIGNATURES = {
     "omc_nn_feature_stats": (C.c_int, [_P, _P, _P, _P, _I64, _D, _D, _P]),
 }
 
+# The entry points of include/omc_jump_bounds.h, an extension header of include/omc.h: SIGNATURES is
+# the set that omc.h declares, and stays that set.
+JUMP_BOUNDS_SIGNATURES = {
+    "omc_jump_paths_f32": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Jump), _D, _P, _P, _I64]),
+    "omc_price_american_bounds_jump": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Jump), _D, C.POINTER(BoundsConfig), _P,
+                                                 _P, _P, _P, C.POINTER(Bounds)]),
+}
+
 _lib = None
 _lib_lock = threading.Lock()
 _hip_runtime = None
@@ -383,7 +391,7 @@ def load_library(build_if_missing: bool = True):
                 path = _build.LIB
         _preload_hip_runtime()
         lib = C.CDLL(path)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in {**SIGNATURES, **JUMP_BOUNDS_SIGNATURES}.items():
             fn = getattr(lib, name)  # AttributeError = symbol missing = broken build
             fn.restype = res
             fn.argtypes = args
@@ -647,6 +655,24 @@ class Context:
                                                            n_steps, S0, r, T, v0, kappa, theta, xi, rho,
                                                            seed, stream, pair_offset, scheme))
         return S, V
+
+    def jump_paths(self, params: Params, jump, q=0.0, want_v=False):
+        """The jump generator's matrix (omc_jump_paths_f32) of params.n_paths antithetic paths at (params.seed,
+        params.stream, params.pair_offset), started at (params.S0, params.v0) -> device S [n_steps+1][n_paths], or
+        (S, V) with want_v (Heston: the variance state after every step).  jump: (lambda, mu_j, sigma_j); q: dividend
+        yield.  params.v0 of Heston schemes 0 .. 2 is a start state: a stored full-truncation state may be negative."""
+        n_paths, n_steps = int(params.n_paths), int(params.n_steps)
+        S = self.empty((n_steps + 1, n_paths), np.float32)
+        V = self.empty((n_steps + 1, n_paths), np.float32) if want_v else None
+        try:
+            _check(self.lib, self.lib.omc_jump_paths_f32(self.handle, C.byref(params), C.byref(make_jump(jump)), float(q),
+                                                          S.ptr, V.ptr if want_v else None, S.shape[1]))
+        except Exception:
+            S.free()
+            if want_v:
+                V.free()
+            raise
+        return (S, V) if want_v else S
 
     def gbm_paths_from_normals(self, z_half, S0, r, sigma, T, antithetic=True):
         z = self.to_device(z_half, np.float32)
@@ -1044,6 +1070,20 @@ class Context:
                                 betas, want_q, want_samples, 8 if int(regressors) == 1 else 4, heston=True,
                                 regressors=int(regressors), exercise_every=exercise_every)
 
+    def price_american_bounds_jump(self, params: Params, jump, q=0.0, policy="textbook", n_lower=1_000_000, n_outer=8192,
+                                   n_inner=1024, stream_lower=None, stream_outer=None, stream_inner=None, betas=None,
+                                   want_q=False, want_samples=False, exercise_every=0, suboptimality_check=None):
+        """Andersen-Broadie bounds of the Bermudan game under jump-diffusion (omc_price_american_bounds_jump: Merton on
+        GBM, Bates on Heston scheme reference or full_truncation) -> the dict of price_american_bounds.  jump: (lambda,
+        mu_j, sigma_j); q: dividend yield.  The policy is a function of the spot alone; the inner paths start at the outer
+        spot (Merton) or (spot, variance) state (Bates).  Streams default to params.stream + 1 / 2 / 3.
+        exercise_every: as price_american_bounds takes it.
+        suboptimality_check: as price_american_bounds takes it, "off" or "payoff" ("european" is refused with -40)."""
+        with self._bounds_checking(suboptimality_check):
+            return self._bounds(params, None, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner,
+                                betas, want_q, want_samples, exercise_every=exercise_every,
+                                jump=(make_jump(jump), float(q)))
+
     def price_american_basket_bounds(self, params: Params, basket: Basket, policy="textbook", n_lower=1_000_000,
                                      n_outer=8192, n_inner=1024, stream_lower=None, stream_outer=None, stream_inner=None,
                                      betas=None, want_q=False, want_samples=False, regressors="index",
@@ -1064,7 +1104,7 @@ class Context:
                                 stream_inner, betas, want_q, want_samples, 4 if regressors == "index" else 8)
 
     def _bounds(self, params, basket, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner, betas,
-                want_q, want_samples, cols=4, heston=False, regressors=0, exercise_every=None):
+                want_q, want_samples, cols=4, heston=False, regressors=0, exercise_every=None, jump=None):
         N = int(params.n_steps)
         cfg = BoundsConfig()
         cfg.regressors = regressors  # read by the Heston entry point alone
@@ -1087,8 +1127,11 @@ class Context:
         if basket is None:
             out = Bounds()
             entry = self.lib.omc_price_american_bounds_heston if heston else self.lib.omc_price_american_bounds
+            law = ()
+            if jump is not None:  # (Jump, q): the jump-diffusion entry point takes them after the params
+                entry, law = self.lib.omc_price_american_bounds_jump, (C.byref(jump[0]), jump[1])
             with self._bounds_schedule(exercise_every):  # (the multi-asset calls below leave the option as it is)
-                _check(self.lib, entry(self.handle, C.byref(params), C.byref(cfg), *tail, C.byref(out)))
+                _check(self.lib, entry(self.handle, C.byref(params), *law, C.byref(cfg), *tail, C.byref(out)))
             d = {k: getattr(out, k) for k, _ in Bounds._fields_}
         else:
             bb = BasketBounds()

@@ -947,6 +947,101 @@ def price_american_bounds_heston(S0, K, r, T, n_paths, n_steps, heston_params=No
                               exercise_every=every, n_exercise_dates=len(bounds_exercise_dates(n_steps, every)))
 
 
+@dataclass
+class JumpBoundsResult(BoundsResult):
+    """price_american_bounds_jumps: BoundsResult with the jump law.  The policy is a function of the spot alone; `lower` is
+    what it earns, `upper` bounds the value of the discretised jump-diffusion's game on the grid under ANY policy."""
+    jump_intensity: float = 0.0
+    jump_mean: float = 0.0
+    jump_vol: float = 0.0
+    dividend_yield: float = 0.0
+    model: str = "gbm"
+
+
+def price_american_bounds_jumps(S0, K, r, sigma, T, n_paths, n_steps, jump_intensity, jump_mean=0.0, jump_vol=0.0,
+                                dividend_yield=0.0, model="GBM", option_type="put", policy="textbook", n_lower=1_000_000,
+                                n_outer=8192, n_inner=1024, heston_params=None, heston_scheme="reference", seed=42, stream=0,
+                                betas=None, exercise_every=0, suboptimality_check=None, device=None, ctx=None,
+                                control_variate=False) -> JumpBoundsResult:
+    """Lower and upper bounds on the Bermudan value of a put / call under jump-diffusion (omc_price_american_bounds_jump,
+    DESIGN.md section 28): price_american_bounds on the paths of price_american_jumps -- jump_intensity jumps per year, each
+    multiplying the spot by exp(J), J ~ N(jump_mean, jump_vol^2), drift at r - dividend_yield - jump_intensity (E[e^J] - 1),
+    discounting at r.  model "GBM" is Merton's jump-diffusion, "Heston" is Bates's model (heston_params as
+    price_american_option takes them; heston_scheme "reference" (= "clamp") or "full_truncation").  jump_intensity * T /
+    n_steps may not exceed 1.  The policy (`policy` / `betas` as price_american_bounds takes them) regresses on the spot alone;
+    the inner simulations start at the outer paths' spot (Merton) or (spot, variance) state (Bates) -- the jumps are
+    independent of the past, so that is the whole Markov state and `upper` bounds the value of the discretised game on the
+    grid under any policy.  The bracket for the quote of price_american_jumps, which is a two-pass-flow value and lies above
+    `upper`.  The lower-bound, outer and inner paths use Philox streams stream + 1, + 2, + 3.  One GPU.
+    exercise_every = k >= 2: as price_american_bounds takes it.
+    suboptimality_check: None / "off", or "payoff" (DESIGN.md section 27); "european" and control_variate=True need the
+    European value under jumps per item and are refused."""
+    model_l = str(model).lower()
+    if model_l not in ("gbm", "heston"):
+        raise ValueError("model must be 'GBM' or 'Heston'.")
+    if control_variate:
+        raise ValueError("control_variate: the jump-diffusion bounds have no control variate.")
+    if suboptimality_check == "european":
+        raise ValueError("suboptimality_check='european' is for price_american_bounds only (jump-diffusion takes 'payoff' "
+                         "or 'off').")
+    if suboptimality_check is not None and suboptimality_check not in _ffi.BOUND_CHECKS:
+        raise ValueError(f"suboptimality_check must be one of {list(_ffi.BOUND_CHECKS)} or None.")
+    if exercise_every is None or isinstance(exercise_every, (list, tuple)):
+        raise ValueError("exercise_every must be a non-negative integer.")
+    every = _one_schedule(exercise_every)
+    if every >= 2 and suboptimality_check == "payoff":
+        raise ValueError("sub-optimality checking is for the game on every date (exercise_every must be 0 or 1).")
+    lam, mu, sj, q = float(jump_intensity), float(jump_mean), float(jump_vol), float(dividend_yield)
+    if not (math.isfinite(lam) and lam >= 0.0):
+        raise ValueError("jump_intensity must be finite and non-negative.")
+    if not math.isfinite(mu):
+        raise ValueError("jump_mean must be finite.")
+    if not (math.isfinite(sj) and sj >= 0.0):
+        raise ValueError("jump_vol must be finite and non-negative.")
+    if not math.isfinite(q):
+        raise ValueError("dividend_yield must be finite.")
+    if policy not in _ffi.BOUND_POLICIES:
+        raise ValueError(f"policy must be one of {sorted(_ffi.BOUND_POLICIES)}.")
+    if (policy == "given") != (betas is not None):
+        raise ValueError("betas must be given exactly when policy='given'.")
+    for name, v in (("n_lower", n_lower), ("n_outer", n_outer), ("n_inner", n_inner)):
+        if int(v) < 2 or int(v) % 2:
+            raise ValueError(f"{name} must be an even integer >= 2 (antithetic pairs).")
+    _validate(S0, K, T, r, sigma, n_paths, n_steps, option_type, need_sigma=(model_l == "gbm"))
+    if model_l == "heston":
+        if heston_scheme not in _ffi.HESTON_SCHEMES:
+            raise ValueError(f"heston_scheme must be one of {sorted(_ffi.HESTON_SCHEMES)}.")
+        if _ffi.HESTON_SCHEMES[heston_scheme] not in (_ffi.HESTON_SCHEMES["reference"],
+                                                      _ffi.HESTON_SCHEMES["full_truncation"]):
+            raise ValueError("price bounds under Bates take heston_scheme 'reference' or 'full_truncation'.")
+    if lam * float(T) / int(n_steps) > 1.0:
+        raise ValueError("jump_intensity * T / n_steps must not exceed 1: use more time steps.")
+    M = int(n_paths) // 2 * 2
+    if M <= 0:
+        raise ValueError("num_simulations and num_time_steps must be positive integers.")
+    if model_l == "heston":
+        p = _ffi.make_params(model="heston", is_put=(option_type == "put"), semantics="two_pass", antithetic=True,
+                             heston_scheme=heston_scheme, n_paths=M, n_steps=int(n_steps), S0=S0, K=K, r=r, sigma=sigma or 0.0,
+                             T=T, seed=seed, stream=stream, **heston_defaults(sigma, heston_params))
+    else:
+        p = _ffi.make_params(is_put=(option_type == "put"), semantics="two_pass", antithetic=True, n_paths=M,
+                             n_steps=int(n_steps), S0=S0, K=K, r=r, sigma=sigma, T=T, seed=seed, stream=stream)
+    c = ctx or _ffi.default_context(device)
+    out = c.price_american_bounds_jump(p, (lam, mu, sj), q, policy=policy, n_lower=int(n_lower), n_outer=int(n_outer),
+                                       n_inner=int(n_inner), betas=betas, exercise_every=every,
+                                       suboptimality_check=suboptimality_check)
+    return JumpBoundsResult(lower=out["lower"], se_lower=out["se_lower"], upper=out["upper"], se_upper=out["se_upper"],
+                            ci_lo=out["ci_lo"], ci_hi=out["ci_hi"], n_lower=out["n_lower"], n_outer=out["n_outer"],
+                            n_inner=out["n_inner"], n_exercised_lower=out["n_exercised_lower"],
+                            inner_path_steps=out["inner_path_steps"], policy=policy, betas=out["betas"],
+                            option_type=option_type,
+                            timings_ms=dict(fit=out["ms_fit"], lower=out["ms_lower"], upper=out["ms_upper"],
+                                            total=out["ms_total"]),
+                            exercise_every=every, n_exercise_dates=len(bounds_exercise_dates(n_steps, every)),
+                            suboptimality_check=suboptimality_check or "off",
+                            jump_intensity=lam, jump_mean=mu, jump_vol=sj, dividend_yield=q, model=model_l)
+
+
 def price_bermudan_bounds(S0, K, r, sigma, T, n_paths, n_steps, exercise_every, model="GBM", option_type="put",
                           policy="textbook", n_lower=1_000_000, n_outer=8192, n_inner=1024, heston_params=None,
                           heston_scheme="reference", seed=42, stream=0, betas=None, device=None, ctx=None,

@@ -9,19 +9,21 @@
 
 using namespace omc::abi;
 
-namespace {
+namespace omc::abi {
 
-struct JumpTable {
-    uint32_t thr[omc::kJumpThr];
-    double kappa, drift_rate;
-    int n_thr;  // entries below 2^24
-};
-
-// The argument checks of both entry points and the host side of the jump law, all in float64.
-int compose_jump(const omc_params* p, const omc_jump* j, double q, JumpTable* t)
+// The argument checks of the jump entry points and the host side of the jump law, all in float64 (omc_ctx.h).
+int compose_jump(const omc_params* p, const omc_jump* j, double q, JumpTable* t, bool priced, bool start_state)
 {
     int rc;
-    if ((rc = check_params(p))) return rc;
+    omc_params chk;
+    if (p && start_state && p->model == OMC_MODEL_HESTON && p->heston_scheme != OMC_HESTON_QE) {
+        chk = *p;
+        chk.v0 = 0.0;  // a start state is not validated: a stored full-truncation state may be negative
+        rc = check_params(&chk);
+    } else {
+        rc = check_params(p);
+    }
+    if (rc) return rc;
     if (!j) return fail(-25, "null jump parameters.");
     if (!std::isfinite(q)) return fail(-17, "dividend yield q must be finite.");
     if (!(std::isfinite(j->lambda) && j->lambda >= 0.0)) return fail(-26, "jump intensity lambda must be finite and non-negative.");
@@ -30,7 +32,8 @@ int compose_jump(const omc_params* p, const omc_jump* j, double q, JumpTable* t)
     const double x = j->lambda * p->T / p->n_steps;
     if (!(x <= 1.0)) return fail(-28, "lambda * T / n_steps must not exceed 1: use more time steps.");
     if (!p->antithetic) return fail(-24, "jump paths are antithetic pairs (antithetic = 1).");
-    if (p->semantics != OMC_SEM_TWO_PASS) return fail(-11, "jump-diffusion is priced by the two-pass flow (semantics 2).");
+    if (priced && p->semantics != OMC_SEM_TWO_PASS)
+        return fail(-11, "jump-diffusion is priced by the two-pass flow (semantics 2).");
     t->kappa = std::exp(j->mu_j + j->sigma_j * j->sigma_j / 2.0) - 1.0;
     t->drift_rate = (p->r - q) - j->lambda * t->kappa;
     double pn = std::exp(-x), cn = 0.0;
@@ -44,7 +47,17 @@ int compose_jump(const omc_params* p, const omc_jump* j, double q, JumpTable* t)
     return 0;
 }
 
-}  // namespace
+omc::JumpLaw jump_law(const JumpTable& t, const omc_jump* j)
+{
+    omc::JumpLaw law{};
+    memcpy(law.thr, t.thr, sizeof t.thr);
+    const double L2E = 1.4426950408889634074;
+    law.mj2 = (float)(j->mu_j * L2E);
+    law.sj2 = (float)(j->sigma_j * L2E);
+    return law;
+}
+
+}  // namespace omc::abi
 
 extern "C" {
 
@@ -52,7 +65,7 @@ int omc_jump_table(const omc_params* p, const omc_jump* j, double q, uint32_t th
 {
     JumpTable t;
     int rc;
-    if ((rc = compose_jump(p, j, q, &t))) return rc;
+    if ((rc = compose_jump(p, j, q, &t, true, false))) return rc;
     if (thr) memcpy(thr, t.thr, sizeof t.thr);
     if (kappa) *kappa = t.kappa;
     if (drift_rate) *drift_rate = t.drift_rate;
@@ -66,7 +79,7 @@ int omc_price_american_jump(omc_ctx* c, const omc_params* p, const omc_jump* j, 
     if ((rc = S_keep ? bind_in(c) : bind(c))) return rc;
     if (!out) return fail(-7, "null result pointer.");
     JumpTable t;
-    if ((rc = compose_jump(p, j, q, &t))) return rc;
+    if ((rc = compose_jump(p, j, q, &t, true, false))) return rc;
     if (c->distributed()) return fail(-10, "jump-diffusion pricing runs on one GPU.");
     memset(out, 0, sizeof *out);
     out->kappa = t.kappa;
@@ -80,11 +93,7 @@ int omc_price_american_jump(omc_ctx* c, const omc_params* p, const omc_jump* j, 
     }
     float* S;
     if ((rc = take_full_matrix(c, p, S_keep, &S, &ld))) return rc;
-    omc::JumpGen g{path_spec(c, p, t.drift_rate, S, ld), {}};
-    memcpy(g.law.thr, t.thr, sizeof t.thr);
-    const double L2E = 1.4426950408889634074;
-    g.law.mj2 = (float)(j->mu_j * L2E);
-    g.law.sj2 = (float)(j->sigma_j * L2E);
+    const omc::JumpGen g{path_spec(c, p, t.drift_rate, S, ld), jump_law(t, j)};
     if ((rc = enqueue_generated(c, p, S, ld, [&](hipStream_t st) { return omc::launch_jump_paths(st, g); }))) return rc;
     if ((rc = finish_generated(c, p, &out->base))) return rc;
     out->ms_jump_paths = out->base.ms_paths;

@@ -11,9 +11,11 @@
 #include <vector>
 
 #include "../../include/omc.h"
+#include "../../include/omc_jump_bounds.h"
 #include "omc_basket.h"
 #include "omc_bounds.h"
 #include "omc_comm.h"
+#include "omc_jump.h"
 #include "omc_kernels.h"
 #include "omc_p2p.h"
 
@@ -158,6 +160,19 @@ struct BasketTable {
 // the argument checks of include/omc.h's multi-asset section and the host constants: 0, or the code with the message set
 int compose_basket(const omc_params* p, const omc_basket* k, BasketTable* t);
 omc::BasketLaw basket_law(const BasketTable& t, const omc_basket* k);  // what the kernels take by value
+
+// ---- jump-diffusion: what omc_price_american_jump, omc_jump_paths_f32 and omc_price_american_bounds_jump share
+// (omc_api_jump.hip)
+struct JumpTable {
+    uint32_t thr[omc::kJumpThr];
+    double kappa, drift_rate;
+    int n_thr;  // entries below 2^24
+};
+// the argument checks of include/omc.h's jump-diffusion section and the host side of the law: 0, or the code with the
+// message set.  priced: the two-pass pricing's semantics check (-11); start_state: p->v0 of Heston schemes 0 .. 2 is a
+// stored state and is not validated
+int compose_jump(const omc_params* p, const omc_jump* j, double q, JumpTable* t, bool priced, bool start_state);
+omc::JumpLaw jump_law(const JumpTable& t, const omc_jump* j);  // what the kernels take by value
 
 // ---- Andersen-Broadie bounds: the flow omc_price_american_bounds and omc_price_american_basket_bounds share
 // (omc_api_bounds.hip).  The caller has checked its params; what differs between one asset and several is where the
