@@ -334,6 +334,13 @@ JUMP_BOUNDS_SIGNATURES = {
                                                  _P, _P, _P, C.POINTER(Bounds)]),
 }
 
+# The entry points of include/omc_dividend_bounds.h, an extension header of its own.
+DIVIDEND_BOUNDS_SIGNATURES = {
+    "omc_dividend_paths_f32": (C.c_int, [_P, C.POINTER(Params), _D, _P, _I, _I, _P, _P, _I64]),
+    "omc_price_american_bounds_div": (C.c_int, [_P, C.POINTER(Params), _D, _P, _I, C.POINTER(BoundsConfig), _P, _P, _P, _P,
+                                                C.POINTER(Bounds)]),
+}
+
 _lib = None
 _lib_lock = threading.Lock()
 _hip_runtime = None
@@ -391,7 +398,7 @@ def load_library(build_if_missing: bool = True):
                 path = _build.LIB
         _preload_hip_runtime()
         lib = C.CDLL(path)
-        for name, (res, args) in {**SIGNATURES, **JUMP_BOUNDS_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **JUMP_BOUNDS_SIGNATURES, **DIVIDEND_BOUNDS_SIGNATURES}.items():
             fn = getattr(lib, name)  # AttributeError = symbol missing = broken build
             fn.restype = res
             fn.argtypes = args
@@ -667,6 +674,27 @@ class Context:
         try:
             _check(self.lib, self.lib.omc_jump_paths_f32(self.handle, C.byref(params), C.byref(make_jump(jump)), float(q),
                                                           S.ptr, V.ptr if want_v else None, S.shape[1]))
+        except Exception:
+            S.free()
+            if want_v:
+                V.free()
+            raise
+        return (S, V) if want_v else S
+
+    def dividend_paths(self, params: Params, q=0.0, dividends=(), step_offset=0, want_v=False):
+        """The dividend generator's matrix (omc_dividend_paths_f32) of params.n_paths antithetic paths at (params.seed,
+        params.stream, params.pair_offset), started at (params.S0, params.v0) at date step_offset -> device S
+        [n_steps+1][n_paths], or (S, V) with want_v (Heston: the variance state after every step).  q: dividend yield;
+        dividends: as price_american_div takes them; row k takes the schedule's entry of step step_offset + k.  params.v0 of
+        Heston schemes 0 .. 2 is a start state: a stored full-truncation state may be negative."""
+        arr, n = dividend_array(dividends)
+        n_paths, n_steps = int(params.n_paths), int(params.n_steps)
+        S = self.empty((n_steps + 1, n_paths), np.float32)
+        V = self.empty((n_steps + 1, n_paths), np.float32) if want_v else None
+        try:
+            _check(self.lib, self.lib.omc_dividend_paths_f32(self.handle, C.byref(params), float(q), arr, n,
+                                                              int(step_offset), S.ptr, V.ptr if want_v else None,
+                                                              S.shape[1]))
         except Exception:
             S.free()
             if want_v:
@@ -1084,6 +1112,21 @@ class Context:
                                 betas, want_q, want_samples, exercise_every=exercise_every,
                                 jump=(make_jump(jump), float(q)))
 
+    def price_american_bounds_div(self, params: Params, q=0.0, dividends=(), policy="textbook", n_lower=1_000_000,
+                                  n_outer=8192, n_inner=1024, stream_lower=None, stream_outer=None, stream_inner=None,
+                                  betas=None, want_q=False, want_samples=False, exercise_every=0, suboptimality_check=None):
+        """Andersen-Broadie bounds of the Bermudan game on a stock that pays discrete dividends
+        (omc_price_american_bounds_div: GBM, or Heston scheme reference or full_truncation) -> the dict of
+        price_american_bounds.  q: dividend yield; dividends: as price_american_div takes them.  Exercise at a dividend step
+        earns the ex-dividend payoff.  The policy is a function of the spot alone; the inner paths start at the outer spot
+        (GBM) or (spot, variance) state (Heston) and at the outer date.  Streams default to params.stream + 1 / 2 / 3.
+        exercise_every: as price_american_bounds takes it.
+        suboptimality_check: as price_american_bounds takes it, "off" or "payoff" ("european" is refused with -40)."""
+        arr, n = dividend_array(dividends)
+        with self._bounds_checking(suboptimality_check):
+            return self._bounds(params, None, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner,
+                                betas, want_q, want_samples, exercise_every=exercise_every, dividend=(float(q), arr, n))
+
     def price_american_basket_bounds(self, params: Params, basket: Basket, policy="textbook", n_lower=1_000_000,
                                      n_outer=8192, n_inner=1024, stream_lower=None, stream_outer=None, stream_inner=None,
                                      betas=None, want_q=False, want_samples=False, regressors="index",
@@ -1104,7 +1147,7 @@ class Context:
                                 stream_inner, betas, want_q, want_samples, 4 if regressors == "index" else 8)
 
     def _bounds(self, params, basket, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner, betas,
-                want_q, want_samples, cols=4, heston=False, regressors=0, exercise_every=None, jump=None):
+                want_q, want_samples, cols=4, heston=False, regressors=0, exercise_every=None, jump=None, dividend=None):
         N = int(params.n_steps)
         cfg = BoundsConfig()
         cfg.regressors = regressors  # read by the Heston entry point alone
@@ -1130,6 +1173,8 @@ class Context:
             law = ()
             if jump is not None:  # (Jump, q): the jump-diffusion entry point takes them after the params
                 entry, law = self.lib.omc_price_american_bounds_jump, (C.byref(jump[0]), jump[1])
+            if dividend is not None:  # (q, omc_dividend array, n_div): likewise
+                entry, law = self.lib.omc_price_american_bounds_div, dividend
             with self._bounds_schedule(exercise_every):  # (the multi-asset calls below leave the option as it is)
                 _check(self.lib, entry(self.handle, C.byref(params), *law, C.byref(cfg), *tail, C.byref(out)))
             d = {k: getattr(out, k) for k, _ in Bounds._fields_}

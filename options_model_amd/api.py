@@ -1042,6 +1042,104 @@ def price_american_bounds_jumps(S0, K, r, sigma, T, n_paths, n_steps, jump_inten
                             jump_intensity=lam, jump_mean=mu, jump_vol=sj, dividend_yield=q, model=model_l)
 
 
+@dataclass
+class DividendBoundsResult(BoundsResult):
+    """price_american_bounds_dividends: BoundsResult with the dividend law.  The policy is a function of the spot alone;
+    `lower` is what it earns, `upper` bounds the value of the discretised game on the grid -- exercise at a dividend step
+    earns the ex-dividend payoff -- under ANY policy."""
+    dividend_yield: float = 0.0
+    n_div_steps: int = 0     # time steps on which at least one dividend goes ex
+    first_div_step: int = 0  # the first of them (0: none)
+    model: str = "gbm"
+
+
+def price_american_bounds_dividends(S0, K, r, sigma, T, n_paths, n_steps, dividend_yield=0.0, dividends=(), model="GBM",
+                                    option_type="put", policy="textbook", n_lower=1_000_000, n_outer=8192, n_inner=1024,
+                                    heston_params=None, heston_scheme="reference", seed=42, stream=0, betas=None,
+                                    exercise_every=0, suboptimality_check=None, device=None, ctx=None,
+                                    control_variate=False) -> DividendBoundsResult:
+    """Lower and upper bounds on the Bermudan value of a put / call on a stock that pays dividends
+    (omc_price_american_bounds_div): price_american_bounds on the paths of price_american_dividends --
+    drift at r - dividend_yield, discounting at r, and on every ex-dividend step the spot drops by the dividend; exercise at
+    that step earns the ex-dividend payoff.  dividends: the items price_american_dividends takes.  model "GBM" or "Heston"
+    (heston_params as price_american_option takes them; heston_scheme "reference" (= "clamp") or "full_truncation").  The
+    policy (`policy` / `betas` as price_american_bounds takes them) regresses on the spot alone; the inner simulations start
+    at the outer paths' spot (GBM) or (spot, variance) state (Heston) and at their date -- with a deterministic schedule that
+    is the whole Markov state, so `upper` bounds the value of the discretised game on the grid under any policy.  The
+    bracket for the quote of price_american_dividends, which is a two-pass-flow value.  The lower-bound, outer and inner
+    paths use Philox streams stream + 1, + 2, + 3.  One GPU.
+    exercise_every = k >= 2: as price_american_bounds takes it.
+    suboptimality_check: None / "off", or "payoff" (DESIGN.md section 27); "european" and control_variate=True are refused:
+    the Black-Scholes value is not the European value after a cash dividend."""
+    model_l = str(model).lower()
+    if model_l not in ("gbm", "heston"):
+        raise ValueError("model must be 'GBM' or 'Heston'.")
+    if control_variate:
+        raise ValueError("control_variate: the dividend bounds have no control variate.")
+    if suboptimality_check == "european":
+        raise ValueError("suboptimality_check='european' is for price_american_bounds only (dividends take 'payoff' or "
+                         "'off').")
+    if suboptimality_check is not None and suboptimality_check not in _ffi.BOUND_CHECKS:
+        raise ValueError(f"suboptimality_check must be one of {list(_ffi.BOUND_CHECKS)} or None.")
+    if exercise_every is None or isinstance(exercise_every, (list, tuple)):
+        raise ValueError("exercise_every must be a non-negative integer.")
+    every = _one_schedule(exercise_every)
+    if every >= 2 and suboptimality_check == "payoff":
+        raise ValueError("sub-optimality checking is for the game on every date (exercise_every must be 0 or 1).")
+    q = float(dividend_yield)
+    if not math.isfinite(q):
+        raise ValueError("dividend_yield must be finite.")
+    divs = []
+    for d in dividends:
+        d = tuple(d)
+        if len(d) not in (2, 3):
+            raise ValueError("a dividend is (t, amount) or (t, amount, 'cash' | 'proportional').")
+        kind = d[2] if len(d) == 3 else "cash"
+        if kind not in _ffi.DIVIDEND_KINDS:
+            raise ValueError("a dividend's kind must be 'cash' or 'proportional'.")
+        divs.append((float(d[0]), float(d[1]), kind))
+    if policy not in _ffi.BOUND_POLICIES:
+        raise ValueError(f"policy must be one of {sorted(_ffi.BOUND_POLICIES)}.")
+    if (policy == "given") != (betas is not None):
+        raise ValueError("betas must be given exactly when policy='given'.")
+    for name, v in (("n_lower", n_lower), ("n_outer", n_outer), ("n_inner", n_inner)):
+        if int(v) < 2 or int(v) % 2:
+            raise ValueError(f"{name} must be an even integer >= 2 (antithetic pairs).")
+    _validate(S0, K, T, r, sigma, n_paths, n_steps, option_type, need_sigma=(model_l == "gbm"))
+    if model_l == "heston":
+        if heston_scheme not in _ffi.HESTON_SCHEMES:
+            raise ValueError(f"heston_scheme must be one of {sorted(_ffi.HESTON_SCHEMES)}.")
+        if _ffi.HESTON_SCHEMES[heston_scheme] not in (_ffi.HESTON_SCHEMES["reference"],
+                                                      _ffi.HESTON_SCHEMES["full_truncation"]):
+            raise ValueError("price bounds with dividends take heston_scheme 'reference' or 'full_truncation'.")
+    M = int(n_paths) // 2 * 2
+    if M <= 0:
+        raise ValueError("num_simulations and num_time_steps must be positive integers.")
+    if model_l == "heston":
+        p = _ffi.make_params(model="heston", is_put=(option_type == "put"), semantics="two_pass", antithetic=True,
+                             heston_scheme=heston_scheme, n_paths=M, n_steps=int(n_steps), S0=S0, K=K, r=r, sigma=sigma or 0.0,
+                             T=T, seed=seed, stream=stream, **heston_defaults(sigma, heston_params))
+    else:
+        p = _ffi.make_params(is_put=(option_type == "put"), semantics="two_pass", antithetic=True, n_paths=M,
+                             n_steps=int(n_steps), S0=S0, K=K, r=r, sigma=sigma, T=T, seed=seed, stream=stream)
+    has = _ffi.dividend_schedule(p, q, divs)[2]  # (host only: the library's own checks of the schedule, before a context)
+    c = ctx or _ffi.default_context(device)
+    out = c.price_american_bounds_div(p, q, divs, policy=policy, n_lower=int(n_lower), n_outer=int(n_outer),
+                                      n_inner=int(n_inner), betas=betas, exercise_every=every,
+                                      suboptimality_check=suboptimality_check)
+    return DividendBoundsResult(lower=out["lower"], se_lower=out["se_lower"], upper=out["upper"], se_upper=out["se_upper"],
+                                ci_lo=out["ci_lo"], ci_hi=out["ci_hi"], n_lower=out["n_lower"], n_outer=out["n_outer"],
+                                n_inner=out["n_inner"], n_exercised_lower=out["n_exercised_lower"],
+                                inner_path_steps=out["inner_path_steps"], policy=policy, betas=out["betas"],
+                                option_type=option_type,
+                                timings_ms=dict(fit=out["ms_fit"], lower=out["ms_lower"], upper=out["ms_upper"],
+                                                total=out["ms_total"]),
+                                exercise_every=every, n_exercise_dates=len(bounds_exercise_dates(n_steps, every)),
+                                suboptimality_check=suboptimality_check or "off", dividend_yield=q,
+                                n_div_steps=int(has.sum()), first_div_step=int(has.argmax()) if has.any() else 0,
+                                model=model_l)
+
+
 def price_bermudan_bounds(S0, K, r, sigma, T, n_paths, n_steps, exercise_every, model="GBM", option_type="put",
                           policy="textbook", n_lower=1_000_000, n_outer=8192, n_inner=1024, heston_params=None,
                           heston_scheme="reference", seed=42, stream=0, betas=None, device=None, ctx=None,
