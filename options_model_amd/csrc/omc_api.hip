@@ -613,6 +613,14 @@ omc::PathSpec path_spec(const omc_ctx* c, const omc_params* p, double drift_rate
     return g;
 }
 
+omc::PathSpec path_spec(const omc_ctx* c, const omc_params* p, double drift_rate, float* S, int64_t ld, int64_t n_paths,
+                        uint64_t stream, uint64_t pair_offset)
+{
+    omc::PathSpec g = path_spec(c, p, drift_rate, S, ld);
+    g.n_paths = n_paths; g.stream = (uint32_t)stream; g.pair_offset = pair_offset;
+    return g;
+}
+
 int take_full_matrix(omc_ctx* c, const omc_params* p, float* S_keep, float** S, int64_t* ld)
 {
     if (S_keep && *ld < p->n_paths) return fail(-6, "leading dimension smaller than n_paths.");

@@ -33,17 +33,6 @@ int compose(const omc_params* p, double q, const omc_dividend* d, int n_div, boo
     return omc_dividend_schedule(&chk, q, d, n_div, mul->data(), cash->data(), has->data());
 }
 
-// the generator's descriptor for n_paths paths of p's law at (p->seed, stream, pair_offset) into S [N+1][ld]
-omc::DividendGen dividend_gen(const omc_ctx* c, const omc_params* p, double drift_rate, const omc::DivEntry* tab, float* S,
-                              int64_t ld, int64_t n_paths, uint64_t stream, uint64_t pair_offset)
-{
-    omc::DividendGen g{path_spec(c, p, drift_rate, S, ld), tab};
-    g.paths.n_paths = n_paths;
-    g.paths.stream = (uint32_t)stream;
-    g.paths.pair_offset = pair_offset;
-    return g;
-}
-
 // The call's tables in the context's device buffer: [entries + the closing one | first_after [N+1]].  room() makes the
 // buffer large enough (no launch); upload() copies the images and returns when they are copied (they are the caller's
 // pageable memory).
@@ -87,7 +76,7 @@ extern "C" int omc_dividend_paths_f32(omc_ctx* c, const omc_params* p, double q,
     const DeviceTables dt{tab, none};
     if ((rc = dt.room(c))) return rc;
     HIP_TRY(dt.upload(c, &d_tab, nullptr));
-    const omc::DividendGen g = dividend_gen(c, p, p->r - q, d_tab, S, ld, p->n_paths, p->stream, p->pair_offset);
+    const omc::DividendGen g{path_spec(c, p, p->r - q, S, ld), d_tab};
     HIP_TRY(V ? omc::launch_dividend_paths_sv(c->stream, g, V) : omc::launch_dividend_paths(c->stream, g));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
@@ -113,41 +102,27 @@ extern "C" int omc_price_american_bounds_div(omc_ctx* c, const omc_params* p, do
     std::vector<omc::DivStart> first;
     omc::dividend_tables(p->n_steps, mul.data(), cash.data(), has.data(), 0, &tab, &first);
     omc::BoundsArgs a{};
-    omc::DividendBoundsLaw l{heston ? 1 : 0, p->heston_scheme, rq, p->sigma, p->T, p->v0, p->kappa, p->theta, p->xi, p->rho,
-                             nullptr, nullptr, nullptr};
+    omc::DividendBoundsLaw l{{heston ? 1 : 0, p->heston_scheme, rq, p->sigma, p->T, p->v0, p->kappa, p->theta, p->xi, p->rho,
+                              nullptr}, nullptr, nullptr};
     // the tables go to the device with the first hook that enqueues work: a refusal of run_bounds launches nothing
     const DeviceTables dt{tab, first};
     if ((rc = dt.room(c))) return rc;
     auto tables = [&]() { return l.tab ? hipSuccess : dt.upload(c, &l.tab, &l.first); };
     BoundsFlow f;
-    f.d = heston ? 2 : 1;  // normals per step
-    if (heston && cfg->n_outer > 0)  // (sizes are checked in run_bounds, before the room is used)
-        f.extra_bytes = sizeof(float) * (size_t)(p->n_steps + 1) * (size_t)cfg->n_outer;
+    one_asset_flow(f, a, l, l.d, p, cfg);
     f.fit_paths = [&](float* S, int64_t ld) -> int {
         HIP_TRY(tables());
-        HIP_TRY(omc::launch_dividend_paths(c->stream,
-                                           dividend_gen(c, p, rq, l.tab, S, ld, p->n_paths, p->stream, p->pair_offset)));
+        HIP_TRY(omc::launch_dividend_paths(c->stream, omc::DividendGen{path_spec(c, p, rq, S, ld), l.tab}));
         return 0;
     };
-    f.bind = [&](const omc::BoundsArgs& common, char* extra) {
-        a = common;
-        a.s0 = (float)p->S0;  // the generator's start value, so every spot is the generator's
-        l.Vo = heston ? (const float*)extra : nullptr;
-    };
-    f.lower = [&](hipStream_t st, double* res) {
+    // (a given policy has no fit: the lower sweep is then the first hook that enqueues work)
+    f.lower = [&, lower = f.lower](hipStream_t st, double* res) {
         const hipError_t e = tables();
-        return e != hipSuccess ? e : omc::dividend_bounds_lower(st, a, l, res);
+        return e != hipSuccess ? e : lower(st, res);
     };
     f.outer = [&](hipStream_t st) {  // the outer paths: spots and, under Heston, the variance state, KEEP
-        const omc::DividendGen g = dividend_gen(c, p, rq, l.tab, (float*)a.So, a.n_outer, a.n_outer, cfg->stream_outer, 0);
-        return heston ? omc::launch_dividend_paths_sv(st, g, (float*)l.Vo) : omc::launch_dividend_paths(st, g);
-    };
-    f.inner = [&](hipStream_t st, int64_t i0, int64_t ni) { return omc::dividend_bounds_inner(st, a, l, i0, ni); };
-    f.inner_check = [&](hipStream_t st, const omc::BoundsCheck& k, int64_t i0, int64_t ni) {  // section 27: the payoff check
-        return omc::dividend_bounds_check_inner(st, a, l, k, i0, ni);
-    };
-    f.inner_sched = [&](hipStream_t st, const omc::BoundsSched& sc, int64_t i0, int64_t ni) {
-        return omc::dividend_bounds_sched_inner(st, a, l, sc, i0, ni);
+        const omc::DividendGen g{path_spec(c, p, rq, (float*)a.So, a.n_outer, a.n_outer, cfg->stream_outer, 0), l.tab};
+        return heston ? omc::launch_dividend_paths_sv(st, g, (float*)l.d.Vo) : omc::launch_dividend_paths(st, g);
     };
     return run_bounds(c, p, cfg, betas, betas_out, q_out, samples_out, out, f);
 }

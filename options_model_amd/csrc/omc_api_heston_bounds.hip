@@ -24,8 +24,11 @@ extern "C" int omc_heston_paths_sv_f32(omc_ctx* c, float* S, float* V, int64_t l
     if (!V) return fail(-7, "null variance matrix pointer.");
     if (n_paths & 1) return fail(-3, "antithetic layout needs an even n_paths.");
     if ((rc = check_heston_scheme(scheme, kappa, theta, xi))) return rc;
-    HIP_TRY(omc::launch_heston_paths_sv(c->stream, S, V, ld, n_paths, n_steps, S0, r, T, v0, kappa, theta, xi, rho, seed,
-                                        (uint32_t)stream, pair_offset, scheme));
+    omc::PathSpec s{};
+    s.model = 1; s.scheme = scheme; s.n_paths = n_paths; s.n_steps = n_steps; s.S0 = S0; s.r = r; s.T = T;
+    s.v0 = v0; s.kappa = kappa; s.theta = theta; s.xi = xi; s.rho = rho;
+    s.seed = seed; s.pair_offset = pair_offset; s.stream = (uint32_t)stream; s.S = S; s.ld = ld;
+    HIP_TRY(omc::launch_heston_paths_sv(c->stream, s, V));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -42,7 +45,8 @@ static int heston_sv_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_co
     const int N = p->n_steps;
     if (N > omc::kHestonSvMaxSteps) return fail(-16, "the spot + variance policy takes at most 512 dates.");
     omc::BoundsArgs a{};
-    omc::HestonSvLaw l{{p->r, p->T, p->v0, p->kappa, p->theta, p->xi, p->rho, p->heston_scheme, nullptr}, nullptr, 1.0 / vbar};
+    omc::HestonSvLaw l{{1, p->heston_scheme, p->r, p->sigma, p->T, p->v0, p->kappa, p->theta, p->xi, p->rho, nullptr}, nullptr,
+                       1.0 / vbar};
     const bool fitted = cfg->policy != OMC_POLICY_GIVEN;
     const int64_t ld_fit = padded_ld(p->n_paths);  // ensure_paths' leading dimension of the fitting paths
     const size_t pol_bytes = sizeof(double) * omc::kRunnerupCols * (size_t)(N + 1);
@@ -73,8 +77,7 @@ static int heston_sv_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_co
         }
         if (ld != ld_fit) return fail(999, "the fitting paths' leading dimension changed under the spot + variance fit.");
         float* V = (float*)(room + o_fit);
-        HIP_TRY(omc::launch_heston_paths_sv(c->stream, S, V, ld, p->n_paths, N, p->S0, p->r, p->T, p->v0, p->kappa, p->theta,
-                                            p->xi, p->rho, p->seed, (uint32_t)p->stream, p->pair_offset, p->heston_scheme));
+        HIP_TRY(omc::launch_heston_paths_sv(c->stream, path_spec(c, p, p->r, S, ld), V));
         omc::HestonSvFit fit{};
         fit.S = S; fit.V = V; fit.ld = ld; fit.M = p->n_paths;
         fit.N = N; fit.is_put = a.is_put; fit.K = a.K; fit.invK = a.invK; fit.inv_vbar = l.inv_vbar;
@@ -85,9 +88,8 @@ static int heston_sv_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_co
     };
     f.lower = [&](hipStream_t st, double* res) { return omc::heston_sv_lower(st, a, l, res); };
     f.outer = [&](hipStream_t st) {  // the outer paths: spots and variance state, KEEP
-        return omc::launch_heston_paths_sv(st, (float*)a.So, (float*)l.h.Vo, a.n_outer, a.n_outer, a.N, p->S0, p->r, p->T,
-                                           p->v0, p->kappa, p->theta, p->xi, p->rho, p->seed, (uint32_t)cfg->stream_outer, 0,
-                                           p->heston_scheme);
+        return omc::launch_heston_paths_sv(st, path_spec(c, p, p->r, (float*)a.So, a.n_outer, a.n_outer, cfg->stream_outer, 0),
+                                           (float*)l.h.Vo);
     };
     f.inner = [&](hipStream_t st, int64_t i0, int64_t ni) { return omc::heston_sv_inner(st, a, l, i0, ni); };
     f.walk = [&](hipStream_t st, double* res) { return omc::heston_sv_walk(st, a, l, res); };
@@ -112,29 +114,13 @@ extern "C" int omc_price_american_bounds_heston(omc_ctx* c, const omc_params* p,
         return heston_sv_bounds(c, p, cfg, betas, betas_out, q_out, samples_out, out);
     if (cfg->regressors != OMC_HESTON_REG_SPOT) return fail(-4, "unknown regressors (spot or spot + variance).");
     omc::BoundsArgs a{};
-    omc::HestonBoundsLaw h{p->r, p->T, p->v0, p->kappa, p->theta, p->xi, p->rho, p->heston_scheme, nullptr};
+    omc::DiffusionLaw h{1, p->heston_scheme, p->r, p->sigma, p->T, p->v0, p->kappa, p->theta, p->xi, p->rho, nullptr};
     BoundsFlow f;
-    f.d = 2;  // two normals per step
-    if (cfg->n_outer > 0)  // (sizes are checked in run_bounds, before the room is used)
-        f.extra_bytes = sizeof(float) * (size_t)(p->n_steps + 1) * (size_t)cfg->n_outer;
+    one_asset_flow(f, a, h, h, p, cfg);
     f.fit_paths = [&](float* S, int64_t ld) { return enqueue_paths(c, p, S, ld, false); };
-    f.bind = [&](const omc::BoundsArgs& common, char* extra) {
-        a = common;
-        a.s0 = (float)p->S0;  // the generator's start value, so every spot is the generator's
-        h.Vo = (const float*)extra;
-    };
-    f.lower = [&](hipStream_t st, double* res) { return omc::heston_bounds_lower(st, a, h, res); };
     f.outer = [&](hipStream_t st) {  // the outer paths: spots and variance state, KEEP
-        return omc::launch_heston_paths_sv(st, (float*)a.So, (float*)h.Vo, a.n_outer, a.n_outer, a.N, p->S0, p->r, p->T, p->v0,
-                                           p->kappa, p->theta, p->xi, p->rho, p->seed, (uint32_t)cfg->stream_outer, 0,
-                                           p->heston_scheme);
-    };
-    f.inner = [&](hipStream_t st, int64_t i0, int64_t ni) { return omc::heston_bounds_inner(st, a, h, i0, ni); };
-    f.inner_check = [&](hipStream_t st, const omc::BoundsCheck& k, int64_t i0, int64_t ni) {  // section 27: the payoff check
-        return omc::heston_bounds_check_inner(st, a, h, k, i0, ni);
-    };
-    f.inner_sched = [&](hipStream_t st, const omc::BoundsSched& sc, int64_t i0, int64_t ni) {
-        return omc::heston_bounds_sched_inner(st, a, h, sc, i0, ni);
+        return omc::launch_heston_paths_sv(st, path_spec(c, p, p->r, (float*)a.So, a.n_outer, a.n_outer, cfg->stream_outer, 0),
+                                           (float*)h.Vo);
     };
     return run_bounds(c, p, cfg, betas, betas_out, q_out, samples_out, out, f);
 }

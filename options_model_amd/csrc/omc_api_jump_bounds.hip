@@ -11,17 +11,6 @@ using namespace omc::abi;
 
 namespace {
 
-// the generator's descriptor for n_paths paths of p's law at (p->seed, stream, pair_offset) into S [N+1][ld]
-omc::JumpGen jump_gen(const omc_ctx* c, const omc_params* p, const omc::JumpLaw& law, double drift_rate, float* S, int64_t ld,
-                      int64_t n_paths, uint64_t stream, uint64_t pair_offset)
-{
-    omc::JumpGen g{path_spec(c, p, drift_rate, S, ld), law};
-    g.paths.n_paths = n_paths;
-    g.paths.stream = (uint32_t)stream;
-    g.paths.pair_offset = pair_offset;
-    return g;
-}
-
 // (lambda = 0 leaves the compensator out: 0 * kappa is not formed, as omc_price_american_jump has it)
 double drift_of(const omc_params* p, const omc_jump* j, double q, const JumpTable& t)
 {
@@ -38,8 +27,7 @@ extern "C" int omc_jump_paths_f32(omc_ctx* c, const omc_params* p, const omc_jum
     if ((rc = compose_jump(p, j, q, &t, false, true))) return rc;
     if ((rc = check_matrix(S, ld, p->n_paths))) return rc;
     if (V && p->model != OMC_MODEL_HESTON) return fail(-7, "a variance matrix is kept under Heston only (V must be NULL).");
-    const omc::JumpGen g =
-        jump_gen(c, p, jump_law(t, j), drift_of(p, j, q, t), S, ld, p->n_paths, p->stream, p->pair_offset);
+    const omc::JumpGen g{path_spec(c, p, drift_of(p, j, q, t), S, ld), jump_law(t, j)};
     HIP_TRY(V ? omc::launch_jump_paths_sv(c->stream, g, V) : omc::launch_jump_paths(c->stream, g));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
@@ -61,32 +49,17 @@ extern "C" int omc_price_american_bounds_jump(omc_ctx* c, const omc_params* p, c
     const double rj = drift_of(p, j, q, t);
     const omc::JumpLaw law = jump_law(t, j);
     omc::BoundsArgs a{};
-    omc::JumpBoundsLaw l{heston ? 1 : 0, p->heston_scheme, rj, p->sigma, p->T, p->v0, p->kappa, p->theta, p->xi, p->rho,
-                         nullptr, law};
+    omc::JumpBoundsLaw l{{heston ? 1 : 0, p->heston_scheme, rj, p->sigma, p->T, p->v0, p->kappa, p->theta, p->xi, p->rho, nullptr},
+                         law};
     BoundsFlow f;
-    f.d = heston ? 2 : 1;  // normals per step
-    if (heston && cfg->n_outer > 0)  // (sizes are checked in run_bounds, before the room is used)
-        f.extra_bytes = sizeof(float) * (size_t)(p->n_steps + 1) * (size_t)cfg->n_outer;
+    one_asset_flow(f, a, l, l.d, p, cfg);
     f.fit_paths = [&](float* S, int64_t ld) -> int {
-        HIP_TRY(omc::launch_jump_paths(c->stream, jump_gen(c, p, law, rj, S, ld, p->n_paths, p->stream, p->pair_offset)));
+        HIP_TRY(omc::launch_jump_paths(c->stream, omc::JumpGen{path_spec(c, p, rj, S, ld), law}));
         return 0;
     };
-    f.bind = [&](const omc::BoundsArgs& common, char* extra) {
-        a = common;
-        a.s0 = (float)p->S0;  // the generator's start value, so every spot is the generator's
-        l.Vo = heston ? (const float*)extra : nullptr;
-    };
-    f.lower = [&](hipStream_t st, double* res) { return omc::jump_bounds_lower(st, a, l, res); };
     f.outer = [&](hipStream_t st) {  // the outer paths: spots and, under Heston, the variance state, KEEP
-        const omc::JumpGen g = jump_gen(c, p, law, rj, (float*)a.So, a.n_outer, a.n_outer, cfg->stream_outer, 0);
-        return heston ? omc::launch_jump_paths_sv(st, g, (float*)l.Vo) : omc::launch_jump_paths(st, g);
-    };
-    f.inner = [&](hipStream_t st, int64_t i0, int64_t ni) { return omc::jump_bounds_inner(st, a, l, i0, ni); };
-    f.inner_check = [&](hipStream_t st, const omc::BoundsCheck& k, int64_t i0, int64_t ni) {  // section 27: the payoff check
-        return omc::jump_bounds_check_inner(st, a, l, k, i0, ni);
-    };
-    f.inner_sched = [&](hipStream_t st, const omc::BoundsSched& sc, int64_t i0, int64_t ni) {
-        return omc::jump_bounds_sched_inner(st, a, l, sc, i0, ni);
+        const omc::JumpGen g{path_spec(c, p, rj, (float*)a.So, a.n_outer, a.n_outer, cfg->stream_outer, 0), law};
+        return heston ? omc::launch_jump_paths_sv(st, g, (float*)l.d.Vo) : omc::launch_jump_paths(st, g);
     };
     return run_bounds(c, p, cfg, betas, betas_out, q_out, samples_out, out, f);
 }

@@ -102,11 +102,9 @@ hipError_t asian2_lower(hipStream_t st, const RunnerupArgs& a, double* result)
 hipError_t asian2_inner(hipStream_t st, const RunnerupArgs& a, int64_t i0, int64_t ni)
 {
     if (!asian2_ok(a)) return hipErrorInvalidValue;
-    const int64_t items = ni * a.g.v.N;
-    int64_t nb = (items + 3) / 4;
-    if (nb > 2048) nb = 2048;
+    const unsigned nb = bounds_inner_grid(ni * a.g.v.N);
     for_assets(a.g.d, [&](auto d) {
-        hipLaunchKernelGGL((asian2_inner_kernel<d()>), dim3((unsigned)nb), dim3(kBlock), asian2_policy_lds(a), st, a, i0, ni);
+        hipLaunchKernelGGL((asian2_inner_kernel<d()>), dim3(nb), dim3(kBlock), asian2_policy_lds(a), st, a, i0, ni);
     });
     return hipGetLastError();
 }

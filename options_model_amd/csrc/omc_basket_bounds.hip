@@ -212,9 +212,7 @@ hipError_t basket_bounds_lower(hipStream_t st, const BasketBoundsArgs& a, double
 hipError_t basket_bounds_inner(hipStream_t st, const BasketBoundsArgs& a, int64_t i0, int64_t ni)
 {
     if (a.d < 1 || a.d > kBasketMax) return hipErrorInvalidValue;
-    const int64_t items = ni * a.v.N;
-    int64_t g = (items + 3) / 4;
-    if (g > 2048) g = 2048;
+    const unsigned g = bounds_inner_grid(ni * a.v.N);
     if (basket_kind_is_asian(a.law.kind)) {
         if (!a.Co) return hipErrorInvalidValue;
         for_assets(a.d, [&](auto d) {
@@ -233,9 +231,7 @@ hipError_t basket_bounds_inner(hipStream_t st, const BasketBoundsArgs& a, int64_
 hipError_t basket_bounds_check_inner(hipStream_t st, const BasketBoundsArgs& a, const BoundsCheck& k, int64_t i0, int64_t ni)
 {
     if (a.d < 1 || a.d > kBasketMax) return hipErrorInvalidValue;
-    const int64_t items = ni * a.v.N;  // the dense sweep's grid: the kept items are a subset
-    int64_t g = (items + 3) / 4;
-    if (g > 2048) g = 2048;
+    const unsigned g = bounds_inner_grid(ni * a.v.N);  // the dense sweep's grid: the kept items are a subset
     if (basket_kind_is_asian(a.law.kind)) {
         if (!a.Co) return hipErrorInvalidValue;
         for_assets(a.d, [&](auto d) {

@@ -31,6 +31,15 @@ struct BoundsArgs {
 };
 
 int64_t bounds_lower_blocks(const BoundsArgs& a);
+// the grid of every inner sweep: four item waves per workgroup (the control variate's lane groups: per_block items), at
+// most 2048 workgroups
+inline unsigned bounds_inner_grid(int64_t items, int64_t per_block = 4)
+{
+    const int64_t g = (items + per_block - 1) / per_block;
+    return (unsigned)(g > 2048 ? 2048 : g);
+}
+// dynamic LDS of the sweeps that decide on one float32 index: the exercise tables, a uint4 per date
+inline size_t bounds_table_lds(int N) { return sizeof(uint4) * (size_t)(N + 1); }
 hipError_t bounds_lower(hipStream_t st, const BoundsArgs& a, double* result);
 // Q^_t[i] for outer paths [i0, i0 + ni) and t = 0..N-1
 hipError_t bounds_inner(hipStream_t st, const BoundsArgs& a, int64_t i0, int64_t ni);
@@ -88,5 +97,21 @@ hipError_t bounds_check_compact(hipStream_t st, const BoundsArgs& a, const Bound
 hipError_t bounds_check_inner(hipStream_t st, const BoundsArgs& a, const BoundsCheck& k, int64_t i0, int64_t ni);
 hipError_t bounds_check_inner_cv(hipStream_t st, const BoundsCvArgs& c, const BoundsCheck& k, int form, int64_t i0, int64_t ni);
 hipError_t bounds_check_walk(hipStream_t st, const BoundsArgs& a, const BoundsCheck& k, double* result);
+
+// The diffusion of a one-asset law as the host knows it (Heston, jump-diffusion and dividend bounds: omc_bounds_law_dev.h);
+// the launchers turn it into the generators' float32 constants (diffusion_args: gbm_step_constants or make_heston at the
+// drift rate), so every spot is the generator's.
+struct DiffusionLaw {
+    int model, scheme;  // model 0 GBM, 1 Heston (scheme 0 reference clamp, 1 full truncation)
+    double drift_rate;  // the rate of the paths (the discounts stay at r)
+    double sigma, T, v0, kappa, theta, xi, rho;
+    const float* Vo;    // Heston: [N+1][n_outer] the variance state of the outer paths
+};
+// the kernels' model number (0 GBM, 1 / 2 Heston scheme 0 / 1), or -1 for a law that has no kernels
+inline int diffusion_model(const DiffusionLaw& l)
+{
+    if (l.model == 0) return 0;
+    return l.model == 1 && (l.scheme == 0 || l.scheme == 1) ? l.scheme + 1 : -1;
+}
 
 }  // namespace omc

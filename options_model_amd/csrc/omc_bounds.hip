@@ -20,10 +20,8 @@
 // (omc_bounds_cv_dev.h, section 26), and the kernels of sub-optimality checking (omc_bounds_check_dev.h, section 27).
 #include <cmath>
 
-#include "omc_bounds_check_dev.h"
 #include "omc_bounds_cv_dev.h"
-#include "omc_bounds_dev.h"
-#include "omc_bounds_sched_dev.h"
+#include "omc_bounds_law_dev.h"
 
 namespace omc {
 
@@ -33,7 +31,9 @@ struct GbmBoundsModel {
     using Start = float;
     struct Spots { float a, b; };
     using Normals = float[4];
+    using Args = BoundsArgs;
     const BoundsArgs& a;
+    static __device__ __forceinline__ const BoundsArgs& common(const Args& a) { return a; }
     __device__ __forceinline__ Start lower_start() const { return a.s0; }
     __device__ __forceinline__ Start inner_start(int t, int64_t i) const { return a.So[(size_t)t * a.n_outer + i]; }
     __device__ __forceinline__ void reset(Spots& s, Start s0) const { s.a = s.b = s0; }
@@ -49,15 +49,11 @@ struct GbmBoundsModel {
     __device__ __forceinline__ float index_a(const Spots& s) const { return s.a; }
     __device__ __forceinline__ float index_b(const Spots& s) const { return s.b; }
 };
+// its four sweeps are omc_bounds_law_dev.h's wrappers and launchers with the one Model, whatever the number
+template <int>
+using GbmSweepModel = GbmBoundsModel;
 
 // ------------------------------------------------------------------ lower bound
-__global__ __launch_bounds__(kBlock) void bounds_lower_kernel(BoundsArgs a, int nblk)
-{
-    extern __shared__ uint4 sh_bt[];
-    __shared__ double red[kNQ * kRedStride];
-    bounds_lower_body(a, GbmBoundsModel{a}, nblk, sh_bt, red);
-}
-
 int64_t bounds_lower_blocks(const BoundsArgs& a)
 {
     const int64_t P = a.n_lower / 2;
@@ -67,26 +63,13 @@ int64_t bounds_lower_blocks(const BoundsArgs& a)
 
 hipError_t bounds_lower(hipStream_t st, const BoundsArgs& a, double* result)
 {
-    const int nblk = (int)bounds_lower_blocks(a);
-    hipLaunchKernelGGL(bounds_lower_kernel, dim3(nblk), dim3(kBlock), sizeof(uint4) * (size_t)(a.N + 1), st, a, nblk);
-    return lsm_finalize(st, a.part, nullptr, result, nblk, 0);
+    return launch_bounds_lower<GbmSweepModel, 0>(st, 0, a, a, result);
 }
 
 // ------------------------------------------------------------------ inner simulations
-__global__ __launch_bounds__(kBlock) void bounds_inner_kernel(BoundsArgs a, int64_t i0, int64_t ni)
-{
-    extern __shared__ uint4 sh_bt[];
-    bounds_inner_body(a, GbmBoundsModel{a}, i0, ni, sh_bt);
-}
-
 hipError_t bounds_inner(hipStream_t st, const BoundsArgs& a, int64_t i0, int64_t ni)
 {
-    const int64_t items = ni * a.N;
-    int64_t g = (items + 3) / 4;
-    if (g > 2048) g = 2048;
-    hipLaunchKernelGGL(bounds_inner_kernel, dim3((unsigned)g), dim3(kBlock), sizeof(uint4) * (size_t)(a.N + 1), st, a,
-                       i0, ni);
-    return hipGetLastError();
+    return launch_bounds_inner<GbmSweepModel, 0>(st, 0, a, a, i0, ni);
 }
 
 // ------------------------------------------------------------------ outer walk
@@ -158,21 +141,9 @@ bool bounds_schedule_ok(const BoundsSched& sc, int N)
     return sc.k >= 1 && sc.J >= 1 && sc.tau1 >= 1 && sc.tau1 <= sc.k && (int64_t)sc.tau1 + (int64_t)(sc.J - 1) * sc.k == N;
 }
 
-__global__ __launch_bounds__(kBlock) void bounds_sched_inner_kernel(BoundsArgs a, BoundsSched sc, int64_t i0, int64_t ni)
-{
-    extern __shared__ uint4 sh_bt[];
-    bounds_sched_inner_body(a, sc, GbmBoundsModel{a}, i0, ni, sh_bt);
-}
-
 hipError_t bounds_sched_inner(hipStream_t st, const BoundsArgs& a, const BoundsSched& sc, int64_t i0, int64_t ni)
 {
-    if (!bounds_schedule_ok(sc, a.N)) return hipErrorInvalidValue;
-    const int64_t items = ni * sc.J;
-    int64_t g = (items + 3) / 4;
-    if (g > 2048) g = 2048;
-    hipLaunchKernelGGL(bounds_sched_inner_kernel, dim3((unsigned)g), dim3(kBlock), sizeof(uint4) * (size_t)(a.N + 1), st, a,
-                       sc, i0, ni);
-    return hipGetLastError();
+    return launch_bounds_sched_inner<GbmSweepModel, 0>(st, 0, a, a, sc, i0, ni);
 }
 
 __global__ __launch_bounds__(kBlock) void bounds_sched_walk_kernel(BoundsArgs a, BoundsSched sc, int nblk)
@@ -245,7 +216,7 @@ __global__ __launch_bounds__(kBlock) void bounds_lower_cv_kernel(BoundsCvArgs c,
 hipError_t bounds_lower_cv(hipStream_t st, const BoundsCvArgs& c, double* result)
 {
     const int nblk = (int)bounds_lower_blocks(c.b);
-    hipLaunchKernelGGL(bounds_lower_cv_kernel, dim3(nblk), dim3(kBlock), sizeof(uint4) * (size_t)(c.b.N + 1), st, c, nblk);
+    hipLaunchKernelGGL(bounds_lower_cv_kernel, dim3(nblk), dim3(kBlock), bounds_table_lds(c.b.N), st, c, nblk);
     return lsm_finalize(st, c.b.part, nullptr, result, nblk, 0);
 }
 
@@ -273,10 +244,9 @@ hipError_t launch_inner_cv(hipStream_t st, const BoundsCvArgs& c, const BoundsSc
 {
     const int64_t items = ni * (Sched ? sc.J : c.b.N);
     const int64_t per_block = (kBlock / 64) * (64 / G);
-    int64_t g = (items + per_block - 1) / per_block;
-    if (g > 2048) g = 2048;
-    hipLaunchKernelGGL((bounds_inner_cv_kernel<G, Sched, Park>), dim3((unsigned)g), dim3(kBlock),
-                       sizeof(uint4) * (size_t)(c.b.N + 1), st, c, sc, i0, ni);
+    const unsigned g = bounds_inner_grid(items, per_block);
+    hipLaunchKernelGGL((bounds_inner_cv_kernel<G, Sched, Park>), dim3(g), dim3(kBlock),
+                       bounds_table_lds(c.b.N), st, c, sc, i0, ni);
     return hipGetLastError();
 }
 
@@ -342,21 +312,9 @@ hipError_t bounds_check_compact(hipStream_t st, const BoundsArgs& a, const Bound
     return hipGetLastError();
 }
 
-__global__ __launch_bounds__(kBlock) void bounds_check_inner_kernel(BoundsArgs a, BoundsCheck k, int64_t i0, int64_t ni)
-{
-    extern __shared__ uint4 sh_bt[];
-    bounds_check_inner_body(a, k, GbmBoundsModel{a}, i0, ni, sh_bt);
-}
-
-// (the grids are the dense sweeps': the kept items are a subset, how many is known on the device alone)
 hipError_t bounds_check_inner(hipStream_t st, const BoundsArgs& a, const BoundsCheck& k, int64_t i0, int64_t ni)
 {
-    const int64_t items = ni * a.N;
-    int64_t g = (items + 3) / 4;
-    if (g > 2048) g = 2048;
-    hipLaunchKernelGGL(bounds_check_inner_kernel, dim3((unsigned)g), dim3(kBlock), sizeof(uint4) * (size_t)(a.N + 1), st, a, k,
-                       i0, ni);
-    return hipGetLastError();
+    return launch_bounds_check_inner<GbmSweepModel, 0>(st, 0, a, a, k, i0, ni);
 }
 
 template <int G, int Park>
@@ -372,10 +330,9 @@ hipError_t launch_check_inner_cv(hipStream_t st, const BoundsCvArgs& c, const Bo
 {
     const int64_t items = ni * c.b.N;
     const int64_t per_block = (kBlock / 64) * (64 / G);
-    int64_t g = (items + per_block - 1) / per_block;
-    if (g > 2048) g = 2048;
-    hipLaunchKernelGGL((bounds_check_inner_cv_kernel<G, kCvPark>), dim3((unsigned)g), dim3(kBlock),
-                       sizeof(uint4) * (size_t)(c.b.N + 1), st, c, k, i0, ni);
+    const unsigned g = bounds_inner_grid(items, per_block);
+    hipLaunchKernelGGL((bounds_check_inner_cv_kernel<G, kCvPark>), dim3(g), dim3(kBlock),
+                       bounds_table_lds(c.b.N), st, c, k, i0, ni);
     return hipGetLastError();
 }
 }  // namespace

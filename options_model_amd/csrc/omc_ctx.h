@@ -142,6 +142,9 @@ int read_kernel_times(const hipEvent_t* evs, const omc_params* p, omc_result* re
 // multi-asset, barrier): DESIGN.md section 14, "adding a generator"
 // which paths: `p` with `drift_rate` as the rate of the paths, the width hint of p's model, the matrix S [N+1][ld]
 omc::PathSpec path_spec(const omc_ctx* c, const omc_params* p, double drift_rate, float* S, int64_t ld);
+// the same law at other paths: n_paths of them at (p->seed, stream, pair_offset)
+omc::PathSpec path_spec(const omc_ctx* c, const omc_params* p, double drift_rate, float* S, int64_t ld, int64_t n_paths,
+                        uint64_t stream, uint64_t pair_offset);
 // the matrix the generator writes: the caller's S_keep (refusal -6 when *ld < n_paths) or the context's own, in full
 int take_full_matrix(omc_ctx* c, const omc_params* p, float* S_keep, float** S, int64_t* ld);
 // events 0 and 1 around gen(stream), the two-pass flow on S with its pass events, event 2, the eight sums -> c->hres
@@ -220,6 +223,33 @@ struct BoundsFlow {
 // the cfg checks (-10, -4, -7, -3, -16), the policy, the sweeps, the walk, the read-back and *out
 int run_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg, const double* betas, double* betas_out,
                double* q_out, double* samples_out, omc_bounds* out, const BoundsFlow& f);
+// The hooks of a one-asset law whose policy sees the spot (Heston, jump-diffusion, dividends): the normals per step, the room
+// for the outer variance state under Heston, the binding of `a` and of the diffusion's Vo, and the four sweeps through the
+// overloads of bounds_lower / bounds_inner / bounds_check_inner / bounds_sched_inner for `law`, whose diffusion `d` is (or is
+// law itself).  a, law and d outlive the flow's run; fit_paths and outer stay the caller's.  (The calls are unqualified: the
+// law's overloads are declared in its own header and found through the arguments' namespace.)
+template <class Law>
+void one_asset_flow(BoundsFlow& f, omc::BoundsArgs& a, Law& law, omc::DiffusionLaw& d, const omc_params* p,
+                    const omc_bounds_config* cfg)
+{
+    const bool heston = d.model != 0;
+    f.d = heston ? 2 : 1;  // normals per step
+    if (heston && cfg->n_outer > 0)  // (sizes are checked in run_bounds, before the room is used)
+        f.extra_bytes = sizeof(float) * (size_t)(p->n_steps + 1) * (size_t)cfg->n_outer;
+    f.bind = [&a, &d, p, heston](const omc::BoundsArgs& common, char* extra) {
+        a = common;
+        a.s0 = (float)p->S0;  // the generator's start value, so every spot is the generator's
+        d.Vo = heston ? (const float*)extra : nullptr;
+    };
+    f.lower = [&a, &law](hipStream_t st, double* res) { return bounds_lower(st, a, law, res); };
+    f.inner = [&a, &law](hipStream_t st, int64_t i0, int64_t ni) { return bounds_inner(st, a, law, i0, ni); };
+    f.inner_check = [&a, &law](hipStream_t st, const omc::BoundsCheck& k, int64_t i0, int64_t ni) {  // section 27: the payoff check
+        return bounds_check_inner(st, a, law, k, i0, ni);
+    };
+    f.inner_sched = [&a, &law](hipStream_t st, const omc::BoundsSched& sc, int64_t i0, int64_t ni) {
+        return bounds_sched_inner(st, a, law, sc, i0, ni);
+    };
+}
 
 // ---- K two-pass pricings of one geometry that share their small launches (grouped sequences, option chains)
 // device bytes one member of a group owns in omc_ctx::gstate: [part1 | gmom | betas | crit | part]

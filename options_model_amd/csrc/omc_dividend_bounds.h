@@ -46,15 +46,12 @@ inline void dividend_tables(int N, const float* mul, const float* cash, const in
     }
 }
 
-// the law of a dividend bounds call as the host knows it; the launchers turn it into the generators' float32 constants
-// (gbm_step_constants, make_heston at the drift rate r - q), so every spot is the dividend generator's
+// the law of a dividend bounds call as the host knows it: the diffusion at the drift rate r - q, so every spot is the
+// dividend generator's, and the device tables
 struct DividendBoundsLaw {
-    int model, scheme;  // model 0 GBM, 1 Heston (scheme 0 reference clamp, 1 full truncation)
-    double drift_rate;  // r - q: the rate of the paths (the discounts stay at r)
-    double sigma, T, v0, kappa, theta, xi, rho;
-    const float* Vo;          // Heston: [N+1][n_outer] the variance state of the outer paths
-    const DivEntry* tab;      // device: the call's table at step_offset = 0
-    const DivStart* first;    // device: [N+1]
+    DiffusionLaw d;
+    const DivEntry* tab;    // device: the call's table at step_offset = 0
+    const DivStart* first;  // device: [N+1]
 };
 
 // launch_dividend_paths' S (one pair per thread) with the variance state V [n_steps+1][ld] beside it, as
@@ -63,11 +60,11 @@ hipError_t launch_dividend_paths_sv(hipStream_t st, const DividendGen& a, float*
 
 // bounds_lower / bounds_inner / bounds_sched_inner / bounds_check_inner (omc_bounds.h) under the dividend law; a model or a
 // scheme that has no kernels is hipErrorInvalidValue
-hipError_t dividend_bounds_lower(hipStream_t st, const BoundsArgs& a, const DividendBoundsLaw& l, double* result);
-hipError_t dividend_bounds_inner(hipStream_t st, const BoundsArgs& a, const DividendBoundsLaw& l, int64_t i0, int64_t ni);
-hipError_t dividend_bounds_sched_inner(hipStream_t st, const BoundsArgs& a, const DividendBoundsLaw& l, const BoundsSched& sc,
-                                       int64_t i0, int64_t ni);
-hipError_t dividend_bounds_check_inner(hipStream_t st, const BoundsArgs& a, const DividendBoundsLaw& l, const BoundsCheck& k,
-                                       int64_t i0, int64_t ni);
+hipError_t bounds_lower(hipStream_t st, const BoundsArgs& a, const DividendBoundsLaw& l, double* result);
+hipError_t bounds_inner(hipStream_t st, const BoundsArgs& a, const DividendBoundsLaw& l, int64_t i0, int64_t ni);
+hipError_t bounds_sched_inner(hipStream_t st, const BoundsArgs& a, const DividendBoundsLaw& l, const BoundsSched& sc, int64_t i0,
+                              int64_t ni);
+hipError_t bounds_check_inner(hipStream_t st, const BoundsArgs& a, const DividendBoundsLaw& l, const BoundsCheck& k, int64_t i0,
+                              int64_t ni);
 
 }  // namespace omc

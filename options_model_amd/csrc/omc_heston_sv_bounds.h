@@ -11,7 +11,7 @@ constexpr int kHestonSvMaxSteps = kRunnerupMaxSteps;  // dates whose policy rows
 // the Heston law of the call, the two-regressor policy and the scale of its second regressor.  Of BoundsArgs the kernels
 // read neither betas nor tab.
 struct HestonSvLaw {
-    HestonBoundsLaw h;
+    DiffusionLaw h;     // model 1, scheme 0 or 1
     const double* pol;  // [N+1][8] device
     double inv_vbar;    // 1 / max(v0, theta): w = fma(V, inv_vbar, -1)
 };

@@ -7,9 +7,9 @@
 //   lower   omc_heston_bounds.hip's lower sweep with the two-regressor stop.
 //   inner   the hot path, omc_heston_bounds.hip's inner simulations with the two-regressor stop.
 //   walk    the outer walk with the two-regressor stop on (So, Vo).
-// The bodies are omc_bounds2_dev.h's, instantiated for schemes 0 and 1.  The path law is HestonBoundsModel's
-// (omc_heston_bounds.hip), restated because that file's kernels keep their instruction streams: normals4(pair, 2 blk) and
-// normals4(pair, 2 blk + 1), four heston_pair_step<SCHEME> per draw, the item's (S_t[i], V_t[i]) read once per wave.  Y is
+// The bodies are omc_bounds2_dev.h's, instantiated for schemes 0 and 1.  The path law is the Heston bounds' own, the shared
+// diffusion (DiffusionModel, omc_bounds_law_dev.h): normals4(pair, 2 blk) and normals4(pair, 2 blk + 1), four
+// heston_pair_step<SCHEME> per draw, the item's (S_t[i], V_t[i]) read once per wave.  Y is
 // the variance as heston_pair_step leaves it -- what the generator stores: scheme 0 floored at 0, scheme 1 unfloored --,
 // scaled by 1 / max(v0, theta).  Every spot is the Heston generator's, the sums are float64 in a fixed order: identical
 // calls return identical bits.  Nothing is indexed at run time (no scratch).
@@ -19,58 +19,29 @@
 #include "omc_heston_sv_bounds.h"
 
 #include "omc_bounds2_dev.h"
-#include "omc_paths_dev.h"
+#include "omc_bounds_law_dev.h"
 
 namespace omc {
 
-// what the kernels take by value: the common arguments, the law's float32 constants, the policy
+// what the kernels take by value: the diffusion and the policy
 struct HestonSvArgs {
-    BoundsArgs v;
-    HestonC hc;
-    float v0;           // (float)v0: the variance every lower pair starts at
-    const float* Vo;    // [N+1][n_outer] variance state of the outer paths
+    DiffusionArgs d;
     const double* pol;  // [N+1][8]
     double inv_vbar;
 };
 
 // the Heston path law; the policy sees (spot, variance) of either partner
 template <int SCHEME>
-struct HestonSvModel {
-    struct Start { float s, v; };
-    struct Spots { float sa, sb, va, vb; };
-    using Normals = float[8];
-    const HestonSvArgs& g;
-    __device__ __forceinline__ Start lower_start() const { return Start{g.v.s0, g.v0}; }
-    // the outer state (S_t[i], V_t[i]): one address per wave, held as scalars
-    __device__ __forceinline__ Start inner_start(int t, int64_t i) const
-    {
-        const size_t at = (size_t)t * g.v.n_outer + i;
-        Start s0;
-        s0.s = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(g.v.So[at])));
-        s0.v = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(g.Vo[at])));
-        return s0;
-    }
-    __device__ __forceinline__ void reset(Spots& s, const Start& s0) const
-    {
-        s.sa = s.sb = s0.s;
-        s.va = s.vb = s0.v;
-    }
-    // four steps: the generator's blocks 2 blk and 2 blk + 1 (one Philox block per two steps)
-    __device__ __forceinline__ void draw(uint64_t pair, uint32_t blk, uint32_t stream, Normals& z) const
-    {
-        normals4(pair, 2 * blk, stream, g.v.k0, g.v.k1, reinterpret_cast<float(&)[4]>(z[0]));
-        normals4(pair, 2 * blk + 1, stream, g.v.k0, g.v.k1, reinterpret_cast<float(&)[4]>(z[4]));
-    }
-    __device__ __forceinline__ void step(Spots& s, const Normals& z, int u) const
-    {
-        heston_pair_step<SCHEME>(g.hc, z[2 * u], z[2 * u + 1], s.sa, s.va, s.sb, s.vb);
-    }
+struct HestonSvModel : DiffusionModel<SCHEME + 1> {
+    using Base = DiffusionModel<SCHEME + 1>;
+    using Spots = typename Base::Spots;
+    __device__ __forceinline__ HestonSvModel(const HestonSvArgs& g) : Base{g.d} {}
     __device__ __forceinline__ Pair2 xy_a(const Spots& s) const { return {s.sa, s.va}; }
     __device__ __forceinline__ Pair2 xy_b(const Spots& s) const { return {s.sb, s.vb}; }
     __device__ __forceinline__ Pair2 xy_outer(int t, int64_t i) const
     {
-        const size_t at = (size_t)t * g.v.n_outer + i;
-        return {g.v.So[at], g.Vo[at]};
+        const size_t at = (size_t)t * this->d.v.n_outer + i;
+        return {this->d.v.So[at], this->d.Vo[at]};
     }
 };
 
@@ -79,21 +50,21 @@ __global__ __launch_bounds__(kBlock) void heston_sv_lower_kernel(HestonSvArgs g,
 {
     extern __shared__ double sh_pol[];
     __shared__ double red[kNQ * kRedStride];
-    bounds2_lower_body(g.v, HestonSvModel<SCHEME>{g}, g.pol, g.inv_vbar, nblk, sh_pol, red);
+    bounds2_lower_body(g.d.v, HestonSvModel<SCHEME>{g}, g.pol, g.inv_vbar, nblk, sh_pol, red);
 }
 
 template <int SCHEME>
 __global__ __launch_bounds__(kBlock) void heston_sv_inner_kernel(HestonSvArgs g, int64_t i0, int64_t ni)
 {
     extern __shared__ double sh_pol[];
-    bounds2_inner_body(g.v, HestonSvModel<SCHEME>{g}, g.pol, g.inv_vbar, i0, ni, sh_pol);
+    bounds2_inner_body(g.d.v, HestonSvModel<SCHEME>{g}, g.pol, g.inv_vbar, i0, ni, sh_pol);
 }
 
 // the walk reads stored states only: the scheme does not enter (the model's is any)
 __global__ __launch_bounds__(kBlock) void heston_sv_walk_kernel(HestonSvArgs g, int nblk)
 {
     __shared__ double red[kNQ * kRedStride];
-    bounds2_walk_body(g.v, HestonSvModel<0>{g}, g.pol, g.inv_vbar, nblk, red);
+    bounds2_walk_body(g.d.v, HestonSvModel<0>{g}, g.pol, g.inv_vbar, nblk, red);
 }
 
 // the (x, y) of a fitting path: column j, row t of S and V
@@ -127,20 +98,10 @@ hipError_t heston_sv_fit(hipStream_t st, const HestonSvFit& f)
 
 static bool sv_ok(const BoundsArgs& a, const HestonSvLaw& l)
 {
-    return (l.h.scheme == 0 || l.h.scheme == 1) && a.N <= kHestonSvMaxSteps;
+    return diffusion_model(l.h) >= 1 && a.N <= kHestonSvMaxSteps;
 }
 
-static HestonSvArgs sv_args(const BoundsArgs& a, const HestonSvLaw& l)
-{
-    HestonSvArgs g{};
-    g.v = a;
-    g.hc = make_heston(l.h.r, l.h.T, a.N, l.h.kappa, l.h.theta, l.h.xi, l.h.rho);
-    g.v0 = (float)l.h.v0;
-    g.Vo = l.h.Vo;
-    g.pol = l.pol;
-    g.inv_vbar = l.inv_vbar;
-    return g;
-}
+static HestonSvArgs sv_args(const BoundsArgs& a, const HestonSvLaw& l) { return {diffusion_args(a, l.h), l.pol, l.inv_vbar}; }
 
 static size_t sv_policy_lds(const BoundsArgs& a) { return sizeof(double) * kRunnerupCols * (size_t)(a.N + 1); }
 
@@ -149,10 +110,9 @@ hipError_t heston_sv_lower(hipStream_t st, const BoundsArgs& a, const HestonSvLa
     if (!sv_ok(a, l)) return hipErrorInvalidValue;
     const HestonSvArgs g = sv_args(a, l);
     const int nblk = (int)bounds_lower_blocks(a);  // the vanilla sweep's grid
-    if (l.h.scheme == 0)
-        hipLaunchKernelGGL((heston_sv_lower_kernel<0>), dim3(nblk), dim3(kBlock), sv_policy_lds(a), st, g, nblk);
-    else
-        hipLaunchKernelGGL((heston_sv_lower_kernel<1>), dim3(nblk), dim3(kBlock), sv_policy_lds(a), st, g, nblk);
+    for_int<0, 1>(l.h.scheme, [&](auto sc) {
+        hipLaunchKernelGGL((heston_sv_lower_kernel<decltype(sc)::value>), dim3(nblk), dim3(kBlock), sv_policy_lds(a), st, g, nblk);
+    });
     return lsm_finalize(st, a.part, nullptr, result, nblk, 0);
 }
 
@@ -160,13 +120,10 @@ hipError_t heston_sv_inner(hipStream_t st, const BoundsArgs& a, const HestonSvLa
 {
     if (!sv_ok(a, l)) return hipErrorInvalidValue;
     const HestonSvArgs g = sv_args(a, l);
-    const int64_t items = ni * a.N;
-    int64_t nb = (items + 3) / 4;
-    if (nb > 2048) nb = 2048;
-    if (l.h.scheme == 0)
-        hipLaunchKernelGGL((heston_sv_inner_kernel<0>), dim3((unsigned)nb), dim3(kBlock), sv_policy_lds(a), st, g, i0, ni);
-    else
-        hipLaunchKernelGGL((heston_sv_inner_kernel<1>), dim3((unsigned)nb), dim3(kBlock), sv_policy_lds(a), st, g, i0, ni);
+    for_int<0, 1>(l.h.scheme, [&](auto sc) {
+        hipLaunchKernelGGL((heston_sv_inner_kernel<decltype(sc)::value>), dim3(bounds_inner_grid(ni * a.N)), dim3(kBlock),
+                           sv_policy_lds(a), st, g, i0, ni);
+    });
     return hipGetLastError();
 }
 

@@ -6,13 +6,10 @@
 
 namespace omc {
 
-// the law of a jump-diffusion bounds call as the host knows it; the launchers turn it into the generators' float32
-// constants (gbm_step_constants, make_heston at the compensated drift rate), so every spot is the jump generator's
+// the law of a jump-diffusion bounds call as the host knows it: the diffusion at the compensated drift rate
+// (r - q) - lambda kappa_J, so every spot is the jump generator's, and the jumps
 struct JumpBoundsLaw {
-    int model, scheme;  // model 0 GBM, 1 Heston (scheme 0 reference clamp, 1 full truncation)
-    double drift_rate;  // (r - q) - lambda kappa_J: the rate of the paths (the discounts stay at r)
-    double sigma, T, v0, kappa, theta, xi, rho;
-    const float* Vo;    // Heston: [N+1][n_outer] the variance state of the outer paths
+    DiffusionLaw d;
     JumpLaw law;
 };
 
@@ -22,11 +19,11 @@ hipError_t launch_jump_paths_sv(hipStream_t st, const JumpGen& a, float* V);
 
 // bounds_lower / bounds_inner / bounds_sched_inner / bounds_check_inner (omc_bounds.h) under the jump law; a model or a
 // scheme that has no kernels is hipErrorInvalidValue
-hipError_t jump_bounds_lower(hipStream_t st, const BoundsArgs& a, const JumpBoundsLaw& l, double* result);
-hipError_t jump_bounds_inner(hipStream_t st, const BoundsArgs& a, const JumpBoundsLaw& l, int64_t i0, int64_t ni);
-hipError_t jump_bounds_sched_inner(hipStream_t st, const BoundsArgs& a, const JumpBoundsLaw& l, const BoundsSched& sc,
-                                   int64_t i0, int64_t ni);
-hipError_t jump_bounds_check_inner(hipStream_t st, const BoundsArgs& a, const JumpBoundsLaw& l, const BoundsCheck& k,
-                                   int64_t i0, int64_t ni);
+hipError_t bounds_lower(hipStream_t st, const BoundsArgs& a, const JumpBoundsLaw& l, double* result);
+hipError_t bounds_inner(hipStream_t st, const BoundsArgs& a, const JumpBoundsLaw& l, int64_t i0, int64_t ni);
+hipError_t bounds_sched_inner(hipStream_t st, const BoundsArgs& a, const JumpBoundsLaw& l, const BoundsSched& sc, int64_t i0,
+                              int64_t ni);
+hipError_t bounds_check_inner(hipStream_t st, const BoundsArgs& a, const JumpBoundsLaw& l, const BoundsCheck& k, int64_t i0,
+                              int64_t ni);
 
 }  // namespace omc

@@ -15,62 +15,38 @@
 // exp2 sit behind that branch.  The thresholds and (mj2, sj2) come by value in the argument block.
 #include "omc_jump_bounds.h"
 
-#include "omc_bounds_check_dev.h"
-#include "omc_bounds_dev.h"
-#include "omc_bounds_sched_dev.h"
+#include "omc_bounds_law_dev.h"
 #include "omc_jump_dev.h"
-#include "omc_paths_dev.h"
 
 namespace omc {
 
-// what the jump-diffusion kernels take by value: the common arguments (v.a, v.b: the GBM step constants at the drift
-// rate), the Heston law's float32 constants at the drift rate, and the jump law
+// what the jump-diffusion kernels take by value: the diffusion at the compensated drift rate and the jump law
 struct JumpBoundsArgs {
-    BoundsArgs v;
-    HestonC hc;
-    float v0;         // (float)v0: the variance every lower pair starts at
-    const float* Vo;  // [N+1][n_outer] variance state of the outer paths (Heston)
+    DiffusionArgs d;
     JumpLaw law;
 };
 
-// the jump path law (the Model of omc_bounds_dev.h); MODEL 0 GBM, 1 / 2 Heston scheme 0 / 1; the policy sees the spot
+// the jump path law (the Model of omc_bounds_dev.h) on the diffusion MODEL 0 GBM, 1 / 2 Heston scheme 0 / 1; the policy
+// sees the spot
 template <int MODEL>
-struct JumpBoundsModel {
-    struct Start { float s, v; };
-    struct Spots { float sa, sb, va, vb; };  // (GBM: va, vb are never read)
+struct JumpBoundsModel : DiffusionModel<MODEL> {
+    using Base = DiffusionModel<MODEL>;
+    using Args = JumpBoundsArgs;
+    using Spots = typename Base::Spots;
     struct Normals {
-        float z[MODEL == 0 ? 4 : 8];  // four steps: one block of GBM, two of Heston
-        uint32_t w[4];                // their count words (top 24 bits)
+        typename Base::Normals z;
+        uint32_t w[4];  // the four steps' count words (top 24 bits)
         uint64_t pair;
         uint32_t blk, stream;
     };
-    const JumpBoundsArgs& g;
-    __device__ __forceinline__ Start lower_start() const { return Start{g.v.s0, g.v0}; }
-    // the outer state (S_t[i], V_t[i]): one address per wave, held as scalars
-    __device__ __forceinline__ Start inner_start(int t, int64_t i) const
-    {
-        const size_t at = (size_t)t * g.v.n_outer + i;
-        Start s0;
-        s0.s = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(g.v.So[at])));
-        if constexpr (MODEL == 0) s0.v = 0.0f;
-        else s0.v = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(g.Vo[at])));
-        return s0;
-    }
-    __device__ __forceinline__ void reset(Spots& s, const Start& s0) const
-    {
-        s.sa = s.sb = s0.s;
-        s.va = s.vb = s0.v;
-    }
-    // four steps of generator pair `pair`: its normals (GBM block blk; Heston blocks 2 blk and 2 blk + 1) and count block blk
+    const Args& g;
+    __device__ __forceinline__ JumpBoundsModel(const Args& g) : Base{g.d}, g(g) {}
+    static __device__ __forceinline__ const BoundsArgs& common(const Args& g) { return g.d.v; }
+    // four steps of generator pair `pair`: the diffusion's normals and count block blk
     __device__ __forceinline__ void draw(uint64_t pair, uint32_t blk, uint32_t stream, Normals& n) const
     {
-        if constexpr (MODEL == 0) {
-            normals4(pair, blk, stream, g.v.k0, g.v.k1, n.z);
-        } else {
-            normals4(pair, 2 * blk, stream, g.v.k0, g.v.k1, reinterpret_cast<float(&)[4]>(n.z[0]));
-            normals4(pair, 2 * blk + 1, stream, g.v.k0, g.v.k1, reinterpret_cast<float(&)[4]>(n.z[4]));
-        }
-        const U4 o = philox4x32_10((uint32_t)pair, (uint32_t)(pair >> 32), 0x40000000u | blk, stream, g.v.k0, g.v.k1);
+        Base::draw(pair, blk, stream, n.z);
+        const U4 o = philox4x32_10((uint32_t)pair, (uint32_t)(pair >> 32), 0x40000000u | blk, stream, g.d.v.k0, g.d.v.k1);
         n.w[0] = o.x >> 8; n.w[1] = o.y >> 8; n.w[2] = o.z >> 8; n.w[3] = o.w >> 8;
         n.pair = pair; n.blk = blk; n.stream = stream;
     }
@@ -78,17 +54,13 @@ struct JumpBoundsModel {
     {
         const bool jumps = n.w[u] >= g.law.thr[0];
         if (__builtin_amdgcn_ballot_w64(jumps) == 0) {  // no lane that takes this step jumps: the vanilla step
-            if constexpr (MODEL == 0) {
-                s.sa = s.sa * fast_exp2(__builtin_fmaf(g.v.b, n.z[u], g.v.a));
-                s.sb = s.sb * fast_exp2(__builtin_fmaf(-g.v.b, n.z[u], g.v.a));
-            } else {
-                heston_pair_step<MODEL - 1>(g.hc, n.z[2 * u], n.z[2 * u + 1], s.sa, s.va, s.sb, s.vb);
-            }
+            Base::step(s, n.z, u);
         } else {
             float jl = 0.0f;
-            if (jumps) jl = jump_log2(g.law, n.w[u], n.pair, (int)(4 * n.blk) + u + 1, n.stream, g.v.k0, g.v.k1);
-            if constexpr (MODEL == 0) {
-                float e = __builtin_fmaf(g.v.b, n.z[u], g.v.a), eb = __builtin_fmaf(-g.v.b, n.z[u], g.v.a);
+            if (jumps) jl = jump_log2(g.law, n.w[u], n.pair, (int)(4 * n.blk) + u + 1, n.stream, g.d.v.k0, g.d.v.k1);
+            if constexpr (MODEL == 0) {  // the jump goes into the step's exponent
+                const BoundsArgs& v = g.d.v;
+                float e = __builtin_fmaf(v.b, n.z[u], v.a), eb = __builtin_fmaf(-v.b, n.z[u], v.a);
                 if (jumps) {
                     e += jl;
                     eb += jl;
@@ -96,7 +68,7 @@ struct JumpBoundsModel {
                 s.sa = s.sa * fast_exp2(e);
                 s.sb = s.sb * fast_exp2(eb);
             } else {
-                heston_pair_step<MODEL - 1>(g.hc, n.z[2 * u], n.z[2 * u + 1], s.sa, s.va, s.sb, s.vb);
+                Base::step(s, n.z, u);
                 if (jumps) {
                     const float f = fast_exp2(jl);
                     s.sa = s.sa * f;
@@ -105,42 +77,7 @@ struct JumpBoundsModel {
             }
         }
     }
-    __device__ __forceinline__ float index_a(const Spots& s) const { return s.sa; }
-    __device__ __forceinline__ float index_b(const Spots& s) const { return s.sb; }
 };
-
-template <int MODEL>
-__global__ __launch_bounds__(kBlock) void jump_bounds_lower_kernel(JumpBoundsArgs g, int nblk)
-{
-    extern __shared__ uint4 sh_bt[];
-    __shared__ double red[kNQ * kRedStride];
-    bounds_lower_body(g.v, JumpBoundsModel<MODEL>{g}, nblk, sh_bt, red);
-}
-
-template <int MODEL>
-__global__ __launch_bounds__(kBlock) void jump_bounds_inner_kernel(JumpBoundsArgs g, int64_t i0, int64_t ni)
-{
-    extern __shared__ uint4 sh_bt[];
-    bounds_inner_body(g.v, JumpBoundsModel<MODEL>{g}, i0, ni, sh_bt);
-}
-
-// the inner sweep of an exercise schedule (omc_bounds_sched_dev.h) under the jump law
-template <int MODEL>
-__global__ __launch_bounds__(kBlock) void jump_bounds_sched_inner_kernel(JumpBoundsArgs g, BoundsSched sc, int64_t i0,
-                                                                         int64_t ni)
-{
-    extern __shared__ uint4 sh_bt[];
-    bounds_sched_inner_body(g.v, sc, JumpBoundsModel<MODEL>{g}, i0, ni, sh_bt);
-}
-
-// the list-driven inner sweep of sub-optimality checking (omc_bounds_check_dev.h) under the jump law
-template <int MODEL>
-__global__ __launch_bounds__(kBlock) void jump_bounds_check_inner_kernel(JumpBoundsArgs g, BoundsCheck k, int64_t i0,
-                                                                         int64_t ni)
-{
-    extern __shared__ uint4 sh_bt[];
-    bounds_check_inner_body(g.v, k, JumpBoundsModel<MODEL>{g}, i0, ni, sh_bt);
-}
 
 // ------------------------------------------------------------------ the generator that keeps the variance
 // jump_paths_kernel<SCHEME + 1, 1> with V beside S: the same counters, the same steps, the same spots
@@ -197,97 +134,33 @@ __global__ __launch_bounds__(kBlock) void jump_paths_sv_kernel(PathArgs g, JumpL
 // ------------------------------------------------------------------ launchers
 hipError_t launch_jump_paths_sv(hipStream_t st, const JumpGen& a, float* V)
 {
-    const PathSpec& s = a.paths;
-    const int64_t P = s.n_paths / 2;
-    if (P <= 0) return hipSuccess;
-    if (s.model != 1 || s.scheme < 0 || s.scheme > 3) return hipErrorInvalidValue;
-    const PathArgs g = make_path_args(s, P);
-    const dim3 grid((unsigned)((P + kBlock - 1) / kBlock)), block(kBlock);
-    for_scheme(s.scheme, [&](auto sc) {
+    return launch_paths_sv(a.paths, [&](auto sc, dim3 grid, dim3 block, const PathArgs& g) {
         hipLaunchKernelGGL((jump_paths_sv_kernel<decltype(sc)::value>), grid, block, 0, st, g, a.law, V);
     });
-    return hipGetLastError();
 }
 
-// the kernels' model number, or -1 for a law that has none
-static int jump_bounds_model(const JumpBoundsLaw& l)
+static JumpBoundsArgs jump_args(const BoundsArgs& a, const JumpBoundsLaw& l) { return {diffusion_args(a, l.d), l.law}; }
+
+hipError_t bounds_lower(hipStream_t st, const BoundsArgs& a, const JumpBoundsLaw& l, double* result)
 {
-    if (l.model == 0) return 0;
-    return l.model == 1 && (l.scheme == 0 || l.scheme == 1) ? l.scheme + 1 : -1;
+    return launch_bounds_lower<JumpBoundsModel, 0, 1, 2>(st, diffusion_model(l.d), a, jump_args(a, l), result);
 }
 
-static JumpBoundsArgs jump_bounds_args(const BoundsArgs& a, const JumpBoundsLaw& l)
+hipError_t bounds_inner(hipStream_t st, const BoundsArgs& a, const JumpBoundsLaw& l, int64_t i0, int64_t ni)
 {
-    JumpBoundsArgs g{};
-    g.v = a;
-    if (l.model == 0) gbm_step_constants(l.drift_rate, l.sigma, l.T, a.N, &g.v.a, &g.v.b);
-    else g.hc = make_heston(l.drift_rate, l.T, a.N, l.kappa, l.theta, l.xi, l.rho);
-    g.v0 = (float)l.v0;
-    g.Vo = l.Vo;
-    g.law = l.law;
-    return g;
+    return launch_bounds_inner<JumpBoundsModel, 0, 1, 2>(st, diffusion_model(l.d), a, jump_args(a, l), i0, ni);
 }
 
-// the inner sweeps' grid: four item waves per workgroup, at most 2048 workgroups (bounds_inner's)
-static unsigned inner_grid(int64_t items)
+hipError_t bounds_sched_inner(hipStream_t st, const BoundsArgs& a, const JumpBoundsLaw& l, const BoundsSched& sc, int64_t i0,
+                              int64_t ni)
 {
-    const int64_t nb = (items + 3) / 4;
-    return (unsigned)(nb > 2048 ? 2048 : nb);
+    return launch_bounds_sched_inner<JumpBoundsModel, 0, 1, 2>(st, diffusion_model(l.d), a, jump_args(a, l), sc, i0, ni);
 }
 
-hipError_t jump_bounds_lower(hipStream_t st, const BoundsArgs& a, const JumpBoundsLaw& l, double* result)
+hipError_t bounds_check_inner(hipStream_t st, const BoundsArgs& a, const JumpBoundsLaw& l, const BoundsCheck& k, int64_t i0,
+                              int64_t ni)
 {
-    const int mo = jump_bounds_model(l);
-    if (mo < 0) return hipErrorInvalidValue;
-    const JumpBoundsArgs g = jump_bounds_args(a, l);
-    const int nblk = (int)bounds_lower_blocks(a);  // the vanilla sweep's grid
-    const size_t lds = sizeof(uint4) * (size_t)(a.N + 1);
-    for_int<0, 1, 2>(mo, [&](auto model) {
-        hipLaunchKernelGGL((jump_bounds_lower_kernel<decltype(model)::value>), dim3(nblk), dim3(kBlock), lds, st, g, nblk);
-    });
-    return lsm_finalize(st, a.part, nullptr, result, nblk, 0);
-}
-
-hipError_t jump_bounds_inner(hipStream_t st, const BoundsArgs& a, const JumpBoundsLaw& l, int64_t i0, int64_t ni)
-{
-    const int mo = jump_bounds_model(l);
-    if (mo < 0) return hipErrorInvalidValue;
-    const JumpBoundsArgs g = jump_bounds_args(a, l);
-    const size_t lds = sizeof(uint4) * (size_t)(a.N + 1);
-    for_int<0, 1, 2>(mo, [&](auto model) {
-        hipLaunchKernelGGL((jump_bounds_inner_kernel<decltype(model)::value>), dim3(inner_grid(ni * a.N)), dim3(kBlock), lds,
-                           st, g, i0, ni);
-    });
-    return hipGetLastError();
-}
-
-hipError_t jump_bounds_sched_inner(hipStream_t st, const BoundsArgs& a, const JumpBoundsLaw& l, const BoundsSched& sc,
-                                   int64_t i0, int64_t ni)
-{
-    const int mo = jump_bounds_model(l);
-    if (mo < 0 || !bounds_schedule_ok(sc, a.N)) return hipErrorInvalidValue;
-    const JumpBoundsArgs g = jump_bounds_args(a, l);
-    const size_t lds = sizeof(uint4) * (size_t)(a.N + 1);
-    for_int<0, 1, 2>(mo, [&](auto model) {
-        hipLaunchKernelGGL((jump_bounds_sched_inner_kernel<decltype(model)::value>), dim3(inner_grid(ni * sc.J)),
-                           dim3(kBlock), lds, st, g, sc, i0, ni);
-    });
-    return hipGetLastError();
-}
-
-hipError_t jump_bounds_check_inner(hipStream_t st, const BoundsArgs& a, const JumpBoundsLaw& l, const BoundsCheck& k,
-                                   int64_t i0, int64_t ni)
-{
-    const int mo = jump_bounds_model(l);
-    if (mo < 0) return hipErrorInvalidValue;
-    const JumpBoundsArgs g = jump_bounds_args(a, l);
-    const size_t lds = sizeof(uint4) * (size_t)(a.N + 1);
-    // the dense sweep's grid: the kept items are a subset
-    for_int<0, 1, 2>(mo, [&](auto model) {
-        hipLaunchKernelGGL((jump_bounds_check_inner_kernel<decltype(model)::value>), dim3(inner_grid(ni * a.N)), dim3(kBlock),
-                           lds, st, g, k, i0, ni);
-    });
-    return hipGetLastError();
+    return launch_bounds_check_inner<JumpBoundsModel, 0, 1, 2>(st, diffusion_model(l.d), a, jump_args(a, l), k, i0, ni);
 }
 
 }  // namespace omc

@@ -443,11 +443,9 @@ hipError_t runnerup_lower(hipStream_t st, const RunnerupArgs& a, double* result)
 hipError_t runnerup_inner(hipStream_t st, const RunnerupArgs& a, int64_t i0, int64_t ni)
 {
     if (!ru_assets_ok(a.g.d) || a.g.v.N > kRunnerupMaxSteps) return hipErrorInvalidValue;
-    const int64_t items = ni * a.g.v.N;
-    int64_t g = (items + 3) / 4;
-    if (g > 2048) g = 2048;
+    const unsigned g = bounds_inner_grid(ni * a.g.v.N);
     for_runnerup_assets(a.g.d, [&](auto d) {
-        hipLaunchKernelGGL((runnerup_inner_kernel<d()>), dim3((unsigned)g), dim3(kBlock), ru_policy_lds(a), st, a, i0, ni);
+        hipLaunchKernelGGL((runnerup_inner_kernel<d()>), dim3(g), dim3(kBlock), ru_policy_lds(a), st, a, i0, ni);
     });
     return hipGetLastError();
 }

@@ -6,12 +6,20 @@ project's own build (options_model_amd/_build.py -v, so -O3 --offload-arch=gfx95
 OMC_HIPCC_FLAGS=-save-temps, each from a copy under --work so that neither tree's own library is replaced, and compares
 
   * per kernel, the lines of the device assembly between its entry label and .Lfunc_end, after comments are dropped and
-    the function's number is taken out of its local labels (.LBB<n>_<m> -> .LBB_<m>);
-  * the -Rpass-analysis=kernel-resource-usage numbers (SGPRs, VGPRs, AGPRs, scratch, LDS, occupancy, spills).
+    the function's number is taken out of its local labels (.LBB<n>_<m> -> .LBB_<m>) and the kernel's own mangled name
+    is replaced by a placeholder; the directive that returns to the code section behind the kernel descriptor is dropped
+    (.text for a plain function, a comdat section of its own for a template instantiation: where the linker puts the
+    code, not what the code is);
+  * the resource numbers (SGPRs, VGPRs, AGPRs, scratch, LDS, occupancy, code length): the "; Kernel info:" block the
+    compiler writes behind each kernel in the assembly.  (The -Rpass-analysis=kernel-resource-usage remarks of the build
+    log carry the same numbers, but the compilations run side by side and share the log: lines of one process are lost to,
+    or land among, another's, and a kernel is then read with its neighbour's numbers.  The log is kept for the reader.)
 
-Kernels are matched by source file and demangled name.  Kernels of the parent that the branch no longer has are listed
-(a change that removes instantiations names them in its description); a kernel that differs, or one only the branch
-has, makes the exit status 1.
+Kernels are matched by source file and demangled name.  A change that renames kernels gives --renames a table of them,
+one "parent demangled name => branch demangled name" per line (# starts a comment): a kernel of the parent that the table
+names is compared with its partner in the branch's build of the same source file.  Kernels of the parent that the branch
+no longer has are listed (a change that removes instantiations names them in its description); a kernel that differs, one
+only the branch has, or an entry of the table whose kernel is missing on its side, makes the exit status 1.
 
   git archive --prefix=parent/ HEAD^ | tar -x -C /tmp/cmp
   python tools/compare_kernels.py --parent /tmp/cmp/parent --branch . --work /tmp/cmp/work -o profiles/<name>_isa.txt
@@ -29,7 +37,6 @@ import sys
 
 DEVICE_ASM = "-hip-amdgcn-amd-amdhsa-gfx950.s"
 LOCAL_LABEL = re.compile(r"\.L([A-Za-z_]+)\d+_(\d+)")
-REMARK = re.compile(r"^remark: (\S+?):\d+:\d+:\s+(.*?) \[-Rpass-analysis=kernel-resource-usage\]\s*$")
 
 
 def build(tree: str, work: str) -> None:
@@ -57,8 +64,8 @@ def demangle(names: list[str]) -> dict[str, str]:
     return {n: n for n in names}
 
 
-def kernels_of(asm_path: str) -> dict[str, list[str]]:
-    """mangled kernel name -> normalised body lines"""
+def kernels_of(asm_path: str) -> dict[str, tuple[list[str], dict[str, str]]]:
+    """mangled kernel name -> (normalised body lines, the numbers of its "; Kernel info:" block)"""
     lines = open(asm_path).read().splitlines()
     names = [ln.split()[1] for ln in lines if ln.strip().startswith(".amdhsa_kernel ")]
     start = {}
@@ -69,48 +76,43 @@ def kernels_of(asm_path: str) -> dict[str, list[str]]:
     out = {}
     for name in names:
         body = []
-        for ln in lines[start[name] + 1:]:
+        for at, ln in enumerate(lines[start[name] + 1:], start[name] + 1):
             if ln.startswith(".Lfunc_end"):
                 break
-            ln = LOCAL_LABEL.sub(r".L\1_\2", ln.split(";", 1)[0]).strip()
-            if ln:
+            ln = LOCAL_LABEL.sub(r".L\1_\2", ln.split(";", 1)[0]).replace(name, "<this kernel>").strip()
+            if ln and ln != ".text" and not ln.startswith(".section\t.text."):
                 body.append(ln)
         else:
             raise RuntimeError(f"{asm_path}: no .Lfunc_end after {name}")
-        out[name] = body
-    return out
-
-
-def resources_of(log_path: str) -> dict[str, dict[str, str]]:
-    """mangled kernel name -> resource numbers.  The compilations run side by side and share the log, so the remarks are
-    taken apart by the source file they name before they are read in order."""
-    per_file: dict[str, list[str]] = {}
-    for ln in open(log_path, errors="replace"):
-        m = REMARK.match(ln)
-        if m:
-            per_file.setdefault(m.group(1), []).append(m.group(2))
-    out: dict[str, dict[str, str]] = {}
-    for texts in per_file.values():
-        cur = None
-        for t in texts:
-            key, _, val = t.partition(":")
-            if key.strip() == "Function Name":
-                cur = out.setdefault(val.strip(), {})
-            elif cur is not None:
-                cur[key.strip()] = val.strip()
+        info = {}
+        at = lines.index("; Kernel info:", at)
+        while at + 1 < len(lines) and lines[at + 1].startswith(";"):
+            at += 1
+            key, _, val = lines[at][1:].partition(":" if ":" in lines[at] else "=")
+            info[key.strip()] = val.strip()
+        out[name] = (body, info)
     return out
 
 
 def collect(work: str):
     temps = os.path.join(work, "temps")
-    res = resources_of(os.path.join(work, "build.log"))
     per_file = {}
     for f in sorted(os.listdir(temps)):
         if f.endswith(DEVICE_ASM):
             ks = kernels_of(os.path.join(temps, f))
             pretty = demangle(list(ks)) if ks else {}
-            per_file[f[:-len(DEVICE_ASM)] + ".hip"] = {pretty[n]: (body, res.get(n)) for n, body in ks.items()}
+            per_file[f[:-len(DEVICE_ASM)] + ".hip"] = {pretty[n]: ks[n] for n in ks}
     return per_file
+
+
+def renames_of(path: str | None) -> dict[str, str]:
+    table = {}
+    for ln in open(path) if path else ():
+        ln = ln.split("#", 1)[0].strip()
+        if ln:
+            old, _, new = ln.partition(" => ")
+            table[old.strip()] = new.strip()
+    return table
 
 
 def main() -> int:
@@ -119,6 +121,7 @@ def main() -> int:
     ap.add_argument("--branch", default=".", help="source tree of the change")
     ap.add_argument("--work", required=True, help="scratch directory for the two builds")
     ap.add_argument("--no-build", action="store_true")
+    ap.add_argument("--renames", help="table of renamed kernels: parent demangled name => branch demangled name")
     ap.add_argument("-o", "--output", default="-")
     a = ap.parse_args()
 
@@ -128,10 +131,17 @@ def main() -> int:
             build(tree, os.path.join(a.work, side))
     parent, branch = (collect(os.path.join(a.work, side)) for side in sides)
 
-    body, only_parent, only_branch = [], [], []
+    renames = renames_of(a.renames)
+    unused = set(renames)
+    body, only_parent, only_branch, renamed = [], [], [], []
     n_cmp = n_same = n_diff = n_res = n_nores = 0
     for src in sorted(set(parent) | set(branch)):
         kp, kb = parent.get(src, {}), branch.get(src, {})
+        for old in [n for n in kp if n in renames and n not in kb]:  # the parent's kernel under its new name
+            unused.discard(old)
+            if renames[old] in kb and renames[old] not in kp:
+                kp[renames[old]] = kp.pop(old)
+                renamed.append((src, old, renames[old]))
         body.append(f"== {src}: {len(kp)} kernels in the parent, {len(kb)} in the branch")
         for name in sorted(set(kp) | set(kb)):
             if name not in kb:
@@ -143,7 +153,7 @@ def main() -> int:
             else:
                 (ap_, rp), (ab, rb) = kp[name], kb[name]
                 n_cmp += 1
-                if rp is None or rb is None:
+                if not rp or not rb:
                     n_nores += 1
                 if ap_ == ab and rp == rb:
                     n_same += 1
@@ -154,9 +164,16 @@ def main() -> int:
                     what = "DIFFERENT" if ap_ != ab else "RESOURCES DIFFER"
                     body.append(f"  {what} ({len(ap_)} -> {len(ab)} lines; {rp} -> {rb})  {name}")
 
-    head = [f"kernels compared: {n_cmp}; identical: {n_same}; instruction streams that differ: {n_diff}",
-            f"kernels whose resource usage differs: {n_res}" + (f" (no resource remark found for {n_nores})" if n_nores else ""),
+    gone = {(src, old) for src, old, _ in renamed}
+    body += ["", f"== renamed ({len(renamed)} kernels, compared above under their new names)"]
+    body += [f"  {src}  {old}  =>  {new}" for src, old, new in renamed]
+    unpaired = sorted(unused) + [f"{src}  {n}" for src, n in only_parent if n in renames and (src, n) not in gone]
+    head = [f"kernels compared: {n_cmp} ({len(renamed)} of them through the rename table); identical: {n_same}; "
+            f"instruction streams that differ: {n_diff}",
+            f"kernels whose resource usage differs: {n_res}" + (f" (no kernel info found for {n_nores})" if n_nores else ""),
             f"kernels only in the parent: {len(only_parent)}; kernels only in the branch: {len(only_branch)}"]
+    if unpaired:
+        head += ["", "entries of the rename table without a pair:"] + [f"  {u}" for u in unpaired]
     for title, lst in (("only in the parent", only_parent), ("only in the branch", only_branch)):
         if lst:
             head.append("")
@@ -169,7 +186,7 @@ def main() -> int:
         with open(a.output, "w") as f:
             f.write(text)
         print("\n".join(head))
-    return 1 if (n_diff or n_res or only_branch or n_nores) else 0
+    return 1 if (n_diff or n_res or only_branch or n_nores or unpaired) else 0
 
 
 if __name__ == "__main__":
