@@ -24,7 +24,8 @@ def __getattr__(name):
                 "price_american_basket_greeks", "BasketGreeksResult", "price_american_bounds_heston",
                 "HestonBoundsResult", "price_asian_option", "price_bermudan_bounds", "bounds_exercise_dates",
                 "price_american_bounds_checked", "price_american_bounds_jumps", "JumpBoundsResult",
-                "price_american_bounds_dividends", "DividendBoundsResult"):
+                "price_american_bounds_dividends", "DividendBoundsResult", "price_barrier_bounds",
+                "BarrierBoundsResult"):
         from . import api
         return getattr(api, name)
     if name in ("AdvancedOptionPricer", "RNGManager", "BlackScholesGreeks", "welford_batch_update",

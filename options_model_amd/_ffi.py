@@ -341,6 +341,13 @@ DIVIDEND_BOUNDS_SIGNATURES = {
                                                 C.POINTER(Bounds)]),
 }
 
+# The entry points of include/omc_barrier_bounds.h, an extension header of its own.
+BARRIER_BOUNDS_SIGNATURES = {
+    "omc_barrier_paths_state_f32": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Barrier), _I, _P, _P, _P, _P, _I64]),
+    "omc_price_american_bounds_barrier": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Barrier), C.POINTER(BoundsConfig), _P, _P,
+                                                    _P, _P, C.POINTER(Bounds)]),
+}
+
 _lib = None
 _lib_lock = threading.Lock()
 _hip_runtime = None
@@ -398,7 +405,8 @@ def load_library(build_if_missing: bool = True):
                 path = _build.LIB
         _preload_hip_runtime()
         lib = C.CDLL(path)
-        for name, (res, args) in {**SIGNATURES, **JUMP_BOUNDS_SIGNATURES, **DIVIDEND_BOUNDS_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **JUMP_BOUNDS_SIGNATURES, **DIVIDEND_BOUNDS_SIGNATURES,
+                                  **BARRIER_BOUNDS_SIGNATURES}.items():
             fn = getattr(lib, name)  # AttributeError = symbol missing = broken build
             fn.restype = res
             fn.argtypes = args
@@ -460,6 +468,16 @@ def make_jump(jump) -> Jump:
         return jump
     lam, mu, sig = jump
     return Jump(float(lam), float(mu), float(sig))
+
+
+def make_barrier(kind, H, monitoring="discrete", american=True) -> Barrier:
+    """omc_barrier of `kind` (a key of BARRIER_KINDS or its code; an unknown key becomes -1, which the library refuses)"""
+    b = Barrier()
+    b.kind = BARRIER_KINDS.get(kind, -1) if isinstance(kind, str) else int(kind)
+    b.monitoring = MONITORING.get(monitoring, -1) if isinstance(monitoring, str) else int(monitoring)
+    b.american = int(bool(american))
+    b.H = float(H)
+    return b
 
 
 def jump_table(params: Params, jump, q=0.0):
@@ -701,6 +719,30 @@ class Context:
                 V.free()
             raise
         return (S, V) if want_v else S
+
+    def barrier_paths_state(self, params: Params, kind, H, start_hit=False, monitoring="discrete"):
+        """The barrier generator with its paths' state kept (omc_barrier_paths_state_f32) of params.n_paths antithetic paths
+        at (params.seed, params.stream, params.pair_offset), started at (params.S0, params.v0) -> device (E, S, V, hit): the
+        encoded index and the real spots [n_steps+1][n_paths], under Heston the variance state (GBM: None), and the int32
+        first-hit step of every path (0 = never).  kind: a key of BARRIER_KINDS or its code.  start_hit: a restart from a
+        state that has been hit (row 0 is encoded as hit, every entry of hit is -1, S0 may lie beyond the barrier);
+        params.v0 of a Heston call is a start state: a stored full-truncation state may be negative."""
+        n_paths, n_steps = int(params.n_paths), int(params.n_steps)
+        heston = int(params.model) == MODELS["heston"]
+        arrs = [self.empty((n_steps + 1, n_paths), np.float32), self.empty((n_steps + 1, n_paths), np.float32),
+                self.empty((n_steps + 1, n_paths), np.float32) if heston else None, self.empty((n_paths,), np.int32)]
+        E, S, V, hit = arrs
+        try:
+            _check(self.lib, self.lib.omc_barrier_paths_state_f32(self.handle, C.byref(params),
+                                                                   C.byref(make_barrier(kind, H, monitoring)),
+                                                                   int(bool(start_hit)), E.ptr, S.ptr, V.ptr if heston else None,
+                                                                   hit.ptr, E.shape[1]))
+        except Exception:
+            for a in arrs:
+                if a is not None:
+                    a.free()
+            raise
+        return E, S, V, hit
 
     def gbm_paths_from_normals(self, z_half, S0, r, sigma, T, antithetic=True):
         z = self.to_device(z_half, np.float32)
@@ -1127,6 +1169,22 @@ class Context:
             return self._bounds(params, None, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner,
                                 betas, want_q, want_samples, exercise_every=exercise_every, dividend=(float(q), arr, n))
 
+    def price_barrier_bounds(self, params: Params, kind, H, monitoring="discrete", policy="textbook", n_lower=1_000_000,
+                             n_outer=8192, n_inner=1024, stream_lower=None, stream_outer=None, stream_inner=None, betas=None,
+                             want_q=False, want_samples=False, exercise_every=0, suboptimality_check=None):
+        """Andersen-Broadie bounds of the American barrier option price_barrier quotes (omc_price_american_bounds_barrier:
+        GBM, or Heston scheme reference or full_truncation; discrete monitoring) -> the dict of price_american_bounds.
+        kind: a key of BARRIER_KINDS or its code.  The policy is a function of the ENCODED index (the spot where the option
+        is live, the dead spot elsewhere); the inner paths start at the outer (spot, hit[, variance]) state; a knocked-out
+        path stops with value 0 and an item of a dead knock-out has q = 0 and no steps.  Streams default to params.stream +
+        1 / 2 / 3.
+        exercise_every: as price_american_bounds takes it (monitoring stays on every step).
+        suboptimality_check: as price_american_bounds takes it, "off" or "payoff" ("european" is refused with -12)."""
+        with self._bounds_checking(suboptimality_check):
+            return self._bounds(params, None, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner,
+                                betas, want_q, want_samples, exercise_every=exercise_every,
+                                barrier=make_barrier(kind, H, monitoring))
+
     def price_american_basket_bounds(self, params: Params, basket: Basket, policy="textbook", n_lower=1_000_000,
                                      n_outer=8192, n_inner=1024, stream_lower=None, stream_outer=None, stream_inner=None,
                                      betas=None, want_q=False, want_samples=False, regressors="index",
@@ -1147,7 +1205,8 @@ class Context:
                                 stream_inner, betas, want_q, want_samples, 4 if regressors == "index" else 8)
 
     def _bounds(self, params, basket, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner, betas,
-                want_q, want_samples, cols=4, heston=False, regressors=0, exercise_every=None, jump=None, dividend=None):
+                want_q, want_samples, cols=4, heston=False, regressors=0, exercise_every=None, jump=None, dividend=None,
+                barrier=None):
         N = int(params.n_steps)
         cfg = BoundsConfig()
         cfg.regressors = regressors  # read by the Heston entry point alone
@@ -1175,6 +1234,8 @@ class Context:
                 entry, law = self.lib.omc_price_american_bounds_jump, (C.byref(jump[0]), jump[1])
             if dividend is not None:  # (q, omc_dividend array, n_div): likewise
                 entry, law = self.lib.omc_price_american_bounds_div, dividend
+            if barrier is not None:  # omc_barrier: likewise
+                entry, law = self.lib.omc_price_american_bounds_barrier, (C.byref(barrier),)
             with self._bounds_schedule(exercise_every):  # (the multi-asset calls below leave the option as it is)
                 _check(self.lib, entry(self.handle, C.byref(params), *law, C.byref(cfg), *tail, C.byref(out)))
             d = {k: getattr(out, k) for k, _ in Bounds._fields_}

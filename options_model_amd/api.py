@@ -1140,6 +1140,105 @@ def price_american_bounds_dividends(S0, K, r, sigma, T, n_paths, n_steps, divide
                                 model=model_l)
 
 
+@dataclass
+class BarrierBoundsResult(BoundsResult):
+    """price_barrier_bounds: BoundsResult for an American barrier option.  The policy is a function of the ENCODED index --
+    the spot where the option is live, a dead spot elsewhere, so it never exercises a dead option; `lower` is what it
+    earns, `upper` bounds the value of the discretised game on the grid under ANY policy that sees the path's state (spot,
+    knocked yes / no, and under Heston the variance)."""
+    barrier: float = 0.0
+    barrier_type: str = "down-and-out"
+    monitoring: str = "discrete"
+    model: str = "gbm"
+
+
+def price_barrier_bounds(S0, K, r, sigma, T, n_paths, n_steps, barrier, barrier_type="down-and-out", option_type="put",
+                         model="GBM", heston_params=None, heston_scheme="reference", policy="textbook", exercise_every=0,
+                         suboptimality_check=None, n_lower=1_000_000, n_outer=8192, n_inner=1024, seed=42, stream=0,
+                         betas=None, device=None, ctx=None, monitoring="discrete",
+                         control_variate=False) -> BarrierBoundsResult:
+    """Lower and upper bounds on the value of the American knock-in / knock-out option that price_barrier_option quotes
+    (omc_price_american_bounds_barrier): price_american_bounds on the barrier generator's paths.
+    The barrier is monitored on every step of the grid (discrete monitoring); a knock-out is dead at its hit step and
+    after it, a knock-in is live from its hit step on; no rebate.  model "GBM" or "Heston" (heston_params as
+    price_american_option takes them; heston_scheme "reference" (= "clamp") or "full_truncation").  The policy (`policy` /
+    `betas` as price_american_bounds takes them) is fitted on the encoded matrix price_barrier_option prices; the inner
+    simulations start at the outer paths' (spot, knocked yes / no[, variance]) state.  The bracket for the quote of
+    price_barrier_option, which is a two-pass-flow value.  The lower-bound, outer and inner paths use Philox streams
+    stream + 1, + 2, + 3.  One GPU.
+    exercise_every = k >= 2: as price_american_bounds takes it; the barrier stays monitored on every
+    step, so daily monitoring with monthly exercise is exercise_every = 21 on a daily grid.
+    suboptimality_check: None / "off", or "payoff" (DESIGN.md section 27); "european" and control_variate=True are refused:
+    a vanilla European value is no bound on a barrier continuation value."""
+    model_l = str(model).lower()
+    if model_l not in ("gbm", "heston"):
+        raise ValueError("model must be 'GBM' or 'Heston'.")
+    if barrier_type not in _ffi.BARRIER_KINDS:
+        raise ValueError(f"barrier_type must be one of {sorted(_ffi.BARRIER_KINDS)}.")
+    if monitoring != "discrete":
+        raise ValueError("monitoring: the barrier bounds take 'discrete' monitoring only.")
+    if control_variate:
+        raise ValueError("control_variate: the barrier bounds have no control variate.")
+    if suboptimality_check == "european":
+        raise ValueError("suboptimality_check='european' is for price_american_bounds only (barrier options take 'payoff' "
+                         "or 'off').")
+    if suboptimality_check is not None and suboptimality_check not in _ffi.BOUND_CHECKS:
+        raise ValueError(f"suboptimality_check must be one of {list(_ffi.BOUND_CHECKS)} or None.")
+    if exercise_every is None or isinstance(exercise_every, (list, tuple)):
+        raise ValueError("exercise_every must be a non-negative integer.")
+    every = _one_schedule(exercise_every)
+    if every >= 2 and suboptimality_check == "payoff":
+        raise ValueError("sub-optimality checking is for the game on every date (exercise_every must be 0 or 1).")
+    H = float(barrier)
+    if not (math.isfinite(H) and H > 0):
+        raise ValueError("barrier H must be finite and positive.")
+    if policy not in _ffi.BOUND_POLICIES:
+        raise ValueError(f"policy must be one of {sorted(_ffi.BOUND_POLICIES)}.")
+    if (policy == "given") != (betas is not None):
+        raise ValueError("betas must be given exactly when policy='given'.")
+    for name, v in (("n_lower", n_lower), ("n_outer", n_outer), ("n_inner", n_inner)):
+        if int(v) < 2 or int(v) % 2:
+            raise ValueError(f"{name} must be an even integer >= 2 (antithetic pairs).")
+    _validate(S0, K, T, r, sigma, n_paths, n_steps, option_type, need_sigma=(model_l == "gbm"))
+    if betas is not None:
+        import numpy as np
+        if np.shape(betas) != (int(n_steps) + 1, 4):
+            raise ValueError(f"betas must have shape ({int(n_steps) + 1}, 4), got {np.shape(betas)}.")
+    if model_l == "heston":
+        if heston_scheme not in _ffi.HESTON_SCHEMES:
+            raise ValueError(f"heston_scheme must be one of {sorted(_ffi.HESTON_SCHEMES)}.")
+        if _ffi.HESTON_SCHEMES[heston_scheme] not in (_ffi.HESTON_SCHEMES["reference"],
+                                                      _ffi.HESTON_SCHEMES["full_truncation"]):
+            raise ValueError("price bounds of barrier options take heston_scheme 'reference' or 'full_truncation'.")
+    up = barrier_type.startswith("up")
+    if (float(S0) >= H) if up else (float(S0) <= H):
+        raise ValueError("S0 lies on or beyond the barrier (the option is already knocked).")
+    M = int(n_paths) // 2 * 2
+    if M <= 0:
+        raise ValueError("num_simulations and num_time_steps must be positive integers.")
+    if model_l == "heston":
+        p = _ffi.make_params(model="heston", is_put=(option_type == "put"), semantics="two_pass", antithetic=True,
+                             heston_scheme=heston_scheme, n_paths=M, n_steps=int(n_steps), S0=S0, K=K, r=r, sigma=sigma or 0.0,
+                             T=T, seed=seed, stream=stream, **heston_defaults(sigma, heston_params))
+    else:
+        p = _ffi.make_params(is_put=(option_type == "put"), semantics="two_pass", antithetic=True, n_paths=M,
+                             n_steps=int(n_steps), S0=S0, K=K, r=r, sigma=sigma, T=T, seed=seed, stream=stream)
+    c = ctx or _ffi.default_context(device)
+    out = c.price_barrier_bounds(p, barrier_type, H, policy=policy, n_lower=int(n_lower), n_outer=int(n_outer),
+                                 n_inner=int(n_inner), betas=betas, exercise_every=every,
+                                 suboptimality_check=suboptimality_check)
+    return BarrierBoundsResult(lower=out["lower"], se_lower=out["se_lower"], upper=out["upper"], se_upper=out["se_upper"],
+                               ci_lo=out["ci_lo"], ci_hi=out["ci_hi"], n_lower=out["n_lower"], n_outer=out["n_outer"],
+                               n_inner=out["n_inner"], n_exercised_lower=out["n_exercised_lower"],
+                               inner_path_steps=out["inner_path_steps"], policy=policy, betas=out["betas"],
+                               option_type=option_type,
+                               timings_ms=dict(fit=out["ms_fit"], lower=out["ms_lower"], upper=out["ms_upper"],
+                                               total=out["ms_total"]),
+                               exercise_every=every, n_exercise_dates=len(bounds_exercise_dates(n_steps, every)),
+                               suboptimality_check=suboptimality_check or "off", barrier=H, barrier_type=barrier_type,
+                               monitoring="discrete", model=model_l)
+
+
 def price_bermudan_bounds(S0, K, r, sigma, T, n_paths, n_steps, exercise_every, model="GBM", option_type="put",
                           policy="textbook", n_lower=1_000_000, n_outer=8192, n_inner=1024, heston_params=None,
                           heston_scheme="reference", seed=42, stream=0, betas=None, device=None, ctx=None,

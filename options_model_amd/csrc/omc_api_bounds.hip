@@ -48,6 +48,8 @@ int run_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg, co
         return fail(-40, "option bounds_suboptimality: these bounds take no sub-optimality check (the all-dates game with a "
                          "policy on the spot or the index; the European check: omc_price_american_bounds).");
     const bool sched = c->bounds_every >= 2;
+    // the list-driven sweep: the sub-optimality check's, or that of a flow that takes items out itself (mode 0)
+    const bool lst = chk >= 1 || (f.mark_items && f.inner_check && !sched && !cv);
     const omc::BoundsSched sc = sched ? omc::bounds_schedule(N, c->bounds_every) : omc::BoundsSched{};
     hipStream_t st = c->stream;
     const bool fitted = policy != OMC_POLICY_GIVEN;
@@ -74,10 +76,10 @@ int run_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg, co
     int64_t blk = (int64_t)(kLaunchSteps / (double)f.d / work1);
     blk = blk < 1 ? 1 : (blk > no ? no : blk);
     const size_t o_keep = o_fb + (sched ? sizeof(double) * 4 * (size_t)(sc.J + 1) : 0);
-    const size_t o_list = o_keep + (chk ? up256((size_t)N * (size_t)no) : 0);
-    const size_t o_cnt = o_list + (chk ? up256(sizeof(uint32_t) * (size_t)blk * (size_t)N) : 0);
-    const size_t o_pd = o_cnt + (chk ? 256 : 0);
-    const size_t pd_bytes = chk ? sizeof(uint32_t) * (size_t)((no + blk - 1) / blk) * (size_t)N : 0;
+    const size_t o_list = o_keep + (lst ? up256((size_t)N * (size_t)no) : 0);
+    const size_t o_cnt = o_list + (lst ? up256(sizeof(uint32_t) * (size_t)blk * (size_t)N) : 0);
+    const size_t o_pd = o_cnt + (lst ? 256 : 0);
+    const size_t pd_bytes = lst ? sizeof(uint32_t) * (size_t)((no + blk - 1) / blk) * (size_t)N : 0;
     if ((rc = c->bnd.ensure(o_pd + pd_bytes))) return rc;
     char* b = (char*)c->bnd.p;
     double* res = (double*)(b + o_res);
@@ -143,11 +145,11 @@ int run_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg, co
     HIP_TRY(hipEventRecord(c->ev[2], st));
     HIP_TRY(f.outer(st));
     HIP_TRY(hipMemsetAsync(a.steps, 0, sizeof(unsigned long long), st));
-    if (chk) {  // the keep mask of every item; Q^ keeps its shape [n_outer][N], a skipped item's entry reads 0
+    if (lst) {  // the keep mask of every item; Q^ keeps its shape [n_outer][N], a skipped item's entry reads 0
         const double* cvt = nullptr;
         if (chk == 2) HIP_TRY(f.euro_table(st, &cvt));
         HIP_TRY(hipMemsetAsync(ck.per_date, 0, pd_bytes, st));
-        HIP_TRY(omc::bounds_check_mark(st, a, ck, cvt));
+        HIP_TRY(chk ? omc::bounds_check_mark(st, a, ck, cvt) : f.mark_items(st, ck));
         HIP_TRY(hipMemsetAsync(a.q, 0, sizeof(double) * (size_t)no * (size_t)N, st));
     }
     if (sched) {  // the scheduled worst case n_inner sum_j (N - tau_j), j = 0 .. J-1
@@ -160,14 +162,14 @@ int run_bounds(omc_ctx* c, const omc_params* p, const omc_bounds_config* cfg, co
     }
     for (int64_t i0 = 0; i0 < no; i0 += blk) {
         const int64_t n = no - i0 < blk ? no - i0 : blk;
-        if (chk) {  // the block's kept items, then the sweep over them: the count stays on the device
+        if (lst) {  // the block's kept items, then the sweep over them: the count stays on the device
             HIP_TRY(omc::bounds_check_compact(st, a, ck, i0, n));
             HIP_TRY(cv ? f.inner_check_cv(st, ck, i0, n) : f.inner_check(st, ck, i0, n));
         }
         else if (cv) HIP_TRY(sched ? f.inner_sched_cv(st, sc, i0, n) : f.inner_cv(st, i0, n));
         else HIP_TRY(sched ? f.inner_sched(st, sc, i0, n) : f.inner(st, i0, n));
     }
-    if (chk) HIP_TRY(omc::bounds_check_walk(st, a, ck, res + 8));
+    if (lst) HIP_TRY(omc::bounds_check_walk(st, a, ck, res + 8));
     else if (sched) HIP_TRY(omc::bounds_sched_walk(st, a, sc, res + 8));
     else HIP_TRY(own ? f.walk(st, res + 8) : omc::bounds_walk(st, a, res + 8));
     HIP_TRY(hipEventRecord(c->ev[3], st));

@@ -158,7 +158,8 @@ __device__ __forceinline__ void bounds_check_inner_body(const BoundsArgs& a, con
                         ++k;
                         const int d = t + k;
                         m.step(s, z, u);
-                        bd_mark(m.index_a(s), m.index_b(s), d, sh_bt[d], a, xa, xb, da, db);
+                        if constexpr (bd_model_stops<Model>::value) bd_mark_stops(m, s, d, sh_bt[d], a, xa, xb, da, db);
+                        else bd_mark(m.index_a(s), m.index_b(s), d, sh_bt[d], a, xa, xb, da, db);
                     }
                 }
             }

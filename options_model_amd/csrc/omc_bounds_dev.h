@@ -11,9 +11,16 @@
 //   draw(pair, blk, stream, z)   the normals of generator pair `pair`, block `blk`
 //   step(spots, z, u)            both partners one step on, with step u of the block (the partner takes -z)
 //   index_a(spots), index_b(spots)   what the policy sees of either partner: a float32 spot for the exercise tables
+// and, only if it declares `static constexpr bool kStops = true` (a path may end for a reason of the law's own: a knock-out,
+// omc_barrier_bounds.hip; the other laws leave it off and their kernels carry no trace of it),
+//   stopped_a(spots, d), stopped_b(spots, d)   the partner stops at the date d being marked whatever the policy says, at its
+//                                        index there
+//   start_dead(start)                    wave-uniform: an item started here simulates nothing (scheduled sweep)
 // and nothing else: the dates, the tables, the payoff, the discount and the outputs are BoundsArgs'.  Everything is inlined
 // into the __global__ function that names the model, which also declares the LDS.
 #pragma once
+#include <type_traits>
+
 #include "omc_bounds.h"
 #include "omc_lsm_dev.h"
 
@@ -60,6 +67,28 @@ __device__ __forceinline__ void bd_mark(float ia, float ib, int d, uint4 iv, con
     db = eb ? d : db;
 }
 
+// a Model that stops paths for a reason of its own says so at compile time (kStops); one that does not is marked by bd_mark
+template <class Model, class = void>
+struct bd_model_stops : std::false_type {};
+template <class Model>
+struct bd_model_stops<Model, std::enable_if_t<Model::kStops>> : std::true_type {};
+
+// bd_mark for a Model with kStops: the law's own stop counts as the rule firing -- the stop date enters the step count and
+// the stopped-before-N count as an exercise at that date would, the value is that of the index there.  The sweeps choose
+// between the two with `if constexpr` at the call itself, so that for every other Model the call is the one it always was.
+template <class Model, class Spots>
+__device__ __forceinline__ void bd_mark_stops(const Model& m, const Spots& s, int d, uint4 iv, const BoundsArgs& a, float& xa,
+                                              float& xb, int& da, int& db)
+{
+    const float ia = m.index_a(s), ib = m.index_b(s);
+    const bool ea = da == 0 && (m.stopped_a(s, d) || bd_stop(ia, d, iv, a));
+    const bool eb = db == 0 && (m.stopped_b(s, d) || bd_stop(ib, d, iv, a));
+    xa = ea ? ia : xa;
+    da = ea ? d : da;
+    xb = eb ? ib : xb;
+    db = eb ? d : db;
+}
+
 // ------------------------------------------------------------------ lower bound
 // one thread per antithetic pair of fresh paths; sh_bt [N+1] dynamic LDS, red [kNQ * kRedStride]
 template <class Model>
@@ -84,7 +113,8 @@ __device__ __forceinline__ void bounds_lower_body(const BoundsArgs& a, const Mod
                 const int d = 4 * blk + u + 1;
                 if (d > N) break;
                 m.step(s, z, u);
-                bd_mark(m.index_a(s), m.index_b(s), d, sh_bt[d], a, xa, xb, da, db);
+                if constexpr (bd_model_stops<Model>::value) bd_mark_stops(m, s, d, sh_bt[d], a, xa, xb, da, db);
+                else bd_mark(m.index_a(s), m.index_b(s), d, sh_bt[d], a, xa, xb, da, db);
             }
         }
         const double v = 0.5 * (bd_value(xa, da, a) + bd_value(xb, db, a));
@@ -131,7 +161,8 @@ __device__ __forceinline__ void bounds_inner_body(const BoundsArgs& a, const Mod
                         ++k;
                         const int d = t + k;
                         m.step(s, z, u);
-                        bd_mark(m.index_a(s), m.index_b(s), d, sh_bt[d], a, xa, xb, da, db);
+                        if constexpr (bd_model_stops<Model>::value) bd_mark_stops(m, s, d, sh_bt[d], a, xa, xb, da, db);
+                        else bd_mark(m.index_a(s), m.index_b(s), d, sh_bt[d], a, xa, xb, da, db);
                     }
                 }
             }

@@ -44,6 +44,7 @@ __device__ __forceinline__ void bounds_sched_inner_body(const BoundsArgs& a, con
         const uint64_t gbase = ((uint64_t)i * (uint64_t)(N + 1) + (uint64_t)t) * (uint64_t)H;
         int64_t j = lane, next = 64;  // this lane's pair; the item's first unstarted pair
         bool act = j < H;
+        if constexpr (bd_model_stops<Model>::value) act = act && !m.start_dead(s0);  // (an item dead at its start: Q^ = 0)
         typename Model::Spots s;
         m.reset(s, s0);
         float xa = 0.0f, xb = 0.0f;
@@ -63,7 +64,8 @@ __device__ __forceinline__ void bounds_sched_inner_body(const BoundsArgs& a, con
                         ++k;
                         m.step(s, z, u);
                         if (--cd == 0) {
-                            bd_mark(m.index_a(s), m.index_b(s), t + k, sh_bt[t + k], a, xa, xb, da, db);
+                            if constexpr (bd_model_stops<Model>::value) bd_mark_stops(m, s, t + k, sh_bt[t + k], a, xa, xb, da, db);
+                            else bd_mark(m.index_a(s), m.index_b(s), t + k, sh_bt[t + k], a, xa, xb, da, db);
                             cd = sc.k;
                         }
                     }

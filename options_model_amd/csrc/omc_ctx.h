@@ -210,6 +210,11 @@ struct BoundsFlow {
     std::function<hipError_t(hipStream_t, const omc::BoundsCheck& k, int64_t i0, int64_t ni)> inner_check;
     std::function<hipError_t(hipStream_t, const omc::BoundsCheck& k, int64_t i0, int64_t ni)> inner_check_cv;
     std::function<hipError_t(hipStream_t, const double** cv)> euro_table;
+    // Items the law itself takes out (a knock-out's dead items; default: none).  A flow that sets
+    // mark_items and inner_check runs the all-dates game list-driven even while the sub-optimality option is off: mark_items
+    // writes bounds_check_mark's outputs (k.mode is 0) by its own rule, the list, inner_check and the walk over the kept
+    // dates are section 27's.  With the option on the mark is bounds_check_mark's, with a schedule the flow is not used.
+    std::function<hipError_t(hipStream_t, const omc::BoundsCheck& k)> mark_items;
     // A policy of the flow's own (omc_api_runnerup_bounds.hip: a rule on two regressors), all three set or none.  With them
     // run_bounds neither uploads nor fits a [N+1][4] table and builds no exercise tables:
     //   own_policy(w, S, ld)   between the fit events: the caller's table to the device (S == nullptr), or the fit on the
