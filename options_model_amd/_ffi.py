@@ -53,12 +53,17 @@ def check_runnerup(regressors, policy, kind, n_assets):
         raise ValueError("regressors='index+runner-up' needs at least two assets.")
 
 
+def heston_regressors_code(regressors):
+    """a key of HESTON_BOUND_REGRESSORS -> its code, omc_bounds_config.regressors (ValueError for anything else)"""
+    if regressors not in HESTON_BOUND_REGRESSORS:
+        raise ValueError(f"regressors must be one of {list(HESTON_BOUND_REGRESSORS)}.")
+    return HESTON_BOUND_REGRESSORS.index(regressors)
+
+
 def check_heston_regressors(regressors, policy, n_steps, v0, theta):
     """The argument checks of regressors="spot+variance" (omc_price_american_bounds_heston with cfg.regressors = 1), raised
     as ValueError before anything touches the device."""
-    if regressors not in HESTON_BOUND_REGRESSORS:
-        raise ValueError(f"regressors must be one of {list(HESTON_BOUND_REGRESSORS)}.")
-    if regressors == "spot":
+    if heston_regressors_code(regressors) == 0:
         return
     if BOUND_POLICIES.get(policy, policy) not in (BOUND_POLICIES["textbook"], BOUND_POLICIES["given"]):
         raise ValueError("regressors='spot+variance' takes policy 'textbook' or 'given'.")
@@ -577,6 +582,8 @@ class Context:
     _bounds_every = 0  # option "bounds_exercise_every" as last set through this object (the ABI has no getter)
     _bounds_cv = 0     # option "bounds_control_variate", likewise
     _bounds_check = 0  # option "bounds_suboptimality", likewise
+    _MIRRORED = {"bounds_exercise_every": "_bounds_every", "bounds_control_variate": "_bounds_cv",
+                 "bounds_suboptimality": "_bounds_check"}
 
     def __init__(self, device: int = 0, stream: int | None = None):
         self.lib = load_library()
@@ -614,12 +621,8 @@ class Context:
 
     def set_option(self, key: str, value: int):
         _check(self.lib, self.lib.omc_set_option(self.handle, key.encode(), int(value)))
-        if key == "bounds_exercise_every":
-            self._bounds_every = int(value)
-        if key == "bounds_control_variate":
-            self._bounds_cv = int(value)
-        if key == "bounds_suboptimality":
-            self._bounds_check = int(value)
+        if key in self._MIRRORED:
+            setattr(self, self._MIRRORED[key], int(value))
 
     def set_allreduce_hook(self, fn):
         """fn(dptr:int, count:int) -> None must sum-all-reduce `count` device doubles in place."""
@@ -1069,52 +1072,41 @@ class Context:
         simulations only where exercise is not known to be sub-optimal; `q` is zero at the skipped items, `lower` is the
         unchecked call's and `upper` is at most its value up to rounding."""
         with self._bounds_control(control_variate), self._bounds_checking(suboptimality_check):
-            return self._bounds(params, None, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner,
-                                betas, want_q, want_samples, exercise_every=exercise_every)
+            return self._bounds("omc_price_american_bounds", (), Bounds, params, policy, n_lower, n_outer, n_inner,
+                                stream_lower, stream_outer, stream_inner, betas, want_q, want_samples,
+                                exercise_every=exercise_every)
 
     @contextlib.contextmanager
+    def _option_for_calls(self, key, value):
+        """option `key` (one of _MIRRORED) = value for the calls inside, the previous value after them (None: the option
+        stays as the context holds it)"""
+        if value is None:
+            yield
+            return
+        before = getattr(self, self._MIRRORED[key])
+        self.set_option(key, value)
+        try:
+            yield
+        finally:
+            self.set_option(key, before)
+
     def _bounds_control(self, control_variate):
         """option "bounds_control_variate" = control_variate for the calls inside, the previous value after them (None: the
         option stays as the context holds it)"""
-        if control_variate is None:
-            yield
-            return
-        before = self._bounds_cv
-        self.set_option("bounds_control_variate", 1 if control_variate else 0)
-        try:
-            yield
-        finally:
-            self.set_option("bounds_control_variate", before)
+        return self._option_for_calls("bounds_control_variate", None if control_variate is None else int(bool(control_variate)))
 
-    @contextlib.contextmanager
     def _bounds_checking(self, suboptimality_check):
         """option "bounds_suboptimality" = the code of suboptimality_check for the calls inside, the previous value after
         them (None: the option stays as the context holds it)"""
-        if suboptimality_check is None:
-            yield
-            return
-        if suboptimality_check not in BOUND_CHECKS:
+        if suboptimality_check is not None and suboptimality_check not in BOUND_CHECKS:
             raise ValueError(f"suboptimality_check must be one of {list(BOUND_CHECKS)} or None.")
-        before = self._bounds_check
-        self.set_option("bounds_suboptimality", BOUND_CHECKS.index(suboptimality_check))
-        try:
-            yield
-        finally:
-            self.set_option("bounds_suboptimality", before)
+        return self._option_for_calls("bounds_suboptimality",
+                                      None if suboptimality_check is None else BOUND_CHECKS.index(suboptimality_check))
 
-    @contextlib.contextmanager
     def _bounds_schedule(self, exercise_every):
         """option "bounds_exercise_every" = exercise_every for the calls inside, the previous value after them (None: the
         option stays as the context holds it)"""
-        if exercise_every is None:
-            yield
-            return
-        before = self._bounds_every
-        self.set_option("bounds_exercise_every", int(exercise_every))
-        try:
-            yield
-        finally:
-            self.set_option("bounds_exercise_every", before)
+        return self._option_for_calls("bounds_exercise_every", exercise_every)
 
     def price_american_bounds_heston(self, params: Params, policy="textbook", n_lower=1_000_000, n_outer=8192,
                                      n_inner=1024, stream_lower=None, stream_outer=None, stream_inner=None, betas=None,
@@ -1132,13 +1124,11 @@ class Context:
         suboptimality_check: as price_american_bounds takes it, "off" or "payoff" with regressors "spot" (anything else is
         refused with -40)."""
         if isinstance(regressors, str):
-            if regressors not in HESTON_BOUND_REGRESSORS:
-                raise ValueError(f"regressors must be one of {list(HESTON_BOUND_REGRESSORS)}.")
-            regressors = HESTON_BOUND_REGRESSORS.index(regressors)
+            regressors = heston_regressors_code(regressors)
         with self._bounds_checking(suboptimality_check):
-            return self._bounds(params, None, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner,
-                                betas, want_q, want_samples, 8 if int(regressors) == 1 else 4, heston=True,
-                                regressors=int(regressors), exercise_every=exercise_every)
+            return self._bounds("omc_price_american_bounds_heston", (), Bounds, params, policy, n_lower, n_outer, n_inner,
+                                stream_lower, stream_outer, stream_inner, betas, want_q, want_samples,
+                                8 if int(regressors) == 1 else 4, regressors=int(regressors), exercise_every=exercise_every)
 
     def price_american_bounds_jump(self, params: Params, jump, q=0.0, policy="textbook", n_lower=1_000_000, n_outer=8192,
                                    n_inner=1024, stream_lower=None, stream_outer=None, stream_inner=None, betas=None,
@@ -1149,10 +1139,11 @@ class Context:
         spot (Merton) or (spot, variance) state (Bates).  Streams default to params.stream + 1 / 2 / 3.
         exercise_every: as price_american_bounds takes it.
         suboptimality_check: as price_american_bounds takes it, "off" or "payoff" ("european" is refused with -40)."""
+        law = (C.byref(make_jump(jump)), float(q))
         with self._bounds_checking(suboptimality_check):
-            return self._bounds(params, None, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner,
-                                betas, want_q, want_samples, exercise_every=exercise_every,
-                                jump=(make_jump(jump), float(q)))
+            return self._bounds("omc_price_american_bounds_jump", law, Bounds, params, policy, n_lower, n_outer, n_inner,
+                                stream_lower, stream_outer, stream_inner, betas, want_q, want_samples,
+                                exercise_every=exercise_every)
 
     def price_american_bounds_div(self, params: Params, q=0.0, dividends=(), policy="textbook", n_lower=1_000_000,
                                   n_outer=8192, n_inner=1024, stream_lower=None, stream_outer=None, stream_inner=None,
@@ -1166,8 +1157,9 @@ class Context:
         suboptimality_check: as price_american_bounds takes it, "off" or "payoff" ("european" is refused with -40)."""
         arr, n = dividend_array(dividends)
         with self._bounds_checking(suboptimality_check):
-            return self._bounds(params, None, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner,
-                                betas, want_q, want_samples, exercise_every=exercise_every, dividend=(float(q), arr, n))
+            return self._bounds("omc_price_american_bounds_div", (float(q), arr, n), Bounds, params, policy, n_lower, n_outer,
+                                n_inner, stream_lower, stream_outer, stream_inner, betas, want_q, want_samples,
+                                exercise_every=exercise_every)
 
     def price_barrier_bounds(self, params: Params, kind, H, monitoring="discrete", policy="textbook", n_lower=1_000_000,
                              n_outer=8192, n_inner=1024, stream_lower=None, stream_outer=None, stream_inner=None, betas=None,
@@ -1180,10 +1172,11 @@ class Context:
         1 / 2 / 3.
         exercise_every: as price_american_bounds takes it (monitoring stays on every step).
         suboptimality_check: as price_american_bounds takes it, "off" or "payoff" ("european" is refused with -12)."""
+        law = (C.byref(make_barrier(kind, H, monitoring)),)
         with self._bounds_checking(suboptimality_check):
-            return self._bounds(params, None, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner,
-                                betas, want_q, want_samples, exercise_every=exercise_every,
-                                barrier=make_barrier(kind, H, monitoring))
+            return self._bounds("omc_price_american_bounds_barrier", law, Bounds, params, policy, n_lower, n_outer, n_inner,
+                                stream_lower, stream_outer, stream_inner, betas, want_q, want_samples,
+                                exercise_every=exercise_every)
 
     def price_american_basket_bounds(self, params: Params, basket: Basket, policy="textbook", n_lower=1_000_000,
                                      n_outer=8192, n_inner=1024, stream_lower=None, stream_outer=None, stream_inner=None,
@@ -1200,13 +1193,17 @@ class Context:
         suboptimality_check: as price_american_bounds takes it, "off" or "payoff" with regressors "index" (anything else is
         refused with -40)."""
         check_runnerup(regressors, policy, int(basket.kind), int(basket.n_assets))
-        with self._bounds_checking(suboptimality_check):
-            return self._bounds(params, basket, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer,
-                                stream_inner, betas, want_q, want_samples, 4 if regressors == "index" else 8)
+        entry = "omc_price_american_basket_bounds" + ("" if regressors == "index" else "_runnerup")
+        with self._bounds_checking(suboptimality_check):  # (no exercise_every: the option "bounds_exercise_every" stays)
+            return self._bounds(entry, (C.byref(basket),), BasketBounds, params, policy, n_lower, n_outer, n_inner,
+                                stream_lower, stream_outer, stream_inner, betas, want_q, want_samples,
+                                4 if regressors == "index" else 8)
 
-    def _bounds(self, params, basket, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner, betas,
-                want_q, want_samples, cols=4, heston=False, regressors=0, exercise_every=None, jump=None, dividend=None,
-                barrier=None):
+    def _bounds(self, entry, law, result, params, policy, n_lower, n_outer, n_inner, stream_lower, stream_outer, stream_inner,
+                betas, want_q, want_samples, cols=4, regressors=0, exercise_every=None):
+        """The one call behind the price_*bounds* methods: entry(ctx, params, *law, cfg, betas, betas_out, q, samples,
+        result) -- `law` are the entry point's own arguments, `result` is Bounds or BasketBounds -- with option
+        "bounds_exercise_every" = exercise_every around it (None: as the context holds it)."""
         N = int(params.n_steps)
         cfg = BoundsConfig()
         cfg.regressors = regressors  # read by the Heston entry point alone
@@ -1226,26 +1223,13 @@ class Context:
         smp = np.zeros(max(int(n_outer), 0)) if want_samples else None
         tail = (b.ctypes.data if b is not None else None, bo.ctypes.data, q.ctypes.data if q is not None else None,
                 smp.ctypes.data if smp is not None else None)
-        if basket is None:
-            out = Bounds()
-            entry = self.lib.omc_price_american_bounds_heston if heston else self.lib.omc_price_american_bounds
-            law = ()
-            if jump is not None:  # (Jump, q): the jump-diffusion entry point takes them after the params
-                entry, law = self.lib.omc_price_american_bounds_jump, (C.byref(jump[0]), jump[1])
-            if dividend is not None:  # (q, omc_dividend array, n_div): likewise
-                entry, law = self.lib.omc_price_american_bounds_div, dividend
-            if barrier is not None:  # omc_barrier: likewise
-                entry, law = self.lib.omc_price_american_bounds_barrier, (C.byref(barrier),)
-            with self._bounds_schedule(exercise_every):  # (the multi-asset calls below leave the option as it is)
-                _check(self.lib, entry(self.handle, C.byref(params), *law, C.byref(cfg), *tail, C.byref(out)))
-            d = {k: getattr(out, k) for k, _ in Bounds._fields_}
-        else:
-            bb = BasketBounds()
-            entry = self.lib.omc_price_american_basket_bounds if cols == 4 else \
-                self.lib.omc_price_american_basket_bounds_runnerup
-            _check(self.lib, entry(self.handle, C.byref(params), C.byref(basket), C.byref(cfg), *tail, C.byref(bb)))
-            d = {k: getattr(bb.bounds, k) for k, _ in Bounds._fields_}
-            d.update(index0=bb.index0, n_assets=bb.n_assets, kind=bb.kind)
+        out = result()
+        with self._bounds_schedule(exercise_every):
+            _check(self.lib, getattr(self.lib, entry)(self.handle, C.byref(params), *law, C.byref(cfg), *tail, C.byref(out)))
+        base = out.bounds if result is BasketBounds else out
+        d = {k: getattr(base, k) for k, _ in Bounds._fields_}
+        if result is BasketBounds:
+            d.update(index0=out.index0, n_assets=out.n_assets, kind=out.kind)
         d["betas"] = bo
         if want_q:
             d["q"] = q

@@ -40,6 +40,8 @@ import math
 import os
 from dataclasses import dataclass, field
 
+import numpy as np
+
 from . import _ffi
 
 _SEM = {"two_pass": "two_pass", "v3": "two_pass", "reference_v3": "two_pass",
@@ -102,6 +104,42 @@ def heston_defaults(sigma, heston_params=None):
     if heston_params:
         hp.update({k: float(v) for k, v in heston_params.items() if k in hp})
     return hp
+
+
+def _even_paths(n_paths):
+    """n_paths rounded down to whole antithetic pairs (ValueError when none is left)"""
+    M = int(n_paths) // 2 * 2
+    if M <= 0:
+        raise ValueError("num_simulations and num_time_steps must be positive integers.")
+    return M
+
+
+def _dividend_items(dividends):
+    """the dividends of a facade -> [(t, amount, kind)]; a bare (t, amount) is a cash dividend (ValueError otherwise)"""
+    divs = []
+    for d in dividends:
+        d = tuple(d)
+        if len(d) not in (2, 3):
+            raise ValueError("a dividend is (t, amount) or (t, amount, 'cash' | 'proportional').")
+        kind = d[2] if len(d) == 3 else "cash"
+        if kind not in _ffi.DIVIDEND_KINDS:
+            raise ValueError("a dividend's kind must be 'cash' or 'proportional'.")
+        divs.append((float(d[0]), float(d[1]), kind))
+    return divs
+
+
+def _jump_args(jump_intensity, jump_mean, jump_vol, dividend_yield):
+    """the jump law and the yield of a facade as floats -> (lam, mu, sj, q), each finite (ValueError otherwise)"""
+    lam, mu, sj, q = float(jump_intensity), float(jump_mean), float(jump_vol), float(dividend_yield)
+    if not (math.isfinite(lam) and lam >= 0.0):
+        raise ValueError("jump_intensity must be finite and non-negative.")
+    if not math.isfinite(mu):
+        raise ValueError("jump_mean must be finite.")
+    if not (math.isfinite(sj) and sj >= 0.0):
+        raise ValueError("jump_vol must be finite and non-negative.")
+    if not math.isfinite(q):
+        raise ValueError("dividend_yield must be finite.")
+    return lam, mu, sj, q
 
 
 def price_american_option(S0, K, r, sigma, T, n_paths, n_steps, model="GBM", option_type="put",
@@ -317,9 +355,7 @@ def price_american_chain(S0, strikes, r, sigma, T, n_paths, n_steps, option_type
             raise ValueError("S0, K, T must be positive.")
         _validate(S0, k, T, r, sigma, n_paths, n_steps, ot, need_sigma=(model_l == "gbm"))
         _validate_scheme(model_l, heston_scheme, sigma, heston_params)
-    M = int(n_paths) // 2 * 2
-    if M <= 0:
-        raise ValueError("num_simulations and num_time_steps must be positive integers.")
+    M = _even_paths(n_paths)
     c = ctx or _ffi.default_context(device)
     p = _ffi.make_params(model=model_l, is_put=True, semantics="two_pass", antithetic=True, heston_scheme=heston_scheme,
                          n_paths=M, n_steps=int(n_steps), S0=S0, K=ks[0], r=r, sigma=sigma or 0.0, T=T, seed=seed,
@@ -476,9 +512,7 @@ def price_barrier_option(S0, K, r, sigma, T, n_paths, n_steps, barrier, barrier_
         raise ValueError("barrier H must be finite and positive.")
     _validate(S0, K, T, r, sigma, n_paths, n_steps, option_type, need_sigma=(model_l == "gbm"))
     _validate_scheme(model_l, heston_scheme, sigma, heston_params)
-    M = int(n_paths) // 2 * 2
-    if M <= 0:
-        raise ValueError("num_simulations and num_time_steps must be positive integers.")
+    M = _even_paths(n_paths)
     c = ctx or _ffi.default_context(device)
     p = _ffi.make_params(model=model_l, is_put=(option_type == "put"), semantics="two_pass", antithetic=True,
                          heston_scheme=heston_scheme, n_paths=M, n_steps=int(n_steps), S0=S0, K=K, r=r,
@@ -533,20 +567,10 @@ def price_american_dividends(S0, K, r, sigma, T, n_paths, n_steps, dividend_yiel
     q = float(dividend_yield)
     if not math.isfinite(q):
         raise ValueError("dividend_yield must be finite.")
-    divs = []
-    for d in dividends:
-        d = tuple(d)
-        if len(d) not in (2, 3):
-            raise ValueError("a dividend is (t, amount) or (t, amount, 'cash' | 'proportional').")
-        kind = d[2] if len(d) == 3 else "cash"
-        if kind not in _ffi.DIVIDEND_KINDS:
-            raise ValueError("a dividend's kind must be 'cash' or 'proportional'.")
-        divs.append((float(d[0]), float(d[1]), kind))
+    divs = _dividend_items(dividends)
     _validate(S0, K, T, r, sigma, n_paths, n_steps, option_type, need_sigma=(model_l == "gbm"))
     _validate_scheme(model_l, heston_scheme, sigma, heston_params)
-    M = int(n_paths) // 2 * 2
-    if M <= 0:
-        raise ValueError("num_simulations and num_time_steps must be positive integers.")
+    M = _even_paths(n_paths)
     c = _ffi.default_context(device)
     p = _ffi.make_params(model=model_l, is_put=(option_type == "put"), semantics="two_pass", antithetic=True,
                          n_paths=M, n_steps=int(n_steps), S0=S0, K=K, r=r, sigma=sigma or 0.0, T=T, seed=seed,
@@ -603,22 +627,12 @@ def price_american_jumps(S0, K, r, sigma, T, n_paths, n_steps, jump_intensity, j
     model_l = str(model).lower()
     if model_l not in ("gbm", "heston"):
         raise ValueError("model must be 'GBM' or 'Heston'.")
-    lam, mu, sj, q = float(jump_intensity), float(jump_mean), float(jump_vol), float(dividend_yield)
-    if not (math.isfinite(lam) and lam >= 0.0):
-        raise ValueError("jump_intensity must be finite and non-negative.")
-    if not math.isfinite(mu):
-        raise ValueError("jump_mean must be finite.")
-    if not (math.isfinite(sj) and sj >= 0.0):
-        raise ValueError("jump_vol must be finite and non-negative.")
-    if not math.isfinite(q):
-        raise ValueError("dividend_yield must be finite.")
+    lam, mu, sj, q = _jump_args(jump_intensity, jump_mean, jump_vol, dividend_yield)
     _validate(S0, K, T, r, sigma, n_paths, n_steps, option_type, need_sigma=(model_l == "gbm"))
     _validate_scheme(model_l, heston_scheme, sigma, heston_params)
     if lam * float(T) / int(n_steps) > 1.0:
         raise ValueError("jump_intensity * T / n_steps must not exceed 1: use more time steps.")
-    M = int(n_paths) // 2 * 2
-    if M <= 0:
-        raise ValueError("num_simulations and num_time_steps must be positive integers.")
+    M = _even_paths(n_paths)
     c = _ffi.default_context(device)
     p = _ffi.make_params(model=model_l, is_put=(option_type == "put"), semantics="two_pass", antithetic=True,
                          n_paths=M, n_steps=int(n_steps), S0=S0, K=K, r=r, sigma=sigma or 0.0, T=T, seed=seed,
@@ -708,9 +722,7 @@ def price_american_basket(spots, K, r, sigmas, T, n_paths, n_steps, correlation=
     S0, sig, q, w, rho = _basket_args(spots, sigmas, weights, dividend_yields, correlation, kind)
     d = len(S0)
     _validate(S0[0], K, T, r, sig[0], n_paths, n_steps, option_type)
-    M = int(n_paths) // 2 * 2
-    if M <= 0:
-        raise ValueError("num_simulations and num_time_steps must be positive integers.")
+    M = _even_paths(n_paths)
     p = _ffi.make_params(model="gbm", is_put=(option_type == "put"), semantics="two_pass", antithetic=True, n_paths=M,
                          n_steps=int(n_steps), S0=S0[0], K=K, r=r, sigma=sig[0], T=T, seed=42 if seed is None else int(seed))
     b = _ffi.make_basket(S0, sig, q, w, rho, kind)
@@ -776,13 +788,9 @@ def price_american_basket_greeks(spots, K, r, sigmas, T, n_paths, n_steps, corre
     S0, sig, q, w, rho = _basket_args(spots, sigmas, weights, dividend_yields, correlation, kind)
     d = len(S0)
     _validate(S0[0], K, T, r, sig[0], n_paths, n_steps, option_type)
-    M = int(n_paths) // 2 * 2
-    if M <= 0:
-        raise ValueError("num_simulations and num_time_steps must be positive integers.")
-    if betas is not None:
-        import numpy as np
-        if np.asarray(betas).shape != (int(n_steps) + 1, 4):
-            raise ValueError(f"betas must have shape ({int(n_steps) + 1}, 4).")
+    M = _even_paths(n_paths)
+    if betas is not None and np.asarray(betas).shape != (int(n_steps) + 1, 4):
+        raise ValueError(f"betas must have shape ({int(n_steps) + 1}, 4).")
     p = _ffi.make_params(model="gbm", is_put=(option_type == "put"), semantics="two_pass", antithetic=True, n_paths=M,
                          n_steps=int(n_steps), S0=S0[0], K=K, r=r, sigma=sig[0], T=T, seed=42 if seed is None else int(seed))
     b = _ffi.make_basket(S0, sig, q, w, rho, kind)
@@ -830,6 +838,98 @@ class BoundsResult:
     suboptimality_check: str = "off"  # "payoff" / "european": inner simulations at the kept items only (section 27)
 
 
+# The argument checks that the bounds facades share, as stages: each facade calls them where its own order of refusals has
+# them, between its own law's checks.
+
+def _model_name(model):
+    model_l = str(model).lower()
+    if model_l not in ("gbm", "heston"):
+        raise ValueError("model must be 'GBM' or 'Heston'.")
+    return model_l
+
+
+def _true_or_false(control_variate):
+    if not isinstance(control_variate, (bool, int)) or control_variate not in (0, 1):
+        raise ValueError("control_variate must be True or False.")
+
+
+def _bounds_sizes(policy, betas, n_lower, n_outer, n_inner):
+    """the policy's name, `betas` exactly with policy "given", and the three sizes in whole antithetic pairs"""
+    if policy not in _ffi.BOUND_POLICIES:
+        raise ValueError(f"policy must be one of {sorted(_ffi.BOUND_POLICIES)}.")
+    if (policy == "given") != (betas is not None):
+        raise ValueError("betas must be given exactly when policy='given'.")
+    for name, v in (("n_lower", n_lower), ("n_outer", n_outer), ("n_inner", n_inner)):
+        if int(v) < 2 or int(v) % 2:
+            raise ValueError(f"{name} must be an even integer >= 2 (antithetic pairs).")
+
+
+# law -> whose bounds have no control variate, who takes 'payoff' or 'off', and whose price bounds take two schemes
+_LAW_WORDS = {"heston": (None, None, "under Heston"),
+              "jump": ("jump-diffusion", "jump-diffusion takes", "under Bates"),
+              "dividend": ("dividend", "dividends take", "with dividends"),
+              "barrier": ("barrier", "barrier options take", "of barrier options")}
+
+
+def _bounds_switches(law, control_variate, suboptimality_check, exercise_every):
+    """What the jump, dividend and barrier laws refuse of the switches of price_american_bounds -- the control variate and
+    the "european" check -- then the check's name and the schedule -> exercise_every as an int."""
+    no_cv, payoff_or_off, _ = _LAW_WORDS[law]
+    if control_variate:
+        raise ValueError(f"control_variate: the {no_cv} bounds have no control variate.")
+    if suboptimality_check == "european":
+        raise ValueError(f"suboptimality_check='european' is for price_american_bounds only ({payoff_or_off} 'payoff' or "
+                         "'off').")
+    if suboptimality_check is not None and suboptimality_check not in _ffi.BOUND_CHECKS:
+        raise ValueError(f"suboptimality_check must be one of {list(_ffi.BOUND_CHECKS)} or None.")
+    every = _one_schedule(exercise_every)
+    if every >= 2 and suboptimality_check == "payoff":
+        raise ValueError("sub-optimality checking is for the game on every date (exercise_every must be 0 or 1).")
+    return every
+
+
+def _bounds_scheme(law, model_l, heston_scheme):
+    """The bounds run on Heston scheme "reference" (= "clamp") or "full_truncation"; price_american_bounds_heston also says
+    which scheme it was given."""
+    if model_l != "heston":
+        return
+    if heston_scheme not in _ffi.HESTON_SCHEMES:
+        raise ValueError(f"heston_scheme must be one of {sorted(_ffi.HESTON_SCHEMES)}.")
+    if _ffi.HESTON_SCHEMES[heston_scheme] not in (_ffi.HESTON_SCHEMES["reference"], _ffi.HESTON_SCHEMES["full_truncation"]):
+        raise ValueError(f"price bounds {_LAW_WORDS[law][2]} take heston_scheme 'reference' or 'full_truncation'"
+                         + (f", not '{heston_scheme}'." if law == "heston" else "."))
+
+
+def _betas_shape(betas, n_steps, cols):
+    if betas is not None and np.shape(betas) != (int(n_steps) + 1, cols):
+        raise ValueError(f"betas must have shape ({int(n_steps) + 1}, {cols}), got {np.shape(betas)}.")
+
+
+def _law_params(model_l, option_type, heston_scheme, heston_params, M, n_steps, S0, K, r, sigma, T, seed, stream):
+    """omc_params of a one-asset bounds call: two-pass flow, M antithetic paths, GBM or Heston"""
+    if model_l == "heston":
+        return _ffi.make_params(model="heston", is_put=(option_type == "put"), semantics="two_pass", antithetic=True,
+                                heston_scheme=heston_scheme, n_paths=M, n_steps=int(n_steps), S0=S0, K=K, r=r,
+                                sigma=sigma or 0.0, T=T, seed=seed, stream=stream, **heston_defaults(sigma, heston_params))
+    return _ffi.make_params(is_put=(option_type == "put"), semantics="two_pass", antithetic=True, n_paths=M,
+                            n_steps=int(n_steps), S0=S0, K=K, r=r, sigma=sigma, T=T, seed=seed, stream=stream)
+
+
+def _game(n_steps, every):
+    """the schedule's two fields of a BoundsResult"""
+    return dict(exercise_every=every, n_exercise_dates=len(bounds_exercise_dates(n_steps, every)))
+
+
+def _bounds_result(cls, out, *, policy, option_type, **law_fields):
+    """The dict of a Context.price_*bounds* call as `cls`: the fields every law has, then the facade's own."""
+    return cls(lower=out["lower"], se_lower=out["se_lower"], upper=out["upper"], se_upper=out["se_upper"],
+               ci_lo=out["ci_lo"], ci_hi=out["ci_hi"], n_lower=out["n_lower"], n_outer=out["n_outer"], n_inner=out["n_inner"],
+               n_exercised_lower=out["n_exercised_lower"], inner_path_steps=out["inner_path_steps"], policy=policy,
+               betas=out["betas"], option_type=option_type,
+               timings_ms=dict(fit=out["ms_fit"], lower=out["ms_lower"], upper=out["ms_upper"], total=out["ms_total"]),
+               **law_fields)
+
+
 def price_american_bounds(S0, K, r, sigma, T, n_paths, n_steps, option_type="put", policy="textbook", n_lower=1_000_000,
                           n_outer=8192, n_inner=1024, seed=42, stream=0, betas=None, device=None,
                           ctx=None, control_variate=False, exercise_every=0) -> BoundsResult:
@@ -842,36 +942,17 @@ def price_american_bounds(S0, K, r, sigma, T, n_paths, n_steps, option_type="put
     control_variate=True: the same paths and stops with the discounted Black-Scholes value of the
     European option as a control variate in the lower bound and in every inner mean -- far smaller standard errors, and an
     upper bound whose bias a small n_inner no longer inflates."""
-    if exercise_every is None or isinstance(exercise_every, (list, tuple)):
-        raise ValueError("exercise_every must be a non-negative integer.")
     every = _one_schedule(exercise_every)
-    if not isinstance(control_variate, (bool, int)) or control_variate not in (0, 1):
-        raise ValueError("control_variate must be True or False.")
-    if policy not in _ffi.BOUND_POLICIES:
-        raise ValueError(f"policy must be one of {sorted(_ffi.BOUND_POLICIES)}.")
-    if (policy == "given") != (betas is not None):
-        raise ValueError("betas must be given exactly when policy='given'.")
-    for name, v in (("n_lower", n_lower), ("n_outer", n_outer), ("n_inner", n_inner)):
-        if int(v) < 2 or int(v) % 2:
-            raise ValueError(f"{name} must be an even integer >= 2 (antithetic pairs).")
+    _true_or_false(control_variate)
+    _bounds_sizes(policy, betas, n_lower, n_outer, n_inner)
     _validate(S0, K, T, r, sigma, n_paths, n_steps, option_type)
-    M = int(n_paths) // 2 * 2
-    if M <= 0:
-        raise ValueError("num_simulations and num_time_steps must be positive integers.")
+    M = _even_paths(n_paths)
     c = ctx or _ffi.default_context(device)
-    p = _ffi.make_params(is_put=(option_type == "put"), semantics="two_pass", n_paths=M, n_steps=int(n_steps), S0=S0, K=K,
-                         r=r, sigma=sigma, T=T, seed=seed, stream=stream)
+    p = _law_params("gbm", option_type, None, None, M, n_steps, S0, K, r, sigma, T, seed, stream)
     out = c.price_american_bounds(p, policy=policy, n_lower=int(n_lower), n_outer=int(n_outer), n_inner=int(n_inner),
                                   betas=betas, exercise_every=every, control_variate=bool(control_variate))
-    return BoundsResult(lower=out["lower"], se_lower=out["se_lower"], upper=out["upper"], se_upper=out["se_upper"],
-                        ci_lo=out["ci_lo"], ci_hi=out["ci_hi"], n_lower=out["n_lower"], n_outer=out["n_outer"],
-                        n_inner=out["n_inner"], n_exercised_lower=out["n_exercised_lower"],
-                        inner_path_steps=out["inner_path_steps"], policy=policy, betas=out["betas"],
-                        option_type=option_type,
-                        timings_ms=dict(fit=out["ms_fit"], lower=out["ms_lower"], upper=out["ms_upper"],
-                                        total=out["ms_total"]),
-                        exercise_every=every, n_exercise_dates=len(bounds_exercise_dates(n_steps, every)),
-                        control_variate=bool(control_variate))
+    return _bounds_result(BoundsResult, out, policy=policy, option_type=option_type, **_game(n_steps, every),
+                          control_variate=bool(control_variate))
 
 
 @dataclass
@@ -901,50 +982,22 @@ def price_american_bounds_heston(S0, K, r, T, n_paths, n_steps, heston_params=No
     table must share).  policy is then "textbook" or "given", n_steps at most 512, and `betas` is [n_steps+1][8] = c0, c1,
     c2 (1, u, u^2 of the spot), c3, c4 (w, w^2 of the variance), c5 (u w), n, 0.
     exercise_every = k >= 2: as price_american_bounds takes it, with regressors "spot" only."""
-    if exercise_every is None or isinstance(exercise_every, (list, tuple)):
-        raise ValueError("exercise_every must be a non-negative integer.")
     every = _one_schedule(exercise_every)
     if every >= 2 and regressors == "spot+variance":
         raise ValueError("the spot + variance policy takes no exercise schedule (exercise_every must be 0 or 1).")
-    if policy not in _ffi.BOUND_POLICIES:
-        raise ValueError(f"policy must be one of {sorted(_ffi.BOUND_POLICIES)}.")
-    if (policy == "given") != (betas is not None):
-        raise ValueError("betas must be given exactly when policy='given'.")
-    for name, v in (("n_lower", n_lower), ("n_outer", n_outer), ("n_inner", n_inner)):
-        if int(v) < 2 or int(v) % 2:
-            raise ValueError(f"{name} must be an even integer >= 2 (antithetic pairs).")
-    if heston_scheme not in _ffi.HESTON_SCHEMES:
-        raise ValueError(f"heston_scheme must be one of {sorted(_ffi.HESTON_SCHEMES)}.")
-    if _ffi.HESTON_SCHEMES[heston_scheme] == _ffi.HESTON_SCHEMES["calibrator"]:
-        raise ValueError("price bounds under Heston take heston_scheme 'reference' or 'full_truncation', not 'calibrator'.")
-    if _ffi.HESTON_SCHEMES[heston_scheme] == _ffi.HESTON_SCHEMES["qe"]:
-        raise ValueError("price bounds under Heston take heston_scheme 'reference' or 'full_truncation', not 'qe'.")
+    _bounds_sizes(policy, betas, n_lower, n_outer, n_inner)
+    _bounds_scheme("heston", "heston", heston_scheme)
     _validate(S0, K, T, r, None, n_paths, n_steps, option_type, need_sigma=False)
-    M = int(n_paths) // 2 * 2
-    if M <= 0:
-        raise ValueError("num_simulations and num_time_steps must be positive integers.")
+    M = _even_paths(n_paths)
     hp = heston_defaults(None, heston_params)
     _ffi.check_heston_regressors(regressors, policy, n_steps, hp["v0"], hp["theta"])
-    cols = 8 if regressors == "spot+variance" else 4
-    if betas is not None:
-        import numpy as np
-        if np.shape(betas) != (int(n_steps) + 1, cols):
-            raise ValueError(f"betas must have shape ({int(n_steps) + 1}, {cols}), got {np.shape(betas)}.")
-    p = _ffi.make_params(model="heston", is_put=(option_type == "put"), semantics="two_pass", antithetic=True,
-                         heston_scheme=heston_scheme, n_paths=M, n_steps=int(n_steps), S0=S0, K=K, r=r, sigma=0.0, T=T,
-                         seed=seed, stream=stream, **hp)
+    _betas_shape(betas, n_steps, 8 if regressors == "spot+variance" else 4)
+    p = _law_params("heston", option_type, heston_scheme, hp, M, n_steps, S0, K, r, None, T, seed, stream)
     c = ctx or _ffi.default_context(device)
     out = c.price_american_bounds_heston(p, policy=policy, n_lower=int(n_lower), n_outer=int(n_outer),
                                          n_inner=int(n_inner), betas=betas, regressors=regressors, exercise_every=every)
-    return HestonBoundsResult(lower=out["lower"], se_lower=out["se_lower"], upper=out["upper"], se_upper=out["se_upper"],
-                              ci_lo=out["ci_lo"], ci_hi=out["ci_hi"], n_lower=out["n_lower"], n_outer=out["n_outer"],
-                              n_inner=out["n_inner"], n_exercised_lower=out["n_exercised_lower"],
-                              inner_path_steps=out["inner_path_steps"], policy=policy, betas=out["betas"],
-                              option_type=option_type,
-                              timings_ms=dict(fit=out["ms_fit"], lower=out["ms_lower"], upper=out["ms_upper"],
-                                              total=out["ms_total"]),
-                              regressors=regressors, variance_scale=max(float(hp["v0"]), float(hp["theta"])),
-                              exercise_every=every, n_exercise_dates=len(bounds_exercise_dates(n_steps, every)))
+    return _bounds_result(HestonBoundsResult, out, policy=policy, option_type=option_type, regressors=regressors,
+                          variance_scale=max(float(hp["v0"]), float(hp["theta"])), **_game(n_steps, every))
 
 
 @dataclass
@@ -976,70 +1029,23 @@ def price_american_bounds_jumps(S0, K, r, sigma, T, n_paths, n_steps, jump_inten
     exercise_every = k >= 2: as price_american_bounds takes it.
     suboptimality_check: None / "off", or "payoff" (DESIGN.md section 27); "european" and control_variate=True need the
     European value under jumps per item and are refused."""
-    model_l = str(model).lower()
-    if model_l not in ("gbm", "heston"):
-        raise ValueError("model must be 'GBM' or 'Heston'.")
-    if control_variate:
-        raise ValueError("control_variate: the jump-diffusion bounds have no control variate.")
-    if suboptimality_check == "european":
-        raise ValueError("suboptimality_check='european' is for price_american_bounds only (jump-diffusion takes 'payoff' "
-                         "or 'off').")
-    if suboptimality_check is not None and suboptimality_check not in _ffi.BOUND_CHECKS:
-        raise ValueError(f"suboptimality_check must be one of {list(_ffi.BOUND_CHECKS)} or None.")
-    if exercise_every is None or isinstance(exercise_every, (list, tuple)):
-        raise ValueError("exercise_every must be a non-negative integer.")
-    every = _one_schedule(exercise_every)
-    if every >= 2 and suboptimality_check == "payoff":
-        raise ValueError("sub-optimality checking is for the game on every date (exercise_every must be 0 or 1).")
-    lam, mu, sj, q = float(jump_intensity), float(jump_mean), float(jump_vol), float(dividend_yield)
-    if not (math.isfinite(lam) and lam >= 0.0):
-        raise ValueError("jump_intensity must be finite and non-negative.")
-    if not math.isfinite(mu):
-        raise ValueError("jump_mean must be finite.")
-    if not (math.isfinite(sj) and sj >= 0.0):
-        raise ValueError("jump_vol must be finite and non-negative.")
-    if not math.isfinite(q):
-        raise ValueError("dividend_yield must be finite.")
-    if policy not in _ffi.BOUND_POLICIES:
-        raise ValueError(f"policy must be one of {sorted(_ffi.BOUND_POLICIES)}.")
-    if (policy == "given") != (betas is not None):
-        raise ValueError("betas must be given exactly when policy='given'.")
-    for name, v in (("n_lower", n_lower), ("n_outer", n_outer), ("n_inner", n_inner)):
-        if int(v) < 2 or int(v) % 2:
-            raise ValueError(f"{name} must be an even integer >= 2 (antithetic pairs).")
+    model_l = _model_name(model)
+    every = _bounds_switches("jump", control_variate, suboptimality_check, exercise_every)
+    lam, mu, sj, q = _jump_args(jump_intensity, jump_mean, jump_vol, dividend_yield)
+    _bounds_sizes(policy, betas, n_lower, n_outer, n_inner)
     _validate(S0, K, T, r, sigma, n_paths, n_steps, option_type, need_sigma=(model_l == "gbm"))
-    if model_l == "heston":
-        if heston_scheme not in _ffi.HESTON_SCHEMES:
-            raise ValueError(f"heston_scheme must be one of {sorted(_ffi.HESTON_SCHEMES)}.")
-        if _ffi.HESTON_SCHEMES[heston_scheme] not in (_ffi.HESTON_SCHEMES["reference"],
-                                                      _ffi.HESTON_SCHEMES["full_truncation"]):
-            raise ValueError("price bounds under Bates take heston_scheme 'reference' or 'full_truncation'.")
+    _bounds_scheme("jump", model_l, heston_scheme)
     if lam * float(T) / int(n_steps) > 1.0:
         raise ValueError("jump_intensity * T / n_steps must not exceed 1: use more time steps.")
-    M = int(n_paths) // 2 * 2
-    if M <= 0:
-        raise ValueError("num_simulations and num_time_steps must be positive integers.")
-    if model_l == "heston":
-        p = _ffi.make_params(model="heston", is_put=(option_type == "put"), semantics="two_pass", antithetic=True,
-                             heston_scheme=heston_scheme, n_paths=M, n_steps=int(n_steps), S0=S0, K=K, r=r, sigma=sigma or 0.0,
-                             T=T, seed=seed, stream=stream, **heston_defaults(sigma, heston_params))
-    else:
-        p = _ffi.make_params(is_put=(option_type == "put"), semantics="two_pass", antithetic=True, n_paths=M,
-                             n_steps=int(n_steps), S0=S0, K=K, r=r, sigma=sigma, T=T, seed=seed, stream=stream)
+    M = _even_paths(n_paths)
+    p = _law_params(model_l, option_type, heston_scheme, heston_params, M, n_steps, S0, K, r, sigma, T, seed, stream)
     c = ctx or _ffi.default_context(device)
     out = c.price_american_bounds_jump(p, (lam, mu, sj), q, policy=policy, n_lower=int(n_lower), n_outer=int(n_outer),
                                        n_inner=int(n_inner), betas=betas, exercise_every=every,
                                        suboptimality_check=suboptimality_check)
-    return JumpBoundsResult(lower=out["lower"], se_lower=out["se_lower"], upper=out["upper"], se_upper=out["se_upper"],
-                            ci_lo=out["ci_lo"], ci_hi=out["ci_hi"], n_lower=out["n_lower"], n_outer=out["n_outer"],
-                            n_inner=out["n_inner"], n_exercised_lower=out["n_exercised_lower"],
-                            inner_path_steps=out["inner_path_steps"], policy=policy, betas=out["betas"],
-                            option_type=option_type,
-                            timings_ms=dict(fit=out["ms_fit"], lower=out["ms_lower"], upper=out["ms_upper"],
-                                            total=out["ms_total"]),
-                            exercise_every=every, n_exercise_dates=len(bounds_exercise_dates(n_steps, every)),
-                            suboptimality_check=suboptimality_check or "off",
-                            jump_intensity=lam, jump_mean=mu, jump_vol=sj, dividend_yield=q, model=model_l)
+    return _bounds_result(JumpBoundsResult, out, policy=policy, option_type=option_type, **_game(n_steps, every),
+                          suboptimality_check=suboptimality_check or "off", jump_intensity=lam, jump_mean=mu, jump_vol=sj,
+                          dividend_yield=q, model=model_l)
 
 
 @dataclass
@@ -1071,73 +1077,25 @@ def price_american_bounds_dividends(S0, K, r, sigma, T, n_paths, n_steps, divide
     exercise_every = k >= 2: as price_american_bounds takes it.
     suboptimality_check: None / "off", or "payoff" (DESIGN.md section 27); "european" and control_variate=True are refused:
     the Black-Scholes value is not the European value after a cash dividend."""
-    model_l = str(model).lower()
-    if model_l not in ("gbm", "heston"):
-        raise ValueError("model must be 'GBM' or 'Heston'.")
-    if control_variate:
-        raise ValueError("control_variate: the dividend bounds have no control variate.")
-    if suboptimality_check == "european":
-        raise ValueError("suboptimality_check='european' is for price_american_bounds only (dividends take 'payoff' or "
-                         "'off').")
-    if suboptimality_check is not None and suboptimality_check not in _ffi.BOUND_CHECKS:
-        raise ValueError(f"suboptimality_check must be one of {list(_ffi.BOUND_CHECKS)} or None.")
-    if exercise_every is None or isinstance(exercise_every, (list, tuple)):
-        raise ValueError("exercise_every must be a non-negative integer.")
-    every = _one_schedule(exercise_every)
-    if every >= 2 and suboptimality_check == "payoff":
-        raise ValueError("sub-optimality checking is for the game on every date (exercise_every must be 0 or 1).")
+    model_l = _model_name(model)
+    every = _bounds_switches("dividend", control_variate, suboptimality_check, exercise_every)
     q = float(dividend_yield)
     if not math.isfinite(q):
         raise ValueError("dividend_yield must be finite.")
-    divs = []
-    for d in dividends:
-        d = tuple(d)
-        if len(d) not in (2, 3):
-            raise ValueError("a dividend is (t, amount) or (t, amount, 'cash' | 'proportional').")
-        kind = d[2] if len(d) == 3 else "cash"
-        if kind not in _ffi.DIVIDEND_KINDS:
-            raise ValueError("a dividend's kind must be 'cash' or 'proportional'.")
-        divs.append((float(d[0]), float(d[1]), kind))
-    if policy not in _ffi.BOUND_POLICIES:
-        raise ValueError(f"policy must be one of {sorted(_ffi.BOUND_POLICIES)}.")
-    if (policy == "given") != (betas is not None):
-        raise ValueError("betas must be given exactly when policy='given'.")
-    for name, v in (("n_lower", n_lower), ("n_outer", n_outer), ("n_inner", n_inner)):
-        if int(v) < 2 or int(v) % 2:
-            raise ValueError(f"{name} must be an even integer >= 2 (antithetic pairs).")
+    divs = _dividend_items(dividends)
+    _bounds_sizes(policy, betas, n_lower, n_outer, n_inner)
     _validate(S0, K, T, r, sigma, n_paths, n_steps, option_type, need_sigma=(model_l == "gbm"))
-    if model_l == "heston":
-        if heston_scheme not in _ffi.HESTON_SCHEMES:
-            raise ValueError(f"heston_scheme must be one of {sorted(_ffi.HESTON_SCHEMES)}.")
-        if _ffi.HESTON_SCHEMES[heston_scheme] not in (_ffi.HESTON_SCHEMES["reference"],
-                                                      _ffi.HESTON_SCHEMES["full_truncation"]):
-            raise ValueError("price bounds with dividends take heston_scheme 'reference' or 'full_truncation'.")
-    M = int(n_paths) // 2 * 2
-    if M <= 0:
-        raise ValueError("num_simulations and num_time_steps must be positive integers.")
-    if model_l == "heston":
-        p = _ffi.make_params(model="heston", is_put=(option_type == "put"), semantics="two_pass", antithetic=True,
-                             heston_scheme=heston_scheme, n_paths=M, n_steps=int(n_steps), S0=S0, K=K, r=r, sigma=sigma or 0.0,
-                             T=T, seed=seed, stream=stream, **heston_defaults(sigma, heston_params))
-    else:
-        p = _ffi.make_params(is_put=(option_type == "put"), semantics="two_pass", antithetic=True, n_paths=M,
-                             n_steps=int(n_steps), S0=S0, K=K, r=r, sigma=sigma, T=T, seed=seed, stream=stream)
+    _bounds_scheme("dividend", model_l, heston_scheme)
+    M = _even_paths(n_paths)
+    p = _law_params(model_l, option_type, heston_scheme, heston_params, M, n_steps, S0, K, r, sigma, T, seed, stream)
     has = _ffi.dividend_schedule(p, q, divs)[2]  # (host only: the library's own checks of the schedule, before a context)
     c = ctx or _ffi.default_context(device)
     out = c.price_american_bounds_div(p, q, divs, policy=policy, n_lower=int(n_lower), n_outer=int(n_outer),
                                       n_inner=int(n_inner), betas=betas, exercise_every=every,
                                       suboptimality_check=suboptimality_check)
-    return DividendBoundsResult(lower=out["lower"], se_lower=out["se_lower"], upper=out["upper"], se_upper=out["se_upper"],
-                                ci_lo=out["ci_lo"], ci_hi=out["ci_hi"], n_lower=out["n_lower"], n_outer=out["n_outer"],
-                                n_inner=out["n_inner"], n_exercised_lower=out["n_exercised_lower"],
-                                inner_path_steps=out["inner_path_steps"], policy=policy, betas=out["betas"],
-                                option_type=option_type,
-                                timings_ms=dict(fit=out["ms_fit"], lower=out["ms_lower"], upper=out["ms_upper"],
-                                                total=out["ms_total"]),
-                                exercise_every=every, n_exercise_dates=len(bounds_exercise_dates(n_steps, every)),
-                                suboptimality_check=suboptimality_check or "off", dividend_yield=q,
-                                n_div_steps=int(has.sum()), first_div_step=int(has.argmax()) if has.any() else 0,
-                                model=model_l)
+    return _bounds_result(DividendBoundsResult, out, policy=policy, option_type=option_type, **_game(n_steps, every),
+                          suboptimality_check=suboptimality_check or "off", dividend_yield=q, n_div_steps=int(has.sum()),
+                          first_div_step=int(has.argmax()) if has.any() else 0, model=model_l)
 
 
 @dataclass
@@ -1170,73 +1128,31 @@ def price_barrier_bounds(S0, K, r, sigma, T, n_paths, n_steps, barrier, barrier_
     step, so daily monitoring with monthly exercise is exercise_every = 21 on a daily grid.
     suboptimality_check: None / "off", or "payoff" (DESIGN.md section 27); "european" and control_variate=True are refused:
     a vanilla European value is no bound on a barrier continuation value."""
-    model_l = str(model).lower()
-    if model_l not in ("gbm", "heston"):
-        raise ValueError("model must be 'GBM' or 'Heston'.")
+    model_l = _model_name(model)
     if barrier_type not in _ffi.BARRIER_KINDS:
         raise ValueError(f"barrier_type must be one of {sorted(_ffi.BARRIER_KINDS)}.")
     if monitoring != "discrete":
         raise ValueError("monitoring: the barrier bounds take 'discrete' monitoring only.")
-    if control_variate:
-        raise ValueError("control_variate: the barrier bounds have no control variate.")
-    if suboptimality_check == "european":
-        raise ValueError("suboptimality_check='european' is for price_american_bounds only (barrier options take 'payoff' "
-                         "or 'off').")
-    if suboptimality_check is not None and suboptimality_check not in _ffi.BOUND_CHECKS:
-        raise ValueError(f"suboptimality_check must be one of {list(_ffi.BOUND_CHECKS)} or None.")
-    if exercise_every is None or isinstance(exercise_every, (list, tuple)):
-        raise ValueError("exercise_every must be a non-negative integer.")
-    every = _one_schedule(exercise_every)
-    if every >= 2 and suboptimality_check == "payoff":
-        raise ValueError("sub-optimality checking is for the game on every date (exercise_every must be 0 or 1).")
+    every = _bounds_switches("barrier", control_variate, suboptimality_check, exercise_every)
     H = float(barrier)
     if not (math.isfinite(H) and H > 0):
         raise ValueError("barrier H must be finite and positive.")
-    if policy not in _ffi.BOUND_POLICIES:
-        raise ValueError(f"policy must be one of {sorted(_ffi.BOUND_POLICIES)}.")
-    if (policy == "given") != (betas is not None):
-        raise ValueError("betas must be given exactly when policy='given'.")
-    for name, v in (("n_lower", n_lower), ("n_outer", n_outer), ("n_inner", n_inner)):
-        if int(v) < 2 or int(v) % 2:
-            raise ValueError(f"{name} must be an even integer >= 2 (antithetic pairs).")
+    _bounds_sizes(policy, betas, n_lower, n_outer, n_inner)
     _validate(S0, K, T, r, sigma, n_paths, n_steps, option_type, need_sigma=(model_l == "gbm"))
-    if betas is not None:
-        import numpy as np
-        if np.shape(betas) != (int(n_steps) + 1, 4):
-            raise ValueError(f"betas must have shape ({int(n_steps) + 1}, 4), got {np.shape(betas)}.")
-    if model_l == "heston":
-        if heston_scheme not in _ffi.HESTON_SCHEMES:
-            raise ValueError(f"heston_scheme must be one of {sorted(_ffi.HESTON_SCHEMES)}.")
-        if _ffi.HESTON_SCHEMES[heston_scheme] not in (_ffi.HESTON_SCHEMES["reference"],
-                                                      _ffi.HESTON_SCHEMES["full_truncation"]):
-            raise ValueError("price bounds of barrier options take heston_scheme 'reference' or 'full_truncation'.")
+    _betas_shape(betas, n_steps, 4)
+    _bounds_scheme("barrier", model_l, heston_scheme)
     up = barrier_type.startswith("up")
     if (float(S0) >= H) if up else (float(S0) <= H):
         raise ValueError("S0 lies on or beyond the barrier (the option is already knocked).")
-    M = int(n_paths) // 2 * 2
-    if M <= 0:
-        raise ValueError("num_simulations and num_time_steps must be positive integers.")
-    if model_l == "heston":
-        p = _ffi.make_params(model="heston", is_put=(option_type == "put"), semantics="two_pass", antithetic=True,
-                             heston_scheme=heston_scheme, n_paths=M, n_steps=int(n_steps), S0=S0, K=K, r=r, sigma=sigma or 0.0,
-                             T=T, seed=seed, stream=stream, **heston_defaults(sigma, heston_params))
-    else:
-        p = _ffi.make_params(is_put=(option_type == "put"), semantics="two_pass", antithetic=True, n_paths=M,
-                             n_steps=int(n_steps), S0=S0, K=K, r=r, sigma=sigma, T=T, seed=seed, stream=stream)
+    M = _even_paths(n_paths)
+    p = _law_params(model_l, option_type, heston_scheme, heston_params, M, n_steps, S0, K, r, sigma, T, seed, stream)
     c = ctx or _ffi.default_context(device)
     out = c.price_barrier_bounds(p, barrier_type, H, policy=policy, n_lower=int(n_lower), n_outer=int(n_outer),
                                  n_inner=int(n_inner), betas=betas, exercise_every=every,
                                  suboptimality_check=suboptimality_check)
-    return BarrierBoundsResult(lower=out["lower"], se_lower=out["se_lower"], upper=out["upper"], se_upper=out["se_upper"],
-                               ci_lo=out["ci_lo"], ci_hi=out["ci_hi"], n_lower=out["n_lower"], n_outer=out["n_outer"],
-                               n_inner=out["n_inner"], n_exercised_lower=out["n_exercised_lower"],
-                               inner_path_steps=out["inner_path_steps"], policy=policy, betas=out["betas"],
-                               option_type=option_type,
-                               timings_ms=dict(fit=out["ms_fit"], lower=out["ms_lower"], upper=out["ms_upper"],
-                                               total=out["ms_total"]),
-                               exercise_every=every, n_exercise_dates=len(bounds_exercise_dates(n_steps, every)),
-                               suboptimality_check=suboptimality_check or "off", barrier=H, barrier_type=barrier_type,
-                               monitoring="discrete", model=model_l)
+    return _bounds_result(BarrierBoundsResult, out, policy=policy, option_type=option_type, **_game(n_steps, every),
+                          suboptimality_check=suboptimality_check or "off", barrier=H, barrier_type=barrier_type,
+                          monitoring="discrete", model=model_l)
 
 
 def price_bermudan_bounds(S0, K, r, sigma, T, n_paths, n_steps, exercise_every, model="GBM", option_type="put",
@@ -1252,8 +1168,7 @@ def price_bermudan_bounds(S0, K, r, sigma, T, n_paths, n_steps, exercise_every, 
     if exercise_every is None or isinstance(exercise_every, (list, tuple)):
         raise ValueError("exercise_every must be a non-negative integer.")
     model_l = str(model).lower()
-    if not isinstance(control_variate, (bool, int)) or control_variate not in (0, 1):
-        raise ValueError("control_variate must be True or False.")
+    _true_or_false(control_variate)
     if control_variate and model_l == "heston":
         raise ValueError("control_variate: the Black-Scholes control variate is for model 'GBM' only.")
     if model_l == "gbm":
@@ -1284,15 +1199,10 @@ def price_american_bounds_checked(S0, K, r, sigma, T, n_paths, n_steps, check="e
     exercise_every must be 0 or 1."""
     if check not in _ffi.BOUND_CHECKS:
         raise ValueError(f"check must be one of {list(_ffi.BOUND_CHECKS)}.")
-    if exercise_every is None or isinstance(exercise_every, (list, tuple)):
-        raise ValueError("exercise_every must be a non-negative integer.")
     if _one_schedule(exercise_every) >= 2:
         raise ValueError("sub-optimality checking is for the game on every date (exercise_every must be 0 or 1).")
-    model_l = str(model).lower()
-    if model_l not in ("gbm", "heston"):
-        raise ValueError("model must be 'GBM' or 'Heston'.")
-    if not isinstance(control_variate, (bool, int)) or control_variate not in (0, 1):
-        raise ValueError("control_variate must be True or False.")
+    model_l = _model_name(model)
+    _true_or_false(control_variate)
     if model_l == "heston" and control_variate:
         raise ValueError("control_variate: the Black-Scholes control variate is for model 'GBM' only.")
     if model_l == "heston" and check == "european":
@@ -1352,21 +1262,13 @@ def price_american_basket_bounds(spots, K, r, sigmas, T, n_paths, n_steps, corre
         raise ValueError("suboptimality_check='european' is for one GBM asset (price_american_bounds_checked).")
     if suboptimality_check == "payoff" and regressors != "index":
         raise ValueError("suboptimality_check='payoff' is for regressors='index'.")
-    if policy not in _ffi.BOUND_POLICIES:
-        raise ValueError(f"policy must be one of {sorted(_ffi.BOUND_POLICIES)}.")
-    if (policy == "given") != (betas is not None):
-        raise ValueError("betas must be given exactly when policy='given'.")
-    for name, v in (("n_lower", n_lower), ("n_outer", n_outer), ("n_inner", n_inner)):
-        if int(v) < 2 or int(v) % 2:
-            raise ValueError(f"{name} must be an even integer >= 2 (antithetic pairs).")
+    _bounds_sizes(policy, betas, n_lower, n_outer, n_inner)
     S0, sig, q, w, rho = _basket_args(spots, sigmas, weights, dividend_yields, correlation, kind)
     _ffi.check_runnerup(regressors, policy, kind, len(S0))
     if regressors == "index+spot" and int(n_steps) > _ffi.HESTON_SV_MAX_STEPS:
         raise ValueError(f"regressors='index+spot' takes at most {_ffi.HESTON_SV_MAX_STEPS} steps.")
     _validate(S0[0], K, T, r, sig[0], n_paths, n_steps, option_type)
-    M = int(n_paths) // 2 * 2
-    if M <= 0:
-        raise ValueError("num_simulations and num_time_steps must be positive integers.")
+    M = _even_paths(n_paths)
     p = _ffi.make_params(model="gbm", is_put=(option_type == "put"), semantics="two_pass", antithetic=True, n_paths=M,
                          n_steps=int(n_steps), S0=S0[0], K=K, r=r, sigma=sig[0], T=T, seed=seed, stream=stream)
     b = _ffi.make_basket(S0, sig, q, w, rho, kind)
@@ -1377,15 +1279,9 @@ def price_american_basket_bounds(spots, K, r, sigmas, T, n_paths, n_steps, corre
     out = c.price_american_basket_bounds(p, b, policy=policy, n_lower=int(n_lower), n_outer=int(n_outer),
                                          n_inner=int(n_inner), betas=betas, regressors=regressors,
                                          suboptimality_check=suboptimality_check)
-    return BasketBoundsResult(lower=out["lower"], se_lower=out["se_lower"], upper=out["upper"], se_upper=out["se_upper"],
-                              ci_lo=out["ci_lo"], ci_hi=out["ci_hi"], n_lower=out["n_lower"], n_outer=out["n_outer"],
-                              n_inner=out["n_inner"], n_exercised_lower=out["n_exercised_lower"],
-                              inner_path_steps=out["inner_path_steps"], policy=policy, betas=out["betas"],
-                              option_type=option_type,
-                              timings_ms=dict(fit=out["ms_fit"], lower=out["ms_lower"], upper=out["ms_upper"],
-                                              total=out["ms_total"]),
-                              index0=out["index0"], n_assets=out["n_assets"], kind=kind, regressors=regressors,
-                              suboptimality_check=suboptimality_check or "off")
+    return _bounds_result(BasketBoundsResult, out, policy=policy, option_type=option_type, index0=out["index0"],
+                          n_assets=out["n_assets"], kind=kind, regressors=regressors,
+                          suboptimality_check=suboptimality_check or "off")
 
 
 _ASIAN_AVERAGING = {"arithmetic": "asian", "geometric": "asian-geometric"}
