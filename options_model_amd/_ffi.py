@@ -152,6 +152,12 @@ class DivResult(C.Structure):
                 ("first_div_step", C.c_int32)]
 
 
+class DivGreeks(C.Structure):
+    """omc_div_greeks (include/omc_dividend_greeks.h): omc_greeks plus epsilon (dV/dq) and the dividend steps."""
+    _fields_ = [("g", Greeks), ("epsilon", C.c_double), ("se_epsilon", C.c_double), ("n_div_steps", C.c_int32),
+                ("first_div_step", C.c_int32)]
+
+
 class Jump(C.Structure):
     """omc_jump: lambda (jumps per year), mu_j and sigma_j (mean and standard deviation of a jump's log size)."""
     _fields_ = [("lambda_", C.c_double), ("mu_j", C.c_double), ("sigma_j", C.c_double)]
@@ -353,6 +359,11 @@ BARRIER_BOUNDS_SIGNATURES = {
                                                     _P, _P, C.POINTER(Bounds)]),
 }
 
+# The entry point of include/omc_dividend_greeks.h, an extension header of its own.
+DIVIDEND_GREEKS_SIGNATURES = {
+    "omc_price_american_div_greeks": (C.c_int, [_P, C.POINTER(Params), _D, _P, _I, _D, _P, _P, C.POINTER(DivGreeks)]),
+}
+
 _lib = None
 _lib_lock = threading.Lock()
 _hip_runtime = None
@@ -411,7 +422,7 @@ def load_library(build_if_missing: bool = True):
         _preload_hip_runtime()
         lib = C.CDLL(path)
         for name, (res, args) in {**SIGNATURES, **JUMP_BOUNDS_SIGNATURES, **DIVIDEND_BOUNDS_SIGNATURES,
-                                  **BARRIER_BOUNDS_SIGNATURES}.items():
+                                  **BARRIER_BOUNDS_SIGNATURES, **DIVIDEND_GREEKS_SIGNATURES}.items():
             fn = getattr(lib, name)  # AttributeError = symbol missing = broken build
             fn.restype = res
             fn.argtypes = args
@@ -994,6 +1005,31 @@ class Context:
                                                           S_keep.ptr if S_keep else None,
                                                           S_keep.shape[1] if S_keep else 0))
         return _with_base(out)
+
+    def price_american_dividend_greeks(self, params: Params, q=0.0, dividends=(), bump=0.01, betas=None, want_betas=False):
+        """Frozen-policy pathwise Greeks of price_american_div's product (omc_price_american_div_greeks) -> dict: the base
+        pricing's keys plus delta, gamma, vega, rho, theta, epsilon (dV/dq; raw units), se_*, bump, price_up, price_down,
+        n_exercised_up / _down, ms_greeks, n_div_steps, first_div_step.  One forward sweep on regenerated paths replaces
+        pass 2.  Heston gives delta and gamma, the others are NaN.  `betas` [n_steps+1][4] freezes a given policy (an
+        all-n <= 0 table: the European option); want_betas adds the policy used."""
+        arr, n = dividend_array(dividends)
+        N = int(params.n_steps)
+        b = None
+        if betas is not None:
+            b = np.ascontiguousarray(betas, np.float64)
+            if b.shape != (N + 1, 4):
+                raise ValueError(f"betas must have shape ({N + 1}, 4), got {b.shape}.")
+        bo = np.zeros((N + 1, 4)) if want_betas else None
+        out = DivGreeks()
+        _check(self.lib, self.lib.omc_price_american_div_greeks(self.handle, C.byref(params), float(q), arr, n, float(bump),
+                                                                 b.ctypes.data if b is not None else None,
+                                                                 bo.ctypes.data if bo is not None else None, C.byref(out)))
+        d = _with_base(out.g)
+        d.update(epsilon=out.epsilon, se_epsilon=out.se_epsilon, n_div_steps=out.n_div_steps,
+                 first_div_step=out.first_div_step)
+        if want_betas:
+            d["betas"] = bo
+        return d
 
     def price_american_jump(self, params: Params, jump, q=0.0, S_keep: DeviceArray | None = None):
         """American option under jump-diffusion (omc_price_american_jump: Merton on GBM, Bates on Heston) -> dict: the

@@ -587,6 +587,87 @@ def price_american_dividends(S0, K, r, sigma, T, n_paths, n_steps, dividend_yiel
 
 
 @dataclass
+class DividendGreeksResult:
+    """price_american_dividend_greeks: the frozen-policy price and its pathwise Greeks in raw units (per unit S0 / S0^2 /
+    sigma / r / q / year), their standard errors, the bumped scenarios and the policy used.  Heston: vega, rho, theta and
+    epsilon are NaN."""
+    price: float
+    stderr: float
+    delta: float
+    gamma: float
+    vega: float
+    rho: float
+    theta: float
+    epsilon: float
+    se_delta: float
+    se_gamma: float
+    se_vega: float
+    se_rho: float
+    se_theta: float
+    se_epsilon: float
+    price_up: float
+    price_down: float
+    bump: float
+    n_paths: int
+    n_exercised: int
+    n_exercised_up: int
+    n_exercised_down: int
+    sum_nitm: int
+    folded: bool
+    dividend_steps: int
+    first_dividend_step: int
+    dividend_yield: float
+    model: str
+    option_type: str
+    betas: object = None  # numpy [n_steps+1][4]: b0, b1, b2, n
+    timings_ms: dict = field(default_factory=dict)
+
+    def __float__(self):
+        return float(self.price)
+
+
+def price_american_dividend_greeks(S0, K, r, sigma, T, n_paths, n_steps, dividend_yield=0.0, dividends=(), model="GBM",
+                                   option_type="put", heston_params=None, heston_scheme="reference", seed=42, stream=0,
+                                   bump=0.01, betas=None, device=None, ctx=None) -> DividendGreeksResult:
+    """Delta, gamma, vega, rho, theta and epsilon (dV/d dividend_yield) of the American price price_american_dividends
+    quotes, with the exercise policy pass 1 fits -- or `betas` [n_steps+1][4] -- held fixed (omc_price_american_div_greeks,
+    DESIGN.md section 32).  One forward sweep regenerates the paths and carries their tangents through every dividend: a
+    cash dividend makes the spot affine in S0, which price_american_greeks' scaled paths cannot follow.  theta is -dV/dT at
+    fixed n_steps with the dividends fixed on their steps and at their amounts; there is no sensitivity to a dividend's
+    amount.  Heston gives delta and gamma; the others are NaN.  dividends and heston_scheme: as price_american_dividends
+    takes them.  Antithetic paths, one GPU."""
+    model_l = str(model).lower()
+    if model_l not in ("gbm", "heston"):
+        raise ValueError("model must be 'GBM' or 'Heston'.")
+    q = float(dividend_yield)
+    if not math.isfinite(q):
+        raise ValueError("dividend_yield must be finite.")
+    if not (0.0 < float(bump) <= 0.5):
+        raise ValueError("bump must lie in (0, 0.5].")
+    divs = _dividend_items(dividends)
+    _validate(S0, K, T, r, sigma, n_paths, n_steps, option_type, need_sigma=(model_l == "gbm"))
+    _validate_scheme(model_l, heston_scheme, sigma, heston_params)
+    M = _even_paths(n_paths)
+    p = _ffi.make_params(model=model_l, is_put=(option_type == "put"), semantics="two_pass", antithetic=True,
+                         n_paths=M, n_steps=int(n_steps), S0=S0, K=K, r=r, sigma=sigma or 0.0, T=T, seed=seed,
+                         stream=stream, heston_scheme=heston_scheme, **heston_defaults(sigma, heston_params))
+    _ffi.dividend_schedule(p, q, divs)  # (host only: the library's own checks of the schedule, before a context)
+    c = ctx or _ffi.default_context(device)
+    out = c.price_american_dividend_greeks(p, q, divs, bump=float(bump), betas=betas, want_betas=True)
+    var = max(out["sumsq"] / M - out["price"] ** 2, 0.0)
+    return DividendGreeksResult(
+        price=out["price"], stderr=math.sqrt(var / M), delta=out["delta"], gamma=out["gamma"], vega=out["vega"],
+        rho=out["rho"], theta=out["theta"], epsilon=out["epsilon"], se_delta=out["se_delta"], se_gamma=out["se_gamma"],
+        se_vega=out["se_vega"], se_rho=out["se_rho"], se_theta=out["se_theta"], se_epsilon=out["se_epsilon"],
+        price_up=out["price_up"], price_down=out["price_down"], bump=out["bump"], n_paths=M,
+        n_exercised=out["n_exercised"], n_exercised_up=out["n_exercised_up"], n_exercised_down=out["n_exercised_down"],
+        sum_nitm=out["sum_nitm"], folded=bool(out["folded"]), dividend_steps=out["n_div_steps"],
+        first_dividend_step=out["first_div_step"], dividend_yield=q, model=model_l, option_type=option_type,
+        betas=out["betas"],
+        timings_ms=dict(paths=out["ms_paths"], pass1=out["ms_pass1"], greeks=out["ms_greeks"], total=out["ms_total"]))
+
+
+@dataclass
 class JumpResult:
     """price_american_jumps: price / stderr (the convention of PriceResult), the exercise counts, the compensator
     kappa = E[e^J] - 1 and the drift rate (r - q) - lambda kappa the paths ran at."""

@@ -207,6 +207,65 @@ __device__ __forceinline__ void heston_pair_step(const HestonC& c, float z1, flo
     }
 }
 
+// ---- the step as its two growth factors (the dividend Greeks sweep, omc_dividend_greeks.hip)
+// heston_pair_step's variance update with the spot update left to the caller: ga / gb are what the step multiplies the
+// two partners' spots by -- heston_grow below applies one -- and depend on no spot, so several spots (and their
+// S0-tangents) per partner step on ONE variance update.  It stands BESIDE heston_pair_step and repeats its operations in
+// its order: heston_grow<SCHEME>(s, ga) has the bits heston_pair_step<SCHEME> leaves in s (checked on the device by
+// tests/test_gpu_dividend_greeks.py), and no existing kernel's code changes.
+template <int SCHEME>
+__device__ __forceinline__ void heston_pair_factors(const HestonC& c, float z1, float z2, float& v, float& vb, float& ga,
+                                                    float& gb)
+{
+    if constexpr (SCHEME == 3) {
+#pragma clang fp contract(off)
+        const float ma = __builtin_fmaf(v - c.theta, c.qe_e, c.theta), mb = __builtin_fmaf(vb - c.theta, c.qe_e, c.theta);
+        const float s2a = __builtin_fmaf(v, c.qe_c1, c.qe_c2), s2b = __builtin_fmaf(vb, c.qe_c1, c.qe_c2);
+        const float m2a = ma * ma, m2b = mb * mb;
+        const bool ea = s2a > 1.5f * m2a, eb = s2b > 1.5f * m2b;
+        float vna = qe_quadratic(ma, s2a, m2a, z1), vnb = qe_quadratic(mb, s2b, m2b, -z1);
+        if (__builtin_amdgcn_ballot_w64(ea || eb) != 0) {
+            if (ea) vna = qe_exponential(ma, s2a, m2a, z1);
+            if (eb) vnb = qe_exponential(mb, s2b, m2b, -z1);
+        }
+        ga = gb = 1.0f;  // qe_spot's own expression on a spot of 1: 1 * x is x, so s * ga is qe_spot's product
+        qe_spot(c, v, vna, z2, ga);
+        qe_spot(c, vb, vnb, -z2, gb);
+        v = vna;
+        vb = vnb;
+    } else if constexpr (SCHEME == 2) {  // arithmetic Euler: s <- fma(s, g, s)
+        const float w2 = __builtin_fmaf(c.rho, z1, c.rho2 * z2);
+        {
+            const float vp = floor_at(v, 1e-8f);
+            const float sq = __builtin_amdgcn_sqrtf(vp);
+            const float vn = __builtin_fmaf(c.xi_sqdt * sq, w2, __builtin_fmaf(c.kdt, c.theta - vp, vp));
+            ga = __builtin_fmaf(sq * c.sqdt, z1, c.rdt);
+            v = floor_at(vn, 1e-8f);
+        }
+        {
+            const float vp = floor_at(vb, 1e-8f);
+            const float sq = __builtin_amdgcn_sqrtf(vp);
+            const float vn = __builtin_fmaf(c.xi_sqdt * sq, -w2, __builtin_fmaf(c.kdt, c.theta - vp, vp));
+            gb = __builtin_fmaf(sq * c.sqdt, -z1, c.rdt);
+            vb = floor_at(vn, 1e-8f);
+        }
+    } else {
+        const float w2 = __builtin_fmaf(c.rho, z1, c.rho2 * z2);
+        const float tw = c.xi_sqdt * w2;
+        const float az = c.l2e_sqdt * z1;
+        ga = gb = 1.0f;
+        heston_path_step<SCHEME>(c, tw, az, ga, v);
+        heston_path_step<SCHEME>(c, -tw, -az, gb, vb);
+    }
+}
+// a spot (or an S0-tangent: the map is linear) through the step whose factor is g
+template <int SCHEME>
+__device__ __forceinline__ float heston_grow(float s, float g)
+{
+    if constexpr (SCHEME == 2) return __builtin_fmaf(s, g, s);
+    else return s * g;
+}
+
 // ---- what the exotic generators (dividend, jump, barrier) share with the bodies here
 // The vanilla step of one antithetic pair from its Philox block z: MODEL 0 GBM, step i = 0 .. 3 of the block (gbm_paths_body's
 // operations); MODEL 1/2/3/4 Heston scheme 0/1/2/3, step i = 0, 1 of the block (heston_paths_body's)
