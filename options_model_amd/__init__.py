@@ -25,7 +25,8 @@ def __getattr__(name):
                 "HestonBoundsResult", "price_asian_option", "price_bermudan_bounds", "bounds_exercise_dates",
                 "price_american_bounds_checked", "price_american_bounds_jumps", "JumpBoundsResult",
                 "price_american_bounds_dividends", "DividendBoundsResult", "price_barrier_bounds",
-                "BarrierBoundsResult", "price_american_dividend_greeks", "DividendGreeksResult"):
+                "BarrierBoundsResult", "price_american_dividend_greeks", "DividendGreeksResult",
+                "price_american_chain_bounds", "ChainBoundsResult"):
         from . import api
         return getattr(api, name)
     if name in ("AdvancedOptionPricer", "RNGManager", "BlackScholesGreeks", "welford_batch_update",

@@ -226,6 +226,13 @@ class ChainInfo(C.Structure):
 
 
 CHAIN_MAX = 256
+CHAIN_BOUNDS_MAX = 8  # OMC_CHAIN_BOUNDS_MAX: entries of a chain of price bounds that ride on one simulation at most
+
+
+class ChainBoundsInfo(C.Structure):
+    """omc_chain_bounds_info: the steps the chain's inner pairs were simulated for, its groups and its phase times."""
+    _fields_ = [("inner_path_steps_simulated", C.c_int64), ("n_groups", C.c_int32), ("entries_per_group", C.c_int32),
+                ("ms_fit", C.c_double), ("ms_lower", C.c_double), ("ms_upper", C.c_double), ("ms_total", C.c_double)]
 
 
 class MlpJob(C.Structure):
@@ -364,6 +371,12 @@ DIVIDEND_GREEKS_SIGNATURES = {
     "omc_price_american_div_greeks": (C.c_int, [_P, C.POINTER(Params), _D, _P, _I, _D, _P, _P, C.POINTER(DivGreeks)]),
 }
 
+# The entry point of include/omc_chain_bounds.h, an extension header of its own.
+CHAIN_BOUNDS_SIGNATURES = {
+    "omc_price_american_chain_bounds": (C.c_int, [_P, C.POINTER(Params), C.POINTER(ChainEntry), _I, C.POINTER(BoundsConfig),
+                                                  _P, _P, _P, _P, C.POINTER(Bounds), C.POINTER(ChainBoundsInfo)]),
+}
+
 _lib = None
 _lib_lock = threading.Lock()
 _hip_runtime = None
@@ -422,7 +435,7 @@ def load_library(build_if_missing: bool = True):
         _preload_hip_runtime()
         lib = C.CDLL(path)
         for name, (res, args) in {**SIGNATURES, **JUMP_BOUNDS_SIGNATURES, **DIVIDEND_BOUNDS_SIGNATURES,
-                                  **BARRIER_BOUNDS_SIGNATURES, **DIVIDEND_GREEKS_SIGNATURES}.items():
+                                  **BARRIER_BOUNDS_SIGNATURES, **DIVIDEND_GREEKS_SIGNATURES, **CHAIN_BOUNDS_SIGNATURES}.items():
             fn = getattr(lib, name)  # AttributeError = symbol missing = broken build
             fn.restype = res
             fn.argtypes = args
@@ -1501,6 +1514,60 @@ class Context:
             for i in range(n):
                 out[i]["betas"] = bo[i]
         return out, {k: getattr(info, k) for k, _ in ChainInfo._fields_ if k != "reserved"}
+
+    def price_american_chain_bounds(self, params: Params, strikes, is_put=True, policy="textbook", n_lower=1_000_000,
+                                    n_outer=8192, n_inner=1024, stream_lower=None, stream_outer=None, stream_inner=None,
+                                    betas=None, want_q=False, want_samples=False, exercise_every=0):
+        """Andersen-Broadie bounds of every quote of a chain from one set of fresh paths (omc_price_american_chain_bounds;
+        GBM, or Heston scheme reference or full_truncation) -> (list of the dicts of price_american_bounds, info dict).
+        strikes, is_put and exercise_every as price_american_chain takes them (an entry with exercise_every != 0 is refused
+        with -44); params.K / params.is_put are ignored.  policy and the sizes as price_american_bounds; betas: the tables
+        of policy "given", [n][n_steps+1][4].  Entry i carries the bits of its own price_american_bounds /
+        price_american_bounds_heston call in betas, lower, se_lower, n_exercised_lower and inner_path_steps -- and in q,
+        samples, upper and se_upper while n_inner <= 128; beyond, those differ by the order of float64 sums.  Streams default
+        to params.stream + 1 / 2 / 3.  info: inner_path_steps_simulated, n_groups, entries_per_group and the phase times."""
+        ks = [float(k) for k in strikes]
+        n = len(ks)
+        every = [int(exercise_every)] * n if isinstance(exercise_every, (int, np.integer)) else [int(k) for k in exercise_every]
+        if len(every) != n:
+            raise ValueError("one exercise_every per strike.")
+        sides = [int(bool(is_put))] * n if isinstance(is_put, (bool, int, np.integer)) else [int(bool(s)) for s in is_put]
+        if len(sides) != n:
+            raise ValueError("one side per strike.")
+        ent = (ChainEntry * max(n, 1))()
+        for i in range(n):
+            ent[i].K, ent[i].is_put, ent[i].exercise_every = ks[i], sides[i], every[i]
+        N, m, no = int(params.n_steps), max(n, 1), max(int(n_outer), 0)
+        cfg = BoundsConfig()
+        cfg.policy = BOUND_POLICIES.get(policy, -1) if isinstance(policy, str) else int(policy)
+        cfg.n_lower, cfg.n_outer, cfg.n_inner = int(n_lower), int(n_outer), int(n_inner)
+        base = int(params.stream)
+        cfg.stream_lower = base + 1 if stream_lower is None else int(stream_lower)
+        cfg.stream_outer = base + 2 if stream_outer is None else int(stream_outer)
+        cfg.stream_inner = base + 3 if stream_inner is None else int(stream_inner)
+        b = None
+        if betas is not None:
+            b = np.ascontiguousarray(betas, np.float64)
+            if b.shape != (n, N + 1, 4):
+                raise ValueError(f"betas must have shape ({n}, {N + 1}, 4), got {b.shape}.")
+        bo = np.zeros((m, N + 1, 4))
+        q = np.zeros((m, no, N)) if want_q else None
+        smp = np.zeros((m, no)) if want_samples else None
+        res = (Bounds * m)()
+        info = ChainBoundsInfo()
+        _check(self.lib, self.lib.omc_price_american_chain_bounds(
+            self.handle, C.byref(params), ent, n, C.byref(cfg), b.ctypes.data if b is not None else None, bo.ctypes.data,
+            q.ctypes.data if q is not None else None, smp.ctypes.data if smp is not None else None, res, C.byref(info)))
+        outs = []
+        for i in range(n):
+            d = {k: getattr(res[i], k) for k, _ in Bounds._fields_}
+            d["betas"] = bo[i]
+            if want_q:
+                d["q"] = q[i]
+            if want_samples:
+                d["samples"] = smp[i]
+            outs.append(d)
+        return outs, {k: getattr(info, k) for k, _ in ChainBoundsInfo._fields_}
 
     def chain_width(self, params: Params, n: int) -> int:
         """Entries per fused launch of a chain of n entries like params (omc_chain_width; 1 = unfused route, 0 = invalid)."""

@@ -1081,6 +1081,79 @@ def price_american_bounds_heston(S0, K, r, T, n_paths, n_steps, heston_params=No
                           variance_scale=max(float(hp["v0"]), float(hp["theta"])), **_game(n_steps, every))
 
 
+class ChainBoundsResult(list):
+    """price_american_chain_bounds: one BoundsResult (HestonBoundsResult under Heston) per quote, in the caller's order,
+    and what the chain as a whole did: `inner_path_steps_simulated` (the steps its inner pairs were simulated for -- at least
+    the largest and at most the sum of the entries' inner_path_steps), `n_groups` (the entries ride on one simulation in
+    groups of at most `entries_per_group`) and `timings_ms` (fit, lower, upper, total of the whole call)."""
+
+    def __init__(self, entries, strikes, option_types, inner_path_steps_simulated, n_groups, entries_per_group, timings_ms):
+        super().__init__(entries)
+        self.strikes = strikes
+        self.option_types = option_types
+        self.inner_path_steps_simulated = inner_path_steps_simulated
+        self.n_groups = n_groups
+        self.entries_per_group = entries_per_group
+        self.timings_ms = timings_ms
+
+
+def _chain_quotes(strikes, option_types):
+    """strikes / option_types of a chain -> the strikes as floats and one side per strike (ValueError otherwise)"""
+    try:
+        ks = [float(k) for k in strikes]
+    except TypeError:
+        raise ValueError("strikes must be a sequence of numbers.") from None
+    if not ks:
+        raise ValueError("strikes must not be empty.")
+    if len(ks) > _ffi.CHAIN_MAX:
+        raise ValueError(f"a chain has at most {_ffi.CHAIN_MAX} entries.")
+    types = [option_types] * len(ks) if isinstance(option_types, str) else list(option_types)
+    if len(types) != len(ks):
+        raise ValueError("option_types must be one string or one per strike.")
+    return ks, types
+
+
+def price_american_chain_bounds(S0, strikes, r, sigma, T, n_paths, n_steps, option_types="put", model="GBM",
+                                heston_params=None, heston_scheme="reference", policy="textbook", n_lower=1_000_000,
+                                n_outer=8192, n_inner=1024, seed=42, stream=0, betas=None, device=None,
+                                ctx=None) -> ChainBoundsResult:
+    """Lower and upper bounds for every quote of one expiry -- `strikes`, each a put or a call (`option_types`: one string
+    for all, or one per strike) -- from ONE set of fitting, lower-bound, outer and inner paths
+    (omc_price_american_chain_bounds).  Entry i equals price_american_bounds(S0, strikes[i], ...,
+    option_type=option_types[i]) -- under model="Heston" price_american_bounds_heston with regressors "spot" -- at the same
+    sizes, seed and stream: bit for bit in betas, lower, se_lower, n_exercised_lower and inner_path_steps, and in upper and
+    se_upper while n_inner <= 128; beyond, upper differs by the order of float64 sums.  policy as
+    price_american_bounds takes it; with "given", `betas` is [len(strikes)][n_steps+1][4].  heston_scheme "reference"
+    (= "clamp") or "full_truncation".  No exercise schedule, control variate or sub-optimality check.  One GPU."""
+    model_l = _model_name(model)
+    ks, types = _chain_quotes(strikes, option_types)
+    _bounds_sizes(policy, betas, n_lower, n_outer, n_inner)
+    _bounds_scheme("heston", model_l, heston_scheme)
+    heston = model_l == "heston"
+    for k, ot in zip(ks, types):
+        if not (math.isfinite(k) and k > 0):
+            raise ValueError("S0, K, T must be positive.")
+        _validate(S0, k, T, r, None if heston else sigma, n_paths, n_steps, ot, need_sigma=not heston)
+    if betas is not None and np.shape(betas) != (len(ks), int(n_steps) + 1, 4):
+        raise ValueError(f"betas must have shape ({len(ks)}, {int(n_steps) + 1}, 4), got {np.shape(betas)}.")
+    M = _even_paths(n_paths)
+    hp = heston_defaults(None, heston_params) if heston else None
+    p = _law_params(model_l, types[0], heston_scheme, hp, M, n_steps, S0, ks[0], r, None if heston else sigma, T, seed, stream)
+    c = ctx or _ffi.default_context(device)
+    outs, info = c.price_american_chain_bounds(p, ks, [ot == "put" for ot in types], policy=policy, n_lower=int(n_lower),
+                                               n_outer=int(n_outer), n_inner=int(n_inner), betas=betas)
+    if heston:
+        law = dict(regressors="spot", variance_scale=max(float(hp["v0"]), float(hp["theta"])))
+        entries = [_bounds_result(HestonBoundsResult, out, policy=policy, option_type=ot, **law, **_game(n_steps, 0))
+                   for out, ot in zip(outs, types)]
+    else:
+        entries = [_bounds_result(BoundsResult, out, policy=policy, option_type=ot, **_game(n_steps, 0))
+                   for out, ot in zip(outs, types)]
+    return ChainBoundsResult(entries, ks, types, info["inner_path_steps_simulated"], info["n_groups"],
+                             info["entries_per_group"],
+                             dict(fit=info["ms_fit"], lower=info["ms_lower"], upper=info["ms_upper"], total=info["ms_total"]))
+
+
 @dataclass
 class JumpBoundsResult(BoundsResult):
     """price_american_bounds_jumps: BoundsResult with the jump law.  The policy is a function of the spot alone; `lower` is
