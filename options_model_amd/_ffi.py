@@ -169,6 +169,15 @@ class JumpResult(C.Structure):
                 ("n_thresholds", C.c_int32), ("reserved", C.c_int32)]
 
 
+class JumpGreeks(C.Structure):
+    """omc_jump_greeks (include/omc_jump_greeks.h): omc_greeks plus epsilon (dV/dq), the jump Greeks and the jump count."""
+    _fields_ = [("g", Greeks), ("epsilon", C.c_double), ("se_epsilon", C.c_double),
+                ("dlambda", C.c_double), ("se_dlambda", C.c_double), ("dmu_j", C.c_double), ("se_dmu_j", C.c_double),
+                ("dsigma_j", C.c_double), ("se_dsigma_j", C.c_double),
+                ("theta_score", C.c_double), ("se_theta_score", C.c_double),
+                ("kappa", C.c_double), ("drift_rate", C.c_double), ("n_jumps", C.c_int64)]
+
+
 class Basket(C.Structure):
     """omc_basket: n_assets (1 .. 8), kind (BASKET_KINDS), per-asset S0 / sigma / q / w, and rho row-major [d][d]."""
     _fields_ = [("n_assets", C.c_int32), ("kind", C.c_int32), ("S0", C.c_double * 8), ("sigma", C.c_double * 8),
@@ -377,6 +386,12 @@ CHAIN_BOUNDS_SIGNATURES = {
                                                   _P, _P, _P, _P, C.POINTER(Bounds), C.POINTER(ChainBoundsInfo)]),
 }
 
+# The entry point of include/omc_jump_greeks.h, an extension header of its own.
+JUMP_GREEKS_SIGNATURES = {
+    "omc_price_american_jump_greeks": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Jump), _D, _D, _P, _P,
+                                                 C.POINTER(JumpGreeks)]),
+}
+
 _lib = None
 _lib_lock = threading.Lock()
 _hip_runtime = None
@@ -435,7 +450,8 @@ def load_library(build_if_missing: bool = True):
         _preload_hip_runtime()
         lib = C.CDLL(path)
         for name, (res, args) in {**SIGNATURES, **JUMP_BOUNDS_SIGNATURES, **DIVIDEND_BOUNDS_SIGNATURES,
-                                  **BARRIER_BOUNDS_SIGNATURES, **DIVIDEND_GREEKS_SIGNATURES, **CHAIN_BOUNDS_SIGNATURES}.items():
+                                  **BARRIER_BOUNDS_SIGNATURES, **DIVIDEND_GREEKS_SIGNATURES, **CHAIN_BOUNDS_SIGNATURES,
+                                  **JUMP_GREEKS_SIGNATURES}.items():
             fn = getattr(lib, name)  # AttributeError = symbol missing = broken build
             fn.restype = res
             fn.argtypes = args
@@ -1053,6 +1069,32 @@ class Context:
                                                            C.byref(out), S_keep.ptr if S_keep else None,
                                                            S_keep.shape[1] if S_keep else 0))
         return _with_base(out)
+
+    def price_american_jump_greeks(self, params: Params, jump, q=0.0, bump=0.01, betas=None, want_betas=False):
+        """Frozen-policy Greeks of price_american_jump's product (omc_price_american_jump_greeks) -> dict: the base
+        pricing's keys plus delta, gamma, vega, rho, theta, epsilon (dV/dq), dlambda, dmu_j, dsigma_j, theta_score (raw
+        units), se_*, bump, price_up, price_down, n_exercised_up / _down, ms_greeks, kappa, drift_rate, n_jumps.  One
+        forward sweep on regenerated paths replaces pass 2; dlambda and theta carry a score-function term.  Heston (Bates)
+        gives delta and gamma, the others are NaN; at lambda = 0 dlambda is NaN.  `betas` [n_steps+1][4] freezes a given
+        policy (an all-n <= 0 table: the European option); want_betas adds the policy used."""
+        N = int(params.n_steps)
+        b = None
+        if betas is not None:
+            b = np.ascontiguousarray(betas, np.float64)
+            if b.shape != (N + 1, 4):
+                raise ValueError(f"betas must have shape ({N + 1}, 4), got {b.shape}.")
+        bo = np.zeros((N + 1, 4)) if want_betas else None
+        out = JumpGreeks()
+        _check(self.lib, self.lib.omc_price_american_jump_greeks(self.handle, C.byref(params), C.byref(make_jump(jump)),
+                                                                  float(q), float(bump),
+                                                                  b.ctypes.data if b is not None else None,
+                                                                  bo.ctypes.data if bo is not None else None, C.byref(out)))
+        d = _with_base(out.g)
+        for name, _ in JumpGreeks._fields_[1:]:
+            d[name] = getattr(out, name)
+        if want_betas:
+            d["betas"] = bo
+        return d
 
     def price_american_basket(self, params: Params, basket: Basket, S_keep: DeviceArray | None = None,
                               assets_keep: DeviceArray | None = None):

@@ -730,6 +730,98 @@ def price_american_jumps(S0, K, r, sigma, T, n_paths, n_steps, jump_intensity, j
 
 
 @dataclass
+class JumpGreeksResult:
+    """price_american_jump_greeks: the frozen-policy price and its Greeks in raw units (per unit S0 / S0^2 / sigma / r / q /
+    year / jump_intensity / jump_mean / jump_vol), their standard errors, the bumped scenarios and the policy used.
+    theta_score is the score-function part of theta (already inside theta).  Heston (Bates): everything but delta and
+    gamma is NaN; at jump_intensity = 0 dlambda is NaN."""
+    price: float
+    stderr: float
+    delta: float
+    gamma: float
+    vega: float
+    rho: float
+    theta: float
+    epsilon: float
+    dlambda: float
+    dmu_j: float
+    dsigma_j: float
+    theta_score: float
+    se_delta: float
+    se_gamma: float
+    se_vega: float
+    se_rho: float
+    se_theta: float
+    se_epsilon: float
+    se_dlambda: float
+    se_dmu_j: float
+    se_dsigma_j: float
+    se_theta_score: float
+    price_up: float
+    price_down: float
+    bump: float
+    n_paths: int
+    n_exercised: int
+    n_exercised_up: int
+    n_exercised_down: int
+    sum_nitm: int
+    n_jumps: int
+    kappa: float
+    drift_rate: float
+    jump_intensity: float
+    jump_mean: float
+    jump_vol: float
+    dividend_yield: float
+    model: str
+    option_type: str
+    betas: object = None  # numpy [n_steps+1][4]: b0, b1, b2, n
+    timings_ms: dict = field(default_factory=dict)
+
+    def __float__(self):
+        return float(self.price)
+
+
+def price_american_jump_greeks(S0, K, r, sigma, T, n_paths, n_steps, jump_intensity, jump_mean=0.0, jump_vol=0.0,
+                               dividend_yield=0.0, model="GBM", option_type="put", heston_params=None,
+                               heston_scheme="reference", seed=42, stream=0, bump=0.01, betas=None, device=None,
+                               ctx=None) -> JumpGreeksResult:
+    """Delta, gamma, vega, rho, theta, epsilon (dV/d dividend_yield) and the jump Greeks dlambda, dmu_j, dsigma_j
+    (dV/d jump_intensity, jump_mean, jump_vol) of the American price price_american_jumps quotes, with the exercise policy
+    pass 1 fits -- or `betas` [n_steps+1][4] -- held fixed (omc_price_american_jump_greeks).  One
+    forward sweep regenerates the paths with their jump counts and sizes: with jumps the stored spot no longer gives the
+    Brownian value price_american_greeks reads back from it.  A step's jump count is an integer, so dlambda and theta
+    carry a score-function term next to their pathwise part; theta is -dV/dT at fixed n_steps.  Heston (Bates) gives
+    delta and gamma; the others are NaN.  jump_intensity * T / n_steps may not exceed 1.  Antithetic paths, one GPU."""
+    model_l = str(model).lower()
+    if model_l not in ("gbm", "heston"):
+        raise ValueError("model must be 'GBM' or 'Heston'.")
+    lam, mu, sj, q = _jump_args(jump_intensity, jump_mean, jump_vol, dividend_yield)
+    if not (0.0 < float(bump) <= 0.5):
+        raise ValueError("bump must lie in (0, 0.5].")
+    _validate(S0, K, T, r, sigma, n_paths, n_steps, option_type, need_sigma=(model_l == "gbm"))
+    _validate_scheme(model_l, heston_scheme, sigma, heston_params)
+    if lam * float(T) / int(n_steps) > 1.0:
+        raise ValueError("jump_intensity * T / n_steps must not exceed 1: use more time steps.")
+    M = _even_paths(n_paths)
+    p = _ffi.make_params(model=model_l, is_put=(option_type == "put"), semantics="two_pass", antithetic=True,
+                         n_paths=M, n_steps=int(n_steps), S0=S0, K=K, r=r, sigma=sigma or 0.0, T=T, seed=seed,
+                         stream=stream, heston_scheme=heston_scheme, **heston_defaults(sigma, heston_params))
+    c = ctx or _ffi.default_context(device)
+    out = c.price_american_jump_greeks(p, (lam, mu, sj), q, bump=float(bump), betas=betas, want_betas=True)
+    var = max(out["sumsq"] / M - out["price"] ** 2, 0.0)
+    names = ("delta", "gamma", "vega", "rho", "theta", "epsilon", "dlambda", "dmu_j", "dsigma_j", "theta_score")
+    return JumpGreeksResult(
+        price=out["price"], stderr=math.sqrt(var / M), **{k: out[k] for k in names},
+        **{"se_" + k: out["se_" + k] for k in names},
+        price_up=out["price_up"], price_down=out["price_down"], bump=out["bump"], n_paths=M,
+        n_exercised=out["n_exercised"], n_exercised_up=out["n_exercised_up"], n_exercised_down=out["n_exercised_down"],
+        sum_nitm=out["sum_nitm"], n_jumps=out["n_jumps"], kappa=out["kappa"], drift_rate=out["drift_rate"],
+        jump_intensity=lam, jump_mean=mu, jump_vol=sj, dividend_yield=q, model=model_l, option_type=option_type,
+        betas=out["betas"],
+        timings_ms=dict(paths=out["ms_paths"], pass1=out["ms_pass1"], greeks=out["ms_greeks"], total=out["ms_total"]))
+
+
+@dataclass
 class BasketResult:
     """price_american_basket: price / stderr (the convention of PriceResult), the exercise counts and the index of the
     initial spots.  The exercise policy behind the price is a function of the INDEX alone."""
