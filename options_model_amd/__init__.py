@@ -27,7 +27,7 @@ def __getattr__(name):
                 "price_american_bounds_dividends", "DividendBoundsResult", "price_barrier_bounds",
                 "BarrierBoundsResult", "price_american_dividend_greeks", "DividendGreeksResult",
                 "price_american_chain_bounds", "ChainBoundsResult", "price_american_jump_greeks",
-                "JumpGreeksResult"):
+                "JumpGreeksResult", "price_american_chain_greeks", "ChainGreeksResult", "price_bermudan_greeks"):
         from . import api
         return getattr(api, name)
     if name in ("AdvancedOptionPricer", "RNGManager", "BlackScholesGreeks", "welford_batch_update",

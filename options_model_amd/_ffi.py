@@ -244,6 +244,13 @@ class ChainBoundsInfo(C.Structure):
                 ("ms_fit", C.c_double), ("ms_lower", C.c_double), ("ms_upper", C.c_double), ("ms_total", C.c_double)]
 
 
+class ChainGreeksInfo(C.Structure):
+    """omc_chain_greeks_info: storage, groups and sweep launches of a chain's Greeks and its phase times."""
+    _fields_ = [("folded", C.c_int32), ("n_groups", C.c_int32), ("n_sweep_launches", C.c_int32),
+                ("entries_per_launch", C.c_int32),
+                ("ms_paths", C.c_double), ("ms_pass1", C.c_double), ("ms_greeks", C.c_double), ("ms_total", C.c_double)]
+
+
 class MlpJob(C.Structure):
     """omc_mlp_job: one network of a batch trained side by side (omc_mlp_train_epoch_batch)."""
     _fields_ = [("data", C.c_void_p), ("n_rows", C.c_int64), ("batch", C.c_int64),
@@ -392,6 +399,12 @@ JUMP_GREEKS_SIGNATURES = {
                                                  C.POINTER(JumpGreeks)]),
 }
 
+# The entry point of include/omc_chain_greeks.h, an extension header of its own.
+CHAIN_GREEKS_SIGNATURES = {
+    "omc_price_american_chain_greeks": (C.c_int, [_P, C.POINTER(Params), C.POINTER(ChainEntry), _I, _D, _P, _P,
+                                                  C.POINTER(Greeks), C.POINTER(ChainGreeksInfo)]),
+}
+
 _lib = None
 _lib_lock = threading.Lock()
 _hip_runtime = None
@@ -451,7 +464,7 @@ def load_library(build_if_missing: bool = True):
         lib = C.CDLL(path)
         for name, (res, args) in {**SIGNATURES, **JUMP_BOUNDS_SIGNATURES, **DIVIDEND_BOUNDS_SIGNATURES,
                                   **BARRIER_BOUNDS_SIGNATURES, **DIVIDEND_GREEKS_SIGNATURES, **CHAIN_BOUNDS_SIGNATURES,
-                                  **JUMP_GREEKS_SIGNATURES}.items():
+                                  **JUMP_GREEKS_SIGNATURES, **CHAIN_GREEKS_SIGNATURES}.items():
             fn = getattr(lib, name)  # AttributeError = symbol missing = broken build
             fn.restype = res
             fn.argtypes = args
@@ -1610,6 +1623,43 @@ class Context:
                 d["samples"] = smp[i]
             outs.append(d)
         return outs, {k: getattr(info, k) for k, _ in ChainBoundsInfo._fields_}
+
+    def price_american_chain_greeks(self, params: Params, strikes, is_put=True, bump=0.01, betas=None, want_betas=False,
+                                    exercise_every=0):
+        """Frozen-policy pathwise Greeks of every quote of a chain from one set of paths (omc_price_american_chain_greeks) ->
+        (list of the dicts of price_american_greeks, info dict).  strikes, is_put and exercise_every as price_american_chain
+        takes them; params.K / params.is_put are ignored.  An American entry carries the bits of its own
+        price_american_greeks call; a Bermudan entry (exercise_every >= 2) those of that call with its masked policy given
+        (but sum_nitm).  betas: one given policy per entry, [n][n_steps+1][4]; want_betas adds the policy used as "betas".
+        info: folded, n_groups, n_sweep_launches, entries_per_launch and the phase times."""
+        ks = [float(k) for k in strikes]
+        n = len(ks)
+        every = [int(exercise_every)] * n if isinstance(exercise_every, (int, np.integer)) else [int(k) for k in exercise_every]
+        if len(every) != n:
+            raise ValueError("one exercise_every per strike.")
+        sides = [int(bool(is_put))] * n if isinstance(is_put, (bool, int, np.integer)) else [int(bool(s)) for s in is_put]
+        if len(sides) != n:
+            raise ValueError("one side per strike.")
+        ent = (ChainEntry * max(n, 1))()
+        for i in range(n):
+            ent[i].K, ent[i].is_put, ent[i].exercise_every = ks[i], sides[i], every[i]
+        N, m = int(params.n_steps), max(n, 1)
+        b = None
+        if betas is not None:
+            b = np.ascontiguousarray(betas, np.float64)
+            if b.shape != (n, N + 1, 4):
+                raise ValueError(f"betas must have shape ({n}, {N + 1}, 4), got {b.shape}.")
+        bo = np.zeros((m, N + 1, 4)) if want_betas else None
+        res = (Greeks * m)()
+        info = ChainGreeksInfo()
+        _check(self.lib, self.lib.omc_price_american_chain_greeks(
+            self.handle, C.byref(params), ent, n, float(bump), b.ctypes.data if b is not None else None,
+            bo.ctypes.data if bo is not None else None, res, C.byref(info)))
+        outs = [_with_base(res[i]) for i in range(n)]
+        if want_betas:
+            for i in range(n):
+                outs[i]["betas"] = bo[i]
+        return outs, {k: getattr(info, k) for k, _ in ChainGreeksInfo._fields_}
 
     def chain_width(self, params: Params, n: int) -> int:
         """Entries per fused launch of a chain of n entries like params (omc_chain_width; 1 = unfused route, 0 = invalid)."""

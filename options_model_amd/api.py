@@ -322,17 +322,9 @@ class ChainResult:
         return self.entries[i]
 
 
-def price_american_chain(S0, strikes, r, sigma, T, n_paths, n_steps, option_types="put", model="GBM", heston_params=None,
-                         heston_scheme="reference", seed=42, stream=0, device=None, ctx=None, exercise_every=None,
-                         n_gpus=1) -> ChainResult:
-    """Every quote of one expiry -- `strikes`, each a put or a call (`option_types`: one string for all, or one per
-    strike) -- from ONE set of paths (omc_price_american_chain): two-pass flow, polynomial regressor, antithetic pairs,
-    one GPU.  entries[i] equals price_american_option(S0, strikes[i], ..., option_type=option_types[i]) bit for bit.
-    exercise_every: None (every quote American), one int for all quotes or one per strike -- 0 or 1 every date, k >= 2 a
-    Bermudan quote that may exercise early only at every k-th date counted back from expiry (exercise_dates); the
-    American, Bermudan and European (k >= n_steps) values of a strike then come from the same paths.
-    heston_scheme (model="Heston"): "reference" (= "clamp"), "full_truncation", "calibrator", or "qe" -- Andersen's (2008)
-    quadratic-exponential rule, which needs kappa > 0, theta > 0 and xi > 0 (ValueError otherwise)."""
+def _chain_checked(S0, strikes, r, sigma, T, n_paths, n_steps, option_types, model, heston_params, heston_scheme,
+                   exercise_every, n_gpus):
+    """price_american_chain's argument checks, in its order -> (model, strikes, sides, schedules, paths); ValueError otherwise"""
     model_l = str(model).lower()
     if model_l not in ("gbm", "heston"):
         raise ValueError("model must be 'GBM' or 'Heston'.")
@@ -355,7 +347,22 @@ def price_american_chain(S0, strikes, r, sigma, T, n_paths, n_steps, option_type
             raise ValueError("S0, K, T must be positive.")
         _validate(S0, k, T, r, sigma, n_paths, n_steps, ot, need_sigma=(model_l == "gbm"))
         _validate_scheme(model_l, heston_scheme, sigma, heston_params)
-    M = _even_paths(n_paths)
+    return model_l, ks, types, every, _even_paths(n_paths)
+
+
+def price_american_chain(S0, strikes, r, sigma, T, n_paths, n_steps, option_types="put", model="GBM", heston_params=None,
+                         heston_scheme="reference", seed=42, stream=0, device=None, ctx=None, exercise_every=None,
+                         n_gpus=1) -> ChainResult:
+    """Every quote of one expiry -- `strikes`, each a put or a call (`option_types`: one string for all, or one per
+    strike) -- from ONE set of paths (omc_price_american_chain): two-pass flow, polynomial regressor, antithetic pairs,
+    one GPU.  entries[i] equals price_american_option(S0, strikes[i], ..., option_type=option_types[i]) bit for bit.
+    exercise_every: None (every quote American), one int for all quotes or one per strike -- 0 or 1 every date, k >= 2 a
+    Bermudan quote that may exercise early only at every k-th date counted back from expiry (exercise_dates); the
+    American, Bermudan and European (k >= n_steps) values of a strike then come from the same paths.
+    heston_scheme (model="Heston"): "reference" (= "clamp"), "full_truncation", "calibrator", or "qe" -- Andersen's (2008)
+    quadratic-exponential rule, which needs kappa > 0, theta > 0 and xi > 0 (ValueError otherwise)."""
+    model_l, ks, types, every, M = _chain_checked(S0, strikes, r, sigma, T, n_paths, n_steps, option_types, model,
+                                                  heston_params, heston_scheme, exercise_every, n_gpus)
     c = ctx or _ffi.default_context(device)
     p = _ffi.make_params(model=model_l, is_put=True, semantics="two_pass", antithetic=True, heston_scheme=heston_scheme,
                          n_paths=M, n_steps=int(n_steps), S0=S0, K=ks[0], r=r, sigma=sigma or 0.0, T=T, seed=seed,
@@ -461,6 +468,81 @@ def price_american_greeks(S0, K, r, sigma, T, n_paths, n_steps, model="GBM", opt
                         option_type=option_type,
                         timings_ms=dict(paths=out["ms_paths"], pass1=out["ms_pass1"], greeks=out["ms_greeks"],
                                         total=out["ms_total"]))
+
+
+@dataclass
+class ChainGreeksResult:
+    """price_american_chain_greeks: one GreeksResult per quote, in the caller's order, the quotes' schedules (entry_info[i]:
+    exercise_every, n_early_dates, sum_nitm) and what the chain as a whole did."""
+    entries: list
+    strikes: list
+    option_types: list
+    exercise_every: list = field(default_factory=list)  # per quote: 0 = every date
+    entry_info: list = field(default_factory=list)      # per quote: dict(exercise_every, n_early_dates, sum_nitm)
+    timings_ms: dict = field(default_factory=dict)  # whole chain: paths, pass1, greeks, total
+    info: dict = field(default_factory=dict)        # folded, n_groups, n_sweep_launches, entries_per_launch
+
+    def __len__(self):
+        return len(self.entries)
+
+    def __getitem__(self, i):
+        return self.entries[i]
+
+
+def price_american_chain_greeks(S0, strikes, r, sigma, T, n_paths, n_steps, option_types="put", exercise_every=None,
+                                model="GBM", heston_params=None, heston_scheme="reference", bump=0.01, betas=None, seed=42,
+                                stream=0, device=None, ctx=None) -> ChainGreeksResult:
+    """Delta, gamma, vega, rho and theta of every quote of one expiry -- `strikes`, sides (`option_types`) and schedules
+    (`exercise_every`) as price_american_chain takes them -- from ONE set of paths (omc_price_american_chain_greeks, DESIGN.md
+    section 35).  An American entry equals price_american_greeks(S0, strikes[i], ..., option_type=option_types[i]) bit for
+    bit; a Bermudan entry (exercise_every >= 2) is the frozen-policy estimator of price_bermudan_option: the American,
+    Bermudan and European (k >= n_steps) hedges of a strike then come from the same paths.  betas: None, or one given policy
+    per quote, [len(strikes)][n_steps+1][4].  Heston: vega, rho, theta are NaN.  One GPU."""
+    model_l, ks, types, every, M = _chain_checked(S0, strikes, r, sigma, T, n_paths, n_steps, option_types, model,
+                                                  heston_params, heston_scheme, exercise_every, 1)
+    if not (0.0 < float(bump) <= 0.5):
+        raise ValueError("bump must lie in (0, 0.5].")
+    if betas is not None and np.shape(betas) != (len(ks), int(n_steps) + 1, 4):
+        raise ValueError(f"betas must have shape ({len(ks)}, {int(n_steps) + 1}, 4), got {np.shape(betas)}.")
+    c = ctx or _ffi.default_context(device)
+    p = _ffi.make_params(model=model_l, is_put=True, semantics="two_pass", antithetic=True, heston_scheme=heston_scheme,
+                         n_paths=M, n_steps=int(n_steps), S0=S0, K=ks[0], r=r, sigma=sigma or 0.0, T=T, seed=seed,
+                         stream=stream, **heston_defaults(sigma, heston_params))
+    outs, info = c.price_american_chain_greeks(p, ks, [ot == "put" for ot in types], bump=float(bump), betas=betas,
+                                               exercise_every=every)
+    entries, entry_info = [], []
+    for out, ot, k in zip(outs, types, every):
+        var = max(out["sumsq"] / M - out["price"] ** 2, 0.0)
+        g = GreeksResult(price=out["price"], stderr=math.sqrt(var / M), delta=out["delta"], gamma=out["gamma"],
+                         vega=out["vega"], rho=out["rho"], theta=out["theta"], se_delta=out["se_delta"],
+                         se_gamma=out["se_gamma"], se_vega=out["se_vega"], se_rho=out["se_rho"], se_theta=out["se_theta"],
+                         price_up=out["price_up"], price_down=out["price_down"], bump=out["bump"], n_paths=M,
+                         n_exercised=out["n_exercised"], folded=bool(out["folded"]), model=model_l, option_type=ot,
+                         timings_ms=dict(paths=out["ms_paths"], pass1=out["ms_pass1"], greeks=out["ms_greeks"],
+                                         total=out["ms_total"]))
+        entries.append(g)
+        entry_info.append(dict(exercise_every=k, n_early_dates=len(exercise_dates(n_steps, k)), sum_nitm=out["sum_nitm"]))
+    return ChainGreeksResult(entries=entries, strikes=ks, option_types=types, exercise_every=every, entry_info=entry_info,
+                             timings_ms=dict(paths=info["ms_paths"], pass1=info["ms_pass1"], greeks=info["ms_greeks"],
+                                             total=info["ms_total"]),
+                             info=dict(folded=bool(info["folded"]), n_groups=info["n_groups"],
+                                       n_sweep_launches=info["n_sweep_launches"],
+                                       entries_per_launch=info["entries_per_launch"]))
+
+
+def price_bermudan_greeks(S0, K, r, sigma, T, n_paths, n_steps, exercise_every, model="GBM", option_type="put",
+                          heston_params=None, heston_scheme="reference", bump=0.01, seed=42, stream=0, device=None,
+                          ctx=None) -> GreeksResult:
+    """The frozen-policy pathwise Greeks of the Bermudan option of price_bermudan_option: the one-entry chain
+    (price_american_chain_greeks).  0 or 1 is the American option (price_american_greeks' bits), exercise_every >= n_steps
+    the European Greeks of the flow."""
+    if exercise_every is None or isinstance(exercise_every, (list, tuple)):
+        raise ValueError("exercise_every must be a non-negative integer.")
+    chain = price_american_chain_greeks(S0, [K], r, sigma, T, n_paths, n_steps, option_types=option_type,
+                                        exercise_every=exercise_every, model=model, heston_params=heston_params,
+                                        heston_scheme=heston_scheme, bump=bump, seed=seed, stream=stream, device=device,
+                                        ctx=ctx)
+    return chain.entries[0]
 
 
 @dataclass

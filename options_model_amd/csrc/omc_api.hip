@@ -845,6 +845,14 @@ int omc_set_option(omc_ctx* c, const char* key, int64_t value)
     }
     else if (!strcmp(key, "chain_fused")) c->chain_fused = value ? 1 : 0;
     else if (!strcmp(key, "chain_k")) c->chain_k = value < 1 ? -1 : (int)(value > 16 ? 16 : value);
+    else if (!strcmp(key, "chain_greeks_k")) {
+        if (value != -1 && (value < 1 || value > 16)) return fail(-4, "chain_greeks_k must be -1 (default) or 1 .. 16.");
+        c->chain_greeks_k = (int)value;
+    }
+    else if (!strcmp(key, "chain_greeks_order")) {
+        if (value != 0 && value != 1) return fail(-4, "chain_greeks_order must be 0 (banded) or 1 (plain).");
+        c->chain_greeks_order = (int)value;
+    }
     else if (!strcmp(key, "seq_step_wgs")) c->seq_step_wgs = value > 0 ? (int)value : 0;
     else if (!strcmp(key, "p2p_exchange")) c->p2p_use = value ? 1 : 0;
     else if (!strcmp(key, "p2p_deadline_ms") || !strcmp(key, "p2p_first_deadline_ms")) {

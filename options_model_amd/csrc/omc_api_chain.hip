@@ -40,8 +40,11 @@ omc_params with_entry(const omc_params* p, const omc_chain_entry& e)
     return q;
 }
 
-// the checks of the chain's own arguments; `e` may be null when only p and n are to be judged (omc_chain_width)
-int check_chain(const omc_ctx* c, const omc_params* p, const omc_chain_entry* e, int n)
+}  // namespace
+
+// the checks of the chain's own arguments; `e` may be null when only p and n are to be judged (omc_chain_width).  Shared
+// with omc_price_american_chain_greeks (omc_ctx.h).
+int omc::abi::check_chain(const omc_ctx* c, const omc_params* p, const omc_chain_entry* e, int n)
 {
     int rc;
     if (!p) return fail(-7, "null params.");
@@ -61,6 +64,8 @@ int check_chain(const omc_ctx* c, const omc_params* p, const omc_chain_entry* e,
     if (c->distributed()) return fail(-10, "a chain is priced on one GPU.");
     return 0;
 }
+
+namespace {
 
 // entries per fused launch (0: the unfused route) for the chain's problem on the context's own matrix
 int fused_width(const omc_ctx* c, const omc_params* p, int64_t ld, bool folded)

@@ -91,6 +91,8 @@ int check_sizes(int64_t n_paths, int n_steps);
 int check_matrix(const void* S, int64_t ld, int64_t n_paths);
 int check_lsm_args(const void* S, int64_t ld, int64_t n_paths, int n_steps, double K, double r, double T);
 int check_params(const omc_params* p);
+// the checks of a chain's own arguments (omc_api_chain.hip); `e` may be null when only p and n are to be judged
+int check_chain(const omc_ctx* c, const omc_params* p, const omc_chain_entry* e, int n);
 // a Heston scheme (0 .. 3, else -4) and what it needs of the law: OMC_HESTON_QE divides by kappa and xi and needs a positive
 // long-run mean (-36)
 int check_heston_scheme(int scheme, double kappa, double theta, double xi);
@@ -368,6 +370,13 @@ struct omc_ctx {
     DevBuf chain_sched;        // ... and its Bermudan entries' tables on their scheduled dates (omc::chain_schedule_tables)
     int chain_fused = 0;       // option "chain_fused": 0 = default, the single-strike sweeps per entry; 1 = the fused sweeps
     int chain_k = -1;          // option "chain_k": entries per fused launch at most (-1: what omc_chain.hip allows)
+    // omc_price_american_chain_greeks: the entries' slots, per-workgroup partials of a group, reduced sums of every entry;
+    // the host images of the slots and of the caller's policies (pageable: kept until the call's wait)
+    DevBuf cg_slots, cg_part, cg_res;
+    std::vector<char> cg_hslots;
+    std::vector<double> cg_hgiven, cg_hview, cg_hres;  // ... and of the fits and the sums it reads back
+    int chain_greeks_k = -1;      // option "chain_greeks_k": entries per Greeks sweep launch (-1: 16)
+    int chain_greeks_order = 0;   // option "chain_greeks_order" (measurement): omc::kChainGreeksBanded / kChainGreeksPlain
     struct FoldKey { int N = -1; double c0 = 0, g = 0; } fold_key[2];
     int world = 1;  // ranks whose sums the hook / communicator adds up (equal shards)
     omc_allreduce_fn hook = nullptr;
